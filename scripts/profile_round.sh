@@ -8,9 +8,9 @@ run() { local t=$1; shift; timeout -k 10 $t "$@"; local rc=$?; if [ $rc -ge 124 
 rocprofv3 -L > $OUT/counters_available.txt 2>&1
 for C in $CFGS; do
   case $C in C2) SPP=64; BASE="";; C3) SPP=64; BASE="--no-cpu-baseline";; *) SPP=16; BASE="--no-cpu-baseline";; esac      # two full-size batches (one per path pool), as in the full job
-  echo "== $C bench"; run 600 python3 bench.py --config $C $BASE > $OUT/${C}_bench.json 2> $OUT/${C}_bench.err || exit 1
+  echo "== $C bench"; run 600 python3 bench.py --config $C --full $BASE > $OUT/${C}_bench.json 2> $OUT/${C}_bench.err || exit 1
   cat $OUT/${C}_bench.json | cut -c1-400
-  echo "== $C kernel trace"; run 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${C}_trace -o t -- python3 bench.py --config $C --steps 2 --warmup 1 --no-cpu-baseline > $OUT/${C}_bench_under_rocprof.json 2> $OUT/${C}_trace.err || exit 1
+  echo "== $C kernel trace"; run 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${C}_trace -o t -- python3 bench.py --config $C --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/${C}_bench_under_rocprof.json 2> $OUT/${C}_trace.err || exit 1
   cp $(find $OUT/${C}_trace -name '*kernel_stats.csv' | head -1) $OUT/${C}_kernel_stats.csv
   for P in FETCH_SIZE WRITE_SIZE; do
     echo "== $C pmc $P"; run 900 rocprofv3 --pmc $P --output-format csv -d $OUT/${C}_pmc_$P -o t -- python3 bench.py --config $C --steps 1 --warmup 0 --spp $SPP --no-cpu-baseline --no-stage-timing > $OUT/${C}_pmc_$P.log 2>&1 || exit 1

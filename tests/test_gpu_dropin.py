@@ -11,6 +11,9 @@ from tests.conftest import GOLDEN, ROOT
 pytestmark = pytest.mark.gpu
 HARNESS = os.path.join(ROOT, "oracle", "_ref", "harness")
 PLUGIN = os.path.join(ROOT, "oracle", "_ref", "plugins", "path_hip.so")
+# path_hip.so links libmi355pt.so: the harness runs against THIS tree's library, wherever the plugin was linked (the loader searches
+# LD_LIBRARY_PATH before the plugin's own run path)
+HARNESS_ENV = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (os.path.join(ROOT, "mitsuba-im_amd"), os.environ.get("LD_LIBRARY_PATH")) if p))
 
 
 @pytest.mark.skipif(not (os.path.exists(HARNESS) and os.path.exists(PLUGIN)), reason="reference build (oracle/_ref) or adapter plugin not present")
@@ -18,7 +21,7 @@ def test_plugin_drop_in_through_reference_driver(mi, golden_scenes, tmp_path):
     sc = golden_scenes["cornell_small"]
     path = str(tmp_path / "s.miscene"); mi.scenes.save_scene(sc, path)
     out = str(tmp_path / "hip")
-    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), check=True, timeout=300)
+    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), env=HARNESS_ENV, check=True, timeout=300)
     got = np.load(out + "_target.npy"); meta = np.load(out + "_meta.npy")
     ref = np.load(os.path.join(GOLDEN, "cornell_small_responsive.npz"))["target"]
     assert meta[0] == 0                                   # return code 0 = all sample planes done (integrator.cpp:349-401)
@@ -32,7 +35,7 @@ def test_plugin_drop_in_through_reference_driver(mi, golden_scenes, tmp_path):
     assert np.linalg.norm(g[..., :3] - r[..., :3]) / np.linalg.norm(r[..., :3]) < 1e-2
     assert np.allclose(g[..., 3], r[..., 3], rtol=1e-5)   # alpha sums = spp x table weight
     # external control: stop after two progress() calls -> the interrupt's value comes back as the return code
-    subprocess.run([HARNESS, path, "responsive", "path_hip", "1", out + "_stop"], cwd=os.path.dirname(HARNESS), check=True, timeout=300)
+    subprocess.run([HARNESS, path, "responsive", "path_hip", "1", out + "_stop"], cwd=os.path.dirname(HARNESS), env=HARNESS_ENV, check=True, timeout=300)
     assert np.load(out + "_stop_meta.npy")[0] == 101
 
 
@@ -42,7 +45,7 @@ def test_plugin_drop_in_envmap_scene(mi, golden_scenes, tmp_path):
     smooth-shaded meshes -- everything the adapter flattens from a live mitsuba::Scene."""
     sc = golden_scenes["atrium_small"]
     path = str(tmp_path / "s.miscene"); mi.scenes.save_scene(sc, path); out = str(tmp_path / "hip")
-    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), check=True, timeout=300)
+    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), env=HARNESS_ENV, check=True, timeout=300)
     got = np.load(out + "_target.npy"); ref = np.load(os.path.join(GOLDEN, "atrium_small_responsive.npz"))["target"]
     g, r = got[1:-2, 1:-2], ref[1:-2, 1:-2]
     rel = np.abs(g - r).max(2) / (np.abs(r).max(2) + 1e-6)
@@ -55,7 +58,7 @@ def test_plugin_drop_in_analytic_shapes(mi, golden_scenes, tmp_path):
     the adapter rebuilds each shape's transform from its Properties like the shape's own constructor."""
     sc = golden_scenes["cbox_shapes"]
     path = str(tmp_path / "s.miscene"); mi.scenes.save_scene(sc, path); out = str(tmp_path / "hip")
-    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), check=True, timeout=300)
+    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), env=HARNESS_ENV, check=True, timeout=300)
     got = np.load(out + "_target.npy"); ref = np.load(os.path.join(GOLDEN, "cbox_shapes_responsive.npz"))["target"]
     g, r = got[1:-2, 1:-2], ref[1:-2, 1:-2]
     rel = np.abs(g - r).max(2) / (np.abs(r).max(2) + 1e-6)
@@ -72,7 +75,7 @@ def test_plugin_drop_in_scene_level_emitters(mi, golden_scenes, tmp_path, name):
     bumpmap(mixture) and mask(bumpmap), flattened from their serialised forms."""
     sc = golden_scenes[name]
     path = str(tmp_path / "s.miscene"); mi.scenes.save_scene(sc, path); out = str(tmp_path / "hip")
-    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), check=True, timeout=300)
+    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), env=HARNESS_ENV, check=True, timeout=300)
     got = np.load(out + "_target.npy"); ref = np.load(os.path.join(GOLDEN, name + "_responsive.npz"))["target"]
     g, r = got[1:-2, 1:-2], ref[1:-2, 1:-2]
     rel = np.abs(g - r).max(2) / (np.abs(r).max(2) + 1e-6)
@@ -88,7 +91,7 @@ def test_plugin_drop_in_volumetric(mi, golden_scenes, tmp_path, name):
     Alpha (EOpacity, records.inl:124-137): 1 on an opaque hit, 1 - the transmittance of what lies behind a medium-transition shape, what the sensor's medium removes over two scene radii on a miss."""
     sc = golden_scenes[name]
     path = str(tmp_path / "s.miscene"); mi.scenes.save_scene(sc, path); out = str(tmp_path / "hip")
-    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), check=True, timeout=300)
+    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), env=HARNESS_ENV, check=True, timeout=300)
     got = np.load(out + "_target.npy"); ref = np.load(os.path.join(GOLDEN, name + "_responsive.npz"))["target"]
     g, r = got[1:-2, 1:-2, :3], ref[1:-2, 1:-2, :3]
     rel = np.abs(g - r).max(2) / (np.abs(r).max(2) + 1e-6)
@@ -106,7 +109,7 @@ def test_plugin_drop_in_sunsky(mi, golden_scenes, tmp_path, name):
     front end and the oracle refuse the emitter by name.)"""
     sc = golden_scenes[name]
     path = str(tmp_path / "s.miscene"); mi.scenes.save_scene(sc, path); out = str(tmp_path / "hip")
-    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), check=True, timeout=300)
+    subprocess.run([HARNESS, path, "responsive", "path_hip", "-1", out], cwd=os.path.dirname(HARNESS), env=HARNESS_ENV, check=True, timeout=300)
     got = np.load(out + "_target.npy"); ref = np.load(os.path.join(GOLDEN, name + "_responsive.npz"))["target"]
     g, r = got[1:-2, 1:-2], ref[1:-2, 1:-2]
     rel = np.abs(g - r).max(2) / (np.abs(r).max(2) + 1e-6)
@@ -194,7 +197,7 @@ def test_plugin_classic_face_through_renderjob(mi, golden_scenes, tmp_path, name
     films = {}
     for plugin in ("path", "path_hip"):
         out = str(tmp_path / plugin)
-        subprocess.run([HARNESS, path, "classic", plugin, "4", out], cwd=os.path.dirname(HARNESS), check=True, timeout=300)
+        subprocess.run([HARNESS, path, "classic", plugin, "4", out], cwd=os.path.dirname(HARNESS), env=HARNESS_ENV, check=True, timeout=300)
         meta = np.load(out + "_meta.npy"); films[plugin] = np.load(out + "_film.npy")
         assert meta[0] == 1 and meta[2] >= 1                    # render() succeeded, Film::put was called
     a, b = films["path_hip"], films["path"]
@@ -212,7 +215,7 @@ def test_bench_faces_and_devices(tmp_path):
     (MI355PT_BENCH_DEVICES=0,0) -- same JSON schema as the C-ABI line, the fixed job as `value` and the weak-scaling job beside it."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--spp", "8", "--width", "640", "--height", "360", "--no-cpu-baseline"]
+    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--spp", "8", "--width", "640", "--height", "360", "--full", "--no-cpu-baseline"]
     lines = {}
     for tag, extra, env in (("abi", [], {}), ("classic", ["--face", "classic"], {}), ("responsive", ["--face", "responsive"], {}),
                             ("devices", ["--gpus", "2", "--via", "devices", "--face", "responsive"], {"MI355PT_BENCH_DEVICES": "0,0"})):
@@ -222,3 +225,27 @@ def test_bench_faces_and_devices(tmp_path):
         assert lines[tag]["value"] > 0 and lines[tag]["unit"] == "Msamples/s" and "face" in lines[tag]["config"]
     assert lines["devices"]["n_gpus"] == 2 and lines["devices"]["scaling"] == "strong" and lines["devices"]["weak"]["value"] > 0
     assert lines["abi"]["roofline"] is not None and lines["classic"]["roofline"] is None
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(mi, tmp_path):
+    """bench.py --dump-outputs: the raw film of the last timed step as float32, the same from run to run, and the film the C-ABI hands back for the same scene
+    rendered directly; --steps sets the timed steps, a plain run carries the headline figure only."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    films = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "0", "--spp", "8", "--width", "320", "--height", "180",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and "roofline" not in line and "cpu_baseline" not in line
+        assert sorted(os.listdir(d)) == ["film.npy"]
+        films.append(np.load(d / "film.npy"))
+    S = mi.scenes
+    sc = S.cornell_box(320, 180, 8, sampler=S.SAMPLER_SOBOL, max_depth=8)
+    r = mi.Render(mi.Scene(sc, device=0), device=0); r.run(); ref = r.read_film(0)
+    for f in films:
+        assert f.dtype == np.float32 and f.shape == ref.shape
+        assert (f.view(np.uint32) == ref.view(np.uint32)).all(2).mean() > 0.995 and np.allclose(f, ref, rtol=2e-6, atol=1e-7)

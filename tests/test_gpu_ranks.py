@@ -61,7 +61,7 @@ def test_bench_two_ranks_share_the_card():
     the film reduce (gloo through the host: the rehearsal backend), barrier + max-over-ranks timing, rank 0's JSON line with the fixed job as `value` and the weak job beside it."""
     env = dict(os.environ, MI355PT_SHARE_DEVICE="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "1", "--spp", "8", "--width", "640",
-                          "--height", "360", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                          "--height", "360", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["value"] > 0 and line["weak"]["value"] > 0 and line["weak"]["spp"] == 16

@@ -107,3 +107,23 @@ def test_tile_sharding(mi):
 def importlib_dist(mi):
     import importlib
     return importlib.import_module("mitsuba-im_amd.dist")
+
+
+def test_bench_dump_outputs_size_limit(tmp_path, monkeypatch):
+    """bench.py's --dump-outputs writer: float32 as a whole within the size limit, above it a fixed seeded sample of pixels with their flat indices"""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    small = np.arange(6 * 5 * 3, dtype=np.float64).reshape(6, 5, 3)
+    bench.dump_outputs(str(tmp_path / "a"), {"film": small})
+    got = np.load(tmp_path / "a" / "film.npy")
+    assert got.dtype == np.float32 and (got == small).all()
+    big = np.random.default_rng(1).random((200, 300, 5)).astype(np.float32)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 40_000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"film": big})
+    assert sorted(os.listdir(tmp_path / "b")) == ["film_sample.npy", "film_sample_index.npy"]
+    s, i = np.load(tmp_path / "b" / "film_sample.npy"), np.load(tmp_path / "b" / "film_sample_index.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.nbytes + i.nbytes <= 40_000 and len(s) > 1000
+    assert (np.diff(i) > 0).all() and (s == big.reshape(-1, 5)[i.astype(np.int64)]).all()
+    assert (np.load(tmp_path / "c" / "film_sample_index.npy") == i).all()
