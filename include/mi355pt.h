@@ -248,6 +248,17 @@ int mi_scene_ray_intersect(mi_scene *s, const float *rays8, uint64_t n, mi_inter
 /* Unit-level device entry points used by the parity tests (each runs a small kernel over n items) */
 int mi_debug_intersect(mi_scene *s, const float *rays8, uint64_t n, int any_hit, float *out_hits4);   /* t,u,v,prim (prim<0: miss) */
 int mi_debug_intersect_inst(mi_scene *s, const float *rays8, uint64_t n, int any_hit, float *out_hits4, int32_t *out_instance);   /* + instance index of the hit (-1: scene-level primitive) */
+/* The fused tree walk (the ray cast of large triangle-only scenes) on caller-supplied rays, through the stage the renderer launches.  The n rays are laid, in order,
+ * into n_seg queue segments of seg_counts[i] rays each (counts add up to n; empty segments allowed); thr = refill threshold (1..64 busy lanes), grid = persistent
+ * workgroups (1..16384), lds_stack = stack entries per lane kept in LDS (4 or 10; deeper entries spill to memory).
+ * any_hit = 0: out_hits4 = (t, u, v, prim as its bit pattern; 0xFFFFFFFF: miss); a record still holding 0xFFFFFFFE in all four words belongs to a ray the walk never
+ *              retired.  rays_counted = what the launch added to the closest-hit ray counter.
+ * any_hit = 1: out_hits4 = the accumulator of ray i after `+= (1, 0, 0)` for every unoccluded trace of it: x = 0 occluded, 1 unoccluded, 2 traced twice.  Shadow
+ *              records carry no mint: every ray's mint must be 1e-4.
+ * Scenes with analytic shapes or instances and scenes traced as a triangle packet have no such walk: MI_ERR_UNSUPPORTED (decided before any device work). */
+typedef struct { uint32_t wide, bvh_depth, bvh_stack_direct, max_stack_seen; uint64_t rays_counted; } mi_fused_debug_info;   /* node kind (1: 4-wide), the builder's stack bounds, deepest stack any ray of this call held */
+int mi_debug_intersect_fused(mi_scene *s, const float *rays8, uint64_t n, int any_hit, const uint32_t *seg_counts, uint32_t n_seg, uint32_t thr, uint32_t grid, uint32_t lds_stack,
+                             float *out_hits4, mi_fused_debug_info *info);
 int mi_debug_sobol(mi_scene *s, const uint32_t *px_py_k, uint64_t n, uint32_t ndims, uint64_t *out_index, float *out_values);
 int mi_debug_camera_rays(mi_scene *s, const float *sample_pos2, uint64_t n, float *out_rays8);
 int mi_debug_libm(int fn, const float *x, const float *y, uint64_t n, float *out);   /* the device restatements of glibc's routines (libm_glibc.h) as the kernels call them:

@@ -62,11 +62,15 @@ class MiStats(C.Structure):
                 ("extend_launches", C.c_uint64), ("extend_rays", C.c_uint64), ("extend_launches_all", C.c_uint64)]
 
 
+class MiFusedDebugInfo(C.Structure):
+    _fields_ = [("wide", C.c_uint32), ("bvh_depth", C.c_uint32), ("bvh_stack_direct", C.c_uint32), ("max_stack_seen", C.c_uint32), ("rays_counted", C.c_uint64)]
+
+
 EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_scene_create", "mi_scene_destroy", "mi_scene_set_triangles",
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_film",
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
-           "mi_render_set_profiling", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_sincosf", "mi_debug_libm"]
+           "mi_render_set_profiling", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_sincosf", "mi_debug_libm"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics"]
 
 
@@ -119,6 +123,7 @@ class Lib:
         L.mi_render_set_profiling.argtypes = [vp, i32]
         L.mi_debug_intersect.argtypes = [vp, vp, u64, i32, vp]
         L.mi_debug_intersect_inst.argtypes = [vp, vp, u64, i32, vp, vp]
+        L.mi_debug_intersect_fused.argtypes = [vp, vp, u64, i32, vp, u32, u32, u32, u32, vp, C.POINTER(MiFusedDebugInfo)]
         L.mi_debug_sobol.argtypes = [vp, vp, u64, u32, vp, vp]
         L.mi_debug_camera_rays.argtypes = [vp, vp, u64, vp]
         L.mi_debug_sincosf.argtypes = [vp, u64, vp]
@@ -261,6 +266,22 @@ class Scene:
             inst = np.zeros(len(rays8), np.int32)
             self.L.check(self.L.L.mi_debug_intersect_inst(self.h, _p(rays8), len(rays8), int(any_hit), _p(out), _p(inst))); return out, inst
         self.L.check(self.L.L.mi_debug_intersect(self.h, _p(rays8), len(rays8), int(any_hit), _p(out))); return out
+
+    def intersect_fused(self, rays8, any_hit=False, seg_counts=None, thr=48, grid=1792, lds_stack=10):
+        """The fused walk (csrc/trace_fused.h) on these rays, laid into queue segments of seg_counts rays each (default: segments of 1024).  Returns (hits, info):
+        hits as intersect() gives them (t, u, v, prim; prim < 0: miss / unoccluded, any-hit: prim = 1 for an occluded ray); info = wide, bvh_depth, bvh_stack_direct,
+        max_stack_seen, rays_counted, and `unretired` (closest hit: rays whose record still held the sentinel) or `acc_x` (any hit: how often each ray was found
+        unoccluded -- 0 or 1; 2 = traced twice)."""
+        rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8); n = len(rays8)
+        if seg_counts is None: seg_counts = [1024] * (n // 1024) + ([n % 1024] if n % 1024 else [])
+        seg = np.ascontiguousarray(seg_counts, np.uint32).reshape(-1); raw = np.zeros((n, 4), np.float32); inf = MiFusedDebugInfo()
+        self.L.check(self.L.L.mi_debug_intersect_fused(self.h, _p(rays8), n, int(any_hit), _p(seg), len(seg), thr, grid, lds_stack, _p(raw), C.byref(inf)))
+        info = {k: getattr(inf, k) for k, _ in MiFusedDebugInfo._fields_}; out = raw.copy(); w = raw.view(np.uint32)
+        if any_hit:
+            info["acc_x"] = raw[:, 0].copy(); out[:, 3] = np.where(raw[:, 0] == 0, 1.0, -1.0)
+        else:
+            info["unretired"] = int((w == 0xFFFFFFFE).all(1).sum()); out[:, 3] = np.where(w[:, 3] >= 0xFFFFFFFE, -1.0, w[:, 3].astype(np.float32))
+        return out, info
 
     def sobol(self, px_py_k, ndims):
         a = np.ascontiguousarray(px_py_k, np.uint32).reshape(-1, 3); idx = np.zeros(len(a), np.uint64); vals = np.zeros((len(a), ndims), np.float32)

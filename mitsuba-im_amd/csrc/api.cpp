@@ -38,6 +38,8 @@ void mi_launch_gather_samples(const Queues &, const uint32_t *, uint64_t, float 
 void mi_launch_film_add(float *, const float *, size_t, hipStream_t);
 void mi_launch_debug_intersect(const DScene &, const float *, uint64_t, int, float *, int *, hipStream_t);
 void mi_launch_ray_intersect(const DScene &, const float *, uint64_t, mi_intersection *, hipStream_t);
+void mi_launch_debug_fused(const DScene &, const Queues &, int, uint32_t, uint32_t *, uint32_t, uint32_t, int *, hipStream_t);
+uint32_t mi_fused_lds_stack(void);
 void mi_launch_debug_sobol(const DScene &, const uint32_t *, uint64_t, uint32_t, unsigned long long *, float *, hipStream_t);
 void mi_launch_debug_camera(const DScene &, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_sincosf(const float *, uint64_t, float *, hipStream_t);
@@ -955,6 +957,71 @@ int mi_scene_ray_intersect(mi_scene *s, const float *rays, uint64_t n, mi_inters
     return withBuffers(rays, n * 32, out, n * sizeof(mi_intersection), [&](void *i, void *o) { mi_launch_ray_intersect(s->h.d, (const float *) i, n, (mi_intersection *) o, nullptr); });
 }
 int mi_debug_intersect(mi_scene *s, const float *rays, uint64_t n, int anyHit, float *out) { return mi_debug_intersect_inst(s, rays, n, anyHit, out, nullptr); }
+
+// The fused walk of trace_fused.h on caller-supplied rays: a minimal Queues (rays laid into segments as `seg_counts` says, a zeroed ticket, a spill area sized for
+// the worst case 3 * bvh_depth + 4 entries per lane rather than for the builder's bound -- a wrong bound then fails the caller's comparison instead of writing
+// astray) and ONE launch of the stage production runs.  The refusals read host data only, so they are decided (and testable) before any device call.
+int mi_debug_intersect_fused(mi_scene *s, const float *rays, uint64_t n, int anyHit, const uint32_t *segCounts, uint32_t nSeg, uint32_t thr, uint32_t grid, uint32_t ldsStack,
+                             float *out, mi_fused_debug_info *info) {
+    if (!s || !rays || !out || !info || !segCounts || !n || !nSeg) return fail(MI_ERR_INVALID, "mi_debug_intersect_fused: null argument");
+    const mi::SceneHost &h = s->h;
+    if (!h.analytic.empty()) return fail(MI_ERR_UNSUPPORTED, "mi_debug_intersect_fused: the fused walk serves triangle-only trees, this scene has analytic shapes");
+    if (!h.instances.empty()) return fail(MI_ERR_UNSUPPORTED, "mi_debug_intersect_fused: the fused walk serves triangle-only trees, this scene has instances");
+    {   // committed: what upload() decided; before that: the same rule on the host data
+        const char *noPacket = getenv("MI355PT_NO_PACKET");
+        const bool packet = h.committed ? h.d.packet_n != 0 : (h.idx.size() / 3 <= MI_PACKET_MAX && h.media.empty() && !(noPacket && noPacket[0] == '1'));
+        if (packet) return fail(MI_ERR_UNSUPPORTED, "mi_debug_intersect_fused: this scene is traced as one triangle packet (at most 64 triangles), it has no tree to walk; set MI355PT_NO_PACKET=1");
+    }
+    if (!h.committed) return fail(MI_ERR_INVALID, "mi_debug_intersect_fused: the scene must be committed");
+    const DScene &sc = h.d;
+    if (sc.geo_bytes >= 0xFFFFFF00ull) return fail(MI_ERR_UNSUPPORTED, "mi_debug_intersect_fused: nodes and leaf records exceed the 4 GB the fused walk addresses");
+    if (thr < 1 || thr > 64 || grid < 1 || grid > 16384 || (ldsStack != 4u && ldsStack != mi_fused_lds_stack())) return fail(MI_ERR_INVALID, "mi_debug_intersect_fused: thr in 1..64, grid in 1..16384, lds_stack 4 or 10");
+    uint64_t total = 0; uint32_t cap = 64;
+    for (uint32_t i = 0; i < nSeg; ++i) { total += segCounts[i]; cap = std::max(cap, (segCounts[i] + 63u) / 64u * 64u); }
+    if (total != n) return fail(MI_ERR_INVALID, "mi_debug_intersect_fused: seg_counts must add up to n");
+    const uint64_t slots = (uint64_t) cap * nSeg;
+    if (slots >= (1ull << 28) || n >= (1ull << 28)) return fail(MI_ERR_INVALID, "mi_debug_intersect_fused: fewer than 2^28 slots");
+    if (anyHit) for (uint64_t i = 0; i < n; ++i) if (rays[i * 8 + 3] != MI_EPSILON) return fail(MI_ERR_INVALID, "mi_debug_intersect_fused: a shadow record has no mint of its own, any-hit rays start at MI_EPSILON (1e-4)");
+    HIPCHK(hipSetDevice(h.device));
+    // slot of ray i: segment by segment, in input order
+    std::vector<uint64_t> slotOf(n); { uint64_t i = 0; for (uint32_t sg = 0; sg < nSeg; ++sg) for (uint32_t j = 0; j < segCounts[sg]; ++j) slotOf[i++] = (uint64_t) sg * cap + j; }
+    const uint32_t sentinel = 0xFFFFFFFEu;      // no retired ray leaves this in Queues::hit: prim is a triangle index or 0xFFFFFFFF
+    std::vector<float4> hO(slots, make_float4(0, 0, 0, 0)), hD(slots, make_float4(0, 0, 0, 0)), hC(anyHit ? slots : 0, make_float4(1.0f, 0.0f, 0.0f, 0.0f));
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *r = rays + i * 8; const uint32_t pid = (uint32_t) i; float pidf; memcpy(&pidf, &pid, 4);
+        hO[slotOf[i]] = make_float4(r[0], r[1], r[2], anyHit ? r[7] : r[3]); hD[slotOf[i]] = make_float4(r[4], r[5], r[6], anyHit ? pidf : r[7]);
+    }
+    std::vector<void *> bufs; int rc = MI_OK;
+    auto alloc = [&](size_t bytes) -> void * { void *p = nullptr; if (rc) return p; hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 16)); if (e != hipSuccess) { rc = fail(MI_ERR_DEVICE, std::string("mi_debug_intersect_fused: ") + hipGetErrorString(e)); return nullptr; } bufs.push_back(p); return p; };
+    auto chk = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = fail(MI_ERR_DEVICE, std::string("mi_debug_intersect_fused: ") + hipGetErrorString(e)); };
+    Queues q{}; q.cap = cap; q.n_seg = nSeg;
+    float4 *dO = (float4 *) alloc(slots * 16), *dD = (float4 *) alloc(slots * 16);
+    uint32_t *dCount = (uint32_t *) alloc((size_t) nSeg * 4), *dTicket = (uint32_t *) alloc(4); int *dMaxSp = (int *) alloc(4);
+    q.counters = (unsigned long long *) alloc(32);
+    const size_t spillEntries = (size_t) 3 * sc.bvh_depth + 4;
+    q.stkSpill = (int32_t *) alloc(spillEntries * grid * 256u * 4);      // one column per lane of the grid (workgroups of 256)
+    if (anyHit) { q.shO = dO; q.shD = dD; q.shC = (float4 *) alloc(slots * 16); q.acc = (float4 *) alloc(n * 16); q.shCount = dCount; }
+    else { q.rayO[0] = dO; q.rayD[0] = dD; q.count[0] = dCount; q.hit = (float4 *) alloc(slots * 16); }
+    if (!rc) {
+        chk(hipMemcpy(dO, hO.data(), slots * 16, hipMemcpyHostToDevice)); chk(hipMemcpy(dD, hD.data(), slots * 16, hipMemcpyHostToDevice));
+        chk(hipMemcpy(dCount, segCounts, (size_t) nSeg * 4, hipMemcpyHostToDevice)); chk(hipMemset(dTicket, 0, 4)); chk(hipMemset(dMaxSp, 0, 4)); chk(hipMemset(q.counters, 0, 32));
+        if (anyHit) { chk(hipMemcpy(q.shC, hC.data(), slots * 16, hipMemcpyHostToDevice)); chk(hipMemset(q.acc, 0, n * 16)); }
+        else { std::vector<uint32_t> fill(slots * 4, sentinel); chk(hipMemcpy(q.hit, fill.data(), slots * 16, hipMemcpyHostToDevice)); }
+    }
+    std::vector<float4> res(anyHit ? n : slots);
+    if (!rc) {
+        mi_launch_debug_fused(sc, q, anyHit, ldsStack, dTicket, thr, grid, dMaxSp, nullptr);
+        chk(hipGetLastError()); chk(hipDeviceSynchronize());
+        int maxSp = 0; unsigned long long cnt[4] = {};
+        chk(hipMemcpy(res.data(), anyHit ? q.acc : q.hit, res.size() * 16, hipMemcpyDeviceToHost)); chk(hipMemcpy(&maxSp, dMaxSp, 4, hipMemcpyDeviceToHost)); chk(hipMemcpy(cnt, q.counters, 32, hipMemcpyDeviceToHost));
+        if (!rc) {
+            for (uint64_t i = 0; i < n; ++i) memcpy(out + i * 4, &res[anyHit ? i : slotOf[i]], 16);
+            info->wide = sc.bvh_wide; info->bvh_depth = sc.bvh_depth; info->bvh_stack_direct = sc.bvh_stack_direct; info->max_stack_seen = (uint32_t) maxSp; info->rays_counted = cnt[0];
+        }
+    }
+    for (void *p : bufs) (void) hipFree(p);
+    return rc;
+}
 int mi_debug_sobol(mi_scene *s, const uint32_t *in, uint64_t n, uint32_t ndims, uint64_t *outIdx, float *outVals) {
     if (!s || !s->h.committed || !in || !outIdx || !outVals || !n || !s->h.d.sobol_m32 || ndims > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "mi_debug_sobol: bad argument");
     HIPCHK(hipSetDevice(s->h.device));

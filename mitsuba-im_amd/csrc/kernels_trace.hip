@@ -74,6 +74,14 @@ __global__ __launch_bounds__(WG) void k_shadow_f(DScene sc, Queues q, uint32_t *
     fusedStage<true, WIDE>(sc, q, 0, ticket, thr, s_lds);
 }
 
+// The same walk for mi_debug_intersect_fused (tests/test_gpu_fused_walk.py): the caller lays the rays into segments, picks the refill threshold, the grid and the LDS
+// stack size (LS = 4 drives shallow trees through the spill path), and reads back the deepest stack any ray needed.
+template <bool ANY, bool WIDE, int LS>
+__global__ __launch_bounds__(WG) void k_debug_fused(DScene sc, Queues q, uint32_t *ticket, uint32_t thr, int *maxSp) {
+    __shared__ int s_lds[(LS + 10) * WG];
+    fusedStage<ANY, WIDE, LS, true>(sc, q, 0, ticket, thr, s_lds, maxSp);
+}
+
 // ---------------------------------------------------------------------------------------------- unit-level entry point (parity tests)
 __global__ __launch_bounds__(WG) void k_debug_intersect(DScene sc, const float *rays, uint64_t n, int anyHit, float *out, int *outInst) {
     __shared__ int s_stk[STACK_DEPTH * WG];
@@ -168,6 +176,16 @@ void mi_launch_shadow_fused(const DScene &sc, const Queues &q, uint32_t *ticket,
     const uint32_t g = kFusedGrid;
     if (sc.bvh_wide) hipLaunchKernelGGL((k_shadow_f<true>), dim3(g), dim3(WG), 0, st, sc, q, ticket, kFusedThr); else hipLaunchKernelGGL((k_shadow_f<false>), dim3(g), dim3(WG), 0, st, sc, q, ticket, kFusedThr);
 }
+// ldsStack: 4 or FZ_LDS_STACK (mi_debug_intersect_fused checks it)
+void mi_launch_debug_fused(const DScene &sc, const Queues &q, int anyHit, uint32_t ldsStack, uint32_t *ticket, uint32_t thr, uint32_t grid, int *maxSp, hipStream_t st) {
+#define MI_DBG_FUSED(ANY, WIDE) do { \
+    if (ldsStack == 4u) hipLaunchKernelGGL((k_debug_fused<ANY, WIDE, 4>), dim3(grid), dim3(WG), 0, st, sc, q, ticket, thr, maxSp); \
+    else hipLaunchKernelGGL((k_debug_fused<ANY, WIDE, FZ_LDS_STACK>), dim3(grid), dim3(WG), 0, st, sc, q, ticket, thr, maxSp); } while (0)
+    if (anyHit) { if (sc.bvh_wide) MI_DBG_FUSED(true, true); else MI_DBG_FUSED(true, false); }
+    else { if (sc.bvh_wide) MI_DBG_FUSED(false, true); else MI_DBG_FUSED(false, false); }
+#undef MI_DBG_FUSED
+}
+uint32_t mi_fused_lds_stack(void) { return FZ_LDS_STACK; }
 void mi_launch_ray_intersect(const DScene &sc, const float *rays, uint64_t n, mi_intersection *out, hipStream_t st) { hipLaunchKernelGGL(k_ray_intersect, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, sc, rays, n, out); }
 void mi_launch_debug_intersect(const DScene &sc, const float *rays, uint64_t n, int anyHit, float *out, int *outInst, hipStream_t st) { hipLaunchKernelGGL(k_debug_intersect, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, sc, rays, n, anyHit, out, outInst); }
 }

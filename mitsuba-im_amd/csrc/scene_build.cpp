@@ -166,7 +166,10 @@ struct Builder {
 };
 
 static inline int32_t leafCode(int first, int count) { return ~(int32_t) (first * 8 + (count - 1)); }
-#define BVH_EMPTY_CHILD 0x7FFFFFFD      // unused slot of a 4-wide node (its box is inverted, so it is never taken)
+// Unused slots of a 4-wide node carry an inverted box (qlo 255, qhi 0), but the conservative box tests of trace.h / trace_fused.h can still pass it: the slack
+// 2e-6 * t outgrows the box once the node's extent is below ~2e-6 * t on every axis (small geometry seen from far away).  So the slot's CODE must be harmless
+// too: it names a one-record leaf whose record (k = MI_K_NONE, appended after the tree's own leaf records) no triangle test accepts.
+#define MI_K_NONE 3u                    // TriAccelD::k of a record that is never hit (the value triaccelLoad gives degenerate triangles)
 
 void SceneHost::commitHost() {
     const uint32_t nt = (uint32_t) (idx.size() / 3), na = (uint32_t) analytic.size(), ni = (uint32_t) instances.size(), np = nt + na + ni;
@@ -324,11 +327,13 @@ void SceneHost::commitHost() {
         int root = prims.empty() ? -1 : bld.build(0, (int) prims.size(), 0);
         for (uint32_t i = 0; i < prims.size(); ++i) tris.push_back(accel[bld.order[i]]);
         if (wideBvh) {
+            const int32_t emptyChild = leafCode((int) tris.size(), 1);      // the never-hit record behind every unused slot of this tree
+            { TriAccelD none{}; none.k = MI_K_NONE; none.prim = 0xFFFFFFFFu; tris.push_back(none); }
             // Collapse the binary tree into 4-wide nodes (the inner child with the largest surface area is replaced by its two children until four slots are
             // taken), quantise the child boxes against the node's own box.  Returns the device index; `need` = stack entries from this node down.
             static_assert(sizeof(Bvh4Node) == sizeof(BvhNode), "both node kinds share one array");
             auto area = [](const BuildNode &n) { V3 e = n.hi - n.lo; return e.x * e.y + e.y * e.z + e.z * e.x; };
-            struct Emit { std::vector<BvhNode> &nodes; Builder &bld; int triBase; decltype(area) &areaOf;
+            struct Emit { std::vector<BvhNode> &nodes; Builder &bld; int triBase; int32_t emptyChild; decltype(area) &areaOf;
                 int run(int id, int &need, int &needD) {
                     std::vector<int> kids;
                     if (id < 0) { /* empty tree */ } else if (bld.nodes[id].count > 0) kids.push_back(id); else { kids.push_back(bld.nodes[id].left); kids.push_back(bld.nodes[id].right); }
@@ -350,7 +355,7 @@ void SceneHost::commitHost() {
                     }
                     int sub = 0, subD = 0;
                     for (int c = 0; c < 4; ++c) {
-                        if (c >= (int) kids.size()) { for (int a = 0; a < 3; ++a) { w.qlo[a] |= 255u << (8 * c); } w.child[c] = BVH_EMPTY_CHILD; continue; }
+                        if (c >= (int) kids.size()) { for (int a = 0; a < 3; ++a) { w.qlo[a] |= 255u << (8 * c); } w.child[c] = emptyChild; continue; }
                         const BuildNode &k = bld.nodes[kids[c]];
                         for (int a = 0; a < 3; ++a) {
                             const double step = std::ldexp(1.0, ex[a] - 127), o = comp(lo, a);
@@ -364,11 +369,12 @@ void SceneHost::commitHost() {
                         else { int need = 0, needD = 0; w.child[c] = run(kids[c], need, needD); sub = std::max(sub, need); subD = std::max(subD, needD); }
                     }
                     std::memcpy(&nodes[dev], &w, sizeof(w));
-                    need = sub + (kids.size() > 1 ? 1 : 0);      // one stack entry per level: the node's pending children (trace.h)
-                    needD = subD + (kids.size() > 1 ? (int) kids.size() - 1 : 0);      // child codes pushed one by one (trace_fused.h): up to kids - 1 siblings wait while a subtree is walked
+                    // An unused slot can pass the box test (see MI_K_NONE), so every node counts as if all four slots were taken:
+                    need = sub + 1;       // one stack entry per level: the node's pending children (trace.h)
+                    needD = subD + 3;     // child codes pushed one by one (trace_fused.h): up to three siblings wait while a subtree is walked
                     return dev;
                 } };
-            Emit em{nodes, bld, triBase, area}; int need = 0, needD = 0; const int dev = em.run(root, need, needD); treeNeed.push_back(need + 1); treeNeedDirect.push_back(needD + 1);
+            Emit em{nodes, bld, triBase, emptyChild, area}; int need = 0, needD = 0; const int dev = em.run(root, need, needD); treeNeed.push_back(need + 1); treeNeedDirect.push_back(needD + 1);
             (void) nodeBase; return dev;
         }
         std::vector<int> devIndex(bld.nodes.size(), -1); int nInner = 0;
@@ -392,13 +398,14 @@ void SceneHost::commitHost() {
     for (const mi_shape &sh : shapes) { uint32_t g = slotOf(sh); for (uint32_t t = 0; t < sh.tri_count; ++t) members[g].push_back(sh.first_tri + t); }
     for (uint32_t t = nt; t < np; ++t) members[ng].push_back(t);
     emitTree(members[ng]);                 // the scene level first: a tree's root is the first node it emits, so the scene root is node 0
-    // Hot nodes first (wide scene-level tree without instances): the fused walk (trace_fused.h) keeps the first nodes of the array in LDS, and a node is visited about
-    // as often as its box is large (surface area heuristic) -- on the atrium the 128 most visited of 62 k nodes take 64 % of all node visits.  A pure renumbering
-    // (root stays node 0): every traversal sees the same tree.
+    // Hot nodes first (wide scene-level tree without instances): a node is visited about as often as its box is large (surface area heuristic) -- on the atrium the
+    // 128 most visited of 62 k nodes take 64 % of all node visits -- so sorting the array by box area packs the nodes every ray reads into a few cache lines that
+    // stay resident (the fused walk of trace_fused.h reads nodes from global memory; it keeps only its stack and the ray in LDS).  A pure renumbering (root stays
+    // node 0, leaf codes -- unused slots included -- are negative and untouched): every traversal sees the same tree.
     if (wideBvh && ni == 0 && ng == 0 && nodes.size() > 1) {
         Bvh4Node *w = reinterpret_cast<Bvh4Node *>(nodes.data()); const size_t nn = nodes.size();
         std::vector<float> areaOf(nn, 0.0f); areaOf[0] = std::numeric_limits<float>::infinity();
-        for (size_t i = 0; i < nn; ++i) for (int c = 0; c < 4; ++c) if (w[i].child[c] >= 0 && w[i].child[c] != BVH_EMPTY_CHILD) {
+        for (size_t i = 0; i < nn; ++i) for (int c = 0; c < 4; ++c) if (w[i].child[c] >= 0) {
             const float st[3] = {w[i].step_x, w[i].step_y, w[i].step_z}; float e[3];
             for (int a = 0; a < 3; ++a) e[a] = (float) ((int) ((w[i].qhi[a] >> (8 * c)) & 0xFFu) - (int) ((w[i].qlo[a] >> (8 * c)) & 0xFFu)) * st[a];
             areaOf[w[i].child[c]] = e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
@@ -409,7 +416,7 @@ void SceneHost::commitHost() {
         std::vector<BvhNode> re(nn);
         for (size_t i = 0; i < nn; ++i) {
             Bvh4Node n = w[byArea[i]];
-            for (int c = 0; c < 4; ++c) if (n.child[c] >= 0 && n.child[c] != BVH_EMPTY_CHILD) n.child[c] = newIndex[n.child[c]];
+            for (int c = 0; c < 4; ++c) if (n.child[c] >= 0) n.child[c] = newIndex[n.child[c]];
             std::memcpy(&re[i], &n, sizeof(n));
         }
         nodes.swap(re);

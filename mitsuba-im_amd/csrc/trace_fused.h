@@ -17,7 +17,9 @@
 // counts those: the children behind the nearest one are pushed in slot order (the model: 12.1 instead of 12.0 node visits per ray, no sort network, no 64-bit
 // compares), the Wald test's axis rotation reads the ray from an LDS copy (three ds_read2st64 instead of twelve selects).
 // The arithmetic is trace.h's: same conservative box tests, same exact Wald test, closest hit = minimum t with ties to the lower triangle index -- the result is
-// independent of the visiting order, so (t, u, v, prim) stay bit-identical (tests: test_intersection_bit_exact, test_both_tree_node_kinds, test_fused_walk_*).
+// independent of the visiting order, so (t, u, v, prim) stay bit-identical.  Tests: tests/test_gpu_fused_walk.py hands this walk rays one by one through
+// mi_debug_intersect_fused (test_adversarial_rays, test_empty_slots_far_away, test_stack_spill_small_lds, test_stack_spill_sliver_stack, test_refill_and_segments);
+// test_both_tree_node_kinds and the radiance tests of the large scenes reach it through the path tracer.
 #pragma once
 #include "trace.h"
 
@@ -31,12 +33,14 @@ DEV float fastInv(float d) { const float a = fabsf(d) < 1e-30f ? copysignf(1e-30
 // lane for the ray (o.x o.y o.z o.x o.y | d.x d.y d.z d.x d.y: the components (k, u, v) of a triangle's projection axis k are three consecutive words).
 #define FZ_LDS_STACK 10
 #define FZ_LDS_WORDS ((FZ_LDS_STACK + 10) * WG)
-template <bool ANY, bool WIDE>
-DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *ticket, const uint32_t thr, int *s_lds) {
+// LS: stack entries per lane kept in LDS (s_lds holds (LS + 10) * WG words); production runs LS = FZ_LDS_STACK.  DBG (mi_debug_intersect_fused only): every retired
+// ray adds the deepest stack it saw to *dbgMaxSp with one atomicMax.
+template <bool ANY, bool WIDE, int LS = FZ_LDS_STACK, bool DBG = false>
+DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *ticket, const uint32_t thr, int *s_lds, int *dbgMaxSp = nullptr) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const unsigned long long lt = (1ull << lane) - 1ull;
     int *stk = s_lds + tid;
-    float *rayL = reinterpret_cast<float *>(s_lds + FZ_LDS_STACK * WG) + tid;      // word j of this lane's ray at rayL[j * WG]
+    float *rayL = reinterpret_cast<float *>(s_lds + LS * WG) + tid;      // word j of this lane's ray at rayL[j * WG]
     int *spill = q.stkSpill + ((size_t) blockIdx.x * WG + tid); const size_t spillStride = (size_t) gridDim.x * WG;
     const char *geo = reinterpret_cast<const char *>(sc.nodes);
     const uint32_t triOff = (uint32_t) (reinterpret_cast<const char *>(sc.tris) - geo);      // mi_fused_walk: nodes + leaf records are one allocation smaller than 4 GB
@@ -45,7 +49,7 @@ DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *
     // per-lane ray (o and d live in LDS for the triangle test, 1 / d and -o / d in registers for the box tests)
     v3 inv = V(0, 0, 0), oi = V(0, 0, 0);
     float mint = 0, best = 0, bu = 0, bv = 0; uint32_t bprim = 0xFFFFFFFFu, pid = 0; uint64_t slot = 0;
-    int cur = FZ_IDLE, sp = 0;
+    int cur = FZ_IDLE, sp = 0, spMax = 0;
     // wave-uniform stream cursor
     uint32_t seg = 0, n = 0, nxt = 0; bool more = true; unsigned long long rays = 0;
     while (true) {
@@ -73,7 +77,7 @@ DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *
                         inv = V(fastInv(d.x), fastInv(d.y), fastInv(d.z)); oi = V(-o.x * inv.x, -o.y * inv.y, -o.z * inv.z);      // 1-ulp reciprocals: the box tests are conservative culling only (2e-6 slack)
                         rayL[0] = o.x; rayL[WG] = o.y; rayL[2 * WG] = o.z; rayL[3 * WG] = o.x; rayL[4 * WG] = o.y;
                         rayL[5 * WG] = d.x; rayL[6 * WG] = d.y; rayL[7 * WG] = d.z; rayL[8 * WG] = d.x; rayL[9 * WG] = d.y;
-                        best = maxt; bprim = 0xFFFFFFFFu; bu = 0; bv = 0; cur = 0; sp = 0;
+                        best = maxt; bprim = 0xFFFFFFFFu; bu = 0; bv = 0; cur = 0; sp = 0; if (DBG) spMax = 0;
                     } else if (ANY) {                // the segment misses the scene box: unoccluded
                         const float4 c = q.shC[slot]; float4 a = q.acc[pid]; a.x += c.x; a.y += c.y; a.z += c.z; q.acc[pid] = a;
                     } else q.hit[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
@@ -114,13 +118,13 @@ DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *
                 const int b0 = __builtin_amdgcn_sbfe((int) m, 0, 1), b1 = __builtin_amdgcn_sbfe((int) m, 1, 1);
                 const int lo = (c1 & b0) | (c0 & ~b0), hi = (c3 & b0) | (c2 & ~b0), nearest = (hi & b1) | (lo & ~b1);
                 const int w0 = (key[0] != m) & (key[0] != 0xFFFFFFFFu), w1 = (key[1] != m) & (key[1] != 0xFFFFFFFFu), w2 = (key[2] != m) & (key[2] != 0xFFFFFFFFu), w3 = (key[3] != m) & (key[3] != 0xFFFFFFFFu);
-                if (sp <= FZ_LDS_STACK - 4) {
+                if (sp <= LS - 4) {
                     stk[sp * WG] = c0; sp += w0; stk[sp * WG] = c1; sp += w1; stk[sp * WG] = c2; sp += w2; stk[sp * WG] = c3; sp += w3;
                 } else {
-                    if (w0) { if (sp < FZ_LDS_STACK) stk[sp * WG] = c0; else spill[(size_t) (sp - FZ_LDS_STACK) * spillStride] = c0; ++sp; }
-                    if (w1) { if (sp < FZ_LDS_STACK) stk[sp * WG] = c1; else spill[(size_t) (sp - FZ_LDS_STACK) * spillStride] = c1; ++sp; }
-                    if (w2) { if (sp < FZ_LDS_STACK) stk[sp * WG] = c2; else spill[(size_t) (sp - FZ_LDS_STACK) * spillStride] = c2; ++sp; }
-                    if (w3) { if (sp < FZ_LDS_STACK) stk[sp * WG] = c3; else spill[(size_t) (sp - FZ_LDS_STACK) * spillStride] = c3; ++sp; }
+                    if (w0) { if (sp < LS) stk[sp * WG] = c0; else spill[(size_t) (sp - LS) * spillStride] = c0; ++sp; }
+                    if (w1) { if (sp < LS) stk[sp * WG] = c1; else spill[(size_t) (sp - LS) * spillStride] = c1; ++sp; }
+                    if (w2) { if (sp < LS) stk[sp * WG] = c2; else spill[(size_t) (sp - LS) * spillStride] = c2; ++sp; }
+                    if (w3) { if (sp < LS) stk[sp * WG] = c3; else spill[(size_t) (sp - LS) * spillStride] = c3; ++sp; }
                 }
                 pop = m == 0xFFFFFFFFu; cur = pop ? cur : nearest;
             } else {
@@ -128,9 +132,10 @@ DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *
                 float t0, t1;
                 const bool h0 = slab(r0, r1, inv, oi, mint, best, t0), h1 = slab(r2, r3, inv, oi, mint, best, t1);
                 const bool both = h0 & h1, sw = t1 < t0;
-                if (both) { const int far = sw ? c0 : c1; if (sp < FZ_LDS_STACK) stk[sp * WG] = far; else spill[(size_t) (sp - FZ_LDS_STACK) * spillStride] = far; ++sp; }
+                if (both) { const int far = sw ? c0 : c1; if (sp < LS) stk[sp * WG] = far; else spill[(size_t) (sp - LS) * spillStride] = far; ++sp; }
                 pop = !(h0 | h1); cur = both ? (sw ? c1 : c0) : (h0 ? c0 : (h1 ? c1 : cur));
             }
+            if (DBG) spMax = sp > spMax ? sp : spMax;
         } else if (live) {
             // TriAccel::rayIntersect (triaccel.h:96-158), written without branches: r0 = k n_u n_v n_d | r1 = a_u a_v b_nu b_nv | r2 = c_nu c_nv prim pad.
             // (o_k, o_u, o_v) and (d_k, d_u, d_v) are words k, k + 1, k + 2 of the LDS copy of the ray
@@ -149,16 +154,17 @@ DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *
             }
             pop = (code & 7u) == 0u; cur = pop ? cur : cur - 7;                                  // next triangle: first + 1, remaining - 1
         }
-        {   // pop: one LDS read (or, beyond FZ_LDS_STACK entries, one read of the spill column); an empty stack retires the ray
+        {   // pop: one LDS read (or, beyond LS entries, one read of the spill column); an empty stack retires the ray
             const bool doPop = pop & !finished;
             const int spm = sp > 0 ? sp - 1 : 0;
-            int top = stk[(spm < FZ_LDS_STACK ? spm : FZ_LDS_STACK - 1) * WG];
-            if (doPop && spm >= FZ_LDS_STACK) top = spill[(size_t) (spm - FZ_LDS_STACK) * spillStride];
+            int top = stk[(spm < LS ? spm : LS - 1) * WG];
+            if (doPop && spm >= LS) top = spill[(size_t) (spm - LS) * spillStride];
             finished |= doPop & (sp == 0);
             cur = (doPop & (sp > 0)) ? top : cur; sp = doPop ? spm : sp;
         }
         if (finished) {
             cur = FZ_IDLE;
+            if (DBG) atomicMax(dbgMaxSp, spMax);
             if (ANY) {
                 if (bprim == 0xFFFFFFFFu) { const float4 c = q.shC[slot]; float4 a = q.acc[pid]; a.x += c.x; a.y += c.y; a.z += c.z; q.acc[pid] = a; }
             } else q.hit[slot] = make_float4(best, bu, bv, __uint_as_float(bprim));      // a miss keeps t = the far end of the clipped interval, like traverse()

@@ -994,6 +994,60 @@ def closed_box(width=128, height=128, spp=16, sampler=SAMPLER_SOBOL, max_depth=8
                         width, height, spp, sampler, max_depth, name="closed_box")
 
 
+def _grid_room(b, L, n):
+    """closed cube room [-L, L]^3, every wall an n x n grid of quads (normals face the room)"""
+    def wall(origin, eu, ev):
+        o, u, v = (np.asarray(a, np.float64) for a in (origin, eu, ev))
+        for j in range(n):
+            for i in range(n):
+                b.quad([o + u * (i / n) + v * (j / n), o + u * ((i + 1) / n) + v * (j / n), o + u * ((i + 1) / n) + v * ((j + 1) / n), o + u * (i / n) + v * ((j + 1) / n)])
+    D = 2 * L
+    wall((L, -L, -L), (-D, 0, 0), (0, 0, D)); wall((L, L, -L), (0, 0, D), (-D, 0, 0))      # floor (+y), ceiling (-y)
+    wall((L, -L, L), (-D, 0, 0), (0, D, 0)); wall((-L, -L, -L), (D, 0, 0), (0, D, 0))      # z = +L (-z), z = -L (+z)
+    wall((-L, -L, L), (0, 0, -D), (0, D, 0)); wall((L, -L, -L), (0, 0, D), (0, D, 0))      # x = -L (+x), x = +L (-x)
+
+
+SPECK_EXTENT = 6e-6
+
+
+def speck_room(width=64, height=64, spp=4, sampler=SAMPLER_SOBOL, max_depth=4, room=120.0, patch=3):
+    """Small geometry seen from far away (tests of the tree walks): a closed room of 6 * 3 * 3 * 2 = 108 triangles with a ceiling light, and at the world origin --
+    where fp32 resolves it -- a "speck": a patch of patch x patch quads (18 triangles) of extent SPECK_EXTENT in the plane y = 0.  The speck's tree nodes are
+    so small that, from a distance t beyond ~SPECK_EXTENT / 1e-6, the 2e-6 * t slack of the conservative box tests is larger than the nodes themselves.
+    The patch is perpendicular to the axis its Wald records project along: from that far the Wald test rounds t by more than a triangle, and only then does a ray with
+    a zero direction component keep one answer whatever the tree's leaf padding (tests/test_gpu_fused_walk.py test_speck_rays_short_of_the_slack)."""
+    b = _Builder(); grey = b.bsdf(reflectance=(0.5, 0.5, 0.5)); lightm = b.bsdf(reflectance=(0.5, 0.5, 0.5)); L = float(room)
+    b.begin(); _grid_room(b, L, 3); b.end(grey)
+    b.begin(); b.quad([(0.2 * L, 0.95 * L, -0.2 * L), (0.2 * L, 0.95 * L, 0.2 * L), (-0.2 * L, 0.95 * L, 0.2 * L), (-0.2 * L, 0.95 * L, -0.2 * L)]); b.end(lightm, radiance=(20.0, 20.0, 20.0))
+    h = SPECK_EXTENT / 2
+    def pt(i, j):
+        return (-h + 2 * h * i / patch, 0.0, -h + 2 * h * j / patch)
+    b.begin()
+    for j in range(patch):
+        for i in range(patch): b.quad([pt(i, j), pt(i, j + 1), pt(i + 1, j + 1), pt(i + 1, j)])
+    b.end(grey)
+    cam = look_at((0, 0, -0.9 * L), (0, 0, 0), (0, 1, 0))
+    return finish_scene(b.verts, b.tris, b.shapes, b.bsdfs, b.emitters, cam, 60.0, 0.01, 10 * L, width, height, spp, sampler, max_depth, name="speck_room")
+
+
+def sliver_stack(width=64, height=64, spp=4, sampler=SAMPLER_SOBOL, max_depth=4, side=64, spacing=2e-3):
+    """A tree whose boxes all overlap (tests of the traversal stacks): side x side long thin triangles, each spanning the diagonal of the unit cube, shifted sideways on
+    a grid of `spacing`, so every triangle's box -- and every tree node's -- is nearly the whole cube: a ray through the cube meets nearly every box and almost no
+    triangle, and the walk descends the full depth of the tree with every sibling waiting on its stack.  A floor and a light around it make it renderable."""
+    b = _Builder(); grey = b.bsdf(reflectance=(0.5, 0.5, 0.5)); lightm = b.bsdf(reflectance=(0.5, 0.5, 0.5))
+    diag = np.array([1.0, 1.0, 1.0]); e1 = np.array([1.0, -1.0, 0.0]) / math.sqrt(2.0); e2 = np.array([1.0, 1.0, -2.0]) / math.sqrt(6.0)
+    b.begin()
+    for j in range(side):
+        for i in range(side):
+            off = e1 * ((i - (side - 1) / 2) * spacing) + e2 * ((j - (side - 1) / 2) * spacing)
+            base = len(b.verts); b.verts.extend([tuple(off), tuple(off + diag), tuple(off + diag + e1 * (0.75 * spacing))]); b.tris.append((base, base + 1, base + 2))
+    b.end(grey)
+    b.begin(); b.quad([(3, -0.5, -2), (-2, -0.5, -2), (-2, -0.5, 3), (3, -0.5, 3)]); b.end(grey)                                                  # floor (+y)
+    b.begin(); b.quad([(1.5, 3.0, -0.5), (1.5, 3.0, 1.5), (-0.5, 3.0, 1.5), (-0.5, 3.0, -0.5)]); b.end(lightm, radiance=(20.0, 20.0, 20.0))      # light (-y)
+    cam = look_at((2.5, 1.2, -1.5), (0.5, 0.5, 0.5), (0, 1, 0))
+    return finish_scene(b.verts, b.tris, b.shapes, b.bsdfs, b.emitters, cam, 50.0, 0.01, 100.0, width, height, spp, sampler, max_depth, name="sliver_stack")
+
+
 # conductor eta / k as linear RGB, produced by the reference itself from data/ior/<name>.{eta,k}.spd (RoughConductor constructor,
 # src/bsdfs/roughconductor.cpp:177-189; dumped by oracle/_ref/harness `tables` -> tests/golden/conductor_ior_rgb.npy)
 CONDUCTOR_IOR = {

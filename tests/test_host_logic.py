@@ -127,3 +127,65 @@ def test_bench_dump_outputs_size_limit(tmp_path, monkeypatch):
     assert s.dtype == np.float32 and i.dtype == np.float64 and s.nbytes + i.nbytes <= 40_000 and len(s) > 1000
     assert (np.diff(i) > 0).all() and (s == big.reshape(-1, 5)[i.astype(np.int64)]).all()
     assert (np.load(tmp_path / "c" / "film_sample_index.npy") == i).all()
+
+
+def _uncommitted_scene(mi, sc):
+    """an mi_scene holding sc's geometry (triangles, analytic shapes, instances), not committed: nothing here touches a device"""
+    L = mi.lib(); A = mi.api; h = C.c_void_p(); L.check(L.L.mi_scene_create(C.byref(h)))
+    shapes = (A.MiShape * len(sc.shapes))()
+    for i, s in enumerate(sc.shapes):
+        shapes[i] = A.MiShape(s["first_tri"], s["tri_count"], s["first_vert"], s["vert_count"], s["bsdf"], s["emitter"], s["face_normals"] & 1, s.get("group", 0))
+    L.check(L.L.mi_scene_set_triangles(h, sc.pos.ctypes.data, None, None, sc.idx.ctypes.data, len(sc.pos), len(sc.idx), C.cast(shapes, C.c_void_p), len(sc.shapes)))
+    recs = sc.get("analytic") or []
+    if recs:
+        an = (A.MiAnalytic * len(recs))()
+        for i, a in enumerate(recs):
+            r = A.MiAnalytic(a["type"], a["bsdf"], a["emitter"], a["flags"]); r.to_world[:] = a["to_world"].reshape(-1).tolist(); r.to_object[:] = a["to_object"].reshape(-1).tolist()
+            r.radius, r.length = a["radius"], a["length"]; an[i] = r
+        L.check(L.L.mi_scene_set_analytic(h, C.cast(an, C.c_void_p), len(recs)))
+    insts = sc.get("instances") or []
+    if insts:
+        arr = (A.MiInstance * len(insts))()
+        for i, a in enumerate(insts):
+            r = A.MiInstance(a["group"]); r.to_world[:] = a["to_world"].reshape(-1).tolist(); r.to_object[:] = a["to_object"].reshape(-1).tolist(); arr[i] = r
+        L.check(L.L.mi_scene_set_instances(h, C.cast(arr, C.c_void_p), len(insts)))
+    return h
+
+
+def test_fused_walk_entry_refuses_without_gpu(mi, monkeypatch):
+    """mi_debug_intersect_fused serves triangle-only trees: analytic shapes, instances and packet scenes are refused with MI_ERR_UNSUPPORTED and a message naming the
+    reason -- decided on host data, before the commit check and before any device call, so no kernel runs."""
+    monkeypatch.delenv("MI355PT_NO_PACKET", raising=False)
+    L = mi.lib(); S = mi.scenes
+    rays = np.zeros((1, 8), np.float32); rays[0, 3] = 1e-4; rays[0, 6] = 1; rays[0, 7] = np.inf
+    seg = np.array([1], np.uint32); out = np.zeros((1, 4), np.float32); info = mi.api.MiFusedDebugInfo()
+    def call(h, any_hit=0, n_seg=1, thr=48, grid=1, lds=10):
+        rc = L.L.mi_debug_intersect_fused(h, rays.ctypes.data, 1, any_hit, seg.ctypes.data, n_seg, thr, grid, lds, out.ctypes.data, C.byref(info)); return rc, L.L.mi_last_error()
+    for sc, word in ((S.cbox_shapes(32, 32, 1), b"analytic shapes"), (S.instanced_garden(32, 32, 1), b"instances"), (S.cornell_box(16, 9, 1), b"triangle packet")):
+        h = _uncommitted_scene(mi, sc)
+        for any_hit in (0, 1):
+            rc, msg = call(h, any_hit); assert rc == 3 and word in msg and b"mi_debug_intersect_fused" in msg, (rc, msg)
+        L.L.mi_scene_destroy(h)
+    h = _uncommitted_scene(mi, S.closed_box()); monkeypatch.setenv("MI355PT_NO_PACKET", "1")      # 26 triangles, but the packet is switched off: only the commit is missing
+    rc, msg = call(h); assert rc == 1 and b"must be committed" in msg
+    rc, msg = call(None); assert rc == 1 and b"null argument" in msg
+    L.L.mi_scene_destroy(h)
+
+
+def test_fused_walk_ray_sets_without_gpu(mi):
+    """The numpy side of tests/test_gpu_fused_walk.py (b): the speck scene and its rays meet the precondition of the empty-slot case -- the room has >= 64 triangles, the
+    speck 12 .. 24 of extent ~1e-5 (in its plane y = 0) around the origin, and for >= 1000 rays max_a(2 extent_a / |d_a|) <= 1e-6 t, among them rays along the body diagonals."""
+    from tests import test_gpu_fused_walk as F
+    sc = mi.scenes.speck_room(); s = sc.shapes[-1]; T = s["tri_count"]
+    V = sc.pos[s["first_vert"]:s["first_vert"] + s["vert_count"]]
+    assert len(sc.idx) - T >= 64 and 12 <= T <= 24 and 2 <= F.speck_leaf_bounds(sc)[1] <= 3
+    e = V.max(0) - V.min(0); assert (np.abs(V.max(0) + V.min(0)) < 1e-9).all() and 2e-6 < e[0] < 3e-5 and 2e-6 < e[2] < 3e-5 and e[1] == 0      # flat: see test_speck_rays_short_of_the_slack
+    rays, counts = F.speck_rays(sc)
+    t = np.linalg.norm(rays[:, :3].astype(np.float64), axis=1); d = np.abs(rays[:, 4:7].astype(np.float64))
+    assert counts.sum() >= 1000 and 0.9 < t.min() < 1.1 and 99 < t.max() < 101.1
+    ext = F.speck_extent(sc); assert (ext < 1e-5).all()
+    assert ((2 * ext[None, :] / d[counts]).max(1) <= 1e-6 * t[counts]).all() and t[counts].min() > 10
+    assert (np.abs(d[counts] - 3 ** -0.5) < 1e-6).all(1).sum() >= 100      # body diagonals among them
+    assert (~counts[(d == 0).any(1)]).all()                              # an axis-parallel ray never qualifies: its zero components keep the inverted box shut
+    sl = mi.scenes.sliver_stack(); r = F.sliver_rays(sl)
+    assert 4000 <= len(sl.idx) <= 4200 and len(r) == 2400 and np.allclose(np.linalg.norm(r[:, 4:7], axis=1), 1, atol=1e-6)
