@@ -231,6 +231,45 @@ int mi_render_merge_film(mi_render *dst, mi_render *src);
 /* Debug / parity: Li of individual (px, py, sampleIndex) triples through the very same kernels; out_li[n*3] */
 int mi_render_samples(mi_render *r, const uint32_t *pairs, uint64_t n, float *out_li);
 int mi_render_stats(mi_render *r, mi_stats *out);
+
+/* -- field channels: replaces the `multichannel` integrator with nested `field` integrators (src/integrators/misc/multichannel.cpp:164-221,
+ *    src/integrators/misc/field.cpp:124-177).  Every sample of the radiance film also puts the data of its first camera hit into a field film, at the same film
+ *    position through the same reconstruction filter; the radiance film is what it is without fields.  Kinds in the order of field.cpp's EField; each field is three
+ *    values (a Spectrum), `undefined` is what a camera ray that leaves the scene returns:
+ *      position        its.p
+ *      relPosition     its.p through the inverse of the sensor's world transform: a 3 x 4 matrix, the inverse of mi_scene_set_camera's to_world computed on the host
+ *                      in double precision and rounded to float, applied as a four-term float sum per component
+ *      distance        (t, t, t)
+ *      geoNormal       its.geoFrame.n          shNormal   its.shFrame.n          uv   (u, v, 0)
+ *      albedo          its.shape->getBSDF()->getDiffuseReflectance(its): the (possibly textured, unfiltered lookup: there are no UV partials) diffuse reflectance of
+ *                      diffuse / roughdiffuse / phong / ward, through twosided / bumpmap / normalmap; everything else by the generic rule of src/librender/bsdf.cpp:82-86
+ *                      (eval with wi = wo = (0, 0, 1) under the diffuse-reflection mask, times pi): 0 for the conductors, dielectrics, difftrans and null, opacity x nested
+ *                      for mask, the weighted sum of the children for mixturebsdf / blendbsdf.  Refused (MI_ERR_UNSUPPORTED naming the BSDF) on scenes holding a plastic,
+ *                      roughplastic, coating or roughcoating record -- the material record does not carry their external transmittance -- or a mask over a bumpmap / normalmap
+ *      shapeIndex      index of the hit shape: meshes in mi_scene_set_triangles order, then the analytic shapes; -1 for a hit through an instance (its.shape is then the group
+ *                      member, which is not in the scene's shape list: field.cpp:158-167, skdtree.h:416)
+ *      primIndex       triangle index within its mesh, also for instanced meshes (skdtree.h:418); 0 for analytic shapes (the reference leaves its.primIndex unset there)
+ *    No finite / non-negative check is applied to field values (multichannel.cpp:41-44). */
+#define MI_FIELD_POSITION 0
+#define MI_FIELD_REL_POSITION 1
+#define MI_FIELD_DISTANCE 2
+#define MI_FIELD_GEO_NORMAL 3
+#define MI_FIELD_SH_NORMAL 4
+#define MI_FIELD_UV 5
+#define MI_FIELD_ALBEDO 6
+#define MI_FIELD_SHAPE_INDEX 7
+#define MI_FIELD_PRIM_INDEX 8
+typedef struct { uint32_t field; float undefined[3]; } mi_field;
+/* n <= 8 fields; n = 0 removes them and frees the field film.  Allowed only while the film is clear (no samples since mi_render_create / mi_render_clear), else
+ * MI_ERR_INVALID; an unknown kind or an albedo the scene's BSDFs do not support: MI_ERR_UNSUPPORTED.  Without fields a render launches, allocates and records nothing extra. */
+int mi_render_set_fields(mi_render *r, const mi_field *fields, uint32_t n);
+/* Field film read-back.  layout 0: raw sums (H+2b) x (W+2b) x (3F+1), the three values of every field in list order, then the film's own weight; layout 2: developed
+ * H x W x 3F = sum / weight.  Without fields: MI_ERR_INVALID.  mi_render_clear zeroes the field film, mi_render_run_rows fills its rows, mi_render_merge_film adds it
+ * too when both handles hold the same field list (and fails with MI_ERR_INVALID when they do not). */
+int mi_render_field_film_size(mi_render *r, int layout, uint32_t *height, uint32_t *width, uint32_t *channels, uint32_t *border);
+int mi_render_read_fields(mi_render *r, int layout, float *host_out);
+/* Debug / parity: the fields of individual (px, py, sampleIndex) triples, batched as mi_render_samples: generate, one extend, the field stage (no shading); out[n * 3F] */
+int mi_render_field_samples(mi_render *r, const uint32_t *pairs, uint64_t n, float *out);
 int mi_render_set_profiling(mi_render *r, int enabled);   /* per-stage HIP-event timing: events are recorded between the stage launches of the first stream, nothing is serialised (off by default) */
 
 /* bool Scene::rayIntersect(const Ray &ray, Intersection &its) for a batch of rays (include/mitsuba/render/scene.h:187-243): rays8 = (o.xyz, mint, d.xyz, maxt) per

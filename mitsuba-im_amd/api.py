@@ -62,6 +62,27 @@ class MiStats(C.Structure):
                 ("extend_launches", C.c_uint64), ("extend_rays", C.c_uint64), ("extend_launches_all", C.c_uint64)]
 
 
+class MiField(C.Structure):
+    _fields_ = [("field", C.c_uint32), ("undefined", C.c_float * 3)]
+
+
+# field kinds in the order of the reference's EField (src/integrators/misc/field.cpp:57-67) = MI_FIELD_* of include/mi355pt.h
+FIELD_NAMES = ("position", "relPosition", "distance", "geoNormal", "shNormal", "uv", "albedo", "shapeIndex", "primIndex")
+SCALAR_FIELDS = ("distance", "shapeIndex", "primIndex")      # the three values of these are equal
+
+
+def normalize_fields(fields):
+    """[(name, (r, g, b))] from a list of names or (name, undefined) pairs, `undefined` a float or an RGB triple (default 0)."""
+    out = []
+    for f in fields or []:
+        name, undef = (f, 0.0) if isinstance(f, str) else (f[0], f[1])
+        if name not in FIELD_NAMES:
+            raise ValueError(f"unknown field \"{name}\": must be one of " + ", ".join(FIELD_NAMES))
+        u = np.broadcast_to(np.asarray(undef, np.float32), (3,)) if np.ndim(undef) == 0 else np.asarray(undef, np.float32).reshape(3)
+        out.append((name, tuple(float(x) for x in u)))
+    return out
+
+
 class MiFusedDebugInfo(C.Structure):
     _fields_ = [("wide", C.c_uint32), ("bvh_depth", C.c_uint32), ("bvh_stack_direct", C.c_uint32), ("max_stack_seen", C.c_uint32), ("rays_counted", C.c_uint64)]
 
@@ -69,7 +90,7 @@ class MiFusedDebugInfo(C.Structure):
 EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_scene_create", "mi_scene_destroy", "mi_scene_set_triangles",
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_film",
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
-           "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
+           "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
            "mi_render_set_profiling", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_sincosf", "mi_debug_libm"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics"]
 
@@ -120,6 +141,10 @@ class Lib:
         L.mi_render_read_film_device.argtypes = [vp, i32, vp]
         L.mi_render_samples.argtypes = [vp, vp, u64, vp]
         L.mi_render_stats.argtypes = [vp, C.POINTER(MiStats)]
+        L.mi_render_set_fields.argtypes = [vp, vp, u32]
+        L.mi_render_field_film_size.argtypes = [vp, i32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+        L.mi_render_read_fields.argtypes = [vp, i32, vp]
+        L.mi_render_field_samples.argtypes = [vp, vp, u64, vp]
         L.mi_render_set_profiling.argtypes = [vp, i32]
         L.mi_debug_intersect.argtypes = [vp, vp, u64, i32, vp]
         L.mi_debug_intersect_inst.argtypes = [vp, vp, u64, i32, vp, vp]
@@ -296,7 +321,7 @@ class Render:
     """mi_render handle: the integrator instance (MonteCarloIntegrator properties + sampler)."""
 
     def __init__(self, scene, max_depth=None, rr_depth=None, sampler=None, spp=None, seed=None, device=0, planes_per_batch=0,
-                 strict_normals=None, hide_emitters=None, opacity=False, integrator=None):
+                 strict_normals=None, hide_emitters=None, opacity=False, integrator=None, fields=None):
         sc = scene.sc; L = scene.L; self.L = L; self.scene = scene
         p = MiRenderParams(sc.max_depth if max_depth is None else max_depth, sc.rr_depth if rr_depth is None else rr_depth,
                            sc.strict_normals if strict_normals is None else int(strict_normals),
@@ -305,6 +330,32 @@ class Render:
                            sc.seed if seed is None else seed, device, planes_per_batch, int(opacity), int(sc.get("integrator", 0) or 0) if integrator is None else int(integrator))
         self.params = p
         h = C.c_void_p(); L.check(L.L.mi_render_create(scene.h, C.byref(p), C.byref(h))); self.h = h
+        self.field_names = []
+        if fields is None: fields = sc.get("fields")          # the scene description's own list (scene files with a `multichannel` integrator); [] = none
+        if fields: self.set_fields(fields)
+
+    def set_fields(self, fields):
+        """Field channels of the first camera hit (the reference's `multichannel` + `field` integrators): names out of FIELD_NAMES, or (name, undefined) with a float or an
+        RGB triple for camera rays that leave the scene.  Only while the film is clear; an empty list removes the fields."""
+        fl = normalize_fields(fields); arr = (MiField * max(1, len(fl)))()
+        for i, (name, undef) in enumerate(fl):
+            arr[i].field = FIELD_NAMES.index(name); arr[i].undefined[:] = undef
+        self.L.check(self.L.L.mi_render_set_fields(self.h, C.cast(arr, C.c_void_p), len(fl))); self.field_names = [n for n, _ in fl]
+
+    def field_film_shape(self, layout=2):
+        h, w, c, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self.L.check(self.L.L.mi_render_field_film_size(self.h, layout, C.byref(h), C.byref(w), C.byref(c), C.byref(b)))
+        return h.value, w.value, c.value, b.value
+
+    def read_fields(self, layout=2):
+        """layout 0: raw sums (H+2b) x (W+2b) x (3F+1), weight last; layout 2: developed H x W x 3F (field i in channels 3i .. 3i+2)."""
+        h, w, c, _ = self.field_film_shape(layout); out = np.zeros((h, w, c), np.float32)
+        self.L.check(self.L.L.mi_render_read_fields(self.h, layout, _p(out))); return out
+
+    def field_samples(self, pairs):
+        """The fields of individual (px, py, sampleIndex) triples -> [n, F, 3]."""
+        a = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 3); out = np.zeros((len(a), max(1, len(self.field_names)), 3), np.float32)
+        self.L.check(self.L.L.mi_render_field_samples(self.h, _p(a), len(a), _p(out))); return out
 
     def close(self):
         if getattr(self, "h", None):
@@ -342,6 +393,10 @@ class Render:
     def samples(self, pairs):
         a = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 3); out = np.zeros((len(a), 3), np.float32)
         self.L.check(self.L.L.mi_render_samples(self.h, _p(a), len(a), _p(out))); return out
+
+    def merge_film(self, other):
+        """self += other (raw film sums, field planes included, ray counters): both renders idle, same film, same field list."""
+        self.L.check(self.L.L.mi_render_merge_film(self.h, other.h))
 
     def stats(self):
         s = MiStats(); self.L.check(self.L.L.mi_render_stats(self.h, C.byref(s)))

@@ -12,6 +12,7 @@
 #include <set>
 #include "scene_host.h"
 #include "queues.h"
+#include "fields.h"
 
 extern "C" {
 void mi_launch_generate(const DScene &, const RenderConst &, const Queues &, const BatchDesc &, uint32_t, hipStream_t);
@@ -44,6 +45,9 @@ void mi_launch_debug_sobol(const DScene &, const uint32_t *, uint64_t, uint32_t,
 void mi_launch_debug_camera(const DScene &, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_sincosf(const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_libm(int, const float *, const float *, uint64_t, float *, hipStream_t);
+void mi_launch_field_film(const DScene &, const FieldArgs &, const Queues &, const BatchDesc &, float *, float *, hipStream_t);
+void mi_launch_field_samples(const DScene &, const FieldArgs &, const Queues &, uint64_t, float *, hipStream_t);
+void mi_launch_field_layout(const float *, const float *, float *, int, int, int, int, int, hipStream_t);
 }
 
 // Shading stage dispatch.  Dynamic LDS: Sobol nibble tables + (small scenes) the scene tables + (scenes with non-diffuse BSDFs) the per-wave path-order list.
@@ -89,6 +93,10 @@ struct mi_render {
     // overlap the latency-bound shading kernels of the others on the same CUs (MI355PT_STREAMS = 1..4 pools, default 2)
     enum { kMaxPools = 4 };
     Queues qx[kMaxPools - 1]{}; std::vector<void *> allocsx[kMaxPools - 1]; hipStream_t streamx[kMaxPools - 1] = {}; hipEvent_t filmDone[kMaxPools] = {}, joinEv[kMaxPools] = {}; int nStreams = 1;
+    // field channels (mi_render_set_fields; kernels_field.hip): nothing below exists while nFields = 0.  fieldFilm / fieldSpill: 3 F + 1 SoA planes each; fieldDone[pool]: the
+    // field kernel of the batch last traced on that pool has finished (chains consecutive batches across the streams, as filmDone chains k_film); lastFieldPool: pool of the previous batch of this run
+    uint32_t nFields = 0; mi_field fields[MI_MAX_FIELDS] = {}; FieldArgs fa{}; float *fieldFilm = nullptr, *fieldSpill = nullptr, *fieldTmp = nullptr; size_t fieldFloats = 0; int32_t *dTriShape = nullptr;
+    hipEvent_t fieldDone[kMaxPools] = {}; int lastFieldPool = -1; bool fieldChain = false;
     Queues &pool(int i) { return i ? qx[i - 1] : q; }
     hipStream_t poolStream(int i) { return i ? streamx[i - 1] : stream; }
 };
@@ -699,6 +707,14 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
     HIPCHK(hipMalloc((void **) &r->layoutTmp, r->filmFloats * 4));
     guard.r = nullptr; *out = r; return MI_OK;
 }
+static void releaseFields(mi_render *r) {
+    if (r->fieldFilm) (void) hipFree(r->fieldFilm);
+    if (r->fieldSpill) (void) hipFree(r->fieldSpill);
+    if (r->fieldTmp) (void) hipFree(r->fieldTmp);
+    if (r->dTriShape) (void) hipFree(r->dTriShape);
+    for (hipEvent_t &e : r->fieldDone) if (e) { (void) hipEventDestroy(e); e = nullptr; }
+    r->fieldFilm = r->fieldSpill = r->fieldTmp = nullptr; r->dTriShape = nullptr; r->fieldFloats = 0; r->nFields = 0; r->fa = FieldArgs{};
+}
 void mi_render_destroy(mi_render *r) {
     if (!r) return;
     (void) hipSetDevice(r->scene->h.device);
@@ -711,6 +727,7 @@ void mi_render_destroy(mi_render *r) {
     if (r->spill) (void) hipFree(r->spill);
     if (r->layoutTmp) (void) hipFree(r->layoutTmp);
     if (r->mergeTmp) (void) hipFree(r->mergeTmp);
+    releaseFields(r);
     if (r->dNib) (void) hipFree(r->dNib);
     if (r->pollHost) (void) hipHostFree(r->pollHost);
     if (r->pollEv) (void) hipEventDestroy(r->pollEv);
@@ -724,6 +741,7 @@ void mi_render_destroy(mi_render *r) {
 int mi_render_clear(mi_render *r) {
     if (!r) return fail(MI_ERR_INVALID, "mi_render_clear: null"); HIPCHK(hipSetDevice(r->scene->h.device));
     HIPCHK(hipMemsetAsync(r->film, 0, r->filmFloats * 4, r->stream)); HIPCHK(hipMemsetAsync(r->spill, 0, r->filmFloats * 4, r->stream));
+    if (r->nFields) { HIPCHK(hipMemsetAsync(r->fieldFilm, 0, r->fieldFloats * 4, r->stream)); HIPCHK(hipMemsetAsync(r->fieldSpill, 0, r->fieldFloats * 4, r->stream)); }
     if (r->q.counters) HIPCHK(hipMemsetAsync(r->q.counters, 0, 32, r->stream));
     for (Queues &Q : r->qx) if (Q.counters) HIPCHK(hipMemsetAsync(Q.counters, 0, 32, r->stream));
     HIPCHK(hipStreamSynchronize(r->stream)); r->samplesTotal = 0; r->mergedRays = r->mergedShadow = r->mergedPathLen = r->mergedSamples = 0; r->cancel.store(0); return MI_OK;
@@ -750,6 +768,13 @@ static int traceBatch(mi_render *r, const BatchDesc &bd, const uint32_t *list, s
         mark(r, 1, evUsed, st);
         if (fused && 2 * depth + 1 < MI_TICKETS) mi_launch_extend_fused(sc, Q, buf, Q.ticket + 2 * depth, st); else mi_launch_extend(sc, Q, buf, r->gridExtend, st);
         ++r->launchesAll;
+        if (depth == 1 && r->nFields && !bd.list) {      // field channels of the film samples: q.hit still holds the camera hits, slot = path id (kernels_field.hip)
+            mark(r, 0, evUsed, st);
+            // own-pixel sums are plain read-modify-writes: wait for the previous batch's field kernel on the other stream
+            if (r->fieldChain && r->lastFieldPool >= 0 && r->lastFieldPool != pool) HIPCHK(hipStreamWaitEvent(st, r->fieldDone[r->lastFieldPool], 0));
+            mi_launch_field_film(sc, r->fa, Q, bd, r->fieldFilm, r->fieldSpill, st);
+            if (r->fieldChain) { HIPCHK(hipEventRecord(r->fieldDone[pool], st)); r->lastFieldPool = pool; }
+        }
         if (r->rc.integrator != MI_INTEGRATOR_PATH) {      // the same loop over media: its own shade and shadow stages (kernels_vol.hip, kernels_volmis.hip)
             const size_t lds = r->rc.sampler == MI_SAMPLER_SOBOL ? (size_t) r->rc.nib_dims * r->rc.nib_count * 64 : 16; const bool mis = r->rc.integrator == MI_INTEGRATOR_VOLPATH;
             mark(r, 2, evUsed, st); (mis ? mi_launch_shade_volmis : mi_launch_shade_vol)(sc, r->rc, Q, buf, r->gridShade, lds, st);
@@ -810,7 +835,7 @@ int mi_render_run_rows(mi_render *r, mi_tile tile, uint32_t rowStride, uint32_t 
     const int nPools = (int) std::min<uint32_t>((uint32_t) r->nStreams, std::max(nBatches, 1u));      // more than one batch: round-robin over the pools / streams
     if (nPools > 1) HIPCHK(hipEventRecord(r->joinEv[0], r->stream));
     for (int i = 1; i < nPools; ++i) HIPCHK(hipStreamWaitEvent(r->poolStream(i), r->joinEv[0], 0));
-    int batch = 0, lastFilmPool = -1;
+    int batch = 0, lastFilmPool = -1; r->lastFieldPool = -1; r->fieldChain = nPools > 1;
     for (uint32_t s = s0; s < s1; s += planes, ++batch) {
         if (r->cancel.exchange(0)) { HIPCHK(hipDeviceSynchronize()); return fail(MI_CANCELLED, "render cancelled"); }      // consumed where it is observed
         const int pool = batch % nPools; hipStream_t st = r->poolStream(pool);
@@ -879,6 +904,7 @@ int mi_render_read_film(mi_render *r, int layout, float *host) {
 int mi_render_merge_film(mi_render *dst, mi_render *src) {
     if (!dst || !src || dst == src) return fail(MI_ERR_INVALID, "mi_render_merge_film: two different render handles are needed");
     if (dst->filmFloats != src->filmFloats) return fail(MI_ERR_INVALID, "mi_render_merge_film: the two renders have different films");
+    if (dst->nFields != src->nFields || memcmp(dst->fields, src->fields, sizeof(mi_field) * dst->nFields)) return fail(MI_ERR_INVALID, "mi_render_merge_film: the two renders hold different field lists (mi_render_set_fields)");
     const int dd = dst->scene->h.device, sd = src->scene->h.device; const size_t n = dst->filmFloats;
     HIPCHK(hipSetDevice(dd));
     const float *sFilm = src->film, *sSpill = src->spill;
@@ -902,6 +928,20 @@ int mi_render_merge_film(mi_render *dst, mi_render *src) {
     }
     mi_launch_film_add(dst->film, sFilm, n, dst->stream); mi_launch_film_add(dst->spill, sSpill, n, dst->stream);
     HIPCHK(hipStreamSynchronize(dst->stream)); HIPCHK(hipGetLastError());
+    if (dst->nFields) {      // the field planes, the same way (another device: staged through the host; field films are a debugging / compositing aid, not the multi-device hot path)
+        const size_t nf = dst->fieldFloats; const float *fFilm = src->fieldFilm, *fSpill = src->fieldSpill; float *stage = nullptr;
+        if (dd != sd) {
+            std::vector<float> host(2 * nf);
+            HIPCHK(hipSetDevice(sd)); HIPCHK(hipMemcpy(host.data(), src->fieldFilm, nf * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(host.data() + nf, src->fieldSpill, nf * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipSetDevice(dd)); HIPCHK(hipMalloc((void **) &stage, 2 * nf * 4));
+            if (hipMemcpy(stage, host.data(), 2 * nf * 4, hipMemcpyHostToDevice) != hipSuccess) { (void) hipFree(stage); return fail(MI_ERR_DEVICE, "mi_render_merge_film: cannot stage the field film"); }
+            fFilm = stage; fSpill = stage + nf;
+        }
+        mi_launch_film_add(dst->fieldFilm, fFilm, nf, dst->stream); mi_launch_film_add(dst->fieldSpill, fSpill, nf, dst->stream);
+        hipError_t e = hipStreamSynchronize(dst->stream); if (e == hipSuccess) e = hipGetLastError();
+        if (stage) (void) hipFree(stage);
+        if (e != hipSuccess) return fail(MI_ERR_DEVICE, std::string("mi_render_merge_film: ") + hipGetErrorString(e));
+    }
     unsigned long long c[4]; mi_stats st{};      // the merged handle reports the sum of the ray counters too
     (void) c; if (mi_render_stats(src, &st) == MI_OK) { dst->mergedRays += st.rays; dst->mergedShadow += st.shadow_rays; dst->mergedPathLen += st.path_length_sum; dst->mergedSamples += st.samples; }
     return MI_OK;
@@ -927,6 +967,107 @@ int mi_render_samples(mi_render *r, const uint32_t *pairs, uint64_t n, float *ou
     if (!rc) { hipError_t e = hipMemcpy(outLi, dOut, n * 12, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = fail(MI_ERR_DEVICE, hipGetErrorString(e)); }
     (void) hipFree(dList); (void) hipFree(dOut); (void) hipFree(dSlots);
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------ field channels (kernels_field.hip)
+int mi_render_set_fields(mi_render *r, const mi_field *fields, uint32_t n) {
+    if (!r || (n && !fields)) return fail(MI_ERR_INVALID, "mi_render_set_fields: null argument");
+    if (n > MI_MAX_FIELDS) return fail(MI_ERR_INVALID, "mi_render_set_fields: at most 8 fields");
+    if (r->samplesTotal || r->mergedSamples) return fail(MI_ERR_INVALID, "mi_render_set_fields: the film holds samples (set the fields after mi_render_create or mi_render_clear)");
+    const mi::SceneHost &h = r->scene->h; HIPCHK(hipSetDevice(h.device));
+    uint32_t needs = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (fields[i].field > MI_FIELD_PRIM_INDEX) return fail(MI_ERR_UNSUPPORTED, "mi_render_set_fields: unknown field kind " + std::to_string(fields[i].field) + " (position, relPosition, distance, geoNormal, shNormal, uv, albedo, shapeIndex, primIndex = 0..8)");
+        needs |= 1u << fields[i].field;
+    }
+    if (needs & (1u << MI_FIELD_ALBEDO)) {
+        for (const mi_material &m : h.materials) {
+            const char *name = m.type == MI_BSDF_PLASTIC ? "plastic" : m.type == MI_BSDF_ROUGHPLASTIC ? "roughplastic" : m.type == MI_BSDF_COATING ? "coating" : m.type == MI_BSDF_ROUGHCOATING ? "roughcoating" : nullptr;
+            if (name) return fail(MI_ERR_UNSUPPORTED, std::string("mi_render_set_fields: the albedo field is not implemented for the BSDF `") + name + "` (its external transmittance is not part of the material record)");
+            if (m.type == MI_BSDF_MASK && m.distr < h.materials.size() && (h.materials[m.distr].type == MI_BSDF_BUMPMAP || h.materials[m.distr].type == MI_BSDF_NORMALMAP))
+                return fail(MI_ERR_UNSUPPORTED, "mi_render_set_fields: the albedo field is not implemented for a `mask` over a bumpmap / normalmap (the generic rule evaluates the nested BSDF in the perturbed frame)");
+        }
+    }
+    releaseFields(r);
+    if (!n) return MI_OK;
+    FieldArgs fa{}; fa.n = n; fa.needs = needs; fa.n_meshes = (uint32_t) h.shapes.size();
+    for (uint32_t i = 0; i < n; ++i) { fa.kind[i] = fields[i].field; memcpy(fa.undefined[i], fields[i].undefined, 12); }
+    {   // inverse of the sensor's (affine) world transform in double precision, rounded to float
+        double m[3][3], t[3]; for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) m[i][j] = h.c2w[i * 4 + j]; t[i] = h.c2w[i * 4 + 3]; }
+        const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+        if ((needs & (1u << MI_FIELD_REL_POSITION)) && !(std::fabs(det) > 0)) return fail(MI_ERR_INVALID, "mi_render_set_fields: relPosition needs an invertible camera transform");
+        double inv[3][3];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
+            const int a = (j + 1) % 3, b = (j + 2) % 3, c = (i + 1) % 3, d = (i + 2) % 3;
+            inv[i][j] = (m[a][c] * m[b][d] - m[a][d] * m[b][c]) / det;
+        }
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) fa.w2c[i * 4 + j] = (float) inv[i][j]; fa.w2c[i * 4 + 3] = (float) -(inv[i][0] * t[0] + inv[i][1] * t[1] + inv[i][2] * t[2]); }
+    }
+    struct Undo { mi_render *r; ~Undo() { if (r) releaseFields(r); } } undo{r};
+    if (needs & (1u << MI_FIELD_SHAPE_INDEX)) {
+        std::vector<int32_t> ts(std::max<size_t>(h.idx.size() / 3, 1), -1);
+        for (size_t si = 0; si < h.shapes.size(); ++si) for (uint32_t k = 0; k < h.shapes[si].tri_count; ++k) ts[h.shapes[si].first_tri + k] = h.shapes[si].group ? -1 : (int32_t) si;
+        HIPCHK(hipMalloc((void **) &r->dTriShape, ts.size() * 4)); HIPCHK(hipMemcpy(r->dTriShape, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
+        fa.tri_shape = r->dTriShape;
+    }
+    const size_t W = h.width + 2 * (size_t) h.border, H = h.height + 2 * (size_t) h.border; const size_t floats = W * H * (3 * (size_t) n + 1);
+    HIPCHK(hipMalloc((void **) &r->fieldFilm, floats * 4)); HIPCHK(hipMalloc((void **) &r->fieldSpill, floats * 4)); HIPCHK(hipMalloc((void **) &r->fieldTmp, floats * 4));
+    HIPCHK(hipMemset(r->fieldFilm, 0, floats * 4)); HIPCHK(hipMemset(r->fieldSpill, 0, floats * 4));
+    for (int i = 0; i < r->nStreams; ++i) HIPCHK(hipEventCreateWithFlags(&r->fieldDone[i], hipEventDisableTiming));
+    r->fieldFloats = floats; r->fa = fa; r->nFields = n; memset(r->fields, 0, sizeof(r->fields)); memcpy(r->fields, fields, sizeof(mi_field) * n);
+    undo.r = nullptr;
+    return MI_OK;
+}
+int mi_render_field_film_size(mi_render *r, int layout, uint32_t *height, uint32_t *width, uint32_t *channels, uint32_t *border) {
+    if (!r || (layout != 0 && layout != 2)) return fail(MI_ERR_INVALID, "mi_render_field_film_size: bad argument (layouts 0 and 2)");
+    if (!r->nFields) return fail(MI_ERR_INVALID, "mi_render_field_film_size: the render has no fields (mi_render_set_fields)");
+    const mi::SceneHost &h = r->scene->h; const uint32_t b = (uint32_t) h.border;
+    if (height) *height = layout == 2 ? h.height : h.height + 2 * b;
+    if (width) *width = layout == 2 ? h.width : h.width + 2 * b;
+    if (channels) *channels = layout == 0 ? 3 * r->nFields + 1 : 3 * r->nFields;
+    if (border) *border = layout == 2 ? 0 : b;
+    return MI_OK;
+}
+int mi_render_read_fields(mi_render *r, int layout, float *host) {
+    if (!r || !host || (layout != 0 && layout != 2)) return fail(MI_ERR_INVALID, "mi_render_read_fields: bad argument (layouts 0 and 2)");
+    if (!r->nFields) return fail(MI_ERR_INVALID, "mi_render_read_fields: the render has no fields (mi_render_set_fields)");
+    const mi::SceneHost &h = r->scene->h; HIPCHK(hipSetDevice(h.device));
+    uint32_t hh, ww, cc, bb; mi_render_field_film_size(r, layout, &hh, &ww, &cc, &bb);
+    mi_launch_field_layout(r->fieldFilm, r->fieldSpill, r->fieldTmp, (int) h.width + 2 * h.border, (int) h.height + 2 * h.border, h.border, (int) (3 * r->nFields + 1), layout, r->stream);
+    HIPCHK(hipStreamSynchronize(r->stream)); HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(host, r->fieldTmp, (size_t) hh * ww * cc * 4, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+int mi_render_field_samples(mi_render *r, const uint32_t *pairs, uint64_t n, float *out) {
+    if (!r || !pairs || !out || !n) return fail(MI_ERR_INVALID, "mi_render_field_samples: null argument");
+    if (!r->nFields) return fail(MI_ERR_INVALID, "mi_render_field_samples: the render has no fields (mi_render_set_fields)");
+    const mi::SceneHost &h = r->scene->h; HIPCHK(hipSetDevice(h.device));
+    for (uint64_t i = 0; i < n; ++i) if (pairs[i * 3] >= h.width || pairs[i * 3 + 1] >= h.height) return fail(MI_ERR_INVALID, "mi_render_field_samples: pixel outside the film");
+    if (n > r->poolPaths) { int rc = allocPool(r, n); if (rc) return rc; }
+    if (!r->q.counters) return fail(MI_ERR_DEVICE, "mi_render_field_samples: no path pool");
+    const size_t outBytes = (size_t) n * 3 * r->nFields * 4;
+    uint32_t *dList = nullptr; float *dOut = nullptr;
+    HIPCHK(hipMalloc((void **) &dList, n * 12));
+    if (hipMalloc((void **) &dOut, outBytes) != hipSuccess) { (void) hipFree(dList); return fail(MI_ERR_DEVICE, "mi_render_field_samples: out of device memory"); }
+    BatchDesc bd{}; bd.tile = mi_tile{0, 0, h.width, h.height}; bd.n_pix = (uint32_t) n; bd.n_planes = 1; bd.sample_begin = 0; bd.n_paths = n; bd.list = dList; bd.row_stride = 1;
+    const DScene &sc = r->sc; Queues &Q = r->q; hipStream_t st = r->stream; unsigned long long keep[4];
+    hipError_t e = hipMemcpy(dList, pairs, n * 12, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(keep, Q.counters, 32, hipMemcpyDeviceToHost);      // like mi_render_samples, the parity entry point leaves the ray counters untouched
+    if (e == hipSuccess) {
+        const bool fused = r->rc.integrator == MI_INTEGRATOR_PATH && mi_fused_walk(sc);
+        if (fused) e = hipMemsetAsync(Q.ticket, 0, MI_TICKETS * sizeof(uint32_t), st);
+        if (e == hipSuccess) {
+            mi_launch_generate(sc, r->rc, Q, bd, r->grid, st);
+            if (fused) mi_launch_extend_fused(sc, Q, 0, Q.ticket + 2, st); else mi_launch_extend(sc, Q, 0, r->gridExtend, st);
+            mi_launch_field_samples(sc, r->fa, Q, n, dOut, st);
+            e = hipStreamSynchronize(st); if (e == hipSuccess) e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpy(Q.counters, keep, 32, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost);
+    (void) hipFree(dList); (void) hipFree(dOut);
+    if (e != hipSuccess) return fail(MI_ERR_DEVICE, std::string("mi_render_field_samples: ") + hipGetErrorString(e));
+    return MI_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ unit-level device entry points

@@ -341,6 +341,7 @@ def finish_scene(verts, tris, shapes, bsdfs, emitters, cam_to_world, xfov, near,
     sc.strict_normals = int(strict_normals); sc.hide_emitters = int(hide_emitters)
     sc.sampler = sampler; sc.spp = int(spp); sc.seed = int(seed)
     sc.envmap = envmap          # None or dict(rgb[h,w,3] f32, to_world[4,4], scale)
+    sc.fields = []              # field channels next to the radiance (the reference's multichannel + field integrators): names out of api.FIELD_NAMES or (name, undefined) pairs
     textures = list(textures or [])
     sc.env_texture = 0                              # index + 1 of the texture record holding the environment map's MIP pyramid (camera-ray lookups, envmap.cpp:398-411)
     if envmap is not None and envmap.get("filtered", True):

@@ -943,6 +943,29 @@ class _SceneBuilder:
         if integ is None:
             raise SceneError("the scene has no <integrator> (the reference would insert a direct-illumination integrator, which is not this path)")
         integrators = {"path": S.INTEGRATOR_PATH, "volpath_simple": S.INTEGRATOR_VOLPATH_SIMPLE, "volpath": S.INTEGRATOR_VOLPATH}
+        fields = []; n_nested = 1
+        if integ.type == "field":
+            raise SceneError("a <integrator type=\"field\"> at the root is not supported: nest it in <integrator type=\"multichannel\"> next to a path, volpath_simple or volpath integrator")
+        if integ.type == "multichannel":
+            # src/integrators/misc/multichannel.cpp: every nested integrator sees the same sensor ray and intersection; here: exactly one radiance integrator plus any
+            # number of `field` integrators (src/integrators/misc/field.cpp), in document order = the order of the film's pixelFormat / channelNames lists
+            nested = [c for _, c in integ.children_of("integrator")]; radiance = [c for c in nested if c.type != "field"]
+            for c in radiance:
+                if c.type not in integrators:
+                    raise SceneError(f"integrator \"{c.type}\" is not supported: this framework implements path, volpath_simple and volpath")
+            if len(radiance) != 1:
+                raise SceneError(f"<integrator type=\"multichannel\"> must hold exactly one radiance integrator (path, volpath_simple or volpath) next to its field integrators, found {len(radiance)}")
+            if nested[0] is not radiance[0]:
+                raise SceneError("<integrator type=\"multichannel\">: the radiance integrator must come first (the film's first channel group is the radiance)")
+            from .api import FIELD_NAMES
+            for c in nested[1:]:
+                fname = c.get("field")
+                if fname not in FIELD_NAMES:
+                    raise SceneError(f"<integrator type=\"field\">: invalid 'field' parameter \"{fname}\": must be one of " + ", ".join(FIELD_NAMES))
+                undef = c.get("undefined", 0.0)
+                undef = (float(undef),) * 3 if np.ndim(undef) == 0 else tuple(float(x) for x in np.asarray(undef, f32).reshape(3))
+                c.check_all_used(); fields.append((fname, undef))
+            integ.check_all_used(); n_nested = len(nested); integ = radiance[0]
         if integ.type not in integrators:
             raise SceneError(f"integrator \"{integ.type}\" is not supported: this framework implements path, volpath_simple and volpath")
         max_depth, rr_depth = int(integ.get("maxDepth", -1)), int(integ.get("rrDepth", 5))
@@ -969,6 +992,8 @@ class _SceneBuilder:
                     raise SceneError("Invalid crop window specification!")
             for k in ("banner", "attachLog", "fileFormat", "pixelFormat", "channelNames", "componentFormat", "highQualityEdges", "gamma", "exposure", "tonemapMethod", "key", "burn"):
                 film.get(k)
+            if fields:
+                pixel_formats, channel_names = _film_channel_lists(film, n_nested)
             rf = film.child("rfilter")
             if rf is not None:
                 kinds = {"box": S.FILTER_BOX, "gaussian": S.FILTER_GAUSSIAN, "tent": S.FILTER_TENT, "mitchell": S.FILTER_MITCHELL, "catmullrom": S.FILTER_CATMULLROM, "lanczos": S.FILTER_LANCZOS}
@@ -1087,7 +1112,29 @@ class _SceneBuilder:
             sc.filter_radius = float(f_radius)
         if f_stddev is not None:
             sc.filter_stddev = float(f_stddev)
+        sc.fields = fields                              # [(kind, undefined rgb)] of a `multichannel` integrator; kept with the film's lists for render.py and export_scene
+        if fields:
+            sc.pixel_formats = pixel_formats if film is not None else ["rgb"] * n_nested
+            sc.channel_names = channel_names if film is not None else []
         return sc
+
+
+def _film_channel_lists(film, n_nested):
+    """The film's pixelFormat / channelNames lists as HDRFilm reads them (src/films/hdrfilm.cpp:215-263): tokens separated by blanks or commas, one entry per nested
+    integrator of a multichannel render, `rgb` or `luminance` here."""
+    if not film.has("pixelFormat") and not film.has("channelNames"):
+        return ["rgb"] * n_nested, []                   # nothing said: every nested integrator as rgb, default names (render.py)
+    pf = [t.lower() for t in _tokens(str(film.props.get("pixelFormat", "rgb")))]; cn = _tokens(str(film.props.get("channelNames", "")))
+    if not pf:
+        raise SceneError("At least one pixel format must be specified!")
+    if (len(pf) != 1 and len(cn) != len(pf)) or (len(pf) == 1 and len(cn) > 1):
+        raise SceneError("Number of channel names must match the number of specified pixel formats!")
+    if len(pf) != n_nested:
+        raise SceneError(f"the film's pixelFormat lists {len(pf)} entr{'y' if len(pf) == 1 else 'ies'}, the multichannel integrator holds {n_nested} nested integrators: one entry per nested integrator is needed")
+    for f in pf:
+        if f not in ("rgb", "luminance"):
+            raise SceneError(f"pixelFormat \"{f}\" is not supported with field channels (rgb, luminance)")
+    return pf, cn
 
 
 def load_scene(path, params=None, sampler=None):
@@ -1119,8 +1166,17 @@ def export_scene(sc, directory, name=None, mesh_format="serialized"):
     mat = lambda n, m: f'<transform name="{n}"><matrix value="{fmt(m)}"/></transform>'
     out = ['<?xml version="1.0" encoding="utf-8"?>', '<scene version="0.5.0">']
     integ_name = {S.INTEGRATOR_PATH: "path", S.INTEGRATOR_VOLPATH_SIMPLE: "volpath_simple", S.INTEGRATOR_VOLPATH: "volpath"}[sc.get("integrator", 0) or 0]
-    out.append(f'\t<integrator type="{integ_name}"><integer name="maxDepth" value="{sc.max_depth}"/><integer name="rrDepth" value="{sc.rr_depth}"/>'
-               f'<boolean name="strictNormals" value="{str(bool(sc.strict_normals)).lower()}"/><boolean name="hideEmitters" value="{str(bool(sc.hide_emitters)).lower()}"/></integrator>')
+    radiance_xml = (f'<integrator type="{integ_name}"><integer name="maxDepth" value="{sc.max_depth}"/><integer name="rrDepth" value="{sc.rr_depth}"/>'
+                    f'<boolean name="strictNormals" value="{str(bool(sc.strict_normals)).lower()}"/><boolean name="hideEmitters" value="{str(bool(sc.hide_emitters)).lower()}"/></integrator>')
+    fields = sc.get("fields") or []; film_lists = ""
+    if fields:                                            # multichannel: the radiance integrator first, then one field integrator per entry; the film's lists as they were read
+        from .api import normalize_fields
+        fields = normalize_fields(fields)
+        radiance_xml = '<integrator type="multichannel">' + radiance_xml + "".join(
+            f'<integrator type="field"><string name="field" value="{n}"/>{rgb("undefined", u)}</integrator>' for n, u in fields) + '</integrator>'
+        pf = sc.get("pixel_formats") or ["rgb"] * (1 + len(fields)); cn = sc.get("channel_names") or ["color"] + [n for n, _ in fields]
+        film_lists = f'<string name="pixelFormat" value="{", ".join(pf)}"/><string name="channelNames" value="{", ".join(cn)}"/>'
+    out.append("\t" + radiance_xml)
     media = sc.get("media") or []
     for mi_, m in enumerate(media):                       # the derived sampling parameters are written explicitly, so a reader reproduces them whatever its defaults
         strat = {S.MEDIUM_BALANCE: "balance", S.MEDIUM_SINGLE: "single", S.MEDIUM_MANUAL: "manual"}[m["strategy"]]
@@ -1143,7 +1199,7 @@ def export_scene(sc, directory, name=None, mesh_format="serialized"):
                f'\t\t<sampler type="{smp}"><integer name="sampleCount" value="{sc.spp}"/>{seed}</sampler>\n'
                f'\t\t<film type="hdrfilm">' + (f'<integer name="width" value="{sc.crop[0]}"/><integer name="height" value="{sc.crop[1]}"/><integer name="cropOffsetX" value="{sc.crop[2]}"/>'
                                                 f'<integer name="cropOffsetY" value="{sc.crop[3]}"/><integer name="cropWidth" value="{sc.width}"/><integer name="cropHeight" value="{sc.height}"/>' if sc.get("crop")
-                                                else f'<integer name="width" value="{sc.width}"/><integer name="height" value="{sc.height}"/>') + '<boolean name="banner" value="false"/>'
+                                                else f'<integer name="width" value="{sc.width}"/><integer name="height" value="{sc.height}"/>') + '<boolean name="banner" value="false"/>' + film_lists +
                f'<rfilter type="{filt}">{fprops}</rfilter></film>' + (f'<ref id="medium{sc.sensor_medium}"/>' if media and sc.get("sensor_medium", -1) >= 0 else "") + '\n\t</sensor>')
     distr = {S.DISTR_BECKMANN: "beckmann", S.DISTR_GGX: "ggx", S.DISTR_PHONG: "phong"}
 
