@@ -207,6 +207,23 @@ int mi_scene_commit(mi_scene *s, uint32_t device);   /* BVH build + TriAccel tab
  * ships the scene to every worker (src/librender/renderjob.cpp, sched_remote.cpp).  The host-side build is reused, only the upload is repeated. */
 int mi_scene_clone(mi_scene *s, uint32_t device, mi_scene **out);
 
+/* -- in-place edits of a COMMITTED scene: what the interactive shell does between two short renders (src/im-mts/shell.cpp:236-242 restarts a frame without
+ *    preprocess).  The scene stays committed; the tree, the triangle records, textures, Sobol tables, the environment image and its CDFs are neither rebuilt nor
+ *    sent again.  After an update every result equals that of a fresh mi_scene_create ... mi_scene_commit with the new parameters.
+ *    Values only: the record count, a record's type, a material's texture binding (flags bits 8..23), its anisotropic / nonlinear / sampleVisible bits, `distr` of a
+ *    wrapper (mask, mixturebsdf, bumpmap, normalmap, coating, roughcoating, blendbsdf), the child indices of a mixturebsdf / blendbsdf, the rough-transmittance slice
+ *    (k[1], k[2]) and an emitter's `shape` select kernel variants, table sizes or the per-triangle layout: a change of one of them is MI_ERR_UNSUPPORTED, the message
+ *    names the first offending record, the scene is left as it was.  `twosided` may change.  The value checks of mi_scene_set_materials / _emitters apply.
+ *    Call them between runs: while a render runs on the scene an update returns MI_ERR_INVALID (cancel the run and wait for it first).  A render handle follows the
+ *    scene: its next run traces the edited scene -- after mi_render_clear; a run that would add to a film holding samples of the earlier scene returns MI_ERR_INVALID.
+ *    A replica (mi_scene_clone) is a scene of its own and is updated by its owner. */
+int mi_scene_update_camera(mi_scene *s, const float *sample_to_camera16, const float *to_world16, float near_clip, float far_clip);
+int mi_scene_update_materials(mi_scene *s, const mi_material *materials, uint32_t n);
+int mi_scene_update_emitters(mi_scene *s, const mi_emitter *emitters, uint32_t n);
+int mi_scene_update_envmap_transform(mi_scene *s, const float *to_world16, float scale);   /* envmap scenes only */
+/* revision: in-place edits applied so far; tree_builds: host-side builds (tree, triangle records) this scene has gone through -- an update never moves it.  Either may be NULL */
+int mi_scene_revision(mi_scene *s, uint64_t *revision, uint64_t *tree_builds);
+
 /* -- render: replaces SamplingIntegrator::renderBlock / ImageOrderIntegrator::render over MIPathTracer::Li
  *    (src/librender/integrator.cpp:141-189, :336-402, :469-486; src/integrators/path/path.cpp:119-294) -- */
 int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out);

@@ -21,6 +21,12 @@ int mi_host_preprocess(void *integrator, mi_scene *scene);
 /* Controls = {continu, abort, interrupt}: returns 0 done, -1 *abort set, -2 *continu cleared, otherwise progress()'s non-zero value;
  * targetRGBA: (H+2b)x(W+2b)x4 un-normalised sums; all work on threadIdx 0 */
 int mi_host_render(void *integrator, float *targetRGBA, const int *continu, const int *abort_flag, int (*progress)(double spp, void *user), void *user, int threadIdx, int threadCount);
+/* in-place edits (mi_scene_update_* of mi355pt.h) of the scene given to mi_host_preprocess and of every replica, between two mi_host_render calls; 0 = applied,
+ * otherwise refused (message in mi_host_last_error) and nothing changed */
+int mi_host_set_camera(void *integrator, const float *sample_to_camera16, const float *to_world16, float near_clip, float far_clip);
+int mi_host_set_materials(void *integrator, const mi_material *materials, uint32_t n);
+int mi_host_set_emitters(void *integrator, const mi_emitter *emitters, uint32_t n);
+int mi_host_set_envmap_transform(void *integrator, const float *to_world16, float scale);
 void mi_host_cancel(void *integrator);
 const char *mi_host_statistics(void *integrator);
 #ifdef __cplusplus

@@ -89,10 +89,11 @@ class MiFusedDebugInfo(C.Structure):
 
 EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_scene_create", "mi_scene_destroy", "mi_scene_set_triangles",
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_film",
-           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
+           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
            "mi_render_set_profiling", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_sincosf", "mi_debug_libm"]
-HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics"]
+HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
+                "mi_host_set_camera", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform"]
 
 
 def build(force=False):
@@ -129,6 +130,11 @@ class Lib:
         L.mi_scene_commit.argtypes = [vp, u32]
         L.mi_scene_clone.argtypes = [vp, u32, C.POINTER(vp)]
         L.mi_scene_ray_intersect.argtypes = [vp, vp, u64, vp]
+        L.mi_scene_update_camera.argtypes = [vp, vp, vp, f32, f32]
+        L.mi_scene_update_materials.argtypes = [vp, vp, u32]
+        L.mi_scene_update_emitters.argtypes = [vp, vp, u32]
+        L.mi_scene_update_envmap_transform.argtypes = [vp, vp, f32]
+        L.mi_scene_revision.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
         L.mi_render_merge_film.argtypes = [vp, vp]
         L.mi_render_create.argtypes = [vp, C.POINTER(MiRenderParams), C.POINTER(vp)]
         L.mi_render_destroy.argtypes = [vp]; L.mi_render_destroy.restype = None
@@ -202,6 +208,26 @@ def device_libm(name, x, y=None):
     L.check(L.L.mi_debug_libm(LIBM_FUNCTIONS[name], _p(a), _p(b) if b is not None else None, len(a), _p(out))); return out
 
 
+def pack_materials(bsdfs):
+    """mi_material records from the dict records of a flattened scene (scenes.py)."""
+    mats = (MiMaterial * max(1, len(bsdfs)))()
+    for i, b in enumerate(bsdfs):
+        m = MiMaterial(b["type"], (b["twosided"] & 1) | ((b["sample_visible"] & 1) << 1) | ((b.get("nonlinear", 0) & 1) << 2) | ((b.get("aniso", 0) & 1) << 3) | ((b.get("texture", -1) + 1) << 8), b["distr"], b["alpha"])
+        m.reflectance[:] = b["reflectance"]; m.eta[:] = b["eta"]; m.k[:] = b["k"]; m.specular[:] = b["specular"]
+        mats[i] = m
+    return mats
+
+
+def pack_emitters(emitters):
+    """mi_emitter records from the dict records of a flattened scene."""
+    ems = (MiEmitter * max(1, len(emitters)))()
+    for i, e in enumerate(emitters):
+        em = MiEmitter(e["type"], e["shape"]); em.radiance[:] = e["radiance"]; em.weight = e["weight"]
+        em.cutoff, em.beam = e.get("cutoff", 20.0), e.get("beam", 15.0)
+        em.to_world[:] = np.asarray(e.get("to_world", np.eye(4)), np.float32).reshape(-1).tolist(); ems[i] = em
+    return ems
+
+
 class Scene:
     """mi_scene handle filled from a flattened scene (mitsuba-im_amd/scenes.py)."""
 
@@ -211,16 +237,7 @@ class Scene:
         shapes = (MiShape * len(sc.shapes))()
         for i, s in enumerate(sc.shapes):
             shapes[i] = MiShape(s["first_tri"], s["tri_count"], s["first_vert"], s["vert_count"], s["bsdf"], s["emitter"], (s["face_normals"] & 1) | ((s.get("has_uv", 0) & 1) << 1), s.get("group", 0))
-        mats = (MiMaterial * len(sc.bsdfs))()
-        for i, b in enumerate(sc.bsdfs):
-            m = MiMaterial(b["type"], (b["twosided"] & 1) | ((b["sample_visible"] & 1) << 1) | ((b.get("nonlinear", 0) & 1) << 2) | ((b.get("aniso", 0) & 1) << 3) | ((b.get("texture", -1) + 1) << 8), b["distr"], b["alpha"])
-            m.reflectance[:] = b["reflectance"]; m.eta[:] = b["eta"]; m.k[:] = b["k"]; m.specular[:] = b["specular"]
-            mats[i] = m
-        ems = (MiEmitter * max(1, len(sc.emitters)))()
-        for i, e in enumerate(sc.emitters):
-            em = MiEmitter(e["type"], e["shape"]); em.radiance[:] = e["radiance"]; em.weight = e["weight"]
-            em.cutoff, em.beam = e.get("cutoff", 20.0), e.get("beam", 15.0)
-            em.to_world[:] = np.asarray(e.get("to_world", np.eye(4)), np.float32).reshape(-1).tolist(); ems[i] = em
+        mats = pack_materials(sc.bsdfs); ems = pack_emitters(sc.emitters)
         L.check(L.L.mi_scene_set_triangles(h, _p(sc.pos), _p(sc.nrm), _p(sc.uv), _p(sc.idx), len(sc.pos), len(sc.idx), C.cast(shapes, C.c_void_p), len(sc.shapes)))
         recs = sc.get("analytic") or []
         if recs:
@@ -275,6 +292,34 @@ class Scene:
 
     def __del__(self):
         self.close()
+
+    # in-place edits of the committed scene (mi_scene_update_*): no tree build, no re-upload of the geometry.  Each keeps the description `sc` in step (a refused edit
+    # leaves both as they were), so a later Render(scene) and an oracle built from scene.sc see the edited scene.
+    def update_camera(self, sample_to_camera, cam_to_world, near, far):
+        s2c = np.ascontiguousarray(sample_to_camera, np.float32).reshape(4, 4); c2w = np.ascontiguousarray(cam_to_world, np.float32).reshape(4, 4)
+        self.L.check(self.L.L.mi_scene_update_camera(self.h, _p(s2c), _p(c2w), float(near), float(far)))
+        self.sc.sample_to_camera = s2c; self.sc.cam_to_world = c2w; self.sc.near = float(near); self.sc.far = float(far)
+
+    def update_materials(self, bsdfs):
+        """bsdfs: the full list of dict records, as in the scene description; values may change, structure may not (MiError code 3 names the first offending record)."""
+        bsdfs = list(bsdfs); mats = pack_materials(bsdfs)
+        self.L.check(self.L.L.mi_scene_update_materials(self.h, C.cast(mats, C.c_void_p), len(bsdfs)))
+        self.sc.bsdfs = bsdfs
+
+    def update_emitters(self, emitters):
+        emitters = list(emitters); ems = pack_emitters(emitters)
+        self.L.check(self.L.L.mi_scene_update_emitters(self.h, C.cast(ems, C.c_void_p), len(emitters)))
+        self.sc.emitters = emitters
+
+    def update_envmap(self, to_world, scale):
+        tw = np.ascontiguousarray(to_world, np.float32).reshape(4, 4)
+        self.L.check(self.L.L.mi_scene_update_envmap_transform(self.h, _p(tw), float(scale)))
+        self.sc.envmap = dict(self.sc.envmap, to_world=tw, scale=float(scale))
+
+    def revision(self):
+        """(revision, tree_builds): in-place edits applied so far / host-side tree builds (1 for the life of a committed scene)."""
+        rev, builds = C.c_uint64(), C.c_uint64()
+        self.L.check(self.L.L.mi_scene_revision(self.h, C.byref(rev), C.byref(builds))); return rev.value, builds.value
 
     def ray_intersect(self, rays8):
         """Scene::rayIntersect for a batch of rays -> structured array of mi_intersection records."""
@@ -434,6 +479,15 @@ class HostIntegrator:
             self.calls += 1; return 0
         cb = self._CB(progress)
         return self.L.mi_host_render(self.h, target.ctypes.data if target is not None else None, C.byref(self.cont), C.byref(self.abort), cb, None, 0, 1)
+
+    def set_camera(self, sample_to_camera, cam_to_world, near, far):
+        """MIPathTracerHIP::setCamera: the borrowed scene and every replica, between two render() calls.  (Use this OR Scene.update_camera on a scene, not both:
+        the description scene.sc is kept in step here too.)"""
+        s2c = np.ascontiguousarray(sample_to_camera, np.float32).reshape(4, 4); c2w = np.ascontiguousarray(cam_to_world, np.float32).reshape(4, 4)
+        self.L.mi_host_set_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float]
+        if self.L.mi_host_set_camera(self.h, _p(s2c), _p(c2w), float(near), float(far)) != 0:
+            raise RuntimeError(self.L.mi_host_last_error().decode())
+        sc = self.scene.sc; sc.sample_to_camera = s2c; sc.cam_to_world = c2w; sc.near = float(near); sc.far = float(far)
 
     def statistics(self):
         return (self.L.mi_host_statistics(self.h) or b"").decode()

@@ -622,9 +622,32 @@ static void flatten(const Scene *scene, FlatScene &fs) {
     }
 }
 
+/// What mi_scene_set_camera / mi_scene_update_camera take, as a function of the sensor alone
+struct CameraRecord {
+    float s2c[16], c2w[16], nearClip, farClip; Vector2i cropSize;
+    // rebuild m_sampleToCamera exactly as PerspectiveCameraImpl::configure does (perspective.cpp:150-157); it is a protected member
+    void of(const Sensor *sensor) {
+        if (!sensor->getClass()->derivesFrom(MTS_CLASS(PerspectiveCamera))) SLog(EError, "path_hip: only the perspective camera is implemented");
+        const PerspectiveCamera *cam = static_cast<const PerspectiveCamera *>(sensor);
+        const Film *film = sensor->getFilm();
+        const Vector2i &filmSize = film->getSize(), &crop = film->getCropSize(); const Point2i &cropOffset = film->getCropOffset();
+        // crop window (perspective.cpp:129-136, 150-152): the film of the path is the crop window, the camera maps it onto its part of the full frame
+        Vector2 relSize((Float) crop.x / (Float) filmSize.x, (Float) crop.y / (Float) filmSize.y);
+        Point2 relOffset((Float) cropOffset.x / (Float) filmSize.x, (Float) cropOffset.y / (Float) filmSize.y);
+        Float aspect = cam->getAspect();
+        Transform cameraToSample = Transform::scale(Vector(1.0f / relSize.x, 1.0f / relSize.y, 1.0f)) * Transform::translate(Vector(-relOffset.x, -relOffset.y, 0.0f))
+                                 * Transform::scale(Vector(-0.5f, -0.5f * aspect, 1.0f)) * Transform::translate(Vector(-1.0f, -1.0f / aspect, 0.0f))
+                                 * Transform::perspective(cam->getXFov(), cam->getNearClip(), cam->getFarClip());
+        Matrix4x4 m = cameraToSample.inverse().getMatrix(), w = cam->getWorldTransform(0.0f).getMatrix();
+        for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { s2c[i * 4 + j] = m(i, j); c2w[i * 4 + j] = w(i, j); }
+        nearClip = cam->getNearClip(); farClip = cam->getFarClip(); cropSize = crop;
+    }
+    bool sameValues(const CameraRecord &o) const { return !memcmp(s2c, o.s2c, 64) && !memcmp(c2w, o.c2w, 64) && !memcmp(&nearClip, &o.nearClip, 4) && !memcmp(&farClip, &o.farClip, 4); }
+};
+
 /// mi_scene built from a live scene; owns the handle
 struct GpuScene {
-    mi_scene *scene = nullptr; int border = 0; Vector2i size;
+    mi_scene *scene = nullptr; int border = 0; Vector2i size; CameraRecord camera;   // camera: the one last applied to `scene`
     ~GpuScene() { if (scene) mi_scene_destroy(scene); }
     void build(const Scene *s, const Sensor *sensor, uint32_t device) {
         FlatScene fs; flatten(s, fs);
@@ -642,21 +665,9 @@ struct GpuScene {
         MI_CHECK(mi_scene_set_emitters(scene, fs.emitters.data(), (uint32_t) fs.emitters.size()));
         if (fs.envW) MI_CHECK(mi_scene_set_envmap(scene, fs.envRGB.data(), fs.envW, fs.envH, fs.envToWorld, fs.envScale));
         if (fs.envTexture >= 0) MI_CHECK(mi_scene_set_envmap_filter(scene, fs.envTexture));
-        // camera: rebuild m_sampleToCamera exactly as PerspectiveCameraImpl::configure does (perspective.cpp:150-157); it is a protected member
-        if (!sensor->getClass()->derivesFrom(MTS_CLASS(PerspectiveCamera))) SLog(EError, "path_hip: only the perspective camera is implemented");
-        const PerspectiveCamera *cam = static_cast<const PerspectiveCamera *>(sensor);
-        const Film *film = sensor->getFilm();
-        const Vector2i &filmSize = film->getSize(), &cropSize = film->getCropSize(); const Point2i &cropOffset = film->getCropOffset();
-        // crop window (perspective.cpp:129-136, 150-152): the film of the path is the crop window, the camera maps it onto its part of the full frame
-        Vector2 relSize((Float) cropSize.x / (Float) filmSize.x, (Float) cropSize.y / (Float) filmSize.y);
-        Point2 relOffset((Float) cropOffset.x / (Float) filmSize.x, (Float) cropOffset.y / (Float) filmSize.y);
-        Float aspect = cam->getAspect();
-        Transform cameraToSample = Transform::scale(Vector(1.0f / relSize.x, 1.0f / relSize.y, 1.0f)) * Transform::translate(Vector(-relOffset.x, -relOffset.y, 0.0f))
-                                 * Transform::scale(Vector(-0.5f, -0.5f * aspect, 1.0f)) * Transform::translate(Vector(-1.0f, -1.0f / aspect, 0.0f))
-                                 * Transform::perspective(cam->getXFov(), cam->getNearClip(), cam->getFarClip());
-        Matrix4x4 s2c = cameraToSample.inverse().getMatrix(), c2w = cam->getWorldTransform(0.0f).getMatrix();
-        float a[16], w[16]; for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { a[i * 4 + j] = s2c(i, j); w[i * 4 + j] = c2w(i, j); }
-        MI_CHECK(mi_scene_set_camera(scene, a, w, cam->getNearClip(), cam->getFarClip()));
+        camera.of(sensor);
+        MI_CHECK(mi_scene_set_camera(scene, camera.s2c, camera.c2w, camera.nearClip, camera.farClip));
+        const Film *film = sensor->getFilm(); const Vector2i &cropSize = film->getCropSize();
         const ReconstructionFilter *rf = film->getReconstructionFilter(); std::string fname = rf->getClass()->getName();
         if (fname == "BoxFilter") MI_CHECK(mi_scene_set_film(scene, cropSize.x, cropSize.y, 0, rf->getRadius() - 1e-5f, 0.5f));
         else if (fname == "GaussianFilter") MI_CHECK(mi_scene_set_film(scene, cropSize.x, cropSize.y, 1, 0.5f, rf->getRadius() / 4.0f));
@@ -722,8 +733,15 @@ public:
         } bridge; bridge.self = this; bridge.scene = &scene; bridge.sensor = &sensor; bridge.sampler = &sampler; bridge.target = &target; bridge.controls = controls;
         m_rgba.resize((size_t) (m_gpu.size.x + 2 * m_gpu.border) * (m_gpu.size.y + 2 * m_gpu.border) * 4);
         mi355::Controls c{controls.continu, controls.abort, &bridge};
+        // the sensor of THIS call: the interactive shell moves it and restarts the frame without preprocess (src/im-mts/shell.cpp:236-242).  An unchanged sensor
+        // costs one comparison; a moved one is an in-place edit of the committed scene and of every replica (no flatten, no tree build, no upload)
+        CameraRecord cam; cam.of(&sensor);
+        if (cam.cropSize != m_gpu.size) Log(EError, "path_hip: the sensor's crop size %dx%d differs from the film committed at preprocess (%dx%d); call preprocess again", cam.cropSize.x, cam.cropSize.y, m_gpu.size.x, m_gpu.size.y);
         int rc;
-        try { rc = m_host->render(m_rgba.data(), c, threadIdx, threadCount); }
+        try {
+            if (!cam.sameValues(m_gpu.camera)) { m_host->setCamera(cam.s2c, cam.c2w, cam.nearClip, cam.farClip); m_gpu.camera = cam; }
+            rc = m_host->render(m_rgba.data(), c, threadIdx, threadCount);
+        }
         catch (const std::exception &e) { Log(EError, "%s", e.what()); return -1; }
         publish(m_rgba.data(), target);
         return rc;

@@ -48,6 +48,7 @@ void mi_launch_debug_libm(int, const float *, const float *, uint64_t, float *, 
 void mi_launch_field_film(const DScene &, const FieldArgs &, const Queues &, const BatchDesc &, float *, float *, hipStream_t);
 void mi_launch_field_samples(const DScene &, const FieldArgs &, const Queues &, uint64_t, float *, hipStream_t);
 void mi_launch_field_layout(const float *, const float *, float *, int, int, int, int, int, hipStream_t);
+void mi_launch_patch_material_flags(TriShade *, uint32_t, const uint32_t *, uint32_t, hipStream_t);
 }
 
 // Shading stage dispatch.  Dynamic LDS: Sobol nibble tables + (small scenes) the scene tables + (scenes with non-diffuse BSDFs) the per-wave path-order list.
@@ -74,7 +75,9 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 static std::vector<uint32_t> g_sobolM32; static std::vector<uint64_t> g_sobolVdc, g_sobolVdcInv; static uint32_t g_sobolDims = 0;
 
-struct mi_scene { mi::SceneHost h; };
+// busy: renders executing on this scene (> 0), or an in-place update being applied (-1).  Updates are called between runs; the count turns a caller's mistake into an
+// error instead of a table that changes under a running kernel.
+struct mi_scene { mi::SceneHost h; std::atomic<int> busy{0}; };
 
 struct mi_render {
     mi_scene *scene = nullptr; mi_render_params p{}; RenderConst rc{};
@@ -97,6 +100,7 @@ struct mi_render {
     // field kernel of the batch last traced on that pool has finished (chains consecutive batches across the streams, as filmDone chains k_film); lastFieldPool: pool of the previous batch of this run
     uint32_t nFields = 0; mi_field fields[MI_MAX_FIELDS] = {}; FieldArgs fa{}; float *fieldFilm = nullptr, *fieldSpill = nullptr, *fieldTmp = nullptr; size_t fieldFloats = 0; int32_t *dTriShape = nullptr;
     hipEvent_t fieldDone[kMaxPools] = {}; int lastFieldPool = -1; bool fieldChain = false;
+    uint64_t sceneRev = 0, filmRev = 0;   // scene revision `sc` was copied from / the samples in the film (and the field film) were traced at
     Queues &pool(int i) { return i ? qx[i - 1] : q; }
     hipStream_t poolStream(int i) { return i ? streamx[i - 1] : stream; }
 };
@@ -213,76 +217,12 @@ int mi_scene_set_media(mi_scene *s, const mi_medium *media, uint32_t n, const in
 }
 int mi_scene_set_materials(mi_scene *s, const mi_material *m, uint32_t n) {
     if (!s || !m || !n) return fail(MI_ERR_INVALID, "mi_scene_set_materials: null argument");
-    auto isWrapper = [](uint32_t t) { return t == MI_BSDF_MASK || t == MI_BSDF_MIXTURE || t == MI_BSDF_BUMPMAP || t == MI_BSDF_NORMALMAP || t == MI_BSDF_COATING || t == MI_BSDF_BLEND || t == MI_BSDF_ROUGHCOATING; };
-    auto hasDelta = [](uint32_t t) { return t == MI_BSDF_CONDUCTOR || t == MI_BSDF_DIELECTRIC || t == MI_BSDF_THINDIELECTRIC || t == MI_BSDF_PLASTIC; };
-    for (uint32_t i = 0; i < n; ++i) {
-        if (m[i].type > MI_BSDF_ROUGHCOATING) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: implemented BSDFs: diffuse, roughdiffuse, phong, ward, coating, roughcoating, blendbsdf, roughconductor, conductor, dielectric, plastic, roughdielectric, difftrans, roughplastic, thindielectric, mask, mixturebsdf, bumpmap, normalmap (those without transmission optionally twosided)");
-        if (m[i].type == MI_BSDF_MASK && (m[i].distr >= n || m[m[i].distr].type == MI_BSDF_MASK || (m[i].flags & MI_BSDF_FLAG_TWOSIDED))) return fail(MI_ERR_INVALID, "mi_scene_set_materials: a mask refers to its nested material record by index (not another mask) and cannot itself be twosided");
-        if (m[i].type == MI_BSDF_BLEND) {
-            int deltas = 0;
-            for (int c = 0; c < 2; ++c) {
-                const float idxf = m[i].eta[c];
-                if (!(idxf >= 0) || idxf >= (float) n || isWrapper(m[(uint32_t) idxf].type)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: the two BSDFs of a blendbsdf are plain BSDF records (indices in eta[0], eta[1])");
-                if (((m[(uint32_t) idxf].flags >> 8) & 0xFFFFu)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: textures on the BSDFs inside a blendbsdf are not implemented");
-                deltas += hasDelta(m[(uint32_t) idxf].type);
-            }
-            if (deltas > 1) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a blendbsdf of two BSDFs that both have a Dirac delta component is not implemented");
-        }
-        if (m[i].type == MI_BSDF_ROUGHCOATING) {
-            if (m[i].distr >= n || isWrapper(m[m[i].distr].type)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a roughcoating nests a plain BSDF record (index in `distr`)");
-            const mi_material &nm = m[m[i].distr];
-            if ((nm.flags & MI_BSDF_FLAG_TWOSIDED) || hasDelta(nm.type) || nm.type == MI_BSDF_ROUGHDIELECTRIC || nm.type == MI_BSDF_DIFFTRANS || nm.type == MI_BSDF_NULL)
-                return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: the BSDF under a roughcoating is a reflective one without a Dirac delta lobe, `twosided` goes on the coating");
-            if (!(m[i].eta[0] > 0) || m[i].eta[0] == 1.0f) return fail(MI_ERR_INVALID, "The interior and exterior indices of refraction must be positive and differ!");      // roughcoating.cpp:126-128
-            if (m[i].eta[2] != 0.0f && m[i].eta[2] != 1.0f && m[i].eta[2] != 2.0f) return fail(MI_ERR_INVALID, "Specified an invalid distribution, must be \"beckmann\", \"ggx\", or \"phong\"/\"as\"!");
-            if ((m[i].flags >> 8) & 0xFFFFu) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a textured sigmaA is not implemented");
-        }
-        if (m[i].type == MI_BSDF_COATING) {
-            // adapters nest in the order mask -> bumpmap / normalmap -> coating -> plain BSDF (a coating over a mixturebsdf, or as the child of one, is not implemented)
-            if (m[i].distr >= n || isWrapper(m[m[i].distr].type)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a coating nests a plain BSDF record (index in `distr`)");
-            const mi_material &nm = m[m[i].distr];
-            if ((nm.flags & MI_BSDF_FLAG_TWOSIDED) || nm.type == MI_BSDF_DIELECTRIC || nm.type == MI_BSDF_ROUGHDIELECTRIC || nm.type == MI_BSDF_DIFFTRANS || nm.type == MI_BSDF_THINDIELECTRIC || nm.type == MI_BSDF_NULL)
-                return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: the BSDF under a coating is a reflective one, `twosided` goes on the coating");
-            if (!(m[i].eta[0] > 0) || m[i].eta[0] == 1.0f) return fail(MI_ERR_INVALID, "The interior and exterior indices of refraction must be positive and differ!");      // coating.cpp:119-121
-            if ((m[i].flags >> 8) & 0xFFFFu) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a textured sigmaA is not implemented");
-        }
-        if (m[i].type == MI_BSDF_BUMPMAP || m[i].type == MI_BSDF_NORMALMAP) {
-            // adapters nest in the order mask -> bumpmap / normalmap -> mixturebsdf -> plain BSDF
-            if (m[i].distr >= n || m[m[i].distr].type == MI_BSDF_MASK || m[m[i].distr].type == MI_BSDF_BUMPMAP || m[m[i].distr].type == MI_BSDF_NORMALMAP) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a bumpmap / normalmap nests a plain BSDF or a mixturebsdf (record index in `distr`)");
-            if (m[i].flags & MI_BSDF_FLAG_TWOSIDED) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: put `twosided` on the BSDF nested in a bumpmap / normalmap, not on the adapter");
-            if (!((m[i].flags >> 8) & 0xFFFFu)) return fail(MI_ERR_INVALID, m[i].type == MI_BSDF_BUMPMAP ? "A displacement texture must be specified" : "A normal map texture must be specified");   // bumpmap.cpp:88-89
-        }
-        if (m[i].type == MI_BSDF_MIXTURE) {
-            if (m[i].distr < 2 || m[i].distr > 4) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a mixturebsdf holds 2..4 BSDFs");
-            float total = 0; int deltas = 0;
-            for (uint32_t c = 0; c < m[i].distr; ++c) {
-                const float idxf = c < 3 ? m[i].reflectance[c] : m[i].eta[0], w = c < 3 ? m[i].k[c] : m[i].specular[0];
-                if (!(idxf >= 0) || idxf >= (float) n || isWrapper(m[(uint32_t) idxf].type)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: the children of a mixturebsdf are plain BSDF records (indices in reflectance[0..2], eta[0])");
-                if (((m[(uint32_t) idxf].flags >> 8) & 0xFFFFu)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: textures on the children of a mixturebsdf are not implemented");
-                if (!(w >= 0)) return fail(MI_ERR_INVALID, "Invalid BSDF weight!");                                    // mixturebsdf.cpp:82-83
-                total += w; deltas += hasDelta(m[(uint32_t) idxf].type);
-            }
-            if (!(total > 0)) return fail(MI_ERR_INVALID, "The weights must sum to a value greater than zero!");       // mixturebsdf.cpp:126-127
-            if (deltas > 1) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a mixturebsdf with more than one child that has a Dirac delta component is not implemented");
-        }
-        if ((m[i].type == MI_BSDF_DIELECTRIC || m[i].type == MI_BSDF_ROUGHDIELECTRIC || m[i].type == MI_BSDF_DIFFTRANS || m[i].type == MI_BSDF_THINDIELECTRIC) && (m[i].flags & MI_BSDF_FLAG_TWOSIDED)) return fail(MI_ERR_INVALID, "Only BSDFs without a transmission component can be nested!");   // twosided.cpp:86-88
-        if ((m[i].type == MI_BSDF_DIELECTRIC || m[i].type == MI_BSDF_PLASTIC || m[i].type == MI_BSDF_ROUGHDIELECTRIC || m[i].type == MI_BSDF_ROUGHPLASTIC || m[i].type == MI_BSDF_THINDIELECTRIC) && !(m[i].eta[0] > 0)) return fail(MI_ERR_INVALID, "The interior and exterior indices of refraction must be positive!");
-        if (m[i].type == MI_BSDF_ROUGHPLASTIC && (m[i].distr > 2 || (m[i].flags & MI_BSDF_FLAG_ANISOTROPIC)))
-            return fail(MI_ERR_INVALID, "The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!");        // roughplastic.cpp:225-227
-        if ((m[i].type == MI_BSDF_ROUGHCONDUCTOR || m[i].type == MI_BSDF_ROUGHDIELECTRIC) && m[i].distr > 2) return fail(MI_ERR_INVALID, "Specified an invalid distribution, must be \"beckmann\", \"ggx\", or \"phong\"/\"as\"!");   // microfacet.h:113-115
-        if ((m[i].flags & MI_BSDF_FLAG_ANISOTROPIC) && m[i].type != MI_BSDF_ROUGHCONDUCTOR && m[i].type != MI_BSDF_ROUGHDIELECTRIC && m[i].type != MI_BSDF_WARD) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: anisotropic roughness is implemented for roughconductor and roughdielectric");
-    }
+    { std::string msg; const int rc = mi::validateMaterials(m, n, msg); if (rc) return fail(rc, msg); }
     s->h.materials.assign(m, m + n); s->h.committed = false; return MI_OK;
 }
 int mi_scene_set_emitters(mi_scene *s, const mi_emitter *e, uint32_t n) {
     if (!s || (n && !e)) return fail(MI_ERR_INVALID, "mi_scene_set_emitters: null argument");
-    uint32_t nEnv = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (e[i].type > MI_EMITTER_COLLIMATED || e[i].type == 6u) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_emitters: implemented emitters: area, envmap, constant, point, spot, directional, collimated");
-        nEnv += e[i].type == MI_EMITTER_ENVMAP || e[i].type == MI_EMITTER_CONSTANT;
-        if (e[i].type == MI_EMITTER_SPOT && !(e[i].cutoff >= e[i].beam && e[i].beam >= 0 && e[i].cutoff > 0)) return fail(MI_ERR_INVALID, "mi_scene_set_emitters: spot needs cutoffAngle >= beamWidth >= 0");   // spot.cpp:77
-    }
-    if (nEnv > 1) return fail(MI_ERR_INVALID, "The scene may only contain one environment emitter");      // scene.cpp:542-543
+    { std::string msg; const int rc = mi::validateEmitters(e, n, msg); if (rc) return fail(rc, msg); }
     s->h.emitters.assign(e, e + n); s->h.committed = false; return MI_OK;
 }
 int mi_scene_set_envmap(mi_scene *s, const float *rgb, uint32_t w, uint32_t h, const float *toWorld, float scale) {
@@ -316,36 +256,13 @@ template <typename T> static int up(void **dst, const std::vector<T> &v) {
     return 0;
 }
 void SceneHost::release() {
-    void **ps[] = {&dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
+    void **ps[] = {&dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
     for (void **p : ps) if (*p) { (void) hipFree(*p); *p = nullptr; }
 }
 int SceneHost::upload(int dev) {
     release(); device = dev;
     if (hipSetDevice(dev) != hipSuccess) return 1;
-    std::vector<MaterialD> mats(materials.size());
-    for (size_t i = 0; i < materials.size(); ++i) memcpy(&mats[i], &materials[i], sizeof(MaterialD));
-    for (MaterialD &m : mats) if (m.type == MI_BSDF_ROUGHCOATING) {      // RoughCoating::configure (roughcoating.cpp:205-209): the same weight, thickness in eta[1]
-        float avg = 0.0f; for (int c = 0; c < 3; ++c) avg += (float) exp((double) (m.reflectance[c] * (-2 * m.eta[1])));
-        avg = avg * (1.0f / 3); m.k[0] = 1.0f / (avg + 1.0f);
-    }
-    for (MaterialD &m : mats) if (m.type == MI_BSDF_COATING) {      // SmoothCoating::configure (coating.cpp:182-186): m_specularSamplingWeight from the layer's average absorption -> k[0]
-        float avg = 0.0f; for (int c = 0; c < 3; ++c) avg += (float) exp((double) (m.reflectance[c] * (-2 * m.alpha)));      // Spectrum::exp = math::fastexp per channel, then average()
-        avg = avg * (1.0f / 3); m.k[0] = 1.0f / (avg + 1.0f);
-    }
-    for (MaterialD &m : mats) {          // plastic / roughplastic: m_specularSamplingWeight = sAvg / (dAvg + sAvg) over Texture::getAverage() (plastic.cpp:204-207, roughplastic.cpp:244-246) -> eta[1]
-        if (m.type != MI_BSDF_PLASTIC && m.type != MI_BSDF_ROUGHPLASTIC) continue;
-        float d[3] = {m.reflectance[0], m.reflectance[1], m.reflectance[2]}; const uint32_t tex = (m.flags >> 8) & 0xFFFFu;
-        if (tex && tex <= textures.size()) {     // checkerboard.cpp:102-104, gridtexture.cpp:116-121; a bitmap's average is input (color0, from TMIPMap::getAverage)
-            const mi_texture &t = textures[tex - 1];
-            for (int c = 0; c < 3; ++c) {
-                if (t.type == MI_TEXTURE_CHECKERBOARD) d[c] = (t.color0[c] + t.color1[c]) * 0.5f;
-                else if (t.type == MI_TEXTURE_GRID) { const float iw = std::max(0.0f, 1 - 2 * t.line_width), ia = iw * iw, la = 1 - ia; d[c] = t.color1[c] * la + t.color0[c] * ia; }
-                else d[c] = t.color0[c];
-            }
-        }
-        const float dl = d[0] * 0.212671f + d[1] * 0.715160f + d[2] * 0.072169f, sl = m.specular[0] * 0.212671f + m.specular[1] * 0.715160f + m.specular[2] * 0.072169f;
-        m.eta[1] = sl / (dl + sl);
-    }
+    const std::vector<MaterialD> &mats = materialsD;      // buildMaterialTables() (scene_build.cpp), shared with mi_scene_update_materials
     std::vector<float> filt(filterValues, filterValues + MI_FILTER_RES + 1);
     // tree nodes and leaf records share ONE allocation (nodes first): the fused walk (trace_fused.h) addresses both through one base + a 32-bit byte offset
     std::vector<unsigned char> geo(nodes.size() * sizeof(BvhNode) + std::max<size_t>(tris.size(), 1) * sizeof(TriAccelD) + 16);
@@ -353,7 +270,7 @@ int SceneHost::upload(int dev) {
     if (!tris.empty()) std::memcpy(geo.data() + nodes.size() * sizeof(BvhNode), tris.data(), tris.size() * sizeof(TriAccelD));
     dTris = nullptr;
     int bad = up(&dNodes, geo) | up(&dShade, shade) | up(&dI2, i2) | up(&dNrm, nrm) | up(&dMaterials, mats) |
-              up(&dEmitters, emittersD) | up(&dAnalytic, analyticD) | up(&dInstances, instancesD) | up(&dMaterialTables, materialTables) | up(&dTriUV, triuv) | up(&dTextures, textures) | up(&dEmitterX, emitterX) | up(&dEmitterCdf, emitterCdf) | up(&dAreaCdf, areaCdf) | up(&dFilter, filt);
+              up(&dEmitters, emittersD) | up(&dAnalytic, analyticD) | up(&dInstances, instancesD) | up(&dMaterialTables, materialTables) | up(&dTriUV, triuv) | up(&dTextures, textures) | up(&dEmitterX, emitterX) | up(&dEmitterCdf, emitterCdf) | up(&dAreaCdf, areaCdf) | up(&dFilter, filt) | up(&dMaterialFlags, materialFlagTable);
     if (bad) return 1;
     d = DScene{};
     if (g_sobolDims && logRes <= 16) {
@@ -368,42 +285,33 @@ int SceneHost::upload(int dev) {
     d.nrm = (const float *) dNrm; d.materials = (const MaterialD *) dMaterials; d.emitters = (const EmitterD *) dEmitters;
     d.emitter_cdf = (const float *) dEmitterCdf; d.area_cdf = (const float *) dAreaCdf; d.filter_values = (const float *) dFilter;
     d.analytic = (const AnalyticD *) dAnalytic; d.n_analytic = (uint32_t) analyticD.size();
-    {   // EWA weight table (mipmap.h:297-302; math::fastexp on Linux/x86_64 = (float) exp((double) x)); PerspectiveCameraImpl::m_dx / m_dy (perspective.cpp:159-163)
+    {   // EWA weight table (mipmap.h:297-302; math::fastexp on Linux/x86_64 = (float) exp((double) x))
         std::vector<float> lut(64); for (int i = 0; i < 64; ++i) { float r2 = (float) i / 63.0f; lut[i] = (float) std::exp((double) (-2.0f * r2)) - (float) std::exp((double) -2.0f); }
         if (up(&dTexLevels, texLevels) | up(&dTexTexels, texTexels) | up(&dMipLut, lut)) return 1;
         d.tex_levels = (const uint32_t *) dTexLevels; d.tex_texels = (const float *) dTexTexels; d.mip_lut = (const float *) dMipLut;
-        const float *m = s2c; const float irx = 1.0f / (float) width, iry = 1.0f / (float) height;
-        auto pt = [&](float px, float py, float *o) {
-            float x = m[0] * px + m[1] * py + m[2] * 0.0f + m[3], y = m[4] * px + m[5] * py + m[6] * 0.0f + m[7], z = m[8] * px + m[9] * py + m[10] * 0.0f + m[11], w = m[12] * px + m[13] * py + m[14] * 0.0f + m[15];
-            if (w != 1.0f) { float r = 1.0f / w; x *= r; y *= r; z *= r; }
-            o[0] = x; o[1] = y; o[2] = z; };
-        float p0[3], px[3], py[3]; pt(0.0f, 0.0f, p0); pt(irx, 0.0f, px); pt(0.0f, iry, py);
-        for (int i = 0; i < 3; ++i) { d.cam_dx[i] = px[i] - p0[i]; d.cam_dy[i] = py[i] - p0[i]; }
     }
     d.material_tables = (const float *) dMaterialTables; d.triuv = (const TriUV *) dTriUV; d.textures = (const TextureD *) dTextures;
     bool matTextures = false; for (const auto &m : mats) if ((m.flags >> 8) & 0xFFFFu) matTextures = true;
     d.n_textures = matTextures ? (uint32_t) textures.size() : 0u; d.env_texture = envTexture >= 0 ? (uint32_t) envTexture + 1u : 0u;
     d.instances = (const InstanceD *) dInstances; d.n_instances = (uint32_t) instancesD.size();
     d.emitter_x = (const float *) dEmitterX; d.env_constant = envConstant ? 1u : 0u; d.ext = (!analyticD.empty() || !instancesD.empty() || hasDeltaEmitters || anyUV || matTextures) ? 1u : 0u;
-    memcpy(d.dir_bs_center, dirBsCenter, 12); d.dir_bs_radius = dirBsRadius;
     d.n_tris = nTris; d.n_nodes = (uint32_t) nodes.size(); d.n_emitters = (uint32_t) emittersD.size(); d.n_materials = (uint32_t) mats.size();
-    d.emitter_norm = emitterNorm;
+    syncEmittersD();
     for (int i = 0; i < 3; ++i) { d.aabb_lo[i] = aabbLo[i]; d.aabb_hi[i] = aabbHi[i]; }
-    memcpy(d.s2c, s2c, 64); memcpy(d.c2w, c2w, 64);
-    d.near_clip = nearClip; d.far_clip = farClip; d.inv_res_x = 1.0f / (float) width; d.inv_res_y = 1.0f / (float) height;
+    syncCameraD();      // camera matrices, clip planes, pixel differentials, bounding spheres
+    d.inv_res_x = 1.0f / (float) width; d.inv_res_y = 1.0f / (float) height;
     d.width = width; d.height = height;
     d.filter_radius = filterRadiusEff; d.filter_scale = filterScale; d.border = border;
     d.log_res = logRes; d.resolution = resolution;
     d.env_index = envIndex;
-    d.env_bs_radius = envBsRadius; memcpy(d.env_bs_center, envBsCenter, 12);
     if (envIndex >= 0 && !envConstant) {
         if (up(&dEnvRGB, envRGB) | up(&dEnvCols, envCdfCols) | up(&dEnvRows, envCdfRows) | up(&dEnvWeights, envRowWeights)) return 1;
         if (!envGuideRows.empty()) { if (up(&dEnvGuideRows, envGuideRows) | up(&dEnvGuideCols, envGuideCols)) return 1;
             d.env_guide_rows_t = (const uint16_t *) dEnvGuideRows; d.env_guide_cols_t = (const uint16_t *) dEnvGuideCols; d.env_guide_rows = envGuideKR; d.env_guide_cols = envGuideKC; }
         d.env_rgb = (const float *) dEnvRGB; d.env_cdf_cols = (const float *) dEnvCols; d.env_cdf_rows = (const float *) dEnvRows; d.env_row_weights = (const float *) dEnvWeights;
-        d.env_w = (int) envW; d.env_h = (int) envH; d.env_normalization = envNormalization; d.env_scale = envScale;
-        d.env_pixel_w = 2 * MI_PI / (float) envW; d.env_pixel_h = MI_PI / (float) envH; d.env_bs_radius = envBsRadius;
-        memcpy(d.env_to_world, envToWorld3, 36); memcpy(d.env_to_local, envToLocal3, 36); memcpy(d.env_bs_center, envBsCenter, 12);
+        d.env_w = (int) envW; d.env_h = (int) envH; d.env_normalization = envNormalization;
+        d.env_pixel_w = 2 * MI_PI / (float) envW; d.env_pixel_h = MI_PI / (float) envH;
+        syncEnvD();
     }
     d.bvh_depth = (uint32_t) bvhDepth; d.bvh_wide = wideBvh ? 1u : 0u; d.bvh_stack_direct = (uint32_t) bvhStackDirect;
     d.area_cdf_len = (uint32_t) areaCdf.size();
@@ -509,12 +417,116 @@ int mi_scene_clone(mi_scene *s, uint32_t device, mi_scene **out) {
     mi_scene *c = new mi_scene();
     c->h = s->h;                                    // inputs + host-derived data
     {   // the copy must not own the source's device allocations
-        void **ps[] = {&c->h.dMedia, &c->h.dPrimMedia, &c->h.dPacketGroups, &c->h.dPacketExact, &c->h.dTexLevels, &c->h.dTexTexels, &c->h.dMipLut, &c->h.dTriUV, &c->h.dTextures, &c->h.dMaterialTables, &c->h.dInstances, &c->h.dEmitterX, &c->h.dAnalytic, &c->h.dNodes, &c->h.dTris, &c->h.dShade, &c->h.dI2, &c->h.dNrm, &c->h.dMaterials, &c->h.dEmitters, &c->h.dEmitterCdf, &c->h.dAreaCdf, &c->h.dFilter, &c->h.dSobolM32, &c->h.dSobolVdc, &c->h.dSobolVdcInv, &c->h.dEnvRGB, &c->h.dEnvCols, &c->h.dEnvRows, &c->h.dEnvWeights, &c->h.dEnvGuideRows, &c->h.dEnvGuideCols};
+        void **ps[] = {&c->h.dMaterialFlags, &c->h.dMedia, &c->h.dPrimMedia, &c->h.dPacketGroups, &c->h.dPacketExact, &c->h.dTexLevels, &c->h.dTexTexels, &c->h.dMipLut, &c->h.dTriUV, &c->h.dTextures, &c->h.dMaterialTables, &c->h.dInstances, &c->h.dEmitterX, &c->h.dAnalytic, &c->h.dNodes, &c->h.dTris, &c->h.dShade, &c->h.dI2, &c->h.dNrm, &c->h.dMaterials, &c->h.dEmitters, &c->h.dEmitterCdf, &c->h.dAreaCdf, &c->h.dFilter, &c->h.dSobolM32, &c->h.dSobolVdc, &c->h.dSobolVdcInv, &c->h.dEnvRGB, &c->h.dEnvCols, &c->h.dEnvRows, &c->h.dEnvWeights, &c->h.dEnvGuideRows, &c->h.dEnvGuideCols};
         for (void **p : ps) *p = nullptr;
         c->h.committed = false;
     }
     if (c->h.upload((int) device)) { std::string msg = std::string("mi_scene_clone: upload failed: ") + hipGetErrorString(hipGetLastError()); delete c; return fail(MI_ERR_DEVICE, msg); }
     *out = c; return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ in-place edits (SceneHost::update*, scene_build.cpp)
+// The host side recomputes what commitHost() / upload() derive from the edited inputs; here the small tables go back into their EXISTING allocations (the record counts
+// cannot change, so every size is the one upload() allocated) and, when a material's flag bits moved, one kernel rewrites those bits in the triangle records.
+struct UpdateGuard {
+    mi_scene *s = nullptr;
+    bool enter(mi_scene *sc) { int v = 0; if (!sc->busy.compare_exchange_strong(v, -1)) return false; s = sc; return true; }
+    ~UpdateGuard() { if (s) s->busy.store(0); }
+};
+}  // extern "C"
+template <typename T> static hipError_t push(void *dst, const std::vector<T> &v) { return v.empty() || !dst ? hipSuccess : hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice); }
+extern "C" {
+#define UPDATE_ENTER(name) \
+    if (!s) return fail(MI_ERR_INVALID, name ": null scene"); \
+    if (!s->h.committed) return fail(MI_ERR_INVALID, name ": scene not committed (an update edits a committed scene in place)"); \
+    UpdateGuard updating; if (!updating.enter(s)) return fail(MI_ERR_INVALID, name ": a render is running on this scene (cancel it and wait for the run to return)")
+
+int mi_scene_update_camera(mi_scene *s, const float *s2c, const float *c2w, float nearClip, float farClip) {
+    if (!s || !s2c || !c2w) return fail(MI_ERR_INVALID, "mi_scene_update_camera: null argument");
+    UPDATE_ENTER("mi_scene_update_camera");
+    std::string msg; const int rc = s->h.updateCamera(s2c, c2w, nearClip, farClip, msg); if (rc) return fail(rc, msg);
+    return MI_OK;      // the camera lives in the scene record alone: renders pick it up with their next run
+}
+int mi_scene_update_materials(mi_scene *s, const mi_material *m, uint32_t n) {
+    if (!s || !m || !n) return fail(MI_ERR_INVALID, "mi_scene_update_materials: null argument");
+    UPDATE_ENTER("mi_scene_update_materials");
+    mi::SceneHost &h = s->h; bool flagsChanged = false;
+    std::string msg; const int rc = h.updateMaterials(m, n, msg, &flagsChanged); if (rc) return fail(rc, msg);
+    if (h.materialsD.size() != h.d.n_materials || h.analyticD.size() != h.d.n_analytic || h.shade.size() != h.d.n_tris) return fail(MI_ERR_DEVICE, "mi_scene_update_materials: host tables and device tables disagree in size");
+    HIPCHK(hipSetDevice(h.device));
+    HIPCHK(push(h.dMaterials, h.materialsD));
+    if (flagsChanged) {
+        HIPCHK(push(h.dMaterialFlags, h.materialFlagTable)); HIPCHK(push(h.dAnalytic, h.analyticD));
+        if (h.d.n_tris) { mi_launch_patch_material_flags((TriShade *) h.dShade, h.d.n_tris, (const uint32_t *) h.dMaterialFlags, h.d.n_materials, nullptr); HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(nullptr)); }
+    }
+    return MI_OK;
+}
+int mi_scene_update_emitters(mi_scene *s, const mi_emitter *e, uint32_t n) {
+    if (!s || !e || !n) return fail(MI_ERR_INVALID, "mi_scene_update_emitters: null argument");
+    UPDATE_ENTER("mi_scene_update_emitters");
+    mi::SceneHost &h = s->h; const size_t cdfLen = h.areaCdf.size();
+    std::string msg; const int rc = h.updateEmitters(e, n, msg); if (rc) return fail(rc, msg);
+    if (h.emittersD.size() != h.d.n_emitters || h.areaCdf.size() != cdfLen) return fail(MI_ERR_DEVICE, "mi_scene_update_emitters: host tables and device tables disagree in size");
+    HIPCHK(hipSetDevice(h.device));
+    HIPCHK(push(h.dEmitters, h.emittersD)); HIPCHK(push(h.dEmitterCdf, h.emitterCdf)); HIPCHK(push(h.dEmitterX, h.emitterX));      // the area CDFs depend on geometry only
+    return MI_OK;
+}
+int mi_scene_update_envmap_transform(mi_scene *s, const float *toWorld, float scale) {
+    if (!s || !toWorld) return fail(MI_ERR_INVALID, "mi_scene_update_envmap_transform: null argument");
+    UPDATE_ENTER("mi_scene_update_envmap_transform");
+    std::string msg; const int rc = s->h.updateEnvmapTransform(toWorld, scale, msg); if (rc) return fail(rc, msg);
+    return MI_OK;
+}
+int mi_scene_revision(mi_scene *s, uint64_t *revision, uint64_t *treeBuilds) {
+    if (!s) return fail(MI_ERR_INVALID, "mi_scene_revision: null scene");
+    if (revision) *revision = s->h.revision;
+    if (treeBuilds) *treeBuilds = s->h.treeBuilds;
+    return MI_OK;
+}
+
+// Scene::getBSphere() (aabb.cpp:44-47) of the kd-tree box expanded by the sensor's and the point / spot emitters' positions (scene.cpp:394-421): the distance at which the
+// volumetric integrators place environment hits.  Depends on the camera and on the emitters, so a render recomputes it when the scene has been edited.
+static float alphaDistOf(const mi::SceneHost &h) {
+    float lo[3], hi[3]; for (int i = 0; i < 3; ++i) { lo[i] = h.aabbLo[i]; hi[i] = h.aabbHi[i]; }
+    auto expand = [&](float x, float y, float z) { const float v[3] = {x, y, z}; for (int i = 0; i < 3; ++i) { lo[i] = std::min(lo[i], v[i]); hi[i] = std::max(hi[i], v[i]); } };
+    expand(h.c2w[3], h.c2w[7], h.c2w[11]);
+    for (const mi_emitter &e : h.emitters) if (e.type == MI_EMITTER_POINT || e.type == MI_EMITTER_SPOT || e.type == MI_EMITTER_COLLIMATED) expand(e.to_world[3], e.to_world[7], e.to_world[11]);
+    float c[3], d2 = 0; for (int i = 0; i < 3; ++i) { c[i] = (hi[i] + lo[i]) * 0.5f; const float d = c[i] - hi[i]; d2 += d * d; }
+    (void) c; return std::sqrt(d2) * 2;
+}
+// inverse of the sensor's (affine) world transform in double precision, rounded to float (the relPosition field); false: not invertible
+static bool worldToCamera(const mi::SceneHost &h, float *w2c) {
+    double m[3][3], t[3]; for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) m[i][j] = h.c2w[i * 4 + j]; t[i] = h.c2w[i * 4 + 3]; }
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    double inv[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
+        const int a = (j + 1) % 3, b = (j + 2) % 3, c = (i + 1) % 3, d = (i + 2) % 3;
+        inv[i][j] = (m[a][c] * m[b][d] - m[a][d] * m[b][c]) / det;
+    }
+    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) w2c[i * 4 + j] = (float) inv[i][j]; w2c[i * 4 + 3] = (float) -(inv[i][0] * t[0] + inv[i][1] * t[1] + inv[i][2] * t[2]); }
+    return std::fabs(det) > 0;
+}
+// A render holds a copy of the scene record.  Every entry point that launches kernels calls this first: when the scene has been edited since (mi_scene_update_*), the
+// copy is taken again -- keeping the per-render packet switch -- together with the two constants that depend on the camera.  Also counts the render as running on the
+// scene, so that an update issued meanwhile is refused; RunGuard's destructor ends that.
+struct RunGuard {
+    mi_scene *s = nullptr;
+    bool enter(mi_scene *sc) { int v = sc->busy.load(); while (v >= 0) if (sc->busy.compare_exchange_weak(v, v + 1)) { s = sc; return true; } return false; }
+    ~RunGuard() { if (s) s->busy.fetch_sub(1); }
+};
+static int beginRun(mi_render *r, RunGuard &g, bool film, const char *who) {
+    mi_scene *s = r->scene;
+    if (!g.enter(s)) return fail(MI_ERR_INVALID, std::string(who) + ": the scene is being updated");
+    if (film && (r->samplesTotal || r->mergedSamples) && r->filmRev != s->h.revision)
+        return fail(MI_ERR_INVALID, std::string(who) + ": the film holds samples of the scene before its last update; call mi_render_clear first");
+    if (r->sceneRev != s->h.revision) {
+        r->sc = s->h.d; if (r->rc.integrator != MI_INTEGRATOR_PATH) r->sc.packet_n = 0;
+        r->rc.alpha_dist = alphaDistOf(s->h);
+        if (r->nFields) (void) worldToCamera(s->h, r->fa.w2c);
+        r->sceneRev = s->h.revision;
+    }
+    if (film) r->filmRev = s->h.revision;
+    return MI_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ render
@@ -632,19 +644,12 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
     }
     HIPCHK(hipSetDevice(s->h.device));
     mi_render *r = new mi_render(); r->scene = s; r->p = *p;
-    r->sc = s->h.d; if (vol) r->sc.packet_n = 0;      // packet or tree is decided per render: volpath / volpath_simple on a <= 64-triangle scene without media walk its tree
+    r->sc = s->h.d; r->sceneRev = r->filmRev = s->h.revision; if (vol) r->sc.packet_n = 0;      // packet or tree is decided per render: volpath / volpath_simple on a <= 64-triangle scene without media walk its tree
     struct Guard { mi_render *r; ~Guard() { if (r) mi_render_destroy(r); } } guard{r};      // every early return below releases what was created so far
     r->rc.max_depth = p->max_depth; r->rc.rr_depth = p->rr_depth; r->rc.strict_normals = p->strict_normals; r->rc.hide_emitters = p->hide_emitters; r->rc.opacity = p->opacity;
     r->rc.sobol_scramble = 0;
     // volumetric integrators: the radiance-type bits and the sensor's medium of a fresh path (kernels_vol.hip; volpath_simple.cpp:103-104: maxDepth = 1 gathers emitted radiance only)
-    {   // Scene::getBSphere() (aabb.cpp:44-47) of the kd-tree box expanded by the sensor's and the point / spot emitters' positions (scene.cpp:394-421)
-        float lo[3], hi[3]; for (int i = 0; i < 3; ++i) { lo[i] = s->h.aabbLo[i]; hi[i] = s->h.aabbHi[i]; }
-        auto expand = [&](float x, float y, float z) { const float v[3] = {x, y, z}; for (int i = 0; i < 3; ++i) { lo[i] = std::min(lo[i], v[i]); hi[i] = std::max(hi[i], v[i]); } };
-        expand(s->h.c2w[3], s->h.c2w[7], s->h.c2w[11]);
-        for (const mi_emitter &e : s->h.emitters) if (e.type == MI_EMITTER_POINT || e.type == MI_EMITTER_SPOT || e.type == MI_EMITTER_COLLIMATED) expand(e.to_world[3], e.to_world[7], e.to_world[11]);
-        float c[3], d2 = 0; for (int i = 0; i < 3; ++i) { c[i] = (hi[i] + lo[i]) * 0.5f; const float d = c[i] - hi[i]; d2 += d * d; }
-        r->rc.alpha_dist = std::sqrt(d2) * 2;
-    }
+    r->rc.alpha_dist = alphaDistOf(s->h);
     r->rc.integrator = p->integrator;
     r->rc.state_init = p->integrator == MI_INTEGRATOR_VOLPATH_SIMPLE ? ((1u << 16) | (p->max_depth == 1 ? 0u : (1u << 17)) | (1u << 18) | ((uint32_t) (s->h.d.sensor_medium + 1) << 20))
                      : p->integrator == MI_INTEGRATOR_VOLPATH ? ((1u << 16) | ((uint32_t) (s->h.d.sensor_medium + 1) << 20)) : 0u;      // volpath: ERadiance, nothing else (kernels_volmis.hip)
@@ -744,7 +749,7 @@ int mi_render_clear(mi_render *r) {
     if (r->nFields) { HIPCHK(hipMemsetAsync(r->fieldFilm, 0, r->fieldFloats * 4, r->stream)); HIPCHK(hipMemsetAsync(r->fieldSpill, 0, r->fieldFloats * 4, r->stream)); }
     if (r->q.counters) HIPCHK(hipMemsetAsync(r->q.counters, 0, 32, r->stream));
     for (Queues &Q : r->qx) if (Q.counters) HIPCHK(hipMemsetAsync(Q.counters, 0, 32, r->stream));
-    HIPCHK(hipStreamSynchronize(r->stream)); r->samplesTotal = 0; r->mergedRays = r->mergedShadow = r->mergedPathLen = r->mergedSamples = 0; r->cancel.store(0); return MI_OK;
+    HIPCHK(hipStreamSynchronize(r->stream)); r->samplesTotal = 0; r->mergedRays = r->mergedShadow = r->mergedPathLen = r->mergedSamples = 0; r->filmRev = r->scene->h.revision; r->cancel.store(0); return MI_OK;
 }
 void mi_render_cancel(mi_render *r) { if (r) r->cancel.store(1); }
 int mi_render_set_profiling(mi_render *r, int enabled) { if (!r) return fail(MI_ERR_INVALID, "null"); r->profiling = enabled != 0; return MI_OK; }
@@ -808,6 +813,7 @@ int mi_render_run_rows(mi_render *r, mi_tile tile, uint32_t rowStride, uint32_t 
     if (tile.x1 <= tile.x0 || tile.y1 <= tile.y0 || tile.x1 > h.width || tile.y1 > h.height) return fail(MI_ERR_INVALID, "mi_render_run: tile outside the film");
     if (s1 < s0 || s1 > r->p.spp) return fail(MI_ERR_INVALID, "mi_render_run: sample range outside [0, spp]");
     if (r->p.sampler == MI_SAMPLER_INDEPENDENT && s1 > (1u << 24)) return fail(MI_ERR_INVALID, "mi_render_run: independent stream supports < 2^24 samples per pixel");
+    RunGuard running; { const int rc = beginRun(r, running, true, "mi_render_run"); if (rc) return rc; }
     HIPCHK(hipSetDevice(h.device));
     const uint32_t nrows = (tile.y1 - tile.y0 + rowStride - 1) / rowStride;          // rows y0, y0 + stride, ... below y1
     const uint32_t npix = (tile.x1 - tile.x0) * nrows;
@@ -951,6 +957,7 @@ int mi_render_samples(mi_render *r, const uint32_t *pairs, uint64_t n, float *ou
     if (!r || !pairs || !outLi || !n) return fail(MI_ERR_INVALID, "mi_render_samples: null argument");
     const mi::SceneHost &h = r->scene->h; HIPCHK(hipSetDevice(h.device));
     for (uint64_t i = 0; i < n; ++i) if (pairs[i * 3] >= h.width || pairs[i * 3 + 1] >= h.height) return fail(MI_ERR_INVALID, "mi_render_samples: pixel outside the film");
+    RunGuard running; { const int rc = beginRun(r, running, false, "mi_render_samples"); if (rc) return rc; }
     if (n > r->poolPaths) { int rc = allocPool(r, n); if (rc) return rc; }
     uint32_t *dList = nullptr; float *dOut = nullptr; uint32_t *dSlots = nullptr;
     HIPCHK(hipMalloc((void **) &dList, n * 12)); HIPCHK(hipMalloc((void **) &dOut, n * 12)); HIPCHK(hipMalloc((void **) &dSlots, n * 4));
@@ -992,17 +999,7 @@ int mi_render_set_fields(mi_render *r, const mi_field *fields, uint32_t n) {
     if (!n) return MI_OK;
     FieldArgs fa{}; fa.n = n; fa.needs = needs; fa.n_meshes = (uint32_t) h.shapes.size();
     for (uint32_t i = 0; i < n; ++i) { fa.kind[i] = fields[i].field; memcpy(fa.undefined[i], fields[i].undefined, 12); }
-    {   // inverse of the sensor's (affine) world transform in double precision, rounded to float
-        double m[3][3], t[3]; for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) m[i][j] = h.c2w[i * 4 + j]; t[i] = h.c2w[i * 4 + 3]; }
-        const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-        if ((needs & (1u << MI_FIELD_REL_POSITION)) && !(std::fabs(det) > 0)) return fail(MI_ERR_INVALID, "mi_render_set_fields: relPosition needs an invertible camera transform");
-        double inv[3][3];
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
-            const int a = (j + 1) % 3, b = (j + 2) % 3, c = (i + 1) % 3, d = (i + 2) % 3;
-            inv[i][j] = (m[a][c] * m[b][d] - m[a][d] * m[b][c]) / det;
-        }
-        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) fa.w2c[i * 4 + j] = (float) inv[i][j]; fa.w2c[i * 4 + 3] = (float) -(inv[i][0] * t[0] + inv[i][1] * t[1] + inv[i][2] * t[2]); }
-    }
+    if (!worldToCamera(h, fa.w2c) && (needs & (1u << MI_FIELD_REL_POSITION))) return fail(MI_ERR_INVALID, "mi_render_set_fields: relPosition needs an invertible camera transform");
     struct Undo { mi_render *r; ~Undo() { if (r) releaseFields(r); } } undo{r};
     if (needs & (1u << MI_FIELD_SHAPE_INDEX)) {
         std::vector<int32_t> ts(std::max<size_t>(h.idx.size() / 3, 1), -1);
@@ -1043,6 +1040,7 @@ int mi_render_field_samples(mi_render *r, const uint32_t *pairs, uint64_t n, flo
     if (!r->nFields) return fail(MI_ERR_INVALID, "mi_render_field_samples: the render has no fields (mi_render_set_fields)");
     const mi::SceneHost &h = r->scene->h; HIPCHK(hipSetDevice(h.device));
     for (uint64_t i = 0; i < n; ++i) if (pairs[i * 3] >= h.width || pairs[i * 3 + 1] >= h.height) return fail(MI_ERR_INVALID, "mi_render_field_samples: pixel outside the film");
+    RunGuard running; { const int rc = beginRun(r, running, false, "mi_render_field_samples"); if (rc) return rc; }
     if (n > r->poolPaths) { int rc = allocPool(r, n); if (rc) return rc; }
     if (!r->q.counters) return fail(MI_ERR_DEVICE, "mi_render_field_samples: no path pool");
     const size_t outBytes = (size_t) n * 3 * r->nFields * 4;

@@ -140,6 +140,17 @@ int MIPathTracerHIP::render(float *target, Controls controls, int threadIdx, int
 }
 void MIPathTracerHIP::cancel() { m_cancel.store(1); if (m_render) mi_render_cancel(m_render); for (mi_render *rr : m_replicaRenders) mi_render_cancel(rr); }
 
+// An edit is refused by its checks before anything changes, and the replicas hold the same records as the borrowed scene: either all scenes take it or none does.
+template <typename F> void MIPathTracerHIP::editAll(const char *what, F edit) {
+    if (!m_scene) throw std::runtime_error(std::string(what) + ": preprocess() was not called");
+    check(edit(m_scene), what);
+    for (mi_scene *rs : m_replicaScenes) check(edit(rs), what);
+}
+void MIPathTracerHIP::setCamera(const float *s2c, const float *c2w, float nearClip, float farClip) { editAll("MIPathTracerHIP::setCamera", [&](mi_scene *s) { return mi_scene_update_camera(s, s2c, c2w, nearClip, farClip); }); }
+void MIPathTracerHIP::setMaterials(const mi_material *m, uint32_t n) { editAll("MIPathTracerHIP::setMaterials", [&](mi_scene *s) { return mi_scene_update_materials(s, m, n); }); }
+void MIPathTracerHIP::setEmitters(const mi_emitter *e, uint32_t n) { editAll("MIPathTracerHIP::setEmitters", [&](mi_scene *s) { return mi_scene_update_emitters(s, e, n); }); }
+void MIPathTracerHIP::setEnvmapTransform(const float *toWorld, float scale) { editAll("MIPathTracerHIP::setEnvmapTransform", [&](mi_scene *s) { return mi_scene_update_envmap_transform(s, toWorld, scale); }); }
+
 const char *MIPathTracerHIP::getRealtimeStatistics() {
     if (!m_render) return nullptr;
     mi_stats st{}; if (mi_render_stats(m_render, &st) != MI_OK) return nullptr;
@@ -195,6 +206,11 @@ int mi_host_render(void *h, float *target, const int *continu, const int *abortF
         return ((mi355::MIPathTracerHIP *) h)->render(target, c, threadIdx, threadCount);
     } catch (const std::exception &e) { g_hostErr = e.what(); return 1000; }
 }
+#define HOST_EDIT(call) try { ((mi355::MIPathTracerHIP *) h)->call; return 0; } catch (const std::exception &e) { g_hostErr = e.what(); return 1; }
+int mi_host_set_camera(void *h, const float *s2c, const float *c2w, float nearClip, float farClip) { HOST_EDIT(setCamera(s2c, c2w, nearClip, farClip)) }
+int mi_host_set_materials(void *h, const mi_material *m, uint32_t n) { HOST_EDIT(setMaterials(m, n)) }
+int mi_host_set_emitters(void *h, const mi_emitter *e, uint32_t n) { HOST_EDIT(setEmitters(e, n)) }
+int mi_host_set_envmap_transform(void *h, const float *toWorld, float scale) { HOST_EDIT(setEnvmapTransform(toWorld, scale)) }
 void mi_host_cancel(void *h) { ((mi355::MIPathTracerHIP *) h)->cancel(); }
 const char *mi_host_statistics(void *h) { return ((mi355::MIPathTracerHIP *) h)->getRealtimeStatistics(); }
 }

@@ -52,6 +52,12 @@ public:
     // plain stores between progress() calls.  All work happens on threadIdx 0; other threads return 0 immediately.
     int render(float *targetRGBA, Controls controls, int threadIdx, int threadCount);
     void cancel();
+    // In-place edits of the borrowed scene and of every replica scene (mi_scene_update_*): valid between render() calls, no preprocess() needed afterwards.
+    // Each throws std::runtime_error with the library's message when the edit is refused; the scenes are then unchanged.
+    void setCamera(const float *sampleToCamera16, const float *toWorld16, float nearClip, float farClip);
+    void setMaterials(const mi_material *materials, uint32_t n);
+    void setEmitters(const mi_emitter *emitters, uint32_t n);
+    void setEnvmapTransform(const float *toWorld16, float scale);
     float getLowerSampleBound() const { return 1.0f; }
     const char *getRealtimeStatistics();
     const Properties &getProperties() const { return m_props; }
@@ -61,6 +67,7 @@ private:
     Properties m_props; mi_scene *m_scene = nullptr; mi_render *m_render = nullptr; std::string m_stats; int m_threads = 1;
     std::vector<mi_scene *> m_replicaScenes; std::vector<mi_render *> m_replicaRenders;   // devices[1..]: one scene clone + one render handle each, driven by one host thread each
     void releaseReplicas();
+    template <typename F> void editAll(const char *what, F edit);
     struct Workers; std::unique_ptr<Workers> m_workers;   // one persistent host thread per replica (multi-device renders)
     std::atomic<int> m_cancel{0};   // set by cancel(), reset at the start of render(): a cancel between two batches or two mi_render_run calls is never lost
 };

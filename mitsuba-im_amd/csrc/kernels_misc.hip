@@ -178,6 +178,18 @@ __global__ void k_debug_camera(DScene sc, const float *pos, uint64_t n, float *o
 }
 
 
+// ---------------------------------------------------------------------------------------------- in-place material edits (mi_scene_update_materials)
+// The three material-derived bits of TriShade::flags (back side, no smooth component, not plain diffuse: MI_MATERIAL_FLAG_BITS of scene_host.h) follow the record's material
+// through a per-material table of n_materials words.  One thread per triangle record, grid-stride; a 128-B record is touched in one word only.  Launched only when some
+// material's bits changed: the alternative is to send every record again.
+__global__ void k_patch_material_flags(TriShade *shade, uint32_t nTris, const uint32_t *matFlags, uint32_t nMaterials) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nTris; i += stride) {
+        const uint32_t m = (uint32_t) shade[i].material;
+        if (m < nMaterials) shade[i].flags = (shade[i].flags & ~14u) | (matFlags[m] & 14u);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- launch wrappers (used by api.cpp)
 extern "C" {
 void mi_launch_generate(const DScene &sc, const RenderConst &rc, const Queues &q, const BatchDesc &bd, uint32_t grid, hipStream_t st) { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(WG), 0, st, sc, rc, q, bd); }
@@ -192,4 +204,8 @@ void mi_launch_debug_sobol(const DScene &sc, const uint32_t *in, uint64_t n, uin
 void mi_launch_debug_sincosf(const float *in, uint64_t n, float *out, hipStream_t st) { hipLaunchKernelGGL(k_debug_sincosf, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, in, n, out); }
 void mi_launch_debug_libm(int fn, const float *x, const float *y, uint64_t n, float *out, hipStream_t st) { hipLaunchKernelGGL(k_debug_libm, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, fn, x, y, n, out); }
 void mi_launch_debug_camera(const DScene &sc, const float *pos, uint64_t n, float *out, hipStream_t st) { hipLaunchKernelGGL(k_debug_camera, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, sc, pos, n, out); }
+void mi_launch_patch_material_flags(TriShade *shade, uint32_t nTris, const uint32_t *matFlags, uint32_t nMaterials, hipStream_t st) {
+    const unsigned grid = (unsigned) std::min<uint64_t>(((uint64_t) nTris + 255) / 256, 2048);      // at most 8 workgroups per CU, the loop strides over the rest
+    if (grid) hipLaunchKernelGGL(k_patch_material_flags, dim3(grid), dim3(256), 0, st, shade, nTris, matFlags, nMaterials);
+}
 }

@@ -172,6 +172,7 @@ static inline int32_t leafCode(int first, int count) { return ~(int32_t) (first 
 #define MI_K_NONE 3u                    // TriAccelD::k of a record that is never hit (the value triaccelLoad gives degenerate triangles)
 
 void SceneHost::commitHost() {
+    ++treeBuilds;
     const uint32_t nt = (uint32_t) (idx.size() / 3), na = (uint32_t) analytic.size(), ni = (uint32_t) instances.size(), np = nt + na + ni;
     nTris = nt;
     auto vert = [&](uint32_t i) { return mk(pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]); };
@@ -182,28 +183,7 @@ void SceneHost::commitHost() {
     std::vector<TriAccelD> accel(nt); shade.assign(nt, TriShade{}); i2.assign(nt, 0);
     triuv.assign(uv.empty() ? 0 : nt, TriUV{}); anyUV = false;
     std::vector<V3> tlo(np), thi(np), cen(np);
-    // flags of a shape's material as MIPathTracer::Li sees the (possibly nested) BSDF: bit1 EBackSide / ETransmission somewhere (dRec.refN = 0, records.inl:160-164),
-    // bit2 no smooth component (no emitter sampling, path.cpp:173-174), bit3 anything but a plain diffuse record (class bit of the shading stage)
-    auto leafBackside = [&](const mi_material &mat) { return (mat.flags & MI_BSDF_FLAG_TWOSIDED) != 0 || mat.type == MI_BSDF_DIELECTRIC || mat.type == MI_BSDF_ROUGHDIELECTRIC || mat.type == MI_BSDF_DIFFTRANS || mat.type == MI_BSDF_THINDIELECTRIC || mat.type == MI_BSDF_NULL; };
-    // a `diffuse` with zero reflectance has no component at all -> not ESmooth -> Li skips emitter sampling (diffuse.cpp:99-102, path.cpp:174-176);
-    // conductor / dielectric register delta components only
-    auto leafSmooth = [&](const mi_material &mat) { return mat.type == MI_BSDF_DIFFUSE ? (((mat.flags >> 8) & 0xFFFFu) != 0 || std::max(std::max(mat.reflectance[0], mat.reflectance[1]), mat.reflectance[2]) > 0)
-                                                                                         : (mat.type != MI_BSDF_CONDUCTOR && mat.type != MI_BSDF_DIELECTRIC && mat.type != MI_BSDF_THINDIELECTRIC && mat.type != MI_BSDF_NULL); };
-    auto materialFlags = [&](int bsdf) {
-        const mi_material *mat = &materials[bsdf]; bool masked = false, wrapped = false;
-        if (mat->type == MI_BSDF_MASK) { masked = true; mat = &materials[mat->distr]; }          // mask.cpp:104-121: the nested BSDF's components + an ENull | EFrontSide | EBackSide one
-        if (mat->type == MI_BSDF_BUMPMAP || mat->type == MI_BSDF_NORMALMAP) { wrapped = true; mat = &materials[mat->distr]; }     // the nested BSDF's component types (bumpmap.cpp:97-100)
-        bool backside, smooth, coated = false;
-        if (mat->type == MI_BSDF_COATING || mat->type == MI_BSDF_ROUGHCOATING) { coated = true; wrapped = true; mat = &materials[mat->distr]; }      // coating.cpp:166-173: the nested components + a delta reflection that is EFrontSide | EBackSide
-        if (mat->type == MI_BSDF_BLEND) {                                                           // the two BSDFs' components (blendbsdf.cpp:103-134)
-            backside = (mat->flags & MI_BSDF_FLAG_TWOSIDED) != 0; smooth = false; wrapped = true;
-            for (int c = 0; c < 2; ++c) { const mi_material &ch = materials[(uint32_t) mat->eta[c]]; backside |= leafBackside(ch); smooth |= leafSmooth(ch); }
-        } else if (mat->type == MI_BSDF_MIXTURE) {                                                         // the children's components (mixturebsdf.cpp:150-166)
-            backside = (mat->flags & MI_BSDF_FLAG_TWOSIDED) != 0; smooth = false; wrapped = true;
-            for (uint32_t c = 0; c < mat->distr; ++c) { const mi_material &ch = materials[(uint32_t) (c < 3 ? mat->reflectance[c] : mat->eta[0])]; backside |= leafBackside(ch); smooth |= leafSmooth(ch); }
-        } else { backside = leafBackside(*mat); smooth = leafSmooth(*mat); }
-        return ((backside || masked || coated) ? 2u : 0u) | (smooth ? 0u : 4u) | ((mat->type != MI_BSDF_DIFFUSE || masked || wrapped) ? 8u : 0u);
-    };
+    buildMaterialTables();      // per-material flag bits of the records below (materialFlagBits)
     for (uint32_t t = 0; t < nt; ++t) {
         uint32_t a = idx[t * 3], b = idx[t * 3 + 1], c = idx[t * 3 + 2];
         V3 p0 = vert(a), p1 = vert(b), p2 = vert(c);
@@ -214,7 +194,7 @@ void SceneHost::commitHost() {
         ts.material = sh.bsdf; ts.emitter = sh.emitter;
         bool faceN = (sh.flags & 1u) || nrm.empty();
         const bool hasUV = (sh.flags & 2u) && !uv.empty();
-        ts.flags = (faceN ? 1u : 0u) | materialFlags(sh.bsdf) | (hasUV ? 16u : 0u);
+        ts.flags = (faceN ? 1u : 0u) | materialFlagTable[sh.bsdf] | (hasUV ? 16u : 0u);
         ts.local_prim = t - sh.first_tri; ts.i0 = a; ts.i1 = b; i2[t] = c;
         // face frame: skdtree.h:367-371 (face normal), util.cpp:605-610 (computeShadingFrame with dpdu = p1 - p0)
         V3 side1 = p1 - p0, side2 = p2 - p0, fn = cross(side1, side2);
@@ -259,7 +239,7 @@ void SceneHost::commitHost() {
     std::vector<V3> alo(na), ahi(na);
     for (uint32_t i = 0; i < na; ++i) {
         V3 tl, th; analyticPrepare(analytic[i], analyticD[i], alo[i], ahi[i], tl, th);
-        analyticD[i].flags = (analytic[i].flags & 1u) | materialFlags(analytic[i].bsdf);
+        analyticD[i].flags = (analytic[i].flags & 1u) | materialFlagTable[analytic[i].bsdf];
         V3 e = th - tl; float mag = std::max(std::max(std::fabs(tl.x) + std::fabs(th.x), std::fabs(tl.y) + std::fabs(th.y)), std::fabs(tl.z) + std::fabs(th.z));
         float pad = 1e-4f * std::max(std::max(e.x, e.y), e.z) + 2e-5f * mag + 1e-7f;
         tlo[nt + i] = tl - mk(pad, pad, pad); thi[nt + i] = th + mk(pad, pad, pad); cen[nt + i] = (tl + th) * 0.5f;
@@ -477,6 +457,134 @@ void SceneHost::commitHost() {
     if (packetGroups.empty()) packetGroups.push_back(PacketGroupD{});
     if (packetExact.empty()) packetExact.push_back(TriAccelD{});
 
+    buildEmitterTables();
+
+    /* --- reconstruction filter table (src/libcore/rfilter.cpp:37-56; eval of src/rfilters/box.cpp:31-48, gaussian.cpp:30-57, tent.cpp:36-38,
+     * mitchell.cpp:49-61, catmullrom.cpp:36-49, lanczos.cpp:36-46).  filter_radius / filter_stddev carry: box radius; gaussian stddev (in
+     * filter_stddev); mitchell B, C; lanczos lobes (in filter_radius) */
+    {
+        const uint32_t kind = filterKind;
+        float radius = kind == 0 ? filterRadius + 1e-5f : kind == 1 ? 4.0f * filterStddev : kind == 2 ? 1.0f : kind == 5 ? (float) (int) filterRadius : 2.0f;
+        float alpha = -1.0f / (2.0f * filterStddev * filterStddev), bias = std::exp(alpha * radius * radius);
+        const float B = kind == 3 ? filterRadius : 0.0f, C = kind == 3 ? filterStddev : 0.5f;
+        float sum = 0.0f;
+        for (int i = 0; i < MI_FILTER_RES; ++i) {
+            float x = (radius * (float) i) / (float) MI_FILTER_RES, v;
+            if (kind == 0) v = std::fabs(x) <= radius ? 1.0f : 0.0f;
+            else if (kind == 1) v = std::max(0.0f, std::exp(alpha * x * x) - bias);
+            else if (kind == 2) v = std::max(0.0f, 1.0f - std::fabs(x / radius));
+            else if (kind == 5) {
+                float ax = std::fabs(x);
+                if (ax < 1e-4f) v = 1.0f; else if (ax > radius) v = 0.0f;
+                else { float x1 = MI_PI * ax, x2 = x1 / radius; v = (std::sin(x1) * std::sin(x2)) / (x1 * x2); }
+            } else {
+                float ax = std::fabs(x), x2 = ax * ax, x3 = x2 * ax;
+                if (ax < 1) v = 1.0f / 6.0f * ((12 - 9 * B - 6 * C) * x3 + (-18 + 12 * B + 6 * C) * x2 + (6 - 2 * B));
+                else if (ax < 2) v = 1.0f / 6.0f * ((-B - 6 * C) * x3 + (6 * B + 30 * C) * x2 + (-12 * B - 48 * C) * ax + (8 * B + 24 * C));
+                else v = 0.0f;
+            }
+            filterValues[i] = v; sum += v;
+        }
+        filterValues[MI_FILTER_RES] = 0.0f;
+        filterScale = (float) MI_FILTER_RES / radius; filterRadiusEff = radius;
+        border = (int) std::ceil(radius - 0.5f);
+        sum *= 2 * radius / (float) MI_FILTER_RES;
+        float norm = 1.0f / sum;
+        for (int i = 0; i < MI_FILTER_RES; ++i) filterValues[i] *= norm;
+    }
+    // --- environment emitter tables (envmap.cpp:264-330 configure)
+    buildBoundingSpheres();
+    if (envIndex >= 0 && !envConstant) {
+        const int W = (int) envW, H = (int) envH;
+        auto texel = [&](int x, int y) { const float *p = &envRGB[((size_t) y * W + x) * 3]; return mk(p[0], p[1], p[2]); };
+        auto lum = [](V3 c) { return c.x * 0.212671f + c.y * 0.715160f + c.z * 0.072169f; };
+        buildEnvTransform();
+        envCdfCols.assign((size_t) (W + 1) * H, 0.0f); envCdfRows.assign((size_t) H + 1, 0.0f); envRowWeights.assign((size_t) H, 0.0f);
+        size_t colPos = 0, rowPos = 0; float rowSum = 0.0f;
+        envCdfRows[rowPos++] = 0;
+        for (int y = 0; y < H; ++y) {
+            float colSum = 0; envCdfCols[colPos++] = 0;
+            for (int x = 0; x < W; ++x) { colSum += lum(texel(x, y)); envCdfCols[colPos++] = colSum; }
+            float normalization = 1.0f / colSum;
+            for (int x = 1; x < W; ++x) envCdfCols[colPos - x - 1] *= normalization;
+            envCdfCols[colPos - 1] = 1.0f;
+            float weight = std::sin(((float) y + 0.5f) * MI_PI / (float) H);
+            envRowWeights[y] = weight; rowSum += colSum * weight; envCdfRows[rowPos++] = rowSum;
+        }
+        float normalization = 1.0f / rowSum;
+        for (int y = 1; y < H; ++y) envCdfRows[rowPos - y - 1] *= normalization;
+        envCdfRows[rowPos - 1] = 1.0f;
+        // guide tables: the index lower_bound(cdf, b / K) for every bucket boundary (b / K is exact: K is a power of two), one table for the rows, one per row for the columns
+        auto pow2ge = [](uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; };
+        envGuideKR = std::min<uint32_t>(pow2ge((uint32_t) H), 4096u); envGuideKC = std::min<uint32_t>(pow2ge((uint32_t) W) / 4u > 0 ? pow2ge((uint32_t) W) / 4u : 1u, 1024u);
+        auto guideOf = [](const float *cdf, uint32_t size, uint32_t K, uint16_t *out) {
+            for (uint32_t b = 0; b <= K; ++b) { const float x = (float) b / (float) K; out[b] = b == K ? (uint16_t) (size + 1) : (uint16_t) (std::lower_bound(cdf, cdf + size + 1, x) - cdf); }
+        };
+        if ((uint32_t) W + 1 < 65535u && (uint32_t) H + 1 < 65535u) {
+            envGuideRows.assign(envGuideKR + 1, 0); guideOf(envCdfRows.data(), (uint32_t) H, envGuideKR, envGuideRows.data());
+            envGuideCols.assign((size_t) H * (envGuideKC + 1), 0);
+            for (int y = 0; y < H; ++y) guideOf(envCdfCols.data() + (size_t) y * (W + 1), (uint32_t) W, envGuideKC, envGuideCols.data() + (size_t) y * (envGuideKC + 1));
+        } else { envGuideRows.clear(); envGuideCols.clear(); envGuideKR = envGuideKC = 0; }
+        envNormalization = 1.0f / (rowSum * (2 * MI_PI / (float) W) * (MI_PI / (float) H));
+    }
+    // Sobol film resolution (src/samplers/sobol.cpp:147-157)
+    { uint32_t r = std::max(width, height), p = 1, l = 0; while (p < r) { p <<= 1; ++l; } resolution = (float) p; logRes = l; }
+}
+
+// ------------------------------------------------------------------------------------------------ pieces shared by commitHost() / upload() and the in-place edits
+uint32_t SceneHost::materialFlagBits(uint32_t bsdf) const {
+    // flags of a shape's material as MIPathTracer::Li sees the (possibly nested) BSDF: bit1 EBackSide / ETransmission somewhere (dRec.refN = 0, records.inl:160-164),
+    // bit2 no smooth component (no emitter sampling, path.cpp:173-174), bit3 anything but a plain diffuse record (class bit of the shading stage)
+    auto leafBackside = [&](const mi_material &mat) { return (mat.flags & MI_BSDF_FLAG_TWOSIDED) != 0 || mat.type == MI_BSDF_DIELECTRIC || mat.type == MI_BSDF_ROUGHDIELECTRIC || mat.type == MI_BSDF_DIFFTRANS || mat.type == MI_BSDF_THINDIELECTRIC || mat.type == MI_BSDF_NULL; };
+    // a `diffuse` with zero reflectance has no component at all -> not ESmooth -> Li skips emitter sampling (diffuse.cpp:99-102, path.cpp:174-176);
+    // conductor / dielectric register delta components only
+    auto leafSmooth = [&](const mi_material &mat) { return mat.type == MI_BSDF_DIFFUSE ? (((mat.flags >> 8) & 0xFFFFu) != 0 || std::max(std::max(mat.reflectance[0], mat.reflectance[1]), mat.reflectance[2]) > 0)
+                                                                                         : (mat.type != MI_BSDF_CONDUCTOR && mat.type != MI_BSDF_DIELECTRIC && mat.type != MI_BSDF_THINDIELECTRIC && mat.type != MI_BSDF_NULL); };
+        const mi_material *mat = &materials[bsdf]; bool masked = false, wrapped = false;
+        if (mat->type == MI_BSDF_MASK) { masked = true; mat = &materials[mat->distr]; }          // mask.cpp:104-121: the nested BSDF's components + an ENull | EFrontSide | EBackSide one
+        if (mat->type == MI_BSDF_BUMPMAP || mat->type == MI_BSDF_NORMALMAP) { wrapped = true; mat = &materials[mat->distr]; }     // the nested BSDF's component types (bumpmap.cpp:97-100)
+        bool backside, smooth, coated = false;
+        if (mat->type == MI_BSDF_COATING || mat->type == MI_BSDF_ROUGHCOATING) { coated = true; wrapped = true; mat = &materials[mat->distr]; }      // coating.cpp:166-173: the nested components + a delta reflection that is EFrontSide | EBackSide
+        if (mat->type == MI_BSDF_BLEND) {                                                           // the two BSDFs' components (blendbsdf.cpp:103-134)
+            backside = (mat->flags & MI_BSDF_FLAG_TWOSIDED) != 0; smooth = false; wrapped = true;
+            for (int c = 0; c < 2; ++c) { const mi_material &ch = materials[(uint32_t) mat->eta[c]]; backside |= leafBackside(ch); smooth |= leafSmooth(ch); }
+        } else if (mat->type == MI_BSDF_MIXTURE) {                                                         // the children's components (mixturebsdf.cpp:150-166)
+            backside = (mat->flags & MI_BSDF_FLAG_TWOSIDED) != 0; smooth = false; wrapped = true;
+            for (uint32_t c = 0; c < mat->distr; ++c) { const mi_material &ch = materials[(uint32_t) (c < 3 ? mat->reflectance[c] : mat->eta[0])]; backside |= leafBackside(ch); smooth |= leafSmooth(ch); }
+        } else { backside = leafBackside(*mat); smooth = leafSmooth(*mat); }
+        return ((backside || masked || coated) ? 2u : 0u) | (smooth ? 0u : 4u) | ((mat->type != MI_BSDF_DIFFUSE || masked || wrapped) ? 8u : 0u);
+}
+void SceneHost::buildMaterialTables() {
+    materialFlagTable.resize(materials.size());
+    for (uint32_t i = 0; i < materials.size(); ++i) materialFlagTable[i] = materialFlagBits(i);
+    // what the reference's configure() derives from a BSDF's own parameters
+    std::vector<MaterialD> &mats = materialsD; mats.resize(materials.size());
+    for (size_t i = 0; i < materials.size(); ++i) memcpy(&mats[i], &materials[i], sizeof(MaterialD));
+    for (MaterialD &m : mats) if (m.type == MI_BSDF_ROUGHCOATING) {      // RoughCoating::configure (roughcoating.cpp:205-209): the same weight, thickness in eta[1]
+        float avg = 0.0f; for (int c = 0; c < 3; ++c) avg += (float) exp((double) (m.reflectance[c] * (-2 * m.eta[1])));
+        avg = avg * (1.0f / 3); m.k[0] = 1.0f / (avg + 1.0f);
+    }
+    for (MaterialD &m : mats) if (m.type == MI_BSDF_COATING) {      // SmoothCoating::configure (coating.cpp:182-186): m_specularSamplingWeight from the layer's average absorption -> k[0]
+        float avg = 0.0f; for (int c = 0; c < 3; ++c) avg += (float) exp((double) (m.reflectance[c] * (-2 * m.alpha)));      // Spectrum::exp = math::fastexp per channel, then average()
+        avg = avg * (1.0f / 3); m.k[0] = 1.0f / (avg + 1.0f);
+    }
+    for (MaterialD &m : mats) {          // plastic / roughplastic: m_specularSamplingWeight = sAvg / (dAvg + sAvg) over Texture::getAverage() (plastic.cpp:204-207, roughplastic.cpp:244-246) -> eta[1]
+        if (m.type != MI_BSDF_PLASTIC && m.type != MI_BSDF_ROUGHPLASTIC) continue;
+        float d[3] = {m.reflectance[0], m.reflectance[1], m.reflectance[2]}; const uint32_t tex = (m.flags >> 8) & 0xFFFFu;
+        if (tex && tex <= textures.size()) {     // checkerboard.cpp:102-104, gridtexture.cpp:116-121; a bitmap's average is input (color0, from TMIPMap::getAverage)
+            const mi_texture &t = textures[tex - 1];
+            for (int c = 0; c < 3; ++c) {
+                if (t.type == MI_TEXTURE_CHECKERBOARD) d[c] = (t.color0[c] + t.color1[c]) * 0.5f;
+                else if (t.type == MI_TEXTURE_GRID) { const float iw = std::max(0.0f, 1 - 2 * t.line_width), ia = iw * iw, la = 1 - ia; d[c] = t.color1[c] * la + t.color0[c] * ia; }
+                else d[c] = t.color0[c];
+            }
+        }
+        const float dl = d[0] * 0.212671f + d[1] * 0.715160f + d[2] * 0.072169f, sl = m.specular[0] * 0.212671f + m.specular[1] * 0.715160f + m.specular[2] * 0.072169f;
+        m.eta[1] = sl / (dl + sl);
+    }
+}
+void SceneHost::buildEmitterTables() {
+    auto vert = [&](uint32_t i) { return mk(pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]); };
     // --- emitters (scene.cpp:383-388; pmf.h:56-58,103-116; trimesh.cpp:389-402; triangle.cpp:61-67)
     const uint32_t ne = (uint32_t) emitters.size();
     emitterCdf.assign(ne + 1, 0.0f); emittersD.assign(ne, EmitterD{}); areaCdf.clear(); emitterNorm = 0.0f;
@@ -521,43 +629,10 @@ void SceneHost::commitHost() {
         d.inv_area = 1.0f / sum;
     }
     if (areaCdf.empty()) areaCdf.push_back(0.0f);
-
-    /* --- reconstruction filter table (src/libcore/rfilter.cpp:37-56; eval of src/rfilters/box.cpp:31-48, gaussian.cpp:30-57, tent.cpp:36-38,
-     * mitchell.cpp:49-61, catmullrom.cpp:36-49, lanczos.cpp:36-46).  filter_radius / filter_stddev carry: box radius; gaussian stddev (in
-     * filter_stddev); mitchell B, C; lanczos lobes (in filter_radius) */
-    {
-        const uint32_t kind = filterKind;
-        float radius = kind == 0 ? filterRadius + 1e-5f : kind == 1 ? 4.0f * filterStddev : kind == 2 ? 1.0f : kind == 5 ? (float) (int) filterRadius : 2.0f;
-        float alpha = -1.0f / (2.0f * filterStddev * filterStddev), bias = std::exp(alpha * radius * radius);
-        const float B = kind == 3 ? filterRadius : 0.0f, C = kind == 3 ? filterStddev : 0.5f;
-        float sum = 0.0f;
-        for (int i = 0; i < MI_FILTER_RES; ++i) {
-            float x = (radius * (float) i) / (float) MI_FILTER_RES, v;
-            if (kind == 0) v = std::fabs(x) <= radius ? 1.0f : 0.0f;
-            else if (kind == 1) v = std::max(0.0f, std::exp(alpha * x * x) - bias);
-            else if (kind == 2) v = std::max(0.0f, 1.0f - std::fabs(x / radius));
-            else if (kind == 5) {
-                float ax = std::fabs(x);
-                if (ax < 1e-4f) v = 1.0f; else if (ax > radius) v = 0.0f;
-                else { float x1 = MI_PI * ax, x2 = x1 / radius; v = (std::sin(x1) * std::sin(x2)) / (x1 * x2); }
-            } else {
-                float ax = std::fabs(x), x2 = ax * ax, x3 = x2 * ax;
-                if (ax < 1) v = 1.0f / 6.0f * ((12 - 9 * B - 6 * C) * x3 + (-18 + 12 * B + 6 * C) * x2 + (6 - 2 * B));
-                else if (ax < 2) v = 1.0f / 6.0f * ((-B - 6 * C) * x3 + (6 * B + 30 * C) * x2 + (-12 * B - 48 * C) * ax + (8 * B + 24 * C));
-                else v = 0.0f;
-            }
-            filterValues[i] = v; sum += v;
-        }
-        filterValues[MI_FILTER_RES] = 0.0f;
-        filterScale = (float) MI_FILTER_RES / radius; filterRadiusEff = radius;
-        border = (int) std::ceil(radius - 0.5f);
-        sum *= 2 * radius / (float) MI_FILTER_RES;
-        float norm = 1.0f / sum;
-        for (int i = 0; i < MI_FILTER_RES; ++i) filterValues[i] *= norm;
-    }
-    // --- environment emitter tables (envmap.cpp:264-330 configure, :336-347 createShape: sphere around kd-tree box + sensor position, x1.5)
     envIndex = -1; envConstant = false;
     for (uint32_t e = 0; e < ne; ++e) if (emitters[e].type == MI_EMITTER_ENVMAP || emitters[e].type == MI_EMITTER_CONSTANT) { envIndex = (int) e; envConstant = emitters[e].type == MI_EMITTER_CONSTANT; }
+}
+void SceneHost::buildBoundingSpheres() {
     {   // bounding spheres: environment emitters (envmap.cpp:336-347, constant.cpp:69-74: scene box incl. the sensor, x 1.5); directional.cpp:87-93 (kd-tree box, x 1.1)
         V3 blo = mk(aabbLo[0], aabbLo[1], aabbLo[2]), bhi = mk(aabbHi[0], aabbHi[1], aabbHi[2]);
         V3 c0 = (bhi + blo) * 0.5f, cm0 = c0 - bhi;
@@ -567,46 +642,169 @@ void SceneHost::commitHost() {
         V3 c = (bhi + blo) * 0.5f, cm = c - bhi;
         envBsCenter[0] = c.x; envBsCenter[1] = c.y; envBsCenter[2] = c.z; envBsRadius = std::max(MI_EPSILON, std::sqrt(dot(cm, cm)) * 1.5f);
     }
-    if (envIndex >= 0 && !envConstant) {
-        const int W = (int) envW, H = (int) envH;
-        auto texel = [&](int x, int y) { const float *p = &envRGB[((size_t) y * W + x) * 3]; return mk(p[0], p[1], p[2]); };
-        auto lum = [](V3 c) { return c.x * 0.212671f + c.y * 0.715160f + c.z * 0.072169f; };
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) envToWorld3[i * 3 + j] = envToWorld[i * 4 + j];
-        { const float *m = envToWorld3; float det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]); float id = 1.0f / det;
-          float *o = envToLocal3;
-          o[0] = (m[4] * m[8] - m[5] * m[7]) * id; o[1] = (m[2] * m[7] - m[1] * m[8]) * id; o[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-          o[3] = (m[5] * m[6] - m[3] * m[8]) * id; o[4] = (m[0] * m[8] - m[2] * m[6]) * id; o[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-          o[6] = (m[3] * m[7] - m[4] * m[6]) * id; o[7] = (m[1] * m[6] - m[0] * m[7]) * id; o[8] = (m[0] * m[4] - m[1] * m[3]) * id; }
-        envCdfCols.assign((size_t) (W + 1) * H, 0.0f); envCdfRows.assign((size_t) H + 1, 0.0f); envRowWeights.assign((size_t) H, 0.0f);
-        size_t colPos = 0, rowPos = 0; float rowSum = 0.0f;
-        envCdfRows[rowPos++] = 0;
-        for (int y = 0; y < H; ++y) {
-            float colSum = 0; envCdfCols[colPos++] = 0;
-            for (int x = 0; x < W; ++x) { colSum += lum(texel(x, y)); envCdfCols[colPos++] = colSum; }
-            float normalization = 1.0f / colSum;
-            for (int x = 1; x < W; ++x) envCdfCols[colPos - x - 1] *= normalization;
-            envCdfCols[colPos - 1] = 1.0f;
-            float weight = std::sin(((float) y + 0.5f) * MI_PI / (float) H);
-            envRowWeights[y] = weight; rowSum += colSum * weight; envCdfRows[rowPos++] = rowSum;
-        }
-        float normalization = 1.0f / rowSum;
-        for (int y = 1; y < H; ++y) envCdfRows[rowPos - y - 1] *= normalization;
-        envCdfRows[rowPos - 1] = 1.0f;
-        // guide tables: the index lower_bound(cdf, b / K) for every bucket boundary (b / K is exact: K is a power of two), one table for the rows, one per row for the columns
-        auto pow2ge = [](uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; };
-        envGuideKR = std::min<uint32_t>(pow2ge((uint32_t) H), 4096u); envGuideKC = std::min<uint32_t>(pow2ge((uint32_t) W) / 4u > 0 ? pow2ge((uint32_t) W) / 4u : 1u, 1024u);
-        auto guideOf = [](const float *cdf, uint32_t size, uint32_t K, uint16_t *out) {
-            for (uint32_t b = 0; b <= K; ++b) { const float x = (float) b / (float) K; out[b] = b == K ? (uint16_t) (size + 1) : (uint16_t) (std::lower_bound(cdf, cdf + size + 1, x) - cdf); }
-        };
-        if ((uint32_t) W + 1 < 65535u && (uint32_t) H + 1 < 65535u) {
-            envGuideRows.assign(envGuideKR + 1, 0); guideOf(envCdfRows.data(), (uint32_t) H, envGuideKR, envGuideRows.data());
-            envGuideCols.assign((size_t) H * (envGuideKC + 1), 0);
-            for (int y = 0; y < H; ++y) guideOf(envCdfCols.data() + (size_t) y * (W + 1), (uint32_t) W, envGuideKC, envGuideCols.data() + (size_t) y * (envGuideKC + 1));
-        } else { envGuideRows.clear(); envGuideCols.clear(); envGuideKR = envGuideKC = 0; }
-        envNormalization = 1.0f / (rowSum * (2 * MI_PI / (float) W) * (MI_PI / (float) H));
+}
+void SceneHost::buildEnvTransform() {
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) envToWorld3[i * 3 + j] = envToWorld[i * 4 + j];
+    { const float *m = envToWorld3; float det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]); float id = 1.0f / det;
+      float *o = envToLocal3;
+      o[0] = (m[4] * m[8] - m[5] * m[7]) * id; o[1] = (m[2] * m[7] - m[1] * m[8]) * id; o[2] = (m[1] * m[5] - m[2] * m[4]) * id;
+      o[3] = (m[5] * m[6] - m[3] * m[8]) * id; o[4] = (m[0] * m[8] - m[2] * m[6]) * id; o[5] = (m[2] * m[3] - m[0] * m[5]) * id;
+      o[6] = (m[3] * m[7] - m[4] * m[6]) * id; o[7] = (m[1] * m[6] - m[0] * m[7]) * id; o[8] = (m[0] * m[4] - m[1] * m[3]) * id; }
+}
+// d.cam_dx / d.cam_dy: PerspectiveCameraImpl::m_dx / m_dy (perspective.cpp:159-163)
+void SceneHost::syncCameraD() {
+    memcpy(d.s2c, s2c, 64); memcpy(d.c2w, c2w, 64); d.near_clip = nearClip; d.far_clip = farClip;
+    const float *m = s2c; const float irx = 1.0f / (float) width, iry = 1.0f / (float) height;
+    auto pt = [&](float px, float py, float *o) {
+        float x = m[0] * px + m[1] * py + m[2] * 0.0f + m[3], y = m[4] * px + m[5] * py + m[6] * 0.0f + m[7], z = m[8] * px + m[9] * py + m[10] * 0.0f + m[11], w = m[12] * px + m[13] * py + m[14] * 0.0f + m[15];
+        if (w != 1.0f) { float r = 1.0f / w; x *= r; y *= r; z *= r; }
+        o[0] = x; o[1] = y; o[2] = z; };
+    float p0[3], px[3], py[3]; pt(0.0f, 0.0f, p0); pt(irx, 0.0f, px); pt(0.0f, iry, py);
+    for (int i = 0; i < 3; ++i) { d.cam_dx[i] = px[i] - p0[i]; d.cam_dy[i] = py[i] - p0[i]; }
+    memcpy(d.dir_bs_center, dirBsCenter, 12); d.dir_bs_radius = dirBsRadius;
+    d.env_bs_radius = envBsRadius; memcpy(d.env_bs_center, envBsCenter, 12);
+}
+void SceneHost::syncEmittersD() { d.emitter_norm = emitterNorm; }
+void SceneHost::syncEnvD() {
+    if (envIndex < 0 || envConstant) return;
+    d.env_scale = envScale; memcpy(d.env_to_world, envToWorld3, 36); memcpy(d.env_to_local, envToLocal3, 36);
+}
+
+// ------------------------------------------------------------------------------------------------ in-place edits of a committed scene
+// An edit changes numbers.  Whatever selects kernel variants, table sizes or the per-triangle layout is fixed at commit: such a change is refused, naming the first record.
+int SceneHost::updateCamera(const float *s2cIn, const float *c2wIn, float nearIn, float farIn, std::string &msg) {
+    if (!s2cIn || !c2wIn) { msg = "mi_scene_update_camera: null argument"; return MI_ERR_INVALID; }
+    if (!committed) { msg = "mi_scene_update_camera: scene not committed"; return MI_ERR_INVALID; }
+    memcpy(s2c, s2cIn, 64); memcpy(c2w, c2wIn, 64); nearClip = nearIn; farClip = farIn;
+    buildBoundingSpheres();      // the environment emitters' sphere includes the sensor position
+    syncCameraD(); ++revision;
+    return MI_OK;
+}
+int SceneHost::updateMaterials(const mi_material *m, uint32_t n, std::string &msg, bool *flagsChanged) {
+    if (flagsChanged) *flagsChanged = false;
+    if (!m || !n) { msg = "mi_scene_update_materials: null argument"; return MI_ERR_INVALID; }
+    if (!committed) { msg = "mi_scene_update_materials: scene not committed"; return MI_ERR_INVALID; }
+    if (n != materials.size()) { msg = "mi_scene_update_materials: the record count changes (" + std::to_string(materials.size()) + " -> " + std::to_string(n) + "); commit a new scene"; return MI_ERR_UNSUPPORTED; }
+    auto refuse = [&](uint32_t i, const char *what) { msg = "mi_scene_update_materials: material " + std::to_string(i) + " changes " + what + "; an update changes values only, commit a new scene"; return MI_ERR_UNSUPPORTED; };
+    for (uint32_t i = 0; i < n; ++i) {
+        const mi_material &a = materials[i], &b = m[i];
+        if (a.type != b.type) return refuse(i, "its type");
+        if ((a.flags ^ b.flags) & 0xFFFF00u) return refuse(i, "its texture binding");
+        if ((a.flags ^ b.flags) & (MI_BSDF_FLAG_ANISOTROPIC | MI_BSDF_FLAG_NONLINEAR | MI_BSDF_FLAG_SAMPLE_VISIBLE)) return refuse(i, "its anisotropic / nonlinear / sampleVisible bit");
+        const uint32_t t = a.type;
+        if ((t == MI_BSDF_MASK || t == MI_BSDF_MIXTURE || t == MI_BSDF_BUMPMAP || t == MI_BSDF_NORMALMAP || t == MI_BSDF_COATING || t == MI_BSDF_ROUGHCOATING || t == MI_BSDF_BLEND) && a.distr != b.distr)
+            return refuse(i, "`distr` of a wrapper (its nested record / child count)");
+        if (t == MI_BSDF_MIXTURE) for (uint32_t c = 0; c < a.distr && c < 4; ++c) if ((c < 3 ? a.reflectance[c] : a.eta[0]) != (c < 3 ? b.reflectance[c] : b.eta[0])) return refuse(i, "the child indices of a mixturebsdf");
+        if (t == MI_BSDF_BLEND && (a.eta[0] != b.eta[0] || a.eta[1] != b.eta[1])) return refuse(i, "the child indices of a blendbsdf");
+        if ((t == MI_BSDF_ROUGHPLASTIC || t == MI_BSDF_ROUGHCOATING) && (a.k[1] != b.k[1] || a.k[2] != b.k[2])) return refuse(i, "the offset / length of its rough-transmittance slice (k[1], k[2])");
     }
-    // Sobol film resolution (src/samplers/sobol.cpp:147-157)
-    { uint32_t r = std::max(width, height), p = 1, l = 0; while (p < r) { p <<= 1; ++l; } resolution = (float) p; logRes = l; }
+    { const int rc = validateMaterials(m, n, msg); if (rc) return rc; }
+    materials.assign(m, m + n);
+    const std::vector<uint32_t> before = materialFlagTable;
+    buildMaterialTables();
+    if (before != materialFlagTable) {      // the bits sit in every primitive that uses the material, group members included
+        for (TriShade &ts : shade) ts.flags = (ts.flags & ~MI_MATERIAL_FLAG_BITS) | materialFlagTable[ts.material];
+        for (size_t i = 0; i < analyticD.size(); ++i) analyticD[i].flags = (analyticD[i].flags & ~MI_MATERIAL_FLAG_BITS) | materialFlagTable[analytic[i].bsdf];
+        if (flagsChanged) *flagsChanged = true;
+    }
+    ++revision;
+    return MI_OK;
+}
+int SceneHost::updateEmitters(const mi_emitter *e, uint32_t n, std::string &msg) {
+    if (!e || !n) { msg = "mi_scene_update_emitters: null argument"; return MI_ERR_INVALID; }
+    if (!committed) { msg = "mi_scene_update_emitters: scene not committed"; return MI_ERR_INVALID; }
+    if (n != emitters.size()) { msg = "mi_scene_update_emitters: the record count changes (" + std::to_string(emitters.size()) + " -> " + std::to_string(n) + "); commit a new scene"; return MI_ERR_UNSUPPORTED; }
+    for (uint32_t i = 0; i < n; ++i) {
+        const char *what = emitters[i].type != e[i].type ? "its type" : emitters[i].shape != e[i].shape ? "its shape" : nullptr;
+        if (what) { msg = "mi_scene_update_emitters: emitter " + std::to_string(i) + " changes " + what + "; an update changes values only, commit a new scene"; return MI_ERR_UNSUPPORTED; }
+    }
+    { const int rc = validateEmitters(e, n, msg); if (rc) return rc; }
+    emitters.assign(e, e + n);
+    buildEmitterTables(); syncEmittersD(); ++revision;
+    return MI_OK;
+}
+int SceneHost::updateEnvmapTransform(const float *toWorld16, float scale, std::string &msg) {
+    if (!toWorld16) { msg = "mi_scene_update_envmap_transform: null argument"; return MI_ERR_INVALID; }
+    if (!committed) { msg = "mi_scene_update_envmap_transform: scene not committed"; return MI_ERR_INVALID; }
+    if (envIndex < 0 || envConstant) { msg = "mi_scene_update_envmap_transform: the scene has no envmap emitter"; return MI_ERR_INVALID; }
+    memcpy(envToWorld, toWorld16, 64); envScale = scale;
+    buildEnvTransform(); syncEnvD(); ++revision;      // the CDFs are over unscaled luminance: they stay
+    return MI_OK;
+}
+
+int validateMaterials(const mi_material *m, uint32_t n, std::string &msg) {
+    auto fail = [&](int code, const char *text) { msg = text; return code; };
+    auto isWrapper = [](uint32_t t) { return t == MI_BSDF_MASK || t == MI_BSDF_MIXTURE || t == MI_BSDF_BUMPMAP || t == MI_BSDF_NORMALMAP || t == MI_BSDF_COATING || t == MI_BSDF_BLEND || t == MI_BSDF_ROUGHCOATING; };
+    auto hasDelta = [](uint32_t t) { return t == MI_BSDF_CONDUCTOR || t == MI_BSDF_DIELECTRIC || t == MI_BSDF_THINDIELECTRIC || t == MI_BSDF_PLASTIC; };
+    for (uint32_t i = 0; i < n; ++i) {
+        if (m[i].type > MI_BSDF_ROUGHCOATING) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: implemented BSDFs: diffuse, roughdiffuse, phong, ward, coating, roughcoating, blendbsdf, roughconductor, conductor, dielectric, plastic, roughdielectric, difftrans, roughplastic, thindielectric, mask, mixturebsdf, bumpmap, normalmap (those without transmission optionally twosided)");
+        if (m[i].type == MI_BSDF_MASK && (m[i].distr >= n || m[m[i].distr].type == MI_BSDF_MASK || (m[i].flags & MI_BSDF_FLAG_TWOSIDED))) return fail(MI_ERR_INVALID, "mi_scene_set_materials: a mask refers to its nested material record by index (not another mask) and cannot itself be twosided");
+        if (m[i].type == MI_BSDF_BLEND) {
+            int deltas = 0;
+            for (int c = 0; c < 2; ++c) {
+                const float idxf = m[i].eta[c];
+                if (!(idxf >= 0) || idxf >= (float) n || isWrapper(m[(uint32_t) idxf].type)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: the two BSDFs of a blendbsdf are plain BSDF records (indices in eta[0], eta[1])");
+                if (((m[(uint32_t) idxf].flags >> 8) & 0xFFFFu)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: textures on the BSDFs inside a blendbsdf are not implemented");
+                deltas += hasDelta(m[(uint32_t) idxf].type);
+            }
+            if (deltas > 1) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a blendbsdf of two BSDFs that both have a Dirac delta component is not implemented");
+        }
+        if (m[i].type == MI_BSDF_ROUGHCOATING) {
+            if (m[i].distr >= n || isWrapper(m[m[i].distr].type)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a roughcoating nests a plain BSDF record (index in `distr`)");
+            const mi_material &nm = m[m[i].distr];
+            if ((nm.flags & MI_BSDF_FLAG_TWOSIDED) || hasDelta(nm.type) || nm.type == MI_BSDF_ROUGHDIELECTRIC || nm.type == MI_BSDF_DIFFTRANS || nm.type == MI_BSDF_NULL)
+                return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: the BSDF under a roughcoating is a reflective one without a Dirac delta lobe, `twosided` goes on the coating");
+            if (!(m[i].eta[0] > 0) || m[i].eta[0] == 1.0f) return fail(MI_ERR_INVALID, "The interior and exterior indices of refraction must be positive and differ!");      // roughcoating.cpp:126-128
+            if (m[i].eta[2] != 0.0f && m[i].eta[2] != 1.0f && m[i].eta[2] != 2.0f) return fail(MI_ERR_INVALID, "Specified an invalid distribution, must be \"beckmann\", \"ggx\", or \"phong\"/\"as\"!");
+            if ((m[i].flags >> 8) & 0xFFFFu) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a textured sigmaA is not implemented");
+        }
+        if (m[i].type == MI_BSDF_COATING) {
+            // adapters nest in the order mask -> bumpmap / normalmap -> coating -> plain BSDF (a coating over a mixturebsdf, or as the child of one, is not implemented)
+            if (m[i].distr >= n || isWrapper(m[m[i].distr].type)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a coating nests a plain BSDF record (index in `distr`)");
+            const mi_material &nm = m[m[i].distr];
+            if ((nm.flags & MI_BSDF_FLAG_TWOSIDED) || nm.type == MI_BSDF_DIELECTRIC || nm.type == MI_BSDF_ROUGHDIELECTRIC || nm.type == MI_BSDF_DIFFTRANS || nm.type == MI_BSDF_THINDIELECTRIC || nm.type == MI_BSDF_NULL)
+                return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: the BSDF under a coating is a reflective one, `twosided` goes on the coating");
+            if (!(m[i].eta[0] > 0) || m[i].eta[0] == 1.0f) return fail(MI_ERR_INVALID, "The interior and exterior indices of refraction must be positive and differ!");      // coating.cpp:119-121
+            if ((m[i].flags >> 8) & 0xFFFFu) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a textured sigmaA is not implemented");
+        }
+        if (m[i].type == MI_BSDF_BUMPMAP || m[i].type == MI_BSDF_NORMALMAP) {
+            // adapters nest in the order mask -> bumpmap / normalmap -> mixturebsdf -> plain BSDF
+            if (m[i].distr >= n || m[m[i].distr].type == MI_BSDF_MASK || m[m[i].distr].type == MI_BSDF_BUMPMAP || m[m[i].distr].type == MI_BSDF_NORMALMAP) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a bumpmap / normalmap nests a plain BSDF or a mixturebsdf (record index in `distr`)");
+            if (m[i].flags & MI_BSDF_FLAG_TWOSIDED) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: put `twosided` on the BSDF nested in a bumpmap / normalmap, not on the adapter");
+            if (!((m[i].flags >> 8) & 0xFFFFu)) return fail(MI_ERR_INVALID, m[i].type == MI_BSDF_BUMPMAP ? "A displacement texture must be specified" : "A normal map texture must be specified");   // bumpmap.cpp:88-89
+        }
+        if (m[i].type == MI_BSDF_MIXTURE) {
+            if (m[i].distr < 2 || m[i].distr > 4) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a mixturebsdf holds 2..4 BSDFs");
+            float total = 0; int deltas = 0;
+            for (uint32_t c = 0; c < m[i].distr; ++c) {
+                const float idxf = c < 3 ? m[i].reflectance[c] : m[i].eta[0], w = c < 3 ? m[i].k[c] : m[i].specular[0];
+                if (!(idxf >= 0) || idxf >= (float) n || isWrapper(m[(uint32_t) idxf].type)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: the children of a mixturebsdf are plain BSDF records (indices in reflectance[0..2], eta[0])");
+                if (((m[(uint32_t) idxf].flags >> 8) & 0xFFFFu)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: textures on the children of a mixturebsdf are not implemented");
+                if (!(w >= 0)) return fail(MI_ERR_INVALID, "Invalid BSDF weight!");                                    // mixturebsdf.cpp:82-83
+                total += w; deltas += hasDelta(m[(uint32_t) idxf].type);
+            }
+            if (!(total > 0)) return fail(MI_ERR_INVALID, "The weights must sum to a value greater than zero!");       // mixturebsdf.cpp:126-127
+            if (deltas > 1) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: a mixturebsdf with more than one child that has a Dirac delta component is not implemented");
+        }
+        if ((m[i].type == MI_BSDF_DIELECTRIC || m[i].type == MI_BSDF_ROUGHDIELECTRIC || m[i].type == MI_BSDF_DIFFTRANS || m[i].type == MI_BSDF_THINDIELECTRIC) && (m[i].flags & MI_BSDF_FLAG_TWOSIDED)) return fail(MI_ERR_INVALID, "Only BSDFs without a transmission component can be nested!");   // twosided.cpp:86-88
+        if ((m[i].type == MI_BSDF_DIELECTRIC || m[i].type == MI_BSDF_PLASTIC || m[i].type == MI_BSDF_ROUGHDIELECTRIC || m[i].type == MI_BSDF_ROUGHPLASTIC || m[i].type == MI_BSDF_THINDIELECTRIC) && !(m[i].eta[0] > 0)) return fail(MI_ERR_INVALID, "The interior and exterior indices of refraction must be positive!");
+        if (m[i].type == MI_BSDF_ROUGHPLASTIC && (m[i].distr > 2 || (m[i].flags & MI_BSDF_FLAG_ANISOTROPIC)))
+            return fail(MI_ERR_INVALID, "The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!");        // roughplastic.cpp:225-227
+        if ((m[i].type == MI_BSDF_ROUGHCONDUCTOR || m[i].type == MI_BSDF_ROUGHDIELECTRIC) && m[i].distr > 2) return fail(MI_ERR_INVALID, "Specified an invalid distribution, must be \"beckmann\", \"ggx\", or \"phong\"/\"as\"!");   // microfacet.h:113-115
+        if ((m[i].flags & MI_BSDF_FLAG_ANISOTROPIC) && m[i].type != MI_BSDF_ROUGHCONDUCTOR && m[i].type != MI_BSDF_ROUGHDIELECTRIC && m[i].type != MI_BSDF_WARD) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_materials: anisotropic roughness is implemented for roughconductor and roughdielectric");
+    }
+    return MI_OK;
+}
+int validateEmitters(const mi_emitter *e, uint32_t n, std::string &msg) {
+    auto fail = [&](int code, const char *text) { msg = text; return code; };
+    uint32_t nEnv = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (e[i].type > MI_EMITTER_COLLIMATED || e[i].type == 6u) return fail(MI_ERR_UNSUPPORTED, "mi_scene_set_emitters: implemented emitters: area, envmap, constant, point, spot, directional, collimated");
+        nEnv += e[i].type == MI_EMITTER_ENVMAP || e[i].type == MI_EMITTER_CONSTANT;
+        if (e[i].type == MI_EMITTER_SPOT && !(e[i].cutoff >= e[i].beam && e[i].beam >= 0 && e[i].cutoff > 0)) return fail(MI_ERR_INVALID, "mi_scene_set_emitters: spot needs cutoffAngle >= beamWidth >= 0");   // spot.cpp:77
+    }
+    if (nEnv > 1) return fail(MI_ERR_INVALID, "The scene may only contain one environment emitter");      // scene.cpp:542-543
+    return MI_OK;
 }
 
 }  // namespace mi

@@ -38,11 +38,36 @@ struct SceneHost {
     void *dNodes = nullptr, *dTris = nullptr, *dShade = nullptr, *dI2 = nullptr, *dNrm = nullptr, *dMaterials = nullptr, *dEmitters = nullptr,
          *dEmitterCdf = nullptr, *dAnalytic = nullptr, *dInstances = nullptr, *dMaterialTables = nullptr, *dTriUV = nullptr, *dTextures = nullptr, *dTexLevels = nullptr, *dTexTexels = nullptr, *dMipLut = nullptr, *dEmitterX = nullptr, *dAreaCdf = nullptr, *dFilter = nullptr, *dEnvRGB = nullptr, *dEnvCols = nullptr, *dEnvRows = nullptr, *dEnvWeights = nullptr, *dPacketGroups = nullptr, *dPacketExact = nullptr, *dSobolM32 = nullptr, *dSobolVdc = nullptr, *dSobolVdcInv = nullptr;
     DScene d{};
+    // derived from the materials alone (scene_build.cpp): the records the device reads (MaterialD with the sampling weights the reference's configure() computes) and,
+    // per material, the three flag bits of TriShade::flags / AnalyticD::flags (MI_MATERIAL_FLAG_BITS) of every primitive that uses it
+    std::vector<MaterialD> materialsD; std::vector<uint32_t> materialFlagTable; void *dMaterialFlags = nullptr;
+    // in-place edits of a committed scene (mi_scene_update_*): `revision` counts them, `treeBuilds` counts commitHost() runs -- an edit never moves it
+    uint64_t revision = 0, treeBuilds = 0;
 
     void commitHost();          // scene_build.cpp
     int upload(int device);     // api.cpp
     void release();
+    // pieces of commitHost() / upload() that an edit repeats (scene_build.cpp; no device calls)
+    uint32_t materialFlagBits(uint32_t bsdf) const;
+    void buildMaterialTables();         // materialsD + materialFlagTable
+    void buildEmitterTables();          // emittersD, emitterCdf, emitterNorm, emitterX, areaCdf, hasDeltaEmitters, envIndex, envConstant
+    void buildBoundingSpheres();        // dirBs*, envBs* (the latter includes the sensor position)
+    void buildEnvTransform();           // envToWorld3, envToLocal3
+    void syncCameraD();                 // d.s2c, d.c2w, clip planes, cam_dx / cam_dy, env bounding sphere
+    void syncEmittersD();               // d.emitter_norm
+    void syncEnvD();                    // d.env_to_world, d.env_to_local, d.env_scale
+    // The edits.  Each returns MI_OK or an error code with `msg` set and then leaves the scene as it was; on success the host tables above and `d` are those of a
+    // fresh commit with the new inputs, `revision` has advanced, and the caller re-sends the small device tables (api.cpp).
+    int updateCamera(const float *s2c16, const float *c2w16, float nearClip, float farClip, std::string &msg);
+    int updateMaterials(const mi_material *m, uint32_t n, std::string &msg, bool *flagsChanged);
+    int updateEmitters(const mi_emitter *e, uint32_t n, std::string &msg);
+    int updateEnvmapTransform(const float *toWorld16, float scale, std::string &msg);
     ~SceneHost() { release(); }
 };
+
+#define MI_MATERIAL_FLAG_BITS 14u       // bit1 back side, bit2 no smooth component, bit3 not a plain diffuse record
+// value checks of mi_scene_set_materials / mi_scene_set_emitters, shared with the in-place updates (scene_build.cpp)
+int validateMaterials(const mi_material *m, uint32_t n, std::string &msg);
+int validateEmitters(const mi_emitter *e, uint32_t n, std::string &msg);
 
 }  // namespace mi

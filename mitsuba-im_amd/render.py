@@ -8,6 +8,10 @@ keep the linear values; `.png` / `.jpg` get ldrfilm's default sRGB encoding (ima
 A scene whose integrator is `multichannel` (one of path / volpath_simple / volpath plus `field` integrators) writes one OpenEXR file holding the radiance and one channel
 group per field, named by the film's `channelNames` (default: `color`, then the field kinds) and shaped by its `pixelFormat` list: `<name>.R/.G/.B` for `rgb`, `<name>.Y`
 for `luminance`.  Other output formats cannot hold the groups: an error that names `.exr`.
+
+`--orbit N [--orbit-axis x|y|z]` renders a turntable: N frames with the camera rotated in steps of 360 / N degrees about the axis through the centre of the scene's
+box.  The scene is committed once; every frame is an in-place camera edit of the committed scene (Scene.update_camera), a clear and a run -- no tree build, no
+upload -- and is written to `<output>_000.<ext>`, `<output>_001.<ext>`, ...
 """
 import argparse
 import sys
@@ -58,6 +62,36 @@ def field_channel_groups(sc, rgb, fields, field_names):
     return np.stack(planes, 2), chan
 
 
+def orbit_cameras(sc, n, axis="y"):
+    """The n camera-to-world matrices of a turntable: frame f is the scene's camera rotated by 360 f / n degrees about `axis` through the centre of the scene's box
+    (the box of the mesh vertices and of the analytic shapes' origins).  Frame 0 is the scene's own camera, bit for bit."""
+    pts = [np.asarray(sc.pos, np.float64).reshape(-1, 3)] + [np.asarray(a["to_world"], np.float64)[:3, 3].reshape(1, 3) for a in (sc.get("analytic") or [])]
+    pts = np.concatenate(pts); centre = (pts.min(0) + pts.max(0)) * 0.5
+    k = "xyz".index(axis); i, j = (k + 1) % 3, (k + 2) % 3
+    c2w = np.asarray(sc.cam_to_world, np.float64); out = [np.ascontiguousarray(sc.cam_to_world, np.float32)]
+    for f in range(1, n):
+        t = 2.0 * np.pi * f / n; rot = np.eye(4); rot[i, i] = rot[j, j] = np.cos(t); rot[i, j] = -np.sin(t); rot[j, i] = np.sin(t)
+        to_c = np.eye(4); to_c[:3, 3] = -centre; back = np.eye(4); back[:3, 3] = centre
+        out.append(np.ascontiguousarray(back @ rot @ to_c @ c2w, np.float32))
+    return out
+
+
+def write_outputs(sc, render, out, rgb=None, fields=None):
+    """the developed film (and, for a multichannel scene, the field groups) of `render` -> `out`; False (message printed) when the format cannot hold them"""
+    if rgb is None:
+        rgb = render.read_film(2); fields = render.read_fields(2) if render.field_names else None
+    if fields is not None:
+        if not out.endswith(".exr"):
+            print(f"error: {out}: a render with field channels holds several channel groups, which only the .exr output can store", file=sys.stderr)
+            return False
+        from . import imageio
+        planes, chan = field_channel_groups(sc, rgb, fields, render.field_names)
+        imageio.write_exr(out, planes, chan)
+    else:
+        write_image(out, rgb)
+    return True
+
+
 def main(argv=None):
     from . import xml_scene
     from .api import Scene, Render, MiError
@@ -68,21 +102,39 @@ def main(argv=None):
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--sampler", choices=["sobol", "independent"], default=None, help="replace the scene's sampler plugin (keeps its sampleCount)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--orbit", type=int, default=0, metavar="N", help="turntable of N frames about the scene box's centre: one commit, one in-place camera edit per frame")
+    ap.add_argument("--orbit-axis", choices=["x", "y", "z"], default="y")
     a = ap.parse_args(argv)
     params = {}
     for d in a.defines:
         if "=" not in d:
             raise SystemExit(f"-D expects name=value, got {d!r}")
         k, v = d.split("=", 1); params[k] = v
+    if a.orbit < 0:
+        raise SystemExit("--orbit expects a frame count >= 1")
     try:
         t0 = time.perf_counter()
         sc = xml_scene.load_scene(a.scene, params, sampler=a.sampler)
         if a.spp is not None:
             sc.spp = a.spp
+        out = a.output or (a.scene.rsplit(".", 1)[0] + ".exr")          # hdrfilm's default fileFormat (src/films/hdrfilm.cpp: openexr)
         t1 = time.perf_counter()
         scene = Scene(sc, device=a.device)
         render = Render(scene, device=a.device)
         t2 = time.perf_counter()
+        n = sc.width * sc.height * sc.spp
+        if a.orbit:
+            stem, ext = out.rsplit(".", 1); frame_s = []
+            for f, c2w in enumerate(orbit_cameras(sc, a.orbit, a.orbit_axis)):
+                tf = time.perf_counter()
+                scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far); render.clear(); render.run()
+                frame_s.append(time.perf_counter() - tf)
+                if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}"):
+                    return 1
+            rev, builds = scene.revision(); mean = sum(frame_s) / len(frame_s)
+            print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s once ({builds} tree build, {rev} camera edits), "
+                  f"{a.orbit} frames, render {mean:.3f} s per frame ({n / mean / 1e6:.1f} Msamples/s) -> {stem}_000.{ext} .. {stem}_{a.orbit - 1:03d}.{ext}")
+            return 0
         render.run()
         rgb = render.read_film(2)
         fields = render.read_fields(2) if render.field_names else None
@@ -90,17 +142,8 @@ def main(argv=None):
     except (xml_scene.SceneError, MiError, OSError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 1
-    out = a.output or (a.scene.rsplit(".", 1)[0] + ".exr")          # hdrfilm's default fileFormat (src/films/hdrfilm.cpp: openexr)
-    if fields is not None:
-        if not out.endswith(".exr"):
-            print(f"error: {out}: a render with field channels holds several channel groups, which only the .exr output can store", file=sys.stderr)
-            return 1
-        from . import imageio
-        planes, chan = field_channel_groups(sc, rgb, fields, render.field_names)
-        imageio.write_exr(out, planes, chan)
-    else:
-        write_image(out, rgb)
-    n = sc.width * sc.height * sc.spp
+    if not write_outputs(sc, render, out, rgb, fields):
+        return 1
     print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s, "
           f"render {t3 - t2:.3f} s ({n / (t3 - t2) / 1e6:.1f} Msamples/s) -> {out}")
     return 0
