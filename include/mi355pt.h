@@ -221,6 +221,20 @@ int mi_scene_update_camera(mi_scene *s, const float *sample_to_camera16, const f
 int mi_scene_update_materials(mi_scene *s, const mi_material *materials, uint32_t n);
 int mi_scene_update_emitters(mi_scene *s, const mi_emitter *emitters, uint32_t n);
 int mi_scene_update_envmap_transform(mi_scene *s, const float *to_world16, float scale);   /* envmap scenes only */
+/* Vertex edit: new positions pos[n_verts * 3] for the WHOLE concatenated vertex array of mi_scene_set_triangles, and new vertex normals nrm[n_verts * 3] if and only if
+ * the scene was committed with normals.  Indices, texture coordinates and shapes stay as committed.  The device recomputes every per-triangle record (Wald records, the
+ * geometric words of the shading records, UV tangents) and REFITS the existing tree bottom-up: topology, child codes and node numbering stay, every box is recomputed
+ * from the boxes below it.  The scene box, the packet tables of small scenes, the area lights' CDFs and the bounding spheres follow on the host.  Results equal those of
+ * a fresh commit of the new vertices bit for bit (the nearest hit does not depend on the tree).  Like the other updates: between runs, advances `revision`, never moves
+ * `tree_builds`, a render handle follows after mi_render_clear, a replica is a scene of its own.  Returns when the device has finished.
+ * MI_ERR_INVALID: scene not committed, null argument, n_verts differs from the committed count, nrm given for a scene without normals or missing for one with, a
+ * non-finite position or normal (the message names the first vertex), a run in flight.  MI_ERR_UNSUPPORTED: scenes with shape groups / instances (the message names
+ * the first instance): group boxes, instance boxes and the two-level tree are not refitted.  A refused call leaves the scene untouched, and so does a failed allocation
+ * of the edit's own device tables (MI_ERR_DEVICE, "the scene is unchanged").  Any other MI_ERR_DEVICE (a failed copy or launch) comes after the host side has taken the
+ * new vertices: host and device tables are then out of step and the scene must be committed again.
+ * The tree keeps the topology the SAH build chose for the committed vertices; after a large deformation it is no longer the optimum for the new ones and traversal slows
+ * down (results stay exact).  A fresh mi_scene_commit is the remedy. */
+int mi_scene_update_vertices(mi_scene *s, const float *pos, const float *nrm, uint32_t n_verts);
 /* revision: in-place edits applied so far; tree_builds: host-side builds (tree, triangle records) this scene has gone through -- an update never moves it.  Either may be NULL */
 int mi_scene_revision(mi_scene *s, uint64_t *revision, uint64_t *tree_builds);
 
@@ -315,6 +329,17 @@ int mi_debug_intersect_inst(mi_scene *s, const float *rays8, uint64_t n, int any
 typedef struct { uint32_t wide, bvh_depth, bvh_stack_direct, max_stack_seen; uint64_t rays_counted; } mi_fused_debug_info;   /* node kind (1: 4-wide), the builder's stack bounds, deepest stack any ray of this call held */
 int mi_debug_intersect_fused(mi_scene *s, const float *rays8, uint64_t n, int any_hit, const uint32_t *seg_counts, uint32_t n_seg, uint32_t thr, uint32_t grid, uint32_t lds_stack,
                              float *out_hits4, mi_fused_debug_info *info);
+/* One device table of a committed scene as it is now, read back whole: what = MI_GEOMETRY_NODES (64-B tree nodes), _LEAF_RECORDS (48-B Wald records in leaf order,
+ * word 10 = primitive index), _TRI_SHADE (128-B shading records, triangle order), _TRI_UV (48 B, only scenes with texture coordinates), _PACKET_EXACT (48-B Wald records,
+ * triangle order), _PACKET_GROUPS (48-B pass-1 records).  The caller gives the size in bytes (mi_debug_geometry_bytes); a wrong size is MI_ERR_INVALID. */
+#define MI_GEOMETRY_NODES 0
+#define MI_GEOMETRY_LEAF_RECORDS 1
+#define MI_GEOMETRY_TRI_SHADE 2
+#define MI_GEOMETRY_TRI_UV 3
+#define MI_GEOMETRY_PACKET_EXACT 4
+#define MI_GEOMETRY_PACKET_GROUPS 5
+int mi_debug_geometry_bytes(mi_scene *s, uint32_t what, uint64_t *bytes);
+int mi_debug_read_geometry(mi_scene *s, uint32_t what, void *out, uint64_t bytes);
 int mi_debug_sobol(mi_scene *s, const uint32_t *px_py_k, uint64_t n, uint32_t ndims, uint64_t *out_index, float *out_values);
 int mi_debug_camera_rays(mi_scene *s, const float *sample_pos2, uint64_t n, float *out_rays8);
 int mi_debug_libm(int fn, const float *x, const float *y, uint64_t n, float *out);   /* the device restatements of glibc's routines (libm_glibc.h) as the kernels call them:

@@ -27,6 +27,7 @@ int mi_host_set_camera(void *integrator, const float *sample_to_camera16, const 
 int mi_host_set_materials(void *integrator, const mi_material *materials, uint32_t n);
 int mi_host_set_emitters(void *integrator, const mi_emitter *emitters, uint32_t n);
 int mi_host_set_envmap_transform(void *integrator, const float *to_world16, float scale);
+int mi_host_set_vertices(void *integrator, const float *pos, const float *nrm, uint32_t n_verts);   /* mi_scene_update_vertices */
 void mi_host_cancel(void *integrator);
 const char *mi_host_statistics(void *integrator);
 #ifdef __cplusplus

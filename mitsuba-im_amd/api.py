@@ -89,11 +89,11 @@ class MiFusedDebugInfo(C.Structure):
 
 EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_scene_create", "mi_scene_destroy", "mi_scene_set_triangles",
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_film",
-           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
+           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
-           "mi_render_set_profiling", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_sincosf", "mi_debug_libm"]
+           "mi_render_set_profiling", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_geometry_bytes", "mi_debug_read_geometry"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
-                "mi_host_set_camera", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform"]
+                "mi_host_set_camera", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices"]
 
 
 def build(force=False):
@@ -134,6 +134,7 @@ class Lib:
         L.mi_scene_update_materials.argtypes = [vp, vp, u32]
         L.mi_scene_update_emitters.argtypes = [vp, vp, u32]
         L.mi_scene_update_envmap_transform.argtypes = [vp, vp, f32]
+        L.mi_scene_update_vertices.argtypes = [vp, vp, vp, u32]
         L.mi_scene_revision.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
         L.mi_render_merge_film.argtypes = [vp, vp]
         L.mi_render_create.argtypes = [vp, C.POINTER(MiRenderParams), C.POINTER(vp)]
@@ -159,6 +160,8 @@ class Lib:
         L.mi_debug_camera_rays.argtypes = [vp, vp, u64, vp]
         L.mi_debug_sincosf.argtypes = [vp, u64, vp]
         L.mi_debug_libm.argtypes = [i32, vp, vp, u64, vp]
+        L.mi_debug_geometry_bytes.argtypes = [vp, u32, C.POINTER(u64)]
+        L.mi_debug_read_geometry.argtypes = [vp, u32, vp, u64]
 
     def check(self, rc):
         if rc != 0:
@@ -286,6 +289,12 @@ class Scene:
         L.check(L.L.mi_scene_set_film(h, sc.width, sc.height, sc.filter, sc.filter_radius, sc.filter_stddev))
         L.check(L.L.mi_scene_commit(h, device))
 
+    def clone(self, device=0):
+        """mi_scene_clone: a replica on `device` (a scene of its own: the host-side build is reused, every table uploaded again)."""
+        out = Scene.__new__(Scene); out.L = self.L; out.sc = self.sc; out.h = None
+        h = C.c_void_p(); self.L.check(self.L.L.mi_scene_clone(self.h, device, C.byref(h))); out.h = h
+        return out
+
     def close(self):
         if getattr(self, "h", None):
             self.L.L.mi_scene_destroy(self.h); self.h = None
@@ -315,6 +324,24 @@ class Scene:
         tw = np.ascontiguousarray(to_world, np.float32).reshape(4, 4)
         self.L.check(self.L.L.mi_scene_update_envmap_transform(self.h, _p(tw), float(scale)))
         self.sc.envmap = dict(self.sc.envmap, to_world=tw, scale=float(scale))
+
+    def update_vertices(self, pos, nrm=None):
+        """New positions [n_verts, 3] (and vertex normals, if and only if the scene has them) for the committed vertex array: per-triangle records and a refit of the
+        existing tree on the device, no tree build.  Scenes with shape groups / instances are refused (MiError code 3)."""
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3); nrm = None if nrm is None else np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        if nrm is not None and len(nrm) != len(pos): raise ValueError("update_vertices: one normal per vertex")
+        self.L.check(self.L.L.mi_scene_update_vertices(self.h, _p(pos), _p(nrm), len(pos)))
+        self.sc.pos = pos
+        if nrm is not None: self.sc.nrm = nrm
+
+    GEOMETRY_TABLES = {"nodes": (0, 64), "leaf_records": (1, 48), "tri_shade": (2, 128), "tri_uv": (3, 48), "packet_exact": (4, 48), "packet_groups": (5, 48)}
+
+    def read_geometry(self, what):
+        """One device table as it is now -> uint32 array [records, words]: "nodes", "leaf_records" (word 10 = primitive), "tri_shade", "tri_uv", "packet_exact", "packet_groups"."""
+        code, rec = self.GEOMETRY_TABLES[what]; n = C.c_uint64()
+        self.L.check(self.L.L.mi_debug_geometry_bytes(self.h, code, C.byref(n)))
+        out = np.zeros((n.value // rec, rec // 4), np.uint32)
+        self.L.check(self.L.L.mi_debug_read_geometry(self.h, code, _p(out), n.value)); return out
 
     def revision(self):
         """(revision, tree_builds): in-place edits applied so far / host-side tree builds (1 for the life of a committed scene)."""
@@ -488,6 +515,15 @@ class HostIntegrator:
         if self.L.mi_host_set_camera(self.h, _p(s2c), _p(c2w), float(near), float(far)) != 0:
             raise RuntimeError(self.L.mi_host_last_error().decode())
         sc = self.scene.sc; sc.sample_to_camera = s2c; sc.cam_to_world = c2w; sc.near = float(near); sc.far = float(far)
+
+    def set_vertices(self, pos, nrm=None):
+        """MIPathTracerHIP::setVertices: mi_scene_update_vertices on the borrowed scene and on every replica, between two render() calls."""
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3); nrm = None if nrm is None else np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        self.L.mi_host_set_vertices.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        if self.L.mi_host_set_vertices(self.h, _p(pos), _p(nrm), len(pos)) != 0:
+            raise RuntimeError(self.L.mi_host_last_error().decode())
+        self.scene.sc.pos = pos
+        if nrm is not None: self.scene.sc.nrm = nrm
 
     def statistics(self):
         return (self.L.mi_host_statistics(self.h) or b"").decode()

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <set>
 #include "scene_host.h"
+#include "geometry_records.h"
 #include "queues.h"
 #include "fields.h"
 
@@ -49,6 +50,8 @@ void mi_launch_field_film(const DScene &, const FieldArgs &, const Queues &, con
 void mi_launch_field_samples(const DScene &, const FieldArgs &, const Queues &, uint64_t, float *, hipStream_t);
 void mi_launch_field_layout(const float *, const float *, float *, int, int, int, int, int, hipStream_t);
 void mi_launch_patch_material_flags(TriShade *, uint32_t, const uint32_t *, uint32_t, hipStream_t);
+void mi_launch_tri_records(const mi::GeoEditTables &, hipStream_t);
+void mi_launch_refit_level(const mi::GeoEditTables &, const uint32_t *, uint32_t, uint32_t, uint32_t, hipStream_t);
 }
 
 // Shading stage dispatch.  Dynamic LDS: Sobol nibble tables + (small scenes) the scene tables + (scenes with non-diffuse BSDFs) the per-wave path-order list.
@@ -256,7 +259,7 @@ template <typename T> static int up(void **dst, const std::vector<T> &v) {
     return 0;
 }
 void SceneHost::release() {
-    void **ps[] = {&dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
+    void **ps[] = {&dPos, &dLeafSlot, &dLeafBox, &dNodeBox, &dRefitOrder, &dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
     for (void **p : ps) if (*p) { (void) hipFree(*p); *p = nullptr; }
 }
 int SceneHost::upload(int dev) {
@@ -414,10 +417,11 @@ int mi_scene_clone(mi_scene *s, uint32_t device, mi_scene **out) {
     if (!s->h.committed) return fail(MI_ERR_INVALID, "mi_scene_clone: scene not committed");
     int devCount = 0; HIPCHK(hipGetDeviceCount(&devCount));
     if ((int) device >= devCount) return fail(MI_ERR_DEVICE, "mi_scene_clone: no such HIP device");
+    s->h.refreshHostGeometry();                     // after vertex edits the per-triangle mirrors and the nodes are brought up to date only when someone reads them
     mi_scene *c = new mi_scene();
     c->h = s->h;                                    // inputs + host-derived data
     {   // the copy must not own the source's device allocations
-        void **ps[] = {&c->h.dMaterialFlags, &c->h.dMedia, &c->h.dPrimMedia, &c->h.dPacketGroups, &c->h.dPacketExact, &c->h.dTexLevels, &c->h.dTexTexels, &c->h.dMipLut, &c->h.dTriUV, &c->h.dTextures, &c->h.dMaterialTables, &c->h.dInstances, &c->h.dEmitterX, &c->h.dAnalytic, &c->h.dNodes, &c->h.dTris, &c->h.dShade, &c->h.dI2, &c->h.dNrm, &c->h.dMaterials, &c->h.dEmitters, &c->h.dEmitterCdf, &c->h.dAreaCdf, &c->h.dFilter, &c->h.dSobolM32, &c->h.dSobolVdc, &c->h.dSobolVdcInv, &c->h.dEnvRGB, &c->h.dEnvCols, &c->h.dEnvRows, &c->h.dEnvWeights, &c->h.dEnvGuideRows, &c->h.dEnvGuideCols};
+        void **ps[] = {&c->h.dPos, &c->h.dLeafSlot, &c->h.dLeafBox, &c->h.dNodeBox, &c->h.dRefitOrder, &c->h.dMaterialFlags, &c->h.dMedia, &c->h.dPrimMedia, &c->h.dPacketGroups, &c->h.dPacketExact, &c->h.dTexLevels, &c->h.dTexTexels, &c->h.dMipLut, &c->h.dTriUV, &c->h.dTextures, &c->h.dMaterialTables, &c->h.dInstances, &c->h.dEmitterX, &c->h.dAnalytic, &c->h.dNodes, &c->h.dTris, &c->h.dShade, &c->h.dI2, &c->h.dNrm, &c->h.dMaterials, &c->h.dEmitters, &c->h.dEmitterCdf, &c->h.dAreaCdf, &c->h.dFilter, &c->h.dSobolM32, &c->h.dSobolVdc, &c->h.dSobolVdcInv, &c->h.dEnvRGB, &c->h.dEnvCols, &c->h.dEnvRows, &c->h.dEnvWeights, &c->h.dEnvGuideRows, &c->h.dEnvGuideCols};
         for (void **p : ps) *p = nullptr;
         c->h.committed = false;
     }
@@ -475,6 +479,48 @@ int mi_scene_update_envmap_transform(mi_scene *s, const float *toWorld, float sc
     if (!s || !toWorld) return fail(MI_ERR_INVALID, "mi_scene_update_envmap_transform: null argument");
     UPDATE_ENTER("mi_scene_update_envmap_transform");
     std::string msg; const int rc = s->h.updateEnvmapTransform(toWorld, scale, msg); if (rc) return fail(rc, msg);
+    return MI_OK;
+}
+// Vertex edit.  Host: the checks, pos / nrm and the small tables (SceneHost::updateVertices).  Device: the new vertex arrays go up, k_tri_records rewrites every
+// per-triangle record, k_refit refits the existing tree level by level on one stream, the small tables go back into their allocations (the packet groups into a new
+// one when their count grew).  Synchronous like the other updates.
+int mi_scene_update_vertices(mi_scene *s, const float *pos, const float *nrm, uint32_t nVerts) {
+    if (!s || !pos) return fail(MI_ERR_INVALID, "mi_scene_update_vertices: null argument");
+    UPDATE_ENTER("mi_scene_update_vertices");
+    mi::SceneHost &h = s->h; const size_t cdfLen = h.areaCdf.size(), nGroups = h.packetGroups.size();
+    std::string msg; const int rc = h.checkVertices(pos, nrm, nVerts, msg); if (rc) return fail(rc, msg);
+    if (!h.geoPrepared) h.prepareGeometryEdit();      // derived from the committed tables alone: the scene itself is not changed yet
+    if (h.shade.size() != h.d.n_tris || h.nodes.size() != h.d.n_nodes || h.leafSlotOfPrim.size() != h.d.n_tris || h.leafBoxes.size() != h.tris.size() * 6 || h.nodeBoxes.size() != h.nodes.size() * 6 || h.refitOrder.size() > h.nodes.size())
+        return fail(MI_ERR_DEVICE, "mi_scene_update_vertices: host tables and device tables disagree in size");
+    HIPCHK(hipSetDevice(h.device));
+    if (!h.dPos || !h.dNodeBox || !h.dLeafSlot || !h.dLeafBox || !h.dRefitOrder) {      // first edit: the tables a commit does not need -- all five or none, and before the scene changes
+        void **five[] = {&h.dPos, &h.dNodeBox, &h.dLeafSlot, &h.dLeafBox, &h.dRefitOrder};
+        for (void **p : five) if (*p) { (void) hipFree(*p); *p = nullptr; }
+        bool bad = hipMalloc(&h.dPos, std::max<size_t>(h.pos.size() * 4, 16)) != hipSuccess || hipMalloc(&h.dNodeBox, std::max<size_t>(h.nodeBoxes.size() * 4, 16)) != hipSuccess;
+        bad = bad || mi::up(&h.dLeafSlot, h.leafSlotOfPrim) || mi::up(&h.dLeafBox, h.leafBoxes) || mi::up(&h.dRefitOrder, h.refitOrder);
+        if (bad) {
+            const std::string why = hipGetErrorString(hipGetLastError());
+            for (void **p : five) if (*p) { (void) hipFree(*p); *p = nullptr; }
+            return fail(MI_ERR_DEVICE, "mi_scene_update_vertices: allocation failed, the scene is unchanged: " + why);
+        }
+    }
+    // from here on the scene changes; a device error below leaves host and device tables out of step (see the header)
+    h.applyVertices(pos, nrm, nVerts);
+    if (h.emittersD.size() != h.d.n_emitters || h.areaCdf.size() != cdfLen) return fail(MI_ERR_DEVICE, "mi_scene_update_vertices: host tables and device tables disagree in size");
+    HIPCHK(push(h.dPos, h.pos)); HIPCHK(push(h.dNrm, h.nrm));
+    mi::GeoEditTables g{}; g.pos = (const float *) h.dPos; g.nrm = h.nrm.empty() ? nullptr : (const float *) h.dNrm; g.shade = (TriShade *) h.dShade; g.triuv = h.triuv.empty() ? nullptr : (TriUV *) h.dTriUV;
+    g.tris = const_cast<TriAccelD *>(h.d.tris); g.packetExact = (TriAccelD *) h.dPacketExact; g.leafSlot = (const uint32_t *) h.dLeafSlot; g.leafBox = (float *) h.dLeafBox;
+    g.nodes = (BvhNode *) h.dNodes; g.nodeBox = (float *) h.dNodeBox; g.nTris = h.d.n_tris; g.nPacketExact = (uint32_t) std::min<size_t>(h.packetExact.size(), h.d.n_tris); g.wide = h.wideBvh ? 1u : 0u;
+    mi_launch_tri_records(g, nullptr);
+    for (size_t l = 0; l + 1 < h.refitLevelStart.size(); ++l)      // bottom-up: level l reads the boxes levels < l wrote; stream order is the only synchronisation
+        mi_launch_refit_level(g, (const uint32_t *) h.dRefitOrder, h.refitLevelStart[l], h.refitLevelStart[l + 1] - h.refitLevelStart[l], h.d.n_nodes, nullptr);
+    HIPCHK(hipGetLastError());
+    if (h.packetGroups.size() > nGroups) {      // pairs dissolved: the pass-1 table grew
+        void *grown = nullptr; if (mi::up(&grown, h.packetGroups)) return fail(MI_ERR_DEVICE, "mi_scene_update_vertices: allocation failed");
+        HIPCHK(hipStreamSynchronize(nullptr)); (void) hipFree(h.dPacketGroups); h.dPacketGroups = grown; h.d.packet_groups = (const PacketGroupD *) grown;
+    } else HIPCHK(push(h.dPacketGroups, h.packetGroups));
+    HIPCHK(push(h.dEmitters, h.emittersD)); HIPCHK(push(h.dAreaCdf, h.areaCdf));
+    HIPCHK(hipStreamSynchronize(nullptr));
     return MI_OK;
 }
 int mi_scene_revision(mi_scene *s, uint64_t *revision, uint64_t *treeBuilds) {
@@ -1160,6 +1206,35 @@ int mi_debug_intersect_fused(mi_scene *s, const float *rays, uint64_t n, int any
     }
     for (void *p : bufs) (void) hipFree(p);
     return rc;
+}
+// One device table of the scene as it is now: 0 nodes, 1 leaf records, 2 TriShade, 3 TriUV, 4 packet-exact records, 5 packet groups.  mi_debug_geometry_bytes gives the size.
+static int geometryTable(mi_scene *s, uint32_t what, const void **ptr, uint64_t *bytes, const char *who) {
+    if (!s) return fail(MI_ERR_INVALID, std::string(who) + ": null scene");
+    if (!s->h.committed) return fail(MI_ERR_INVALID, std::string(who) + ": scene not committed");
+    const mi::SceneHost &h = s->h;
+    switch (what) {
+    case 0: *ptr = h.dNodes; *bytes = (uint64_t) h.nodes.size() * sizeof(BvhNode); break;
+    case 1: *ptr = h.d.tris; *bytes = (uint64_t) h.tris.size() * sizeof(TriAccelD); break;
+    case 2: *ptr = h.dShade; *bytes = (uint64_t) h.shade.size() * sizeof(TriShade); break;
+    case 3: *ptr = h.dTriUV; *bytes = (uint64_t) h.triuv.size() * sizeof(TriUV); break;
+    case 4: *ptr = h.dPacketExact; *bytes = (uint64_t) h.packetExact.size() * sizeof(TriAccelD); break;
+    case 5: *ptr = h.dPacketGroups; *bytes = (uint64_t) h.packetGroups.size() * sizeof(PacketGroupD); break;
+    default: return fail(MI_ERR_INVALID, std::string(who) + ": unknown table " + std::to_string(what));
+    }
+    return MI_OK;
+}
+int mi_debug_geometry_bytes(mi_scene *s, uint32_t what, uint64_t *bytes) {
+    const void *p = nullptr; uint64_t n = 0; if (!bytes) return fail(MI_ERR_INVALID, "mi_debug_geometry_bytes: null argument");
+    const int rc = geometryTable(s, what, &p, &n, "mi_debug_geometry_bytes"); if (rc) return rc;
+    *bytes = n; return MI_OK;
+}
+int mi_debug_read_geometry(mi_scene *s, uint32_t what, void *out, uint64_t bytes) {
+    const void *p = nullptr; uint64_t n = 0; const int rc = geometryTable(s, what, &p, &n, "mi_debug_read_geometry"); if (rc) return rc;
+    if (bytes != n) return fail(MI_ERR_INVALID, "mi_debug_read_geometry: table " + std::to_string(what) + " holds " + std::to_string(n) + " bytes, the caller gave " + std::to_string(bytes));
+    if (!n) return MI_OK;
+    if (!out) return fail(MI_ERR_INVALID, "mi_debug_read_geometry: null argument");
+    HIPCHK(hipSetDevice(s->h.device)); HIPCHK(hipMemcpy(out, p, n, hipMemcpyDeviceToHost));
+    return MI_OK;
 }
 int mi_debug_sobol(mi_scene *s, const uint32_t *in, uint64_t n, uint32_t ndims, uint64_t *outIdx, float *outVals) {
     if (!s || !s->h.committed || !in || !outIdx || !outVals || !n || !s->h.d.sobol_m32 || ndims > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "mi_debug_sobol: bad argument");

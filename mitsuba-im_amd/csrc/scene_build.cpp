@@ -8,6 +8,7 @@
 // (t, prim, u, v), not the tree layout.  Compiled with -ffp-contract=off: the values computed
 // here feed the bit-exact parity tests.
 #include "scene_host.h"
+#include "geometry_records.h"      // V3, triaccelLoad, the per-triangle derivation, node quantisation: shared with the device (kernels_geometry.hip)
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -15,35 +16,6 @@
 #include <limits>
 
 namespace mi {
-
-struct V3 { float x, y, z; };
-static inline V3 mk(float x, float y, float z) { return V3{x, y, z}; }
-static inline V3 operator+(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-static inline V3 operator-(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-static inline V3 operator*(V3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
-static inline float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-static inline V3 cross(V3 a, V3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-static inline float comp(V3 a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : a.z); }
-static inline V3 normalize(V3 a) { float inv = 1.0f / std::sqrt(dot(a, a)); return a * inv; }
-static inline V3 vmin(V3 a, V3 b) { return mk(std::min(a.x, b.x), std::min(a.y, b.y), std::min(a.z, b.z)); }
-static inline V3 vmax(V3 a, V3 b) { return mk(std::max(a.x, b.x), std::max(a.y, b.y), std::max(a.z, b.z)); }
-
-// reference include/mitsuba/render/triaccel.h:61-94
-static void triaccelLoad(TriAccelD &ta, V3 A, V3 B, V3 C) {
-    static const int wald[4] = {1, 2, 0, 1};
-    V3 b = C - A, c = B - A, N = cross(c, b);
-    int k = 0;
-    for (int j = 0; j < 3; ++j) if (std::fabs(comp(N, j)) > std::fabs(comp(N, k))) k = j;
-    int u = wald[k], v = wald[k + 1];
-    float n_k = comp(N, k), denom = comp(b, u) * comp(c, v) - comp(b, v) * comp(c, u);
-    std::memset(&ta, 0, sizeof(ta));
-    if (denom == 0) { ta.k = 3; return; }
-    ta.k = (uint32_t) k;
-    ta.n_u = comp(N, u) / n_k; ta.n_v = comp(N, v) / n_k; ta.n_d = dot(A, N) / n_k;
-    ta.b_nu = comp(b, u) / denom; ta.b_nv = -comp(b, v) / denom;
-    ta.a_u = comp(A, u); ta.a_v = comp(A, v);
-    ta.c_nu = comp(c, v) / denom; ta.c_nv = -comp(c, u) / denom;
-}
 
 // Analytic shapes: derived constants + Shape::getAABB (rectangle.cpp:100-119, disk.cpp:100-130, sphere.cpp:127-142, cylinder.cpp:105-107, :256-276)
 static inline V3 xfPoint(const float *m, V3 p) { return mk(m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3], m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7], m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11]); }
@@ -98,6 +70,19 @@ static void analyticPrepare(const mi_analytic &a, AnalyticD &d, V3 &lo, V3 &hi, 
     }
     d.n[0] = n.x; d.n[1] = n.y; d.n[2] = n.z; d.dpdu[0] = dpdu.x; d.dpdu[1] = dpdu.y; d.dpdu[2] = dpdu.z;
     d.center[0] = center.x; d.center[1] = center.y; d.center[2] = center.z;
+}
+
+// kd-tree box of the scene = union of the scene-level shapes' AABBs (ShapeKDTree::addShape, skdtree.cpp:68-77) -- meshes outside shape groups, analytic shapes
+// (Shape::getAABB), then `n` further boxes (lo, hi: the instances) -- enlarged like the kd-tree root (gkdtree.h:1213-1220)
+static void enlargeBox(V3 &lo, V3 &hi) { const float eps = 1e-3f; V3 e1 = hi - lo; lo = lo - mk(e1.x * eps + eps, e1.y * eps + eps, e1.z * eps + eps);
+                                         V3 e2 = hi - lo; hi = hi + mk(e2.x * eps + eps, e2.y * eps + eps, e2.z * eps + eps); }
+void SceneHost::buildSceneBox(const float *extra, uint32_t n) {
+    const float inf = std::numeric_limits<float>::infinity(); V3 lo = mk(inf, inf, inf), hi = mk(-inf, -inf, -inf);
+    for (const mi_shape &sh : shapes) { if (sh.group) continue; for (uint32_t v = 0; v < sh.vert_count; ++v) { V3 p = load3(&pos[(size_t) (sh.first_vert + v) * 3]); lo = vmin(lo, p); hi = vmax(hi, p); } }
+    for (const mi_analytic &a : analytic) { AnalyticD d; V3 alo, ahi, tl, th; analyticPrepare(a, d, alo, ahi, tl, th); lo = vmin(lo, alo); hi = vmax(hi, ahi); }
+    for (uint32_t i = 0; i < n; ++i) { lo = vmin(lo, load3(extra + (size_t) i * 6)); hi = vmax(hi, load3(extra + (size_t) i * 6 + 3)); }
+    enlargeBox(lo, hi);
+    store3(aabbLo, lo); store3(aabbHi, hi);
 }
 
 struct BuildNode { V3 lo, hi; int left = -1, right = -1, first = 0, count = 0; };
@@ -169,10 +154,11 @@ static inline int32_t leafCode(int first, int count) { return ~(int32_t) (first 
 // Unused slots of a 4-wide node carry an inverted box (qlo 255, qhi 0), but the conservative box tests of trace.h / trace_fused.h can still pass it: the slack
 // 2e-6 * t outgrows the box once the node's extent is below ~2e-6 * t on every axis (small geometry seen from far away).  So the slot's CODE must be harmless
 // too: it names a one-record leaf whose record (k = MI_K_NONE, appended after the tree's own leaf records) no triangle test accepts.
-#define MI_K_NONE 3u                    // TriAccelD::k of a record that is never hit (the value triaccelLoad gives degenerate triangles)
 
 void SceneHost::commitHost() {
     ++treeBuilds;
+    // a new tree: whatever the vertex edits of the previous one derived (slot table, level order, box scratch, the stale mark) describes a tree that no longer exists
+    geoPrepared = geoStale = false; leafSlotOfPrim.clear(); refitOrder.clear(); refitLevelStart.clear(); leafBoxes.clear(); nodeBoxes.clear();
     const uint32_t nt = (uint32_t) (idx.size() / 3), na = (uint32_t) analytic.size(), ni = (uint32_t) instances.size(), np = nt + na + ni;
     nTris = nt;
     auto vert = [&](uint32_t i) { return mk(pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]); };
@@ -190,49 +176,21 @@ void SceneHost::commitHost() {
         triaccelLoad(accel[t], p0, p1, p2); accel[t].prim = t;
         const mi_shape &sh = shapes[triShape[t]];
         TriShade &ts = shade[t];
-        ts.p0[0] = p0.x; ts.p0[1] = p0.y; ts.p0[2] = p0.z; ts.p1[0] = p1.x; ts.p1[1] = p1.y; ts.p1[2] = p1.z; ts.p2[0] = p2.x; ts.p2[1] = p2.y; ts.p2[2] = p2.z;
         ts.material = sh.bsdf; ts.emitter = sh.emitter;
         bool faceN = (sh.flags & 1u) || nrm.empty();
         const bool hasUV = (sh.flags & 2u) && !uv.empty();
         ts.flags = (faceN ? 1u : 0u) | materialFlagTable[sh.bsdf] | (hasUV ? 16u : 0u);
         ts.local_prim = t - sh.first_tri; ts.i0 = a; ts.i1 = b; i2[t] = c;
-        // face frame: skdtree.h:367-371 (face normal), util.cpp:605-610 (computeShadingFrame with dpdu = p1 - p0)
-        V3 side1 = p1 - p0, side2 = p2 - p0, fn = cross(side1, side2);
-        float len = std::sqrt(dot(fn, fn));
-        if (!(fn.x == 0 && fn.y == 0 && fn.z == 0)) { float r = 1.0f / len; fn = fn * r; }
-        V3 dpdu = side1;
-        if (hasUV) {                                             // TriMesh::computeUVTangents (trimesh.cpp:683-736)
+        if (hasUV) {
             TriUV &tu = triuv[t]; anyUV = true;
             tu.uv0[0] = uv[a * 2]; tu.uv0[1] = uv[a * 2 + 1]; tu.uv1[0] = uv[b * 2]; tu.uv1[1] = uv[b * 2 + 1]; tu.uv2[0] = uv[c * 2]; tu.uv2[1] = uv[c * 2 + 1];
-            float du1 = tu.uv1[0] - tu.uv0[0], dv1 = tu.uv1[1] - tu.uv0[1], du2 = tu.uv2[0] - tu.uv0[0], dv2 = tu.uv2[1] - tu.uv0[1];
-            V3 n = cross(side1, side2); float length = std::sqrt(dot(n, n)); V3 tdu = mk(0, 0, 0), tdv = mk(0, 0, 0);
-            if (length != 0) {
-                float determinant = du1 * dv2 - dv1 * du2;
-                if (determinant == 0) {                         // coordinateSystem(n / length, dpdu, dpdv), util.cpp:594-603
-                    float r = 1.0f / length; V3 an = n * r;
-                    if (std::fabs(an.x) > std::fabs(an.y)) { float invLen = 1.0f / std::sqrt(an.x * an.x + an.z * an.z); tdv = mk(an.z * invLen, 0.0f, -an.x * invLen); }
-                    else { float invLen = 1.0f / std::sqrt(an.y * an.y + an.z * an.z); tdv = mk(0.0f, an.z * invLen, -an.y * invLen); }
-                    tdu = cross(tdv, an);
-                } else {
-                    float invDet = 1.0f / determinant;
-                    tdu = (side1 * dv2 - side2 * dv1) * invDet;
-                    tdv = (side1 * (-du2) + side2 * du1) * invDet;
-                }
-            }
-            tu.dpdu[0] = tdu.x; tu.dpdu[1] = tdu.y; tu.dpdu[2] = tdu.z; tu.dpdv[0] = tdv.x; tu.dpdv[1] = tdv.y; tu.dpdv[2] = tdv.z;
-            dpdu = tdu;
         }
-        V3 s = normalize(dpdu - fn * dot(fn, dpdu)), tt = cross(fn, s);
-        ts.ng[0] = fn.x; ts.ng[1] = fn.y; ts.ng[2] = fn.z; ts.s[0] = s.x; ts.s[1] = s.y; ts.s[2] = s.z; ts.t[0] = tt.x; ts.t[1] = tt.y; ts.t[2] = tt.z;
+        triShadeGeometry(ts, hasUV ? &triuv[t] : nullptr, p0, p1, p2);      // p0..p2, face normal, face frame, UV tangents (geometry_records.h)
         ts.i2 = c;
         if (!faceN) {      // a smooth triangle carries its three vertex normals instead of the (unused) face frame
             for (int k = 0; k < 3; ++k) { ts.s[k] = nrm[a * 3 + k]; ts.t[k] = nrm[b * 3 + k]; ts.n2[k] = nrm[c * 3 + k]; }
         }
-        V3 lo = vmin(vmin(p0, p1), p2), hi = vmax(vmax(p0, p1), p2);
-        // conservative padding: the Wald test is evaluated in its own arithmetic, boxes may only over-approximate
-        V3 e = hi - lo; float mag = std::max(std::max(std::fabs(lo.x) + std::fabs(hi.x), std::fabs(lo.y) + std::fabs(hi.y)), std::fabs(lo.z) + std::fabs(hi.z));
-        float pad = 1e-4f * std::max(std::max(e.x, e.y), e.z) + 2e-5f * mag + 1e-7f;
-        tlo[t] = lo - mk(pad, pad, pad); thi[t] = hi + mk(pad, pad, pad); cen[t] = (lo + hi) * 0.5f;
+        triPaddedBox(p0, p1, p2, tlo[t], thi[t], cen[t]);      // conservative padding (geometry_records.h)
     }
     // --- analytic shapes: device records, boxes
     analyticD.assign(na, AnalyticD{});
@@ -240,39 +198,32 @@ void SceneHost::commitHost() {
     for (uint32_t i = 0; i < na; ++i) {
         V3 tl, th; analyticPrepare(analytic[i], analyticD[i], alo[i], ahi[i], tl, th);
         analyticD[i].flags = (analytic[i].flags & 1u) | materialFlagTable[analytic[i].bsdf];
-        V3 e = th - tl; float mag = std::max(std::max(std::fabs(tl.x) + std::fabs(th.x), std::fabs(tl.y) + std::fabs(th.y)), std::fabs(tl.z) + std::fabs(th.z));
-        float pad = 1e-4f * std::max(std::max(e.x, e.y), e.z) + 2e-5f * mag + 1e-7f;
-        tlo[nt + i] = tl - mk(pad, pad, pad); thi[nt + i] = th + mk(pad, pad, pad); cen[nt + i] = (tl + th) * 0.5f;
+        padBox(tl, th, tlo[nt + i], thi[nt + i], cen[nt + i]);
         TriAccelD rec{}; rec.k = MI_K_ANALYTIC; rec.prim = nt + i; accel.push_back(rec);
     }
     // --- kd-tree boxes of the shape groups and of the scene = union of the member shapes' AABBs (ShapeKDTree::addShape, skdtree.cpp:68-77),
     //     enlarged like the kd-tree root (gkdtree.h:1213-1220); instance boxes = the 8 transformed corners of the group box (instance.cpp:46-64)
     const float inf = std::numeric_limits<float>::infinity();
     uint32_t ng = 0; for (const mi_shape &sh : shapes) ng = std::max(ng, sh.group);
-    std::vector<V3> glo(ng + 1, mk(inf, inf, inf)), ghi(ng + 1, mk(-inf, -inf, -inf));      // slot ng = the scene level
+    std::vector<V3> glo(ng + 1, mk(inf, inf, inf)), ghi(ng + 1, mk(-inf, -inf, -inf));      // slot ng (the scene level) is used by the member lists below; the scene's box is buildSceneBox()
     auto slotOf = [&](const mi_shape &sh) { return sh.group ? sh.group - 1 : ng; };
-    auto enlarge = [](V3 &lo, V3 &hi) { const float eps = 1e-3f; V3 e1 = hi - lo; lo = lo - mk(e1.x * eps + eps, e1.y * eps + eps, e1.z * eps + eps);
-                                        V3 e2 = hi - lo; hi = hi + mk(e2.x * eps + eps, e2.y * eps + eps, e2.z * eps + eps); };
-    for (const mi_shape &sh : shapes) { uint32_t g = slotOf(sh); for (uint32_t v = 0; v < sh.vert_count; ++v) { V3 p = vert(sh.first_vert + v); glo[g] = vmin(glo[g], p); ghi[g] = vmax(ghi[g], p); } }
-    for (uint32_t g = 0; g < ng; ++g) enlarge(glo[g], ghi[g]);
-    for (uint32_t i = 0; i < na; ++i) { glo[ng] = vmin(glo[ng], alo[i]); ghi[ng] = vmax(ghi[ng], ahi[i]); }
+    for (const mi_shape &sh : shapes) { if (!sh.group) continue; uint32_t g = slotOf(sh); for (uint32_t v = 0; v < sh.vert_count; ++v) { V3 p = vert(sh.first_vert + v); glo[g] = vmin(glo[g], p); ghi[g] = vmax(ghi[g], p); } }
+    for (uint32_t g = 0; g < ng; ++g) enlargeBox(glo[g], ghi[g]);
     instancesD.assign(ni, InstanceD{});
+    std::vector<float> instBoxes((size_t) ni * 6);
     for (uint32_t i = 0; i < ni; ++i) {
         const mi_instance &in = instances[i]; const uint32_t g = in.group; V3 blo = mk(inf, inf, inf), bhi = mk(-inf, -inf, -inf);
         for (int c = 0; c < 8; ++c) {
             V3 q = xfPoint(in.to_world, mk(c & 1 ? ghi[g].x : glo[g].x, c & 2 ? ghi[g].y : glo[g].y, c & 4 ? ghi[g].z : glo[g].z));
             blo = vmin(blo, q); bhi = vmax(bhi, q);
         }
-        glo[ng] = vmin(glo[ng], blo); ghi[ng] = vmax(ghi[ng], bhi);
-        V3 e = bhi - blo; float mag = std::max(std::max(std::fabs(blo.x) + std::fabs(bhi.x), std::fabs(blo.y) + std::fabs(bhi.y)), std::fabs(blo.z) + std::fabs(bhi.z));
-        float pad = 1e-4f * std::max(std::max(e.x, e.y), e.z) + 2e-5f * mag + 1e-7f;
-        tlo[nt + na + i] = blo - mk(pad, pad, pad); thi[nt + na + i] = bhi + mk(pad, pad, pad); cen[nt + na + i] = (blo + bhi) * 0.5f;
+        store3(&instBoxes[(size_t) i * 6], blo); store3(&instBoxes[(size_t) i * 6 + 3], bhi);
+        padBox(blo, bhi, tlo[nt + na + i], thi[nt + na + i], cen[nt + na + i]);
         TriAccelD rec{}; rec.k = MI_K_INSTANCE; rec.prim = i; accel.push_back(rec);
         InstanceD &d = instancesD[i]; std::memcpy(d.to_world, in.to_world, 48); std::memcpy(d.to_object, in.to_object, 48);
         d.glo[0] = glo[g].x; d.glo[1] = glo[g].y; d.glo[2] = glo[g].z; d.ghi[0] = ghi[g].x; d.ghi[1] = ghi[g].y; d.ghi[2] = ghi[g].z; d.group = g; d.root = 0;
     }
-    enlarge(glo[ng], ghi[ng]);
-    aabbLo[0] = glo[ng].x; aabbLo[1] = glo[ng].y; aabbLo[2] = glo[ng].z; aabbHi[0] = ghi[ng].x; aabbHi[1] = ghi[ng].y; aabbHi[2] = ghi[ng].z;
+    buildSceneBox(instBoxes.data(), ni);      // aabbLo / aabbHi: scene-level meshes, analytic shapes, instances; enlarged
 
     // --- participating media: device records; per primitive the (interior, exterior) pair of its shape (triangles, then analytic shapes)
     mediaD.assign(media.size(), MediumD{});
@@ -327,24 +278,13 @@ void SceneHost::commitHost() {
                     const float inf = std::numeric_limits<float>::infinity(); V3 lo = mk(inf, inf, inf), hi = mk(-inf, -inf, -inf);
                     for (int k : kids) { lo = vmin(lo, bld.nodes[k].lo); hi = vmax(hi, bld.nodes[k].hi); }
                     if (kids.empty()) { lo = mk(0, 0, 0); hi = mk(0, 0, 0); }
-                    Bvh4Node w; std::memset(&w, 0, sizeof(w)); w.org[0] = lo.x; w.org[1] = lo.y; w.org[2] = lo.z;
-                    int ex[3];
-                    for (int a = 0; a < 3; ++a) {      // step 2^e with 255 steps covering the extent (+ one step of slack for the rounding of org + q * step)
-                        const float ext = comp(hi, a) - comp(lo, a); int e = 0; std::frexp(ext > 0 ? ext / 254.0f : 1e-30f, &e);      // ext / 254 = m 2^e, m in [0.5, 1): 2^e >= ext / 254
-                        e = std::min(std::max(e + 127, 1), 254); ex[a] = e; (a == 0 ? w.step_x : (a == 1 ? w.step_y : w.step_z)) = std::ldexp(1.0f, e - 127);
-                    }
+                    Bvh4Node w; std::memset(&w, 0, sizeof(w));
+                    int ex[3]; wideNodeFrame(w, lo, hi, ex);      // org + the three steps (geometry_records.h: the refit of a vertex edit re-derives them by the same rule)
                     int sub = 0, subD = 0;
                     for (int c = 0; c < 4; ++c) {
-                        if (c >= (int) kids.size()) { for (int a = 0; a < 3; ++a) { w.qlo[a] |= 255u << (8 * c); } w.child[c] = emptyChild; continue; }
+                        if (c >= (int) kids.size()) { wideNodeUnused(w, c); w.child[c] = emptyChild; continue; }
                         const BuildNode &k = bld.nodes[kids[c]];
-                        for (int a = 0; a < 3; ++a) {
-                            const double step = std::ldexp(1.0, ex[a] - 127), o = comp(lo, a);
-                            int ql = (int) std::floor(((double) comp(k.lo, a) - o) / step), qh = (int) std::ceil(((double) comp(k.hi, a) - o) / step);
-                            ql = std::min(std::max(ql, 0), 255); qh = std::min(std::max(qh, 0), 255);
-                            while (ql > 0 && (float) ((float) o + (float) ql * (float) step) > comp(k.lo, a)) --ql;          // the float reconstruction must enclose the child box
-                            while (qh < 255 && (float) ((float) o + (float) qh * (float) step) < comp(k.hi, a)) ++qh;
-                            w.qlo[a] |= (uint32_t) ql << (8 * c); w.qhi[a] |= (uint32_t) qh << (8 * c);
-                        }
+                        wideNodeChild(w, c, ex, lo, k.lo, k.hi);
                         if (k.count > 0) w.child[c] = leafCode(triBase + k.first, k.count);
                         else { int need = 0, needD = 0; w.child[c] = run(kids[c], need, needD); sub = std::max(sub, need); subD = std::max(subD, needD); }
                     }
@@ -418,43 +358,8 @@ void SceneHost::commitHost() {
     // packet mode (no instances, <= MI_PACKET_MAX triangles): exact records in original order + pass-1 group records (pt_types.h PacketGroupD).  Coplanar
     // pairs that form a parallelogram (the two halves of a quad) share one record: for the vertices (X, Y, Z) of a triangle, taken cyclically, the partner is
     // the triangle on {Y, Z, Y + Z - X}.  Degenerate triangles (k = 3) never hit and are dropped.
-    packetExact.assign(accel.begin(), accel.begin() + nt); packetGroups.clear(); packetGK[0] = packetGK[1] = packetGK[2] = 0;
-    {
-        float sx = 0; for (int i = 0; i < 3; ++i) sx = std::max(sx, std::max(std::fabs(aabbLo[i]), std::fabs(aabbHi[i])));
-        packetScale = sx;
-        if (nt <= MI_PACKET_MAX && ni == 0) {
-            const float tol = 1e-6f * std::max(sx, 1e-20f);
-            auto near = [&](V3 a, V3 b) { return std::fabs(a.x - b.x) <= tol && std::fabs(a.y - b.y) <= tol && std::fabs(a.z - b.z) <= tol; };
-            std::vector<uint8_t> used(nt, 0); std::vector<PacketGroupD> byAxis[3];
-            for (uint32_t t1 = 0; t1 < nt; ++t1) {
-                if (used[t1] || accel[t1].k > 2) continue;
-                used[t1] = 1;
-                const V3 P[3] = {vert(idx[t1 * 3]), vert(idx[t1 * 3 + 1]), vert(idx[t1 * 3 + 2])};
-                int partner = -1, rot = 0;
-                for (uint32_t t2 = t1 + 1; t2 < nt && partner < 0; ++t2) {
-                    if (used[t2] || accel[t2].k != accel[t1].k) continue;
-                    const V3 Q[3] = {vert(idx[t2 * 3]), vert(idx[t2 * 3 + 1]), vert(idx[t2 * 3 + 2])};
-                    for (int r = 0; r < 3 && partner < 0; ++r) {
-                        const V3 X = P[r], Y = P[(r + 1) % 3], Z = P[(r + 2) % 3], X2 = Y + Z - X;
-                        for (int a = 0; a < 3 && partner < 0; ++a)      // t2's vertex set == {Y, Z, X2} in any order
-                            for (int b = 0; b < 3 && partner < 0; ++b) { if (b == a) continue; const int c = 3 - a - b;
-                                if (near(Q[a], Y) && near(Q[b], Z) && near(Q[c], X2)) { partner = (int) t2; rot = r; } }
-                    }
-                }
-                // relabel (X, Y, Z) -> (A*, B*, C*) = (Z, X, Y): a cyclic rotation (same plane, same orientation), shared edge YZ = C*A* <-> u* = 0
-                const V3 X = P[rot], Y = P[(rot + 1) % 3], Z = P[(rot + 2) % 3];
-                TriAccelD ta; triaccelLoad(ta, partner >= 0 ? Z : P[0], partner >= 0 ? X : P[1], partner >= 0 ? Y : P[2]);
-                if (ta.k > 2) continue;
-                if (partner >= 0) used[partner] = 1;
-                PacketGroupD g; g.n_u = ta.n_u; g.n_v = ta.n_v; g.n_d = ta.n_d; g.a_u = ta.a_u; g.a_v = ta.a_v; g.b_nu = ta.b_nu; g.b_nv = ta.b_nv; g.c_nu = ta.c_nu; g.c_nv = ta.c_nv;
-                g.margin = 1.1f * (std::fabs(ta.b_nu) + std::fabs(ta.b_nv) + std::fabs(ta.c_nu) + std::fabs(ta.c_nv));
-                g.prim0 = t1; g.prim1 = partner >= 0 ? (uint32_t) partner : 0xFFFFFFFFu;
-                byAxis[ta.k].push_back(g);
-            }
-            for (int axis = 0; axis < 3; ++axis) { packetGroups.insert(packetGroups.end(), byAxis[axis].begin(), byAxis[axis].end()); packetGK[axis] = (uint32_t) packetGroups.size(); }
-        }
-    }
-    if (packetGroups.empty()) packetGroups.push_back(PacketGroupD{});
+    packetExact.assign(accel.begin(), accel.begin() + nt);
+    buildPacketTables();
     if (packetExact.empty()) packetExact.push_back(TriAccelD{});
 
     buildEmitterTables();
@@ -582,6 +487,50 @@ void SceneHost::buildMaterialTables() {
         const float dl = d[0] * 0.212671f + d[1] * 0.715160f + d[2] * 0.072169f, sl = m.specular[0] * 0.212671f + m.specular[1] * 0.715160f + m.specular[2] * 0.072169f;
         m.eta[1] = sl / (dl + sl);
     }
+}
+// Packet mode tables that depend on the vertex positions: packetScale, the pass-1 group records (pair detection over <= MI_PACKET_MAX triangles) and their axis ranges.
+void SceneHost::buildPacketTables() {
+    const uint32_t nt = (uint32_t) (idx.size() / 3), ni = (uint32_t) instances.size();
+    auto vert = [&](uint32_t i) { return mk(pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]); };
+    std::vector<uint32_t> kOf;      // projection axis of every triangle's Wald record (3: degenerate); only the packet needs it
+    if (nt <= MI_PACKET_MAX && ni == 0) { kOf.resize(nt); for (uint32_t t = 0; t < nt; ++t) { TriAccelD ta; triaccelLoad(ta, vert(idx[t * 3]), vert(idx[t * 3 + 1]), vert(idx[t * 3 + 2])); kOf[t] = ta.k; } }
+    packetGroups.clear(); packetGK[0] = packetGK[1] = packetGK[2] = 0;
+    {
+        float sx = 0; for (int i = 0; i < 3; ++i) sx = std::max(sx, std::max(std::fabs(aabbLo[i]), std::fabs(aabbHi[i])));
+        packetScale = sx;
+        if (nt <= MI_PACKET_MAX && ni == 0) {
+            const float tol = 1e-6f * std::max(sx, 1e-20f);
+            auto near = [&](V3 a, V3 b) { return std::fabs(a.x - b.x) <= tol && std::fabs(a.y - b.y) <= tol && std::fabs(a.z - b.z) <= tol; };
+            std::vector<uint8_t> used(nt, 0); std::vector<PacketGroupD> byAxis[3];
+            for (uint32_t t1 = 0; t1 < nt; ++t1) {
+                if (used[t1] || kOf[t1] > 2) continue;
+                used[t1] = 1;
+                const V3 P[3] = {vert(idx[t1 * 3]), vert(idx[t1 * 3 + 1]), vert(idx[t1 * 3 + 2])};
+                int partner = -1, rot = 0;
+                for (uint32_t t2 = t1 + 1; t2 < nt && partner < 0; ++t2) {
+                    if (used[t2] || kOf[t2] != kOf[t1]) continue;
+                    const V3 Q[3] = {vert(idx[t2 * 3]), vert(idx[t2 * 3 + 1]), vert(idx[t2 * 3 + 2])};
+                    for (int r = 0; r < 3 && partner < 0; ++r) {
+                        const V3 X = P[r], Y = P[(r + 1) % 3], Z = P[(r + 2) % 3], X2 = Y + Z - X;
+                        for (int a = 0; a < 3 && partner < 0; ++a)      // t2's vertex set == {Y, Z, X2} in any order
+                            for (int b = 0; b < 3 && partner < 0; ++b) { if (b == a) continue; const int c = 3 - a - b;
+                                if (near(Q[a], Y) && near(Q[b], Z) && near(Q[c], X2)) { partner = (int) t2; rot = r; } }
+                    }
+                }
+                // relabel (X, Y, Z) -> (A*, B*, C*) = (Z, X, Y): a cyclic rotation (same plane, same orientation), shared edge YZ = C*A* <-> u* = 0
+                const V3 X = P[rot], Y = P[(rot + 1) % 3], Z = P[(rot + 2) % 3];
+                TriAccelD ta; triaccelLoad(ta, partner >= 0 ? Z : P[0], partner >= 0 ? X : P[1], partner >= 0 ? Y : P[2]);
+                if (ta.k > 2) continue;
+                if (partner >= 0) used[partner] = 1;
+                PacketGroupD g; g.n_u = ta.n_u; g.n_v = ta.n_v; g.n_d = ta.n_d; g.a_u = ta.a_u; g.a_v = ta.a_v; g.b_nu = ta.b_nu; g.b_nv = ta.b_nv; g.c_nu = ta.c_nu; g.c_nv = ta.c_nv;
+                g.margin = 1.1f * (std::fabs(ta.b_nu) + std::fabs(ta.b_nv) + std::fabs(ta.c_nu) + std::fabs(ta.c_nv));
+                g.prim0 = t1; g.prim1 = partner >= 0 ? (uint32_t) partner : 0xFFFFFFFFu;
+                byAxis[ta.k].push_back(g);
+            }
+            for (int axis = 0; axis < 3; ++axis) { packetGroups.insert(packetGroups.end(), byAxis[axis].begin(), byAxis[axis].end()); packetGK[axis] = (uint32_t) packetGroups.size(); }
+        }
+    }
+    if (packetGroups.empty()) packetGroups.push_back(PacketGroupD{});
 }
 void SceneHost::buildEmitterTables() {
     auto vert = [&](uint32_t i) { return mk(pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]); };
@@ -730,6 +679,77 @@ int SceneHost::updateEnvmapTransform(const float *toWorld16, float scale, std::s
     memcpy(envToWorld, toWorld16, 64); envScale = scale;
     buildEnvTransform(); syncEnvD(); ++revision;      // the CDFs are over unscaled luminance: they stay
     return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ vertex edits (mi_scene_update_vertices)
+// What a vertex edit needs beyond the committed tables, derived once at the first edit: where each triangle's leaf record sits, the padded boxes of the leaf records
+// that do not move (analytic shapes; the never-hit record of unused 4-wide slots stays empty), and the order in which the existing nodes are refitted -- by height,
+// height 0 = every child is a leaf, so that a node comes after all of its inner children.
+void SceneHost::prepareGeometryEdit() {
+    const uint32_t nt = nTris; const float inf = std::numeric_limits<float>::infinity();
+    leafSlotOfPrim.assign(nt, 0u); leafBoxes.assign(tris.size() * 6, 0.0f);
+    for (size_t slot = 0; slot < tris.size(); ++slot) {
+        const TriAccelD &r = tris[slot]; float *box = &leafBoxes[slot * 6];
+        store3(box, mk(inf, inf, inf)); store3(box + 3, mk(-inf, -inf, -inf));
+        if (r.k == MI_K_ANALYTIC && r.prim >= nt && r.prim - nt < analytic.size()) {
+            AnalyticD d; V3 alo, ahi, tl, th, plo, phi, cen; analyticPrepare(analytic[r.prim - nt], d, alo, ahi, tl, th); padBox(tl, th, plo, phi, cen);
+            store3(box, plo); store3(box + 3, phi);
+        } else if (r.k <= MI_K_NONE && r.prim < nt) leafSlotOfPrim[r.prim] = (uint32_t) slot;
+    }
+    const size_t nn = nodes.size(); std::vector<int> height(nn, -1);
+    struct Walk { const std::vector<BvhNode> &nodes; std::vector<int> &height; bool wide;
+        int of(int32_t n) {
+            int h = 0;
+            if (wide) { Bvh4Node w; std::memcpy(&w, &nodes[n], sizeof(w)); for (int c = 0; c < 4; ++c) if (!wideSlotUnused(w, c) && w.child[c] >= 0) h = std::max(h, of(w.child[c]) + 1); }
+            else { const BvhNode &b = nodes[n]; if (b.c0 >= 0) h = std::max(h, of(b.c0) + 1); if (b.c1 >= 0) h = std::max(h, of(b.c1) + 1); }
+            height[n] = h; return h;
+        } } walk{nodes, height, wideBvh};
+    int top = nn ? walk.of(0) : -1;
+    refitLevelStart.assign((size_t) top + 2, 0u); refitOrder.clear();
+    for (size_t i = 0; i < nn; ++i) if (height[i] >= 0) ++refitLevelStart[(size_t) height[i] + 1];
+    for (size_t l = 1; l < refitLevelStart.size(); ++l) refitLevelStart[l] += refitLevelStart[l - 1];
+    refitOrder.resize(refitLevelStart.back());
+    { std::vector<uint32_t> fill(refitLevelStart.begin(), refitLevelStart.end() - 1); for (size_t i = 0; i < nn; ++i) if (height[i] >= 0) refitOrder[fill[(size_t) height[i]]++] = (uint32_t) i; }
+    nodeBoxes.assign(nn * 6, 0.0f);
+    geoPrepared = true;
+}
+int SceneHost::checkVertices(const float *posIn, const float *nrmIn, uint32_t nVerts, std::string &msg) const {
+    const std::string who = "mi_scene_update_vertices: ";
+    if (!posIn) { msg = who + "null argument"; return MI_ERR_INVALID; }
+    if (!committed) { msg = who + "scene not committed"; return MI_ERR_INVALID; }
+    if (!instances.empty()) { msg = who + "instance 0 (of shape group " + std::to_string(instances[0].group) + "): group boxes, instance boxes and the two-level tree are not refitted; commit a new scene"; return MI_ERR_UNSUPPORTED; }
+    for (size_t i = 0; i < shapes.size(); ++i) if (shapes[i].group) { msg = who + "shape " + std::to_string(i) + " is a member of shape group " + std::to_string(shapes[i].group - 1) + " (instances): group boxes are not refitted; commit a new scene"; return MI_ERR_UNSUPPORTED; }
+    if ((size_t) nVerts * 3 != pos.size() || !nTris) { msg = who + "the vertex count changes (" + std::to_string(pos.size() / 3) + " -> " + std::to_string(nVerts) + "); an update moves the committed vertices, commit a new scene"; return MI_ERR_INVALID; }
+    if (nrmIn && nrm.empty()) { msg = who + "vertex normals given, but the scene was committed without normals"; return MI_ERR_INVALID; }
+    if (!nrmIn && !nrm.empty()) { msg = who + "the scene was committed with vertex normals: new normals are required"; return MI_ERR_INVALID; }
+    for (size_t i = 0; i < (size_t) nVerts * 3; ++i) {
+        if (!std::isfinite(posIn[i])) { msg = who + "vertex " + std::to_string(i / 3) + " has a non-finite position"; return MI_ERR_INVALID; }
+        if (nrmIn && !std::isfinite(nrmIn[i])) { msg = who + "vertex " + std::to_string(i / 3) + " has a non-finite normal"; return MI_ERR_INVALID; }
+    }
+    return MI_OK;
+}
+int SceneHost::updateVertices(const float *posIn, const float *nrmIn, uint32_t nVerts, std::string &msg) {
+    { const int rc = checkVertices(posIn, nrmIn, nVerts, msg); if (rc) return rc; }
+    applyVertices(posIn, nrmIn, nVerts); return MI_OK;
+}
+void SceneHost::applyVertices(const float *posIn, const float *nrmIn, uint32_t nVerts) {
+    if (!geoPrepared) prepareGeometryEdit();      // the mirrors are those of the commit here: nothing has been edited yet
+    pos.assign(posIn, posIn + (size_t) nVerts * 3); if (nrmIn) nrm.assign(nrmIn, nrmIn + (size_t) nVerts * 3);
+    // the small tables, by the commit's own pieces
+    buildSceneBox(nullptr, 0); buildPacketTables(); buildEmitterTables(); buildBoundingSpheres();
+    for (int i = 0; i < 3; ++i) { d.aabb_lo[i] = aabbLo[i]; d.aabb_hi[i] = aabbHi[i]; d.packet_gk[i] = packetGK[i]; }
+    d.packet_scale = packetScale; syncCameraD(); syncEmittersD();
+    geoStale = true; ++revision;      // tris, shade, triuv, packetExact, nodes: refreshHostGeometry() before anything reads them
+}
+// The host mirrors of the per-triangle records and of the tree after vertex edits: the same two steps the device runs (geometry_records.h), in the same order.
+void SceneHost::refreshHostGeometry() {
+    if (!geoStale) return;
+    GeoEditTables g{}; g.pos = pos.data(); g.nrm = nrm.empty() ? nullptr : nrm.data(); g.shade = shade.data(); g.triuv = triuv.empty() ? nullptr : triuv.data();
+    g.tris = tris.data(); g.packetExact = packetExact.data(); g.leafSlot = leafSlotOfPrim.data(); g.leafBox = leafBoxes.data(); g.nodes = nodes.data(); g.nodeBox = nodeBoxes.data();
+    g.nTris = nTris; g.nPacketExact = (uint32_t) std::min<size_t>(packetExact.size(), nTris); g.wide = wideBvh ? 1u : 0u;
+    for (uint32_t t = 0; t < nTris; ++t) geoTriRecord(g, t);
+    for (uint32_t n : refitOrder) geoRefitNode(g, n);
+    geoStale = false;
 }
 
 int validateMaterials(const mi_material *m, uint32_t n, std::string &msg) {

@@ -53,6 +53,8 @@ struct SceneHost {
     void buildEmitterTables();          // emittersD, emitterCdf, emitterNorm, emitterX, areaCdf, hasDeltaEmitters, envIndex, envConstant
     void buildBoundingSpheres();        // dirBs*, envBs* (the latter includes the sensor position)
     void buildEnvTransform();           // envToWorld3, envToLocal3
+    void buildSceneBox(const float *extraBoxes, uint32_t n);   // aabbLo / aabbHi from the vertices, the analytic shapes and n further boxes (lo, hi: the instances)
+    void buildPacketTables();           // packetScale, packetGroups, packetGK
     void syncCameraD();                 // d.s2c, d.c2w, clip planes, cam_dx / cam_dy, env bounding sphere
     void syncEmittersD();               // d.emitter_norm
     void syncEnvD();                    // d.env_to_world, d.env_to_local, d.env_scale
@@ -62,6 +64,18 @@ struct SceneHost {
     int updateMaterials(const mi_material *m, uint32_t n, std::string &msg, bool *flagsChanged);
     int updateEmitters(const mi_emitter *e, uint32_t n, std::string &msg);
     int updateEnvmapTransform(const float *toWorld16, float scale, std::string &msg);
+    // Vertex edit: new positions (and normals) for the committed vertex array.  Replaces pos / nrm and the small tables at once; the per-triangle mirrors (tris, shade,
+    // triuv, packetExact) and `nodes` become STALE -- the device recomputes its copies (kernels_geometry.hip) and refreshHostGeometry() brings the mirrors up to date
+    // with the same arithmetic (geometry_records.h) before anything reads them.  Keeping them current eagerly would put the per-triangle host loop back into every edit.
+    int updateVertices(const float *pos, const float *nrm, uint32_t nVerts, std::string &msg);      // = checkVertices, then applyVertices
+    int checkVertices(const float *pos, const float *nrm, uint32_t nVerts, std::string &msg) const;   // every refusal; changes nothing
+    void applyVertices(const float *pos, const float *nrm, uint32_t nVerts);                            // checked arguments only
+    void prepareGeometryEdit();         // first edit: leafSlotOfPrim, leafBoxes of the records that do not move, refitOrder / refitLevelStart
+    void refreshHostGeometry();
+    std::vector<uint32_t> leafSlotOfPrim, refitOrder, refitLevelStart;   // triangle -> its record in `tris`; node indices sorted by height (0 = all children are leaves), level l = refitOrder[refitLevelStart[l] .. refitLevelStart[l + 1])
+    std::vector<float> leafBoxes, nodeBoxes;   // padded box (lo, hi) per leaf record; exact union of the child boxes per node
+    bool geoPrepared = false, geoStale = false;
+    void *dPos = nullptr, *dLeafSlot = nullptr, *dLeafBox = nullptr, *dNodeBox = nullptr, *dRefitOrder = nullptr;   // device side of a vertex edit, allocated at the first one
     ~SceneHost() { release(); }
 };
 

@@ -849,6 +849,34 @@ def textured_room(width=96, height=64, spp=16, sampler=SAMPLER_SOBOL, max_depth=
                         seed=seed, normals=normals, uvs=uvs, name="textured_room", textures=tex)
 
 
+def wavy_sheet(n=32, phase=0.0, amp=0.15, lift=0.0, light_size=0.4, light_x=0.0, width=96, height=64, spp=4, sampler=SAMPLER_SOBOL, max_depth=5, rr_depth=4, seed=0):
+    """A deformable mesh for the vertex-edit tests (Scene.update_vertices): the sheet y = lift + amp sin(3 x + phase) cos(2 z) over [-1, 1]^2 as n x n quads on a shared
+    grid -- smooth normals, texture coordinates, a checkerboard on its diffuse BSDF, so the UV tangents matter -- under a two-triangle area light of half-width
+    light_size at (light_x, lift + 1.5), over a plain floor.  Every call with the same n has the same indices, texture coordinates and shapes: only positions and
+    normals depend on the other parameters."""
+    b = _Builder(); uvs = []; normals = []
+    tex = [make_texture(TEXTURE_CHECKERBOARD, (0.8, 0.75, 0.6), (0.15, 0.2, 0.3), uscale=5.0, vscale=3.0, uoffset=0.13, voffset=-0.2)]
+    sheet = b.bsdf(reflectance=(0.5, 0.5, 0.5), twosided=True); b.bsdfs[sheet]["texture"] = 0
+    plain = b.bsdf(reflectance=(0.6, 0.6, 0.65)); lightm = b.bsdf(reflectance=(0.5, 0.5, 0.5))
+    i, j = np.meshgrid(np.arange(n + 1), np.arange(n + 1)); u = (i / n).reshape(-1); v = (j / n).reshape(-1); x = 2 * u - 1; z = 2 * v - 1
+    y = lift + amp * np.sin(3 * x + phase) * np.cos(2 * z)
+    dydx = amp * 3 * np.cos(3 * x + phase) * np.cos(2 * z); dydz = -amp * 2 * np.sin(3 * x + phase) * np.sin(2 * z); l = np.sqrt(dydx * dydx + 1 + dydz * dydz)
+    b.begin(); b.verts.extend(zip(x.tolist(), y.tolist(), z.tolist())); uvs.extend(zip(u.tolist(), v.tolist())); normals.extend(zip((-dydx / l).tolist(), (1 / l).tolist(), (-dydz / l).tolist()))
+    for jj in range(n):
+        for ii in range(n):
+            a = jj * (n + 1) + ii; c = a + 1; d_ = a + n + 1; e = d_ + 1
+            b.tris.append((a, d_, c)); b.tris.append((c, d_, e))
+    b.end(sheet, face_normals=False)
+    h = lift + 1.5; s_ = light_size
+    b.begin(); b.quad([(light_x + s_, h, -s_), (light_x + s_, h, s_), (light_x - s_, h, s_), (light_x - s_, h, -s_)]); uvs.extend([(0, 0)] * 4); normals.extend([(0, -1, 0)] * 4)
+    b.end(lightm, radiance=(30.0, 27.0, 22.0)); b.shapes[-1]["has_uv"] = 0
+    b.begin(); b.quad([(4, -0.6, -4), (-4, -0.6, -4), (-4, -0.6, 4), (4, -0.6, 4)]); uvs.extend([(0, 0)] * 4); normals.extend([(0, 1, 0)] * 4)
+    b.end(plain); b.shapes[-1]["has_uv"] = 0
+    cam = look_at((0.6, 3.0, -7.0), (0.0, 1.3, 0.0), (0, 1, 0))
+    return finish_scene(b.verts, b.tris, b.shapes, b.bsdfs, b.emitters, cam, 40.0, 0.05, 100.0, width, height, spp, sampler, max_depth, rr_depth,
+                        seed=seed, normals=normals, uvs=uvs, name="wavy_sheet", textures=tex)
+
+
 def bitmap_room(width=96, height=64, spp=16, sampler=SAMPLER_SOBOL, max_depth=6, rr_depth=4, seed=0):
     """The textured room with `bitmap` textures: EWA-filtered floor seen at grazing angles (anisotropic footprints, clamped anisotropy), trilinear
     wall with mirror / clamp wrapping, bilinear mound, nearest-neighbour panel.  Camera hits filter with the ray differentials
