@@ -235,6 +235,20 @@ int mi_scene_update_envmap_transform(mi_scene *s, const float *to_world16, float
  * The tree keeps the topology the SAH build chose for the committed vertices; after a large deformation it is no longer the optimum for the new ones and traversal slows
  * down (results stay exact).  A fresh mi_scene_commit is the remedy. */
 int mi_scene_update_vertices(mi_scene *s, const float *pos, const float *nrm, uint32_t n_verts);
+/* Instance edit: new to_world / to_object for ALL committed instances, in the order of mi_scene_set_instances; `group` of every record must be the committed one.
+ * to_object is taken from the caller, as mi_scene_set_instances takes it: nothing is inverted here.  The device rewrites the two matrices of every instance record and
+ * the box of its leaf in the scene-level tree, then REFITS the scene-level tree bottom-up as a vertex edit does (topology, child codes and node numbering stay).  The
+ * groups' geometry, trees and boxes and every per-triangle record are untouched; the scene box and the bounding spheres that depend on it follow on the host.  Results
+ * equal those of a fresh commit with the new instances bit for bit.  Like the other updates: between runs, advances `revision`, never moves `tree_builds`, a render
+ * handle follows after mi_render_clear, a replica is a scene of its own.  Returns when the device has finished.
+ * MI_ERR_INVALID: null argument, scene not committed, a run in flight, a scene committed without instances ("the scene has no instances"), n differs from the committed
+ * count (the message gives both), a non-finite entry in to_world or to_object (the message names the first instance).  MI_ERR_UNSUPPORTED: an instance whose `group`
+ * differs from the committed one (structural: it selects another tree; the message names the first instance).  A refused call leaves the scene untouched, and so does a
+ * failed allocation of the edit's own device tables (MI_ERR_DEVICE, "the scene is unchanged").  Any other MI_ERR_DEVICE (a failed copy or launch) comes after the host
+ * side has taken the new instances: host and device tables are then out of step and the scene must be committed again.
+ * The scene-level tree keeps the topology the SAH build chose for the committed placement; after large moves traversal slows down (results stay exact).  A fresh
+ * mi_scene_commit is the remedy.  mi_scene_update_vertices still refuses scenes with instances: moving the vertices of group members is not implemented. */
+int mi_scene_update_instances(mi_scene *s, const mi_instance *instances, uint32_t n);
 /* revision: in-place edits applied so far; tree_builds: host-side builds (tree, triangle records) this scene has gone through -- an update never moves it.  Either may be NULL */
 int mi_scene_revision(mi_scene *s, uint64_t *revision, uint64_t *tree_builds);
 
@@ -331,13 +345,16 @@ int mi_debug_intersect_fused(mi_scene *s, const float *rays8, uint64_t n, int an
                              float *out_hits4, mi_fused_debug_info *info);
 /* One device table of a committed scene as it is now, read back whole: what = MI_GEOMETRY_NODES (64-B tree nodes), _LEAF_RECORDS (48-B Wald records in leaf order,
  * word 10 = primitive index), _TRI_SHADE (128-B shading records, triangle order), _TRI_UV (48 B, only scenes with texture coordinates), _PACKET_EXACT (48-B Wald records,
- * triangle order), _PACKET_GROUPS (48-B pass-1 records).  The caller gives the size in bytes (mi_debug_geometry_bytes); a wrong size is MI_ERR_INVALID. */
+ * triangle order), _PACKET_GROUPS (48-B pass-1 records), _INSTANCES (128-B instance records in instance order: to_world 3 x 4, to_object 3 x 4, group box lo, root node,
+ * group box hi, group; size 0 on a scene without instances), _SCENE_BOX (24 B: aabb_lo, then aabb_hi of the scene record the kernels receive).  The caller gives the size in bytes (mi_debug_geometry_bytes); a wrong size is MI_ERR_INVALID. */
 #define MI_GEOMETRY_NODES 0
 #define MI_GEOMETRY_LEAF_RECORDS 1
 #define MI_GEOMETRY_TRI_SHADE 2
 #define MI_GEOMETRY_TRI_UV 3
 #define MI_GEOMETRY_PACKET_EXACT 4
 #define MI_GEOMETRY_PACKET_GROUPS 5
+#define MI_GEOMETRY_INSTANCES 6
+#define MI_GEOMETRY_SCENE_BOX 7
 int mi_debug_geometry_bytes(mi_scene *s, uint32_t what, uint64_t *bytes);
 int mi_debug_read_geometry(mi_scene *s, uint32_t what, void *out, uint64_t bytes);
 int mi_debug_sobol(mi_scene *s, const uint32_t *px_py_k, uint64_t n, uint32_t ndims, uint64_t *out_index, float *out_values);

@@ -89,11 +89,11 @@ class MiFusedDebugInfo(C.Structure):
 
 EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_scene_create", "mi_scene_destroy", "mi_scene_set_triangles",
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_film",
-           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
+           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
            "mi_render_set_profiling", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_geometry_bytes", "mi_debug_read_geometry"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
-                "mi_host_set_camera", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices"]
+                "mi_host_set_camera", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances"]
 
 
 def build(force=False):
@@ -135,6 +135,7 @@ class Lib:
         L.mi_scene_update_emitters.argtypes = [vp, vp, u32]
         L.mi_scene_update_envmap_transform.argtypes = [vp, vp, f32]
         L.mi_scene_update_vertices.argtypes = [vp, vp, vp, u32]
+        L.mi_scene_update_instances.argtypes = [vp, vp, u32]
         L.mi_scene_revision.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
         L.mi_render_merge_film.argtypes = [vp, vp]
         L.mi_render_create.argtypes = [vp, C.POINTER(MiRenderParams), C.POINTER(vp)]
@@ -231,6 +232,14 @@ def pack_emitters(emitters):
     return ems
 
 
+def pack_instances(insts):
+    """mi_instance records from the dict records of a flattened scene (scenes.make_instance)."""
+    arr = (MiInstance * max(1, len(insts)))()
+    for i, a in enumerate(insts):
+        r = MiInstance(a["group"]); r.to_world[:] = np.asarray(a["to_world"], np.float32).reshape(-1).tolist(); r.to_object[:] = np.asarray(a["to_object"], np.float32).reshape(-1).tolist(); arr[i] = r
+    return arr
+
+
 class Scene:
     """mi_scene handle filled from a flattened scene (mitsuba-im_amd/scenes.py)."""
 
@@ -253,10 +262,7 @@ class Scene:
             L.check(L.L.mi_scene_set_analytic(h, C.cast(an, C.c_void_p), len(recs)))
         insts = sc.get("instances") or []
         if insts:
-            arr = (MiInstance * len(insts))()
-            for i, a in enumerate(insts):
-                r = MiInstance(a["group"]); r.to_world[:] = a["to_world"].reshape(-1).tolist(); r.to_object[:] = a["to_object"].reshape(-1).tolist(); arr[i] = r
-            L.check(L.L.mi_scene_set_instances(h, C.cast(arr, C.c_void_p), len(insts)))
+            L.check(L.L.mi_scene_set_instances(h, C.cast(pack_instances(insts), C.c_void_p), len(insts)))
         media = sc.get("media") or []
         if media:                                       # mi_medium has the layout of the oracle's record (oracle/binding.py OrcMedium): 6 floats, uint, 2 floats, uint, float, uint
             buf = np.zeros(len(media), dtype=[("sigma_a", np.float32, 3), ("sigma_s", np.float32, 3), ("strategy", np.uint32), ("sampling_density", np.float32),
@@ -334,10 +340,19 @@ class Scene:
         self.sc.pos = pos
         if nrm is not None: self.sc.nrm = nrm
 
-    GEOMETRY_TABLES = {"nodes": (0, 64), "leaf_records": (1, 48), "tri_shade": (2, 128), "tri_uv": (3, 48), "packet_exact": (4, 48), "packet_groups": (5, 48)}
+    def update_instances(self, instances):
+        """New to_world / to_object for all committed instances (a list of scenes.make_instance records, groups as committed): the instance records and a refit of the
+        scene-level tree on the device, no tree build.  A changed group is refused (MiError code 3), a scene without instances or another count with code 1."""
+        instances = list(instances)
+        self.L.check(self.L.L.mi_scene_update_instances(self.h, C.cast(pack_instances(instances), C.c_void_p), len(instances)))
+        self.sc.instances = instances
+
+    GEOMETRY_TABLES = {"nodes": (0, 64), "leaf_records": (1, 48), "tri_shade": (2, 128), "tri_uv": (3, 48), "packet_exact": (4, 48), "packet_groups": (5, 48),
+                       "instances": (6, 128), "scene_box": (7, 24)}
 
     def read_geometry(self, what):
-        """One device table as it is now -> uint32 array [records, words]: "nodes", "leaf_records" (word 10 = primitive), "tri_shade", "tri_uv", "packet_exact", "packet_groups"."""
+        """One device table as it is now -> uint32 array [records, words]: "nodes", "leaf_records" (word 10 = primitive), "tri_shade", "tri_uv", "packet_exact", "packet_groups", "instances" (word 27 = root node),
+        "scene_box" (one record: aabb_lo, aabb_hi)."""
         code, rec = self.GEOMETRY_TABLES[what]; n = C.c_uint64()
         self.L.check(self.L.L.mi_debug_geometry_bytes(self.h, code, C.byref(n)))
         out = np.zeros((n.value // rec, rec // 4), np.uint32)
@@ -524,6 +539,14 @@ class HostIntegrator:
             raise RuntimeError(self.L.mi_host_last_error().decode())
         self.scene.sc.pos = pos
         if nrm is not None: self.scene.sc.nrm = nrm
+
+    def set_instances(self, instances):
+        """MIPathTracerHIP::setInstances: mi_scene_update_instances on the borrowed scene and on every replica, between two render() calls."""
+        instances = list(instances)
+        self.L.mi_host_set_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        if self.L.mi_host_set_instances(self.h, C.cast(pack_instances(instances), C.c_void_p), len(instances)) != 0:
+            raise RuntimeError(self.L.mi_host_last_error().decode())
+        self.scene.sc.instances = instances
 
     def statistics(self):
         return (self.L.mi_host_statistics(self.h) or b"").decode()

@@ -52,6 +52,7 @@ void mi_launch_field_layout(const float *, const float *, float *, int, int, int
 void mi_launch_patch_material_flags(TriShade *, uint32_t, const uint32_t *, uint32_t, hipStream_t);
 void mi_launch_tri_records(const mi::GeoEditTables &, hipStream_t);
 void mi_launch_refit_level(const mi::GeoEditTables &, const uint32_t *, uint32_t, uint32_t, uint32_t, hipStream_t);
+void mi_launch_instance_records(const mi::InstEditTables &, hipStream_t);
 }
 
 // Shading stage dispatch.  Dynamic LDS: Sobol nibble tables + (small scenes) the scene tables + (scenes with non-diffuse BSDFs) the per-wave path-order list.
@@ -259,7 +260,7 @@ template <typename T> static int up(void **dst, const std::vector<T> &v) {
     return 0;
 }
 void SceneHost::release() {
-    void **ps[] = {&dPos, &dLeafSlot, &dLeafBox, &dNodeBox, &dRefitOrder, &dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
+    void **ps[] = {&dPos, &dLeafSlot, &dLeafBox, &dNodeBox, &dRefitOrder, &dInstXf, &dLeafSlotInst, &dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
     for (void **p : ps) if (*p) { (void) hipFree(*p); *p = nullptr; }
 }
 int SceneHost::upload(int dev) {
@@ -417,11 +418,11 @@ int mi_scene_clone(mi_scene *s, uint32_t device, mi_scene **out) {
     if (!s->h.committed) return fail(MI_ERR_INVALID, "mi_scene_clone: scene not committed");
     int devCount = 0; HIPCHK(hipGetDeviceCount(&devCount));
     if ((int) device >= devCount) return fail(MI_ERR_DEVICE, "mi_scene_clone: no such HIP device");
-    s->h.refreshHostGeometry();                     // after vertex edits the per-triangle mirrors and the nodes are brought up to date only when someone reads them
+    s->h.refreshHostGeometry();                     // after vertex / instance edits the per-triangle mirrors, the instance records and the nodes are brought up to date only when someone reads them
     mi_scene *c = new mi_scene();
     c->h = s->h;                                    // inputs + host-derived data
     {   // the copy must not own the source's device allocations
-        void **ps[] = {&c->h.dPos, &c->h.dLeafSlot, &c->h.dLeafBox, &c->h.dNodeBox, &c->h.dRefitOrder, &c->h.dMaterialFlags, &c->h.dMedia, &c->h.dPrimMedia, &c->h.dPacketGroups, &c->h.dPacketExact, &c->h.dTexLevels, &c->h.dTexTexels, &c->h.dMipLut, &c->h.dTriUV, &c->h.dTextures, &c->h.dMaterialTables, &c->h.dInstances, &c->h.dEmitterX, &c->h.dAnalytic, &c->h.dNodes, &c->h.dTris, &c->h.dShade, &c->h.dI2, &c->h.dNrm, &c->h.dMaterials, &c->h.dEmitters, &c->h.dEmitterCdf, &c->h.dAreaCdf, &c->h.dFilter, &c->h.dSobolM32, &c->h.dSobolVdc, &c->h.dSobolVdcInv, &c->h.dEnvRGB, &c->h.dEnvCols, &c->h.dEnvRows, &c->h.dEnvWeights, &c->h.dEnvGuideRows, &c->h.dEnvGuideCols};
+        void **ps[] = {&c->h.dPos, &c->h.dLeafSlot, &c->h.dLeafBox, &c->h.dNodeBox, &c->h.dRefitOrder, &c->h.dInstXf, &c->h.dLeafSlotInst, &c->h.dMaterialFlags, &c->h.dMedia, &c->h.dPrimMedia, &c->h.dPacketGroups, &c->h.dPacketExact, &c->h.dTexLevels, &c->h.dTexTexels, &c->h.dMipLut, &c->h.dTriUV, &c->h.dTextures, &c->h.dMaterialTables, &c->h.dInstances, &c->h.dEmitterX, &c->h.dAnalytic, &c->h.dNodes, &c->h.dTris, &c->h.dShade, &c->h.dI2, &c->h.dNrm, &c->h.dMaterials, &c->h.dEmitters, &c->h.dEmitterCdf, &c->h.dAreaCdf, &c->h.dFilter, &c->h.dSobolM32, &c->h.dSobolVdc, &c->h.dSobolVdcInv, &c->h.dEnvRGB, &c->h.dEnvCols, &c->h.dEnvRows, &c->h.dEnvWeights, &c->h.dEnvGuideRows, &c->h.dEnvGuideCols};
         for (void **p : ps) *p = nullptr;
         c->h.committed = false;
     }
@@ -520,6 +521,46 @@ int mi_scene_update_vertices(mi_scene *s, const float *pos, const float *nrm, ui
         HIPCHK(hipStreamSynchronize(nullptr)); (void) hipFree(h.dPacketGroups); h.dPacketGroups = grown; h.d.packet_groups = (const PacketGroupD *) grown;
     } else HIPCHK(push(h.dPacketGroups, h.packetGroups));
     HIPCHK(push(h.dEmitters, h.emittersD)); HIPCHK(push(h.dAreaCdf, h.areaCdf));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return MI_OK;
+}
+// Instance edit.  Host: the checks, `instances`, the scene box and what depends on it (SceneHost::updateInstances).  Device: the new transform pairs go up,
+// k_instance_records rewrites the two matrices of every InstanceD and the padded box of its leaf record, k_refit refits the scene-level tree level by level on one
+// stream (the group trees are not reachable from node 0 and stay), the small tables go back into their allocations.  Synchronous like the other updates.
+int mi_scene_update_instances(mi_scene *s, const mi_instance *instances, uint32_t n) {
+    if (!s || !instances) return fail(MI_ERR_INVALID, "mi_scene_update_instances: null argument");
+    UPDATE_ENTER("mi_scene_update_instances");
+    mi::SceneHost &h = s->h;
+    std::string msg; const int rc = h.checkInstances(instances, n, msg); if (rc) return fail(rc, msg);
+    if (!h.geoPrepared) h.prepareGeometryEdit();      // derived from the committed tables alone: the scene itself is not changed yet
+    if (h.instancesD.size() != h.d.n_instances || n != h.d.n_instances || h.nodes.size() != h.d.n_nodes || h.leafSlotOfInstance.size() != n || h.leafBoxes.size() != h.tris.size() * 6 || h.nodeBoxes.size() != h.nodes.size() * 6 || h.refitOrder.size() > h.nodes.size())
+        return fail(MI_ERR_DEVICE, "mi_scene_update_instances: host tables and device tables disagree in size");
+    for (uint32_t slot : h.leafSlotOfInstance) if (slot >= h.tris.size()) return fail(MI_ERR_DEVICE, "mi_scene_update_instances: host tables and device tables disagree in size");
+    HIPCHK(hipSetDevice(h.device));
+    if (!h.dInstXf || !h.dLeafSlotInst || !h.dLeafBox || !h.dNodeBox || !h.dRefitOrder) {      // first edit: the tables a commit does not need -- all five or none, and before the scene changes
+        void **five[] = {&h.dInstXf, &h.dLeafSlotInst, &h.dLeafBox, &h.dNodeBox, &h.dRefitOrder};
+        for (void **p : five) if (*p) { (void) hipFree(*p); *p = nullptr; }
+        bool bad = hipMalloc(&h.dInstXf, std::max<size_t>((size_t) n * 96, 16)) != hipSuccess || hipMalloc(&h.dNodeBox, std::max<size_t>(h.nodeBoxes.size() * 4, 16)) != hipSuccess;
+        bad = bad || mi::up(&h.dLeafSlotInst, h.leafSlotOfInstance) || mi::up(&h.dLeafBox, h.leafBoxes) || mi::up(&h.dRefitOrder, h.refitOrder);
+        if (bad) {
+            const std::string why = hipGetErrorString(hipGetLastError());
+            for (void **p : five) if (*p) { (void) hipFree(*p); *p = nullptr; }
+            return fail(MI_ERR_DEVICE, "mi_scene_update_instances: allocation failed, the scene is unchanged: " + why);
+        }
+    }
+    // from here on the scene changes; a device error below leaves host and device tables out of step (see the header)
+    h.applyInstances(instances, n);
+    if (h.emittersD.size() != h.d.n_emitters) return fail(MI_ERR_DEVICE, "mi_scene_update_instances: host tables and device tables disagree in size");
+    std::vector<float> xf((size_t) n * 24);
+    for (uint32_t i = 0; i < n; ++i) { memcpy(&xf[(size_t) i * 24], instances[i].to_world, 48); memcpy(&xf[(size_t) i * 24 + 12], instances[i].to_object, 48); }
+    HIPCHK(push(h.dInstXf, xf));
+    mi::InstEditTables it{}; it.xf = (const float *) h.dInstXf; it.inst = (InstanceD *) h.dInstances; it.leafSlot = (const uint32_t *) h.dLeafSlotInst; it.leafBox = (float *) h.dLeafBox; it.n = n;
+    mi::GeoEditTables g{}; g.leafBox = (float *) h.dLeafBox; g.nodes = (BvhNode *) h.dNodes; g.nodeBox = (float *) h.dNodeBox; g.wide = h.wideBvh ? 1u : 0u;
+    mi_launch_instance_records(it, nullptr);
+    for (size_t l = 0; l + 1 < h.refitLevelStart.size(); ++l)      // bottom-up over the scene-level tree: level l reads the boxes levels < l wrote; stream order is the only synchronisation
+        mi_launch_refit_level(g, (const uint32_t *) h.dRefitOrder, h.refitLevelStart[l], h.refitLevelStart[l + 1] - h.refitLevelStart[l], h.d.n_nodes, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(push(h.dEmitters, h.emittersD)); HIPCHK(push(h.dEmitterX, h.emitterX));      // as the vertex edit pushes them; the scene record travels with the next run
     HIPCHK(hipStreamSynchronize(nullptr));
     return MI_OK;
 }
@@ -1207,7 +1248,8 @@ int mi_debug_intersect_fused(mi_scene *s, const float *rays, uint64_t n, int any
     for (void *p : bufs) (void) hipFree(p);
     return rc;
 }
-// One device table of the scene as it is now: 0 nodes, 1 leaf records, 2 TriShade, 3 TriUV, 4 packet-exact records, 5 packet groups.  mi_debug_geometry_bytes gives the size.
+// One device table of the scene as it is now: 0 nodes, 1 leaf records, 2 TriShade, 3 TriUV, 4 packet-exact records, 5 packet groups, 6 instance records; 7 = the box
+// of the scene record (held on the host: every run passes the record by value).  mi_debug_geometry_bytes gives the size.
 static int geometryTable(mi_scene *s, uint32_t what, const void **ptr, uint64_t *bytes, const char *who) {
     if (!s) return fail(MI_ERR_INVALID, std::string(who) + ": null scene");
     if (!s->h.committed) return fail(MI_ERR_INVALID, std::string(who) + ": scene not committed");
@@ -1219,6 +1261,8 @@ static int geometryTable(mi_scene *s, uint32_t what, const void **ptr, uint64_t 
     case 3: *ptr = h.dTriUV; *bytes = (uint64_t) h.triuv.size() * sizeof(TriUV); break;
     case 4: *ptr = h.dPacketExact; *bytes = (uint64_t) h.packetExact.size() * sizeof(TriAccelD); break;
     case 5: *ptr = h.dPacketGroups; *bytes = (uint64_t) h.packetGroups.size() * sizeof(PacketGroupD); break;
+    case MI_GEOMETRY_INSTANCES: *ptr = h.dInstances; *bytes = (uint64_t) h.instancesD.size() * sizeof(InstanceD); break;
+    case MI_GEOMETRY_SCENE_BOX: *ptr = nullptr; *bytes = 24; break;
     default: return fail(MI_ERR_INVALID, std::string(who) + ": unknown table " + std::to_string(what));
     }
     return MI_OK;
@@ -1233,6 +1277,7 @@ int mi_debug_read_geometry(mi_scene *s, uint32_t what, void *out, uint64_t bytes
     if (bytes != n) return fail(MI_ERR_INVALID, "mi_debug_read_geometry: table " + std::to_string(what) + " holds " + std::to_string(n) + " bytes, the caller gave " + std::to_string(bytes));
     if (!n) return MI_OK;
     if (!out) return fail(MI_ERR_INVALID, "mi_debug_read_geometry: null argument");
+    if (what == MI_GEOMETRY_SCENE_BOX) { memcpy(out, s->h.d.aabb_lo, 12); memcpy((char *) out + 12, s->h.d.aabb_hi, 12); return MI_OK; }
     HIPCHK(hipSetDevice(s->h.device)); HIPCHK(hipMemcpy(out, p, n, hipMemcpyDeviceToHost));
     return MI_OK;
 }

@@ -1,7 +1,7 @@
 // geometry_records.h -- the arithmetic that turns vertex positions into device records, once, for the host and for the device.
 //
-// mi_scene_commit derives these records on the host (scene_build.cpp, commitHost()); mi_scene_update_vertices derives them again on the device (kernels_geometry.hip)
-// and, when a host mirror is needed, on the host (SceneHost::refreshHostGeometry()).  "After an update every result equals that of a fresh commit" holds bit for bit only
+// mi_scene_commit derives these records on the host (scene_build.cpp, commitHost()); mi_scene_update_vertices and mi_scene_update_instances derive them again on the
+// device (kernels_geometry.hip) and, when a host mirror is needed, on the host (SceneHost::refreshHostGeometry()).  "After an update every result equals that of a fresh commit" holds bit for bit only
 // if all three run the very same operations in the very same order, so they all call the functions below.  Everything here is strict IEEE binary32 / binary64: the
 // translation units that include it are compiled with -ffp-contract=off and correctly rounded divide / square root on both sides.  min / max are the ternaries of
 // std::min / std::max (they differ from fminf / fmaxf on NaN and on signed zeros).
@@ -99,6 +99,19 @@ MI_HD static inline void triPaddedBox(V3 p0, V3 p1, V3 p2, V3 &plo, V3 &phi, V3 
     padBox(lo, hi, plo, phi, cen);
 }
 
+// A point through rows 0..2 of a row-major affine matrix (3 x 4 or 4 x 4).
+MI_HD static inline V3 xfPoint(const float *m, V3 p) { return mk(m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3], m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7], m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11]); }
+// Box of one placement of a shape group = the 8 transformed corners of the group's box (instance.cpp:46-64): [blo, bhi] is what the scene box takes, [plo, phi] the
+// padded box of the instance's leaf record in the scene-level tree.
+MI_HD static inline void instanceBoxes(const float *toWorld, V3 glo, V3 ghi, V3 &blo, V3 &bhi, V3 &plo, V3 &phi, V3 &cen) {
+    const float inf = INFINITY; blo = mk(inf, inf, inf); bhi = mk(-inf, -inf, -inf);
+    for (int c = 0; c < 8; ++c) {
+        V3 q = xfPoint(toWorld, mk(c & 1 ? ghi.x : glo.x, c & 2 ? ghi.y : glo.y, c & 4 ? ghi.z : glo.z));
+        blo = vmin(blo, q); bhi = vmax(bhi, q);
+    }
+    padBox(blo, bhi, plo, phi, cen);
+}
+
 // ---- 4-wide nodes: child box c = org + q * step per axis (pt_types.h Bvh4Node)
 // Biased exponent of the step of one axis: 2^(e - 127) is the smallest power of two with 254 steps covering the extent, clamped to the normal floats.  This is
 // frexp(ext > 0 ? ext / 254 : 1e-30f) read off the bit pattern: a normal float m 2^(E - 127), m in [1, 2), is m / 2 * 2^(E - 126); anything below the normal range
@@ -188,6 +201,19 @@ MI_HD static inline void geoRefitNode(const GeoEditTables &g, uint32_t n) {
         g.nodes[n] = b;
     }
     store3(g.nodeBox + (size_t) n * 6, lo); store3(g.nodeBox + (size_t) n * 6 + 3, hi);
+}
+
+
+// ------------------------------------------------------------------------------------------------ the first step of an instance edit (the second is geoRefitNode)
+// xf[24 * i] = rows 0..2 of the new to_world of instance i, then rows 0..2 of its to_object; leafSlot[i] = position of the instance's MI_K_INSTANCE record among the
+// leaf records.  Rewrites the two matrices of InstanceD[i] (96 of its 128 bytes: glo, ghi, root and group never change) and the padded box of its leaf record.
+struct InstEditTables { const float *xf; InstanceD *inst; const uint32_t *leafSlot; float *leafBox; uint32_t n; };
+MI_HD static inline void geoInstanceRecord(const InstEditTables &g, uint32_t i) {
+    InstanceD &d = g.inst[i]; const float *x = g.xf + (size_t) i * 24;
+    for (int k = 0; k < 12; ++k) { d.to_world[k] = x[k]; d.to_object[k] = x[12 + k]; }
+    V3 blo, bhi, plo, phi, cen; instanceBoxes(x, load3(d.glo), load3(d.ghi), blo, bhi, plo, phi, cen);
+    const uint32_t slot = g.leafSlot[i];
+    store3(g.leafBox + (size_t) slot * 6, plo); store3(g.leafBox + (size_t) slot * 6 + 3, phi);
 }
 
 }  // namespace mi

@@ -17,8 +17,7 @@
 
 namespace mi {
 
-// Analytic shapes: derived constants + Shape::getAABB (rectangle.cpp:100-119, disk.cpp:100-130, sphere.cpp:127-142, cylinder.cpp:105-107, :256-276)
-static inline V3 xfPoint(const float *m, V3 p) { return mk(m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3], m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7], m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11]); }
+// Analytic shapes: derived constants + Shape::getAABB (rectangle.cpp:100-119, disk.cpp:100-130, sphere.cpp:127-142, cylinder.cpp:105-107, :256-276); xfPoint: geometry_records.h
 static inline V3 xfVector(const float *m, V3 v) { return mk(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z, m[8] * v.x + m[9] * v.y + m[10] * v.z); }
 static inline V3 xfNormal(const float *inv, V3 n) { return mk(inv[0] * n.x + inv[4] * n.y + inv[8] * n.z, inv[1] * n.x + inv[5] * n.y + inv[9] * n.z, inv[2] * n.x + inv[6] * n.y + inv[10] * n.z); }
 static inline float length3(V3 a) { return std::sqrt(dot(a, a)); }
@@ -157,8 +156,8 @@ static inline int32_t leafCode(int first, int count) { return ~(int32_t) (first 
 
 void SceneHost::commitHost() {
     ++treeBuilds;
-    // a new tree: whatever the vertex edits of the previous one derived (slot table, level order, box scratch, the stale mark) describes a tree that no longer exists
-    geoPrepared = geoStale = false; leafSlotOfPrim.clear(); refitOrder.clear(); refitLevelStart.clear(); leafBoxes.clear(); nodeBoxes.clear();
+    // a new tree: whatever the vertex or instance edits of the previous one derived (slot tables, level order, box scratch, the stale marks) describes a tree that no longer exists
+    geoPrepared = geoStale = instStale = false; leafSlotOfPrim.clear(); leafSlotOfInstance.clear(); refitOrder.clear(); refitLevelStart.clear(); leafBoxes.clear(); nodeBoxes.clear();
     const uint32_t nt = (uint32_t) (idx.size() / 3), na = (uint32_t) analytic.size(), ni = (uint32_t) instances.size(), np = nt + na + ni;
     nTris = nt;
     auto vert = [&](uint32_t i) { return mk(pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]); };
@@ -212,13 +211,9 @@ void SceneHost::commitHost() {
     instancesD.assign(ni, InstanceD{});
     std::vector<float> instBoxes((size_t) ni * 6);
     for (uint32_t i = 0; i < ni; ++i) {
-        const mi_instance &in = instances[i]; const uint32_t g = in.group; V3 blo = mk(inf, inf, inf), bhi = mk(-inf, -inf, -inf);
-        for (int c = 0; c < 8; ++c) {
-            V3 q = xfPoint(in.to_world, mk(c & 1 ? ghi[g].x : glo[g].x, c & 2 ? ghi[g].y : glo[g].y, c & 4 ? ghi[g].z : glo[g].z));
-            blo = vmin(blo, q); bhi = vmax(bhi, q);
-        }
+        const mi_instance &in = instances[i]; const uint32_t g = in.group; V3 blo, bhi;
+        instanceBoxes(in.to_world, glo[g], ghi[g], blo, bhi, tlo[nt + na + i], thi[nt + na + i], cen[nt + na + i]);      // geometry_records.h: shared with the instance edit
         store3(&instBoxes[(size_t) i * 6], blo); store3(&instBoxes[(size_t) i * 6 + 3], bhi);
-        padBox(blo, bhi, tlo[nt + na + i], thi[nt + na + i], cen[nt + na + i]);
         TriAccelD rec{}; rec.k = MI_K_INSTANCE; rec.prim = i; accel.push_back(rec);
         InstanceD &d = instancesD[i]; std::memcpy(d.to_world, in.to_world, 48); std::memcpy(d.to_object, in.to_object, 48);
         d.glo[0] = glo[g].x; d.glo[1] = glo[g].y; d.glo[2] = glo[g].z; d.ghi[0] = ghi[g].x; d.ghi[1] = ghi[g].y; d.ghi[2] = ghi[g].z; d.group = g; d.root = 0;
@@ -682,19 +677,30 @@ int SceneHost::updateEnvmapTransform(const float *toWorld16, float scale, std::s
 }
 
 // ------------------------------------------------------------------------------------------------ vertex edits (mi_scene_update_vertices)
-// What a vertex edit needs beyond the committed tables, derived once at the first edit: where each triangle's leaf record sits, the padded boxes of the leaf records
-// that do not move (analytic shapes; the never-hit record of unused 4-wide slots stays empty), and the order in which the existing nodes are refitted -- by height,
-// height 0 = every child is a leaf, so that a node comes after all of its inner children.
+// What a vertex or an instance edit needs beyond the committed tables, derived once at the first edit: where each triangle's and each instance's leaf record sits, the
+// padded boxes of the leaf records that the edit's kernel does not write (analytic shapes; on a scene with instances, where only instances move, also the triangles;
+// the never-hit record of unused 4-wide slots stays empty), and the order in which the existing nodes are refitted -- by height, height 0 = every child is a leaf,
+// so that a node comes after all of its inner children.  The walk starts at node 0 and an instance is a leaf, so the order covers the scene-level tree only.
 void SceneHost::prepareGeometryEdit() {
     const uint32_t nt = nTris; const float inf = std::numeric_limits<float>::infinity();
-    leafSlotOfPrim.assign(nt, 0u); leafBoxes.assign(tris.size() * 6, 0.0f);
+    leafSlotOfPrim.assign(nt, 0u); leafSlotOfInstance.assign(instances.size(), 0u); leafBoxes.assign(tris.size() * 6, 0.0f);
     for (size_t slot = 0; slot < tris.size(); ++slot) {
         const TriAccelD &r = tris[slot]; float *box = &leafBoxes[slot * 6];
         store3(box, mk(inf, inf, inf)); store3(box + 3, mk(-inf, -inf, -inf));
         if (r.k == MI_K_ANALYTIC && r.prim >= nt && r.prim - nt < analytic.size()) {
             AnalyticD d; V3 alo, ahi, tl, th, plo, phi, cen; analyticPrepare(analytic[r.prim - nt], d, alo, ahi, tl, th); padBox(tl, th, plo, phi, cen);
             store3(box, plo); store3(box + 3, phi);
-        } else if (r.k <= MI_K_NONE && r.prim < nt) leafSlotOfPrim[r.prim] = (uint32_t) slot;
+        } else if (r.k == MI_K_INSTANCE && r.prim < instances.size()) {
+            leafSlotOfInstance[r.prim] = (uint32_t) slot;
+            const InstanceD &in = instancesD[r.prim]; V3 blo, bhi, plo, phi, cen; instanceBoxes(in.to_world, load3(in.glo), load3(in.ghi), blo, bhi, plo, phi, cen);
+            store3(box, plo); store3(box + 3, phi);
+        } else if (r.k <= MI_K_NONE && r.prim < nt) {
+            leafSlotOfPrim[r.prim] = (uint32_t) slot;
+            if (!instances.empty() && !shapes[triShape[r.prim]].group) {      // no k_tri_records on a scene with instances: the refit reads the scene-level triangles' boxes from here
+                V3 plo, phi, cen; triPaddedBox(load3(&pos[(size_t) idx[(size_t) r.prim * 3] * 3]), load3(&pos[(size_t) idx[(size_t) r.prim * 3 + 1] * 3]), load3(&pos[(size_t) idx[(size_t) r.prim * 3 + 2] * 3]), plo, phi, cen);
+                store3(box, plo); store3(box + 3, phi);
+            }
+        }
     }
     const size_t nn = nodes.size(); std::vector<int> height(nn, -1);
     struct Walk { const std::vector<BvhNode> &nodes; std::vector<int> &height; bool wide;
@@ -741,8 +747,51 @@ void SceneHost::applyVertices(const float *posIn, const float *nrmIn, uint32_t n
     d.packet_scale = packetScale; syncCameraD(); syncEmittersD();
     geoStale = true; ++revision;      // tris, shade, triuv, packetExact, nodes: refreshHostGeometry() before anything reads them
 }
-// The host mirrors of the per-triangle records and of the tree after vertex edits: the same two steps the device runs (geometry_records.h), in the same order.
+// ------------------------------------------------------------------------------------------------ instance edits (mi_scene_update_instances)
+int SceneHost::checkInstances(const mi_instance *in, uint32_t n, std::string &msg) const {
+    const std::string who = "mi_scene_update_instances: ";
+    if (!in) { msg = who + "null argument"; return MI_ERR_INVALID; }
+    if (!committed) { msg = who + "scene not committed"; return MI_ERR_INVALID; }
+    if (instances.empty()) { msg = who + "the scene has no instances"; return MI_ERR_INVALID; }
+    if (n != instances.size()) { msg = who + "the instance count changes (" + std::to_string(instances.size()) + " -> " + std::to_string(n) + "); an update moves the committed instances, commit a new scene"; return MI_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i) for (int k = 0; k < 16; ++k) {
+        if (!std::isfinite(in[i].to_world[k])) { msg = who + "instance " + std::to_string(i) + " has a non-finite to_world"; return MI_ERR_INVALID; }
+        if (!std::isfinite(in[i].to_object[k])) { msg = who + "instance " + std::to_string(i) + " has a non-finite to_object"; return MI_ERR_INVALID; }
+    }
+    for (uint32_t i = 0; i < n; ++i) if (in[i].group != instances[i].group) {
+        msg = who + "instance " + std::to_string(i) + " changes its shape group (" + std::to_string(instances[i].group) + " -> " + std::to_string(in[i].group) + "): that selects another tree; an update changes transforms only, commit a new scene"; return MI_ERR_UNSUPPORTED; }
+    return MI_OK;
+}
+int SceneHost::updateInstances(const mi_instance *in, uint32_t n, std::string &msg) {
+    { const int rc = checkInstances(in, n, msg); if (rc) return rc; }
+    applyInstances(in, n); return MI_OK;
+}
+void SceneHost::applyInstances(const mi_instance *in, uint32_t n) {
+    if (!geoPrepared) prepareGeometryEdit();      // the mirrors are those of the commit here: nothing has been edited yet
+    instances.assign(in, in + n);
+    // the scene box takes the unpadded instance boxes in instance order, as commitHost() does: the same sequence of min / max, down to the sign of a zero
+    std::vector<float> instBoxes((size_t) n * 6);
+    for (uint32_t i = 0; i < n; ++i) {
+        const InstanceD &d0 = instancesD[i]; V3 blo, bhi, plo, phi, cen; instanceBoxes(in[i].to_world, load3(d0.glo), load3(d0.ghi), blo, bhi, plo, phi, cen);
+        store3(&instBoxes[(size_t) i * 6], blo); store3(&instBoxes[(size_t) i * 6 + 3], bhi);
+    }
+    buildSceneBox(instBoxes.data(), n); buildBoundingSpheres();
+    for (int i = 0; i < 3; ++i) { d.aabb_lo[i] = aabbLo[i]; d.aabb_hi[i] = aabbHi[i]; }
+    syncCameraD(); syncEmittersD();
+    instStale = true; ++revision;      // instancesD, nodes: refreshHostGeometry() before anything reads them
+}
+// The host mirrors of the per-triangle records, of the instance records and of the tree after vertex / instance edits: the same two steps the device runs
+// (geometry_records.h), in the same order.
 void SceneHost::refreshHostGeometry() {
+    if (instStale) {
+        std::vector<float> xf((size_t) instances.size() * 24);
+        for (size_t i = 0; i < instances.size(); ++i) { std::memcpy(&xf[i * 24], instances[i].to_world, 48); std::memcpy(&xf[i * 24 + 12], instances[i].to_object, 48); }
+        InstEditTables it{}; it.xf = xf.data(); it.inst = instancesD.data(); it.leafSlot = leafSlotOfInstance.data(); it.leafBox = leafBoxes.data(); it.n = (uint32_t) instancesD.size();
+        for (uint32_t i = 0; i < it.n; ++i) geoInstanceRecord(it, i);
+        GeoEditTables g{}; g.leafBox = leafBoxes.data(); g.nodes = nodes.data(); g.nodeBox = nodeBoxes.data(); g.wide = wideBvh ? 1u : 0u;
+        for (uint32_t n : refitOrder) geoRefitNode(g, n);
+        instStale = false;
+    }
     if (!geoStale) return;
     GeoEditTables g{}; g.pos = pos.data(); g.nrm = nrm.empty() ? nullptr : nrm.data(); g.shade = shade.data(); g.triuv = triuv.empty() ? nullptr : triuv.data();
     g.tris = tris.data(); g.packetExact = packetExact.data(); g.leafSlot = leafSlotOfPrim.data(); g.leafBox = leafBoxes.data(); g.nodes = nodes.data(); g.nodeBox = nodeBoxes.data();

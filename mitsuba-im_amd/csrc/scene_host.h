@@ -70,12 +70,19 @@ struct SceneHost {
     int updateVertices(const float *pos, const float *nrm, uint32_t nVerts, std::string &msg);      // = checkVertices, then applyVertices
     int checkVertices(const float *pos, const float *nrm, uint32_t nVerts, std::string &msg) const;   // every refusal; changes nothing
     void applyVertices(const float *pos, const float *nrm, uint32_t nVerts);                            // checked arguments only
-    void prepareGeometryEdit();         // first edit: leafSlotOfPrim, leafBoxes of the records that do not move, refitOrder / refitLevelStart
+    // Instance edit: new to_world / to_object for every committed instance (the groups stay).  Replaces `instances`, the scene box and what depends on it at once;
+    // instancesD and `nodes` become STALE -- the device rewrites its copies (k_instance_records, k_refit) and refreshHostGeometry() repeats the two steps on the mirrors.
+    int updateInstances(const mi_instance *in, uint32_t n, std::string &msg);      // = checkInstances, then applyInstances
+    int checkInstances(const mi_instance *in, uint32_t n, std::string &msg) const;   // every refusal; changes nothing
+    void applyInstances(const mi_instance *in, uint32_t n);                            // checked arguments only
+    void prepareGeometryEdit();         // first edit: leafSlotOfPrim / leafSlotOfInstance, leafBoxes of the records that do not move, refitOrder / refitLevelStart
     void refreshHostGeometry();
+    std::vector<uint32_t> leafSlotOfInstance;   // instance -> its MI_K_INSTANCE record in `tris`
     std::vector<uint32_t> leafSlotOfPrim, refitOrder, refitLevelStart;   // triangle -> its record in `tris`; node indices sorted by height (0 = all children are leaves), level l = refitOrder[refitLevelStart[l] .. refitLevelStart[l + 1])
     std::vector<float> leafBoxes, nodeBoxes;   // padded box (lo, hi) per leaf record; exact union of the child boxes per node
-    bool geoPrepared = false, geoStale = false;
+    bool geoPrepared = false, geoStale = false, instStale = false;
     void *dPos = nullptr, *dLeafSlot = nullptr, *dLeafBox = nullptr, *dNodeBox = nullptr, *dRefitOrder = nullptr;   // device side of a vertex edit, allocated at the first one
+    void *dInstXf = nullptr, *dLeafSlotInst = nullptr;   // device side of an instance edit (with dLeafBox, dNodeBox, dRefitOrder), allocated at the first one: the 24-float transform pairs, leafSlotOfInstance
     ~SceneHost() { release(); }
 };
 

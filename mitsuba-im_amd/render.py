@@ -12,6 +12,10 @@ for `luminance`.  Other output formats cannot hold the groups: an error that nam
 `--orbit N [--orbit-axis x|y|z]` renders a turntable: N frames with the camera rotated in steps of 360 / N degrees about the axis through the centre of the scene's
 box.  The scene is committed once; every frame is an in-place camera edit of the committed scene (Scene.update_camera), a clear and a run -- no tree build, no
 upload -- and is written to `<output>_000.<ext>`, `<output>_001.<ext>`, ...
+
+`--spin N [--spin-axis x|y|z]` renders N frames in which every instance of a shape group is turned by 360 k / N degrees (frame k) about the axis through its own placed
+origin.  One commit again; every frame is an in-place instance edit (Scene.update_instances: the instance records and a refit of the scene-level tree on the device),
+a clear and a run, written like the orbit's frames.  A scene without instances ends with a message.
 """
 import argparse
 import sys
@@ -76,6 +80,21 @@ def orbit_cameras(sc, n, axis="y"):
     return out
 
 
+def spin_instances(sc, n, axis="y"):
+    """The n instance lists of a spin: in frame f every instance is turned by 360 f / n degrees about `axis` through its own placed origin, to_world (0, 0, 0, 1).
+    Frame 0 holds the scene's own records."""
+    from .scenes import make_instance
+    k = "xyz".index(axis); i, j = (k + 1) % 3, (k + 2) % 3; out = [list(sc.instances)]
+    for f in range(1, n):
+        t = 2.0 * np.pi * f / n; rot = np.eye(4); rot[i, i] = rot[j, j] = np.cos(t); rot[i, j] = -np.sin(t); rot[j, i] = np.sin(t)
+        frame = []
+        for inst in sc.instances:
+            tw = np.asarray(inst["to_world"], np.float64); to_o = np.eye(4); to_o[:3, 3] = -tw[:3, 3]; back = np.eye(4); back[:3, 3] = tw[:3, 3]
+            frame.append(make_instance(inst["group"], back @ rot @ to_o @ tw))
+        out.append(frame)
+    return out
+
+
 def write_outputs(sc, render, out, rgb=None, fields=None):
     """the developed film (and, for a multichannel scene, the field groups) of `render` -> `out`; False (message printed) when the format cannot hold them"""
     if rgb is None:
@@ -104,6 +123,8 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--orbit", type=int, default=0, metavar="N", help="turntable of N frames about the scene box's centre: one commit, one in-place camera edit per frame")
     ap.add_argument("--orbit-axis", choices=["x", "y", "z"], default="y")
+    ap.add_argument("--spin", type=int, default=0, metavar="N", help="N frames with every instance turned about its own origin: one commit, one in-place instance edit per frame")
+    ap.add_argument("--spin-axis", choices=["x", "y", "z"], default="y")
     a = ap.parse_args(argv)
     params = {}
     for d in a.defines:
@@ -112,12 +133,17 @@ def main(argv=None):
         k, v = d.split("=", 1); params[k] = v
     if a.orbit < 0:
         raise SystemExit("--orbit expects a frame count >= 1")
+    if a.spin < 0 or (a.spin and a.orbit):
+        raise SystemExit("--spin expects a frame count >= 1 and cannot be combined with --orbit")
     try:
         t0 = time.perf_counter()
         sc = xml_scene.load_scene(a.scene, params, sampler=a.sampler)
         if a.spp is not None:
             sc.spp = a.spp
         out = a.output or (a.scene.rsplit(".", 1)[0] + ".exr")          # hdrfilm's default fileFormat (src/films/hdrfilm.cpp: openexr)
+        if a.spin and not (sc.get("instances") or []):
+            print(f"error: {a.scene}: --spin turns the instances of shape groups, and this scene has none", file=sys.stderr)
+            return 1
         t1 = time.perf_counter()
         scene = Scene(sc, device=a.device)
         render = Render(scene, device=a.device)
@@ -134,6 +160,18 @@ def main(argv=None):
             rev, builds = scene.revision(); mean = sum(frame_s) / len(frame_s)
             print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s once ({builds} tree build, {rev} camera edits), "
                   f"{a.orbit} frames, render {mean:.3f} s per frame ({n / mean / 1e6:.1f} Msamples/s) -> {stem}_000.{ext} .. {stem}_{a.orbit - 1:03d}.{ext}")
+            return 0
+        if a.spin:
+            stem, ext = out.rsplit(".", 1); frame_s = []
+            for f, insts in enumerate(spin_instances(sc, a.spin, a.spin_axis)):
+                tf = time.perf_counter()
+                scene.update_instances(insts); render.clear(); render.run()
+                frame_s.append(time.perf_counter() - tf)
+                if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}"):
+                    return 1
+            rev, builds = scene.revision(); mean = sum(frame_s) / len(frame_s)
+            print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles, {len(insts)} instances; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s once ({builds} tree build, {rev} instance edits), "
+                  f"{a.spin} frames, render {mean:.3f} s per frame ({n / mean / 1e6:.1f} Msamples/s) -> {stem}_000.{ext} .. {stem}_{a.spin - 1:03d}.{ext}")
             return 0
         render.run()
         rgb = render.read_film(2)
