@@ -247,8 +247,25 @@ int mi_scene_update_vertices(mi_scene *s, const float *pos, const float *nrm, ui
  * failed allocation of the edit's own device tables (MI_ERR_DEVICE, "the scene is unchanged").  Any other MI_ERR_DEVICE (a failed copy or launch) comes after the host
  * side has taken the new instances: host and device tables are then out of step and the scene must be committed again.
  * The scene-level tree keeps the topology the SAH build chose for the committed placement; after large moves traversal slows down (results stay exact).  A fresh
- * mi_scene_commit is the remedy.  mi_scene_update_vertices still refuses scenes with instances: moving the vertices of group members is not implemented. */
+ * mi_scene_commit is the remedy.  mi_scene_update_vertices still refuses scenes with instances: mi_scene_update_geometry (below) moves the vertices of group members. */
 int mi_scene_update_instances(mi_scene *s, const mi_instance *instances, uint32_t n);
+/* Geometry edit: one frame of an animation in one call -- new positions pos[n_verts * 3] (and normals, if and only if the scene was committed with them) for the WHOLE
+ * vertex array, the members of shape groups included, and / or new to_world / to_object for ALL committed instances.  pos = nrm = NULL, n_verts = 0: the vertices stay;
+ * instances = NULL, n_instances = 0: the placements stay; both NULL: MI_ERR_INVALID.  Works on every committed scene: without instances and with instances = NULL it
+ * does what mi_scene_update_vertices does (packet tables included), with `instances` alone what mi_scene_update_instances does.  With vertices on a scene with shape
+ * groups it also recomputes, by the commit's own rules, the group boxes (host), from them glo / ghi of every instance record and the box of its leaf (device), every
+ * per-triangle record and leaf box (device), and REFITS every tree -- the scene level and each group's -- bottom-up on the device; the scene box, the scene-level area
+ * lights' CDFs and the bounding spheres follow on the host.  One push of the inputs, one chain of launches on one stream, one `revision` step; `tree_builds` never
+ * moves.  Results and device tables equal those of a fresh commit of the new description bit for bit.  Returns when the device has finished.
+ * MI_ERR_INVALID: null scene, scene not committed, a run in flight, both parts NULL, a count without its array, n_verts differs from the committed count, nrm given for a
+ * scene without normals or missing for one with, a non-finite position or normal (the message names the first vertex), `instances` on a scene without instances,
+ * n_instances differs from the committed count, a non-finite entry in to_world / to_object (the message names the first instance).  MI_ERR_UNSUPPORTED: an instance
+ * whose `group` differs from the committed one (the message names it).  Every message starts with "mi_scene_update_geometry: ".  All checks come before any change: a
+ * refused call leaves the scene, its revision and its device tables untouched, and so does a failed allocation of the edit's own device tables (MI_ERR_DEVICE, "the
+ * scene is unchanged").  Any other MI_ERR_DEVICE leaves host and device out of step: commit again.  May be mixed freely with mi_scene_update_vertices / _instances,
+ * which stay as they are (the former keeps refusing scenes with shape groups or instances).  Counts, indices, an instance's group, media on group members and analytic
+ * group members are out of reach of an update.  The trees keep the committed topology: after large deformations traversal slows down, a fresh commit is the remedy. */
+int mi_scene_update_geometry(mi_scene *s, const float *pos, const float *nrm, uint32_t n_verts, const mi_instance *instances, uint32_t n_instances);
 /* revision: in-place edits applied so far; tree_builds: host-side builds (tree, triangle records) this scene has gone through -- an update never moves it.  Either may be NULL */
 int mi_scene_revision(mi_scene *s, uint64_t *revision, uint64_t *tree_builds);
 

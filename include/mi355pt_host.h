@@ -29,6 +29,7 @@ int mi_host_set_emitters(void *integrator, const mi_emitter *emitters, uint32_t 
 int mi_host_set_envmap_transform(void *integrator, const float *to_world16, float scale);
 int mi_host_set_vertices(void *integrator, const float *pos, const float *nrm, uint32_t n_verts);   /* mi_scene_update_vertices */
 int mi_host_set_instances(void *integrator, const mi_instance *instances, uint32_t n);   /* mi_scene_update_instances */
+int mi_host_set_geometry(void *integrator, const float *pos, const float *nrm, uint32_t n_verts, const mi_instance *instances, uint32_t n_instances);   /* mi_scene_update_geometry */
 void mi_host_cancel(void *integrator);
 const char *mi_host_statistics(void *integrator);
 #ifdef __cplusplus

@@ -89,11 +89,11 @@ class MiFusedDebugInfo(C.Structure):
 
 EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_scene_create", "mi_scene_destroy", "mi_scene_set_triangles",
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_film",
-           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
+           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
            "mi_render_set_profiling", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_geometry_bytes", "mi_debug_read_geometry"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
-                "mi_host_set_camera", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances"]
+                "mi_host_set_camera", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
 
 
 def build(force=False):
@@ -136,6 +136,7 @@ class Lib:
         L.mi_scene_update_envmap_transform.argtypes = [vp, vp, f32]
         L.mi_scene_update_vertices.argtypes = [vp, vp, vp, u32]
         L.mi_scene_update_instances.argtypes = [vp, vp, u32]
+        L.mi_scene_update_geometry.argtypes = [vp, vp, vp, u32, vp, u32]
         L.mi_scene_revision.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
         L.mi_render_merge_film.argtypes = [vp, vp]
         L.mi_render_create.argtypes = [vp, C.POINTER(MiRenderParams), C.POINTER(vp)]
@@ -347,6 +348,20 @@ class Scene:
         self.L.check(self.L.L.mi_scene_update_instances(self.h, C.cast(pack_instances(instances), C.c_void_p), len(instances)))
         self.sc.instances = instances
 
+    def update_geometry(self, pos=None, nrm=None, instances=None):
+        """One frame of an animation: new positions [n_verts, 3] (and normals, if and only if the scene has them) for the whole vertex array, shape-group members
+        included, and / or new to_world / to_object for all committed instances.  Per-triangle records, group boxes, instance records and a refit of every tree on the
+        device, no tree build.  Works on every committed scene; both parts None is refused (MiError code 1), a changed group with code 3."""
+        if pos is not None: pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        if nrm is not None: nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        if nrm is not None and pos is not None and len(nrm) != len(pos): raise ValueError("update_geometry: one normal per vertex")
+        if instances is not None: instances = list(instances)
+        arr = None if instances is None else C.cast(pack_instances(instances), C.c_void_p)
+        self.L.check(self.L.L.mi_scene_update_geometry(self.h, _p(pos), _p(nrm), 0 if pos is None else len(pos), arr, 0 if instances is None else len(instances)))
+        if pos is not None: self.sc.pos = pos
+        if pos is not None and nrm is not None: self.sc.nrm = nrm
+        if instances is not None: self.sc.instances = instances
+
     GEOMETRY_TABLES = {"nodes": (0, 64), "leaf_records": (1, 48), "tri_shade": (2, 128), "tri_uv": (3, 48), "packet_exact": (4, 48), "packet_groups": (5, 48),
                        "instances": (6, 128), "scene_box": (7, 24)}
 
@@ -539,6 +554,19 @@ class HostIntegrator:
             raise RuntimeError(self.L.mi_host_last_error().decode())
         self.scene.sc.pos = pos
         if nrm is not None: self.scene.sc.nrm = nrm
+
+    def set_geometry(self, pos=None, nrm=None, instances=None):
+        """MIPathTracerHIP::setGeometry: mi_scene_update_geometry on the borrowed scene and on every replica, between two render() calls."""
+        if pos is not None: pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        if nrm is not None: nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        if instances is not None: instances = list(instances)
+        arr = None if instances is None else C.cast(pack_instances(instances), C.c_void_p)
+        self.L.mi_host_set_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        if self.L.mi_host_set_geometry(self.h, _p(pos), _p(nrm), 0 if pos is None else len(pos), arr, 0 if instances is None else len(instances)) != 0:
+            raise RuntimeError(self.L.mi_host_last_error().decode())
+        if pos is not None: self.scene.sc.pos = pos
+        if pos is not None and nrm is not None: self.scene.sc.nrm = nrm
+        if instances is not None: self.scene.sc.instances = instances
 
     def set_instances(self, instances):
         """MIPathTracerHIP::setInstances: mi_scene_update_instances on the borrowed scene and on every replica, between two render() calls."""

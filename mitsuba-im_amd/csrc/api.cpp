@@ -260,7 +260,7 @@ template <typename T> static int up(void **dst, const std::vector<T> &v) {
     return 0;
 }
 void SceneHost::release() {
-    void **ps[] = {&dPos, &dLeafSlot, &dLeafBox, &dNodeBox, &dRefitOrder, &dInstXf, &dLeafSlotInst, &dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
+    void **ps[] = {&dRefitOrderAll, &dGroupBox, &dPos, &dLeafSlot, &dLeafBox, &dNodeBox, &dRefitOrder, &dInstXf, &dLeafSlotInst, &dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
     for (void **p : ps) if (*p) { (void) hipFree(*p); *p = nullptr; }
 }
 int SceneHost::upload(int dev) {
@@ -422,7 +422,7 @@ int mi_scene_clone(mi_scene *s, uint32_t device, mi_scene **out) {
     mi_scene *c = new mi_scene();
     c->h = s->h;                                    // inputs + host-derived data
     {   // the copy must not own the source's device allocations
-        void **ps[] = {&c->h.dPos, &c->h.dLeafSlot, &c->h.dLeafBox, &c->h.dNodeBox, &c->h.dRefitOrder, &c->h.dInstXf, &c->h.dLeafSlotInst, &c->h.dMaterialFlags, &c->h.dMedia, &c->h.dPrimMedia, &c->h.dPacketGroups, &c->h.dPacketExact, &c->h.dTexLevels, &c->h.dTexTexels, &c->h.dMipLut, &c->h.dTriUV, &c->h.dTextures, &c->h.dMaterialTables, &c->h.dInstances, &c->h.dEmitterX, &c->h.dAnalytic, &c->h.dNodes, &c->h.dTris, &c->h.dShade, &c->h.dI2, &c->h.dNrm, &c->h.dMaterials, &c->h.dEmitters, &c->h.dEmitterCdf, &c->h.dAreaCdf, &c->h.dFilter, &c->h.dSobolM32, &c->h.dSobolVdc, &c->h.dSobolVdcInv, &c->h.dEnvRGB, &c->h.dEnvCols, &c->h.dEnvRows, &c->h.dEnvWeights, &c->h.dEnvGuideRows, &c->h.dEnvGuideCols};
+        void **ps[] = {&c->h.dRefitOrderAll, &c->h.dGroupBox, &c->h.dPos, &c->h.dLeafSlot, &c->h.dLeafBox, &c->h.dNodeBox, &c->h.dRefitOrder, &c->h.dInstXf, &c->h.dLeafSlotInst, &c->h.dMaterialFlags, &c->h.dMedia, &c->h.dPrimMedia, &c->h.dPacketGroups, &c->h.dPacketExact, &c->h.dTexLevels, &c->h.dTexTexels, &c->h.dMipLut, &c->h.dTriUV, &c->h.dTextures, &c->h.dMaterialTables, &c->h.dInstances, &c->h.dEmitterX, &c->h.dAnalytic, &c->h.dNodes, &c->h.dTris, &c->h.dShade, &c->h.dI2, &c->h.dNrm, &c->h.dMaterials, &c->h.dEmitters, &c->h.dEmitterCdf, &c->h.dAreaCdf, &c->h.dFilter, &c->h.dSobolM32, &c->h.dSobolVdc, &c->h.dSobolVdcInv, &c->h.dEnvRGB, &c->h.dEnvCols, &c->h.dEnvRows, &c->h.dEnvWeights, &c->h.dEnvGuideRows, &c->h.dEnvGuideCols};
         for (void **p : ps) *p = nullptr;
         c->h.committed = false;
     }
@@ -561,6 +561,74 @@ int mi_scene_update_instances(mi_scene *s, const mi_instance *instances, uint32_
         mi_launch_refit_level(g, (const uint32_t *) h.dRefitOrder, h.refitLevelStart[l], h.refitLevelStart[l + 1] - h.refitLevelStart[l], h.d.n_nodes, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(push(h.dEmitters, h.emittersD)); HIPCHK(push(h.dEmitterX, h.emitterX));      // as the vertex edit pushes them; the scene record travels with the next run
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return MI_OK;
+}
+// Geometry edit: one frame of an animation -- vertices (shape-group members included) and / or instance transforms.  Host: the checks, pos / nrm / instances, the group
+// boxes, the scene box and what depends on it (SceneHost::applyGeometry).  Device, one chain on the null stream: the inputs go up (vertex arrays, group boxes, transform
+// pairs), k_tri_records rewrites every per-triangle record and leaf box, k_instance_records takes the group boxes into InstanceD::glo / ghi and rewrites matrices and
+// instance leaf boxes, k_refit refits level by level -- every tree when vertices moved (nodes of equal height of all trees share a launch), the scene level alone
+// otherwise -- and the small tables go back into their allocations.  Synchronous like the other updates.
+int mi_scene_update_geometry(mi_scene *s, const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *instances, uint32_t nInstances) {
+    if (!s) return fail(MI_ERR_INVALID, "mi_scene_update_geometry: null scene");
+    if (!pos && !instances) return fail(MI_ERR_INVALID, "mi_scene_update_geometry: null argument: neither vertices nor instances given");
+    UPDATE_ENTER("mi_scene_update_geometry");
+    mi::SceneHost &h = s->h; const size_t cdfLen = h.areaCdf.size(), nGroups = h.packetGroups.size();
+    std::string msg; const int rc = h.checkGeometry(pos, nrm, nVerts, instances, nInstances, msg); if (rc) return fail(rc, msg);
+    if (!h.geoPrepared) h.prepareGeometryEdit();      // derived from the committed topology alone: the scene itself is not changed yet
+    const uint32_t ni = (uint32_t) h.instances.size(), ng = (uint32_t) (h.groupBoxes.size() / 6);
+    if (h.shade.size() != h.d.n_tris || h.nodes.size() != h.d.n_nodes || h.leafSlotOfPrim.size() != h.d.n_tris || h.instancesD.size() != h.d.n_instances || ni != h.d.n_instances || h.leafSlotOfInstance.size() != ni ||
+        h.leafBoxes.size() != h.tris.size() * 6 || h.nodeBoxes.size() != h.nodes.size() * 6 || h.refitOrder.size() > h.nodes.size() || h.refitOrderAll.size() > h.nodes.size())
+        return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
+    for (uint32_t slot : h.leafSlotOfInstance) if (slot >= h.tris.size()) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
+    for (uint32_t slot : h.leafSlotOfPrim) if (slot >= h.tris.size()) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
+    for (const InstanceD &in : h.instancesD) if (in.group >= ng) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
+    HIPCHK(hipSetDevice(h.device));
+    {   // The tables a commit does not need.  Only what is MISSING is allocated: after an earlier mi_scene_update_vertices / _instances the device's leaf boxes are current
+        // while their host mirror is stale until refreshHostGeometry() -- they must not be uploaded again.  A leaf-box table that does not exist yet means that no edit
+        // has run since the commit, so the mirror prepareGeometryEdit() filled is current.  Every table of the two older calls is allocated here as well, so that their
+        // own first-edit blocks (which free and re-upload the leaf boxes) find nothing missing afterwards.  dNodeBox stays uninitialised: a node's box is written by the
+        // refit of its level before any higher level reads it.
+        std::vector<void **> mine; bool bad = false;
+        auto raw = [&](void **p, size_t bytes) { if (*p || bad) return; if (hipMalloc(p, std::max<size_t>(bytes, 16)) != hipSuccess) { *p = nullptr; bad = true; } else mine.push_back(p); };
+        auto filled = [&](void **p, const std::vector<uint32_t> &v) { if (*p || bad) return; if (mi::up(p, v)) bad = true; if (*p) mine.push_back(p); };
+        raw(&h.dPos, h.pos.size() * 4); raw(&h.dNodeBox, h.nodeBoxes.size() * 4); raw(&h.dInstXf, (size_t) ni * 96); raw(&h.dGroupBox, (size_t) ng * 24);
+        filled(&h.dLeafSlot, h.leafSlotOfPrim); filled(&h.dLeafSlotInst, h.leafSlotOfInstance); filled(&h.dRefitOrder, h.refitOrder); filled(&h.dRefitOrderAll, h.refitOrderAll);
+        if (!h.dLeafBox && !bad) { if (mi::up(&h.dLeafBox, h.leafBoxes)) bad = true; if (h.dLeafBox) mine.push_back(&h.dLeafBox); }
+        if (bad) {
+            const std::string why = hipGetErrorString(hipGetLastError());
+            for (void **p : mine) { (void) hipFree(*p); *p = nullptr; }
+            return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: allocation failed, the scene is unchanged: " + why);
+        }
+    }
+    // from here on the scene changes; a device error below leaves host and device tables out of step (see the header)
+    h.applyGeometry(pos, nrm, nVerts, instances, nInstances);
+    if (h.emittersD.size() != h.d.n_emitters || h.areaCdf.size() != cdfLen || h.groupBoxes.size() != (size_t) ng * 6) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
+    if (pos) { HIPCHK(push(h.dPos, h.pos)); HIPCHK(push(h.dNrm, h.nrm)); }
+    mi::GeoEditTables g{}; g.pos = (const float *) h.dPos; g.nrm = h.nrm.empty() ? nullptr : (const float *) h.dNrm; g.shade = (TriShade *) h.dShade; g.triuv = h.triuv.empty() ? nullptr : (TriUV *) h.dTriUV;
+    g.tris = const_cast<TriAccelD *>(h.d.tris); g.packetExact = (TriAccelD *) h.dPacketExact; g.leafSlot = (const uint32_t *) h.dLeafSlot; g.leafBox = (float *) h.dLeafBox;
+    g.nodes = (BvhNode *) h.dNodes; g.nodeBox = (float *) h.dNodeBox; g.nTris = h.d.n_tris; g.nPacketExact = (uint32_t) std::min<size_t>(h.packetExact.size(), h.d.n_tris); g.wide = h.wideBvh ? 1u : 0u;
+    if (pos) mi_launch_tri_records(g, nullptr);
+    if (ni) {
+        std::vector<float> xf((size_t) ni * 24);      // the new transforms, or the committed ones again: the instance box also follows the group box
+        for (uint32_t i = 0; i < ni; ++i) { memcpy(&xf[(size_t) i * 24], h.instances[i].to_world, 48); memcpy(&xf[(size_t) i * 24 + 12], h.instances[i].to_object, 48); }
+        HIPCHK(push(h.dInstXf, xf)); HIPCHK(push(h.dGroupBox, h.groupBoxes));
+        mi::InstEditTables it{}; it.xf = (const float *) h.dInstXf; it.inst = (InstanceD *) h.dInstances; it.leafSlot = (const uint32_t *) h.dLeafSlotInst; it.leafBox = (float *) h.dLeafBox; it.n = ni;
+        it.groupBox = (const float *) h.dGroupBox; it.nGroups = ng;
+        mi_launch_instance_records(it, nullptr);
+    }
+    {   // bottom-up: level l reads the boxes levels < l wrote; stream order is the only synchronisation.  Vertices moved: every tree; instances only: the scene level
+        const std::vector<uint32_t> &start = pos ? h.refitLevelStartAll : h.refitLevelStart; const uint32_t *order = (const uint32_t *) (pos ? h.dRefitOrderAll : h.dRefitOrder);
+        for (size_t l = 0; l + 1 < start.size(); ++l) mi_launch_refit_level(g, order, start[l], start[l + 1] - start[l], h.d.n_nodes, nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    if (!ni && pos) {      // the packet tables of a scene without instances, as mi_scene_update_vertices sends them
+        if (h.packetGroups.size() > nGroups) {      // pairs dissolved: the pass-1 table grew
+            void *grown = nullptr; if (mi::up(&grown, h.packetGroups)) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: allocation failed");
+            HIPCHK(hipStreamSynchronize(nullptr)); (void) hipFree(h.dPacketGroups); h.dPacketGroups = grown; h.d.packet_groups = (const PacketGroupD *) grown;
+        } else HIPCHK(push(h.dPacketGroups, h.packetGroups));
+    }
+    HIPCHK(push(h.dEmitters, h.emittersD)); HIPCHK(push(h.dAreaCdf, h.areaCdf)); HIPCHK(push(h.dEmitterX, h.emitterX));
     HIPCHK(hipStreamSynchronize(nullptr));
     return MI_OK;
 }

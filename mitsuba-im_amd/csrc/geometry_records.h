@@ -1,6 +1,6 @@
 // geometry_records.h -- the arithmetic that turns vertex positions into device records, once, for the host and for the device.
 //
-// mi_scene_commit derives these records on the host (scene_build.cpp, commitHost()); mi_scene_update_vertices and mi_scene_update_instances derive them again on the
+// mi_scene_commit derives these records on the host (scene_build.cpp, commitHost()); mi_scene_update_vertices, _instances and _geometry derive them again on the
 // device (kernels_geometry.hip) and, when a host mirror is needed, on the host (SceneHost::refreshHostGeometry()).  "After an update every result equals that of a fresh commit" holds bit for bit only
 // if all three run the very same operations in the very same order, so they all call the functions below.  Everything here is strict IEEE binary32 / binary64: the
 // translation units that include it are compiled with -ffp-contract=off and correctly rounded divide / square root on both sides.  min / max are the ternaries of
@@ -206,12 +206,19 @@ MI_HD static inline void geoRefitNode(const GeoEditTables &g, uint32_t n) {
 
 // ------------------------------------------------------------------------------------------------ the first step of an instance edit (the second is geoRefitNode)
 // xf[24 * i] = rows 0..2 of the new to_world of instance i, then rows 0..2 of its to_object; leafSlot[i] = position of the instance's MI_K_INSTANCE record among the
-// leaf records.  Rewrites the two matrices of InstanceD[i] (96 of its 128 bytes: glo, ghi, root and group never change) and the padded box of its leaf record.
-struct InstEditTables { const float *xf; InstanceD *inst; const uint32_t *leafSlot; float *leafBox; uint32_t n; };
+// leaf records.  Rewrites the two matrices of InstanceD[i] (96 of its 128 bytes) and the padded box of its leaf record.  groupBox (optional; 6 floats per shape group:
+// lo, hi): the groups' boxes after a geometry edit moved their vertices -- the record's glo / ghi (words 24..26, 28..30) are rewritten from the box of the record's own
+// `group` before the instance box is derived from them.  Without it glo / ghi stay; `root` and `group` always stay.
+struct InstEditTables { const float *xf; InstanceD *inst; const uint32_t *leafSlot; float *leafBox; uint32_t n; const float *groupBox; uint32_t nGroups; };
 MI_HD static inline void geoInstanceRecord(const InstEditTables &g, uint32_t i) {
     InstanceD &d = g.inst[i]; const float *x = g.xf + (size_t) i * 24;
     for (int k = 0; k < 12; ++k) { d.to_world[k] = x[k]; d.to_object[k] = x[12 + k]; }
-    V3 blo, bhi, plo, phi, cen; instanceBoxes(x, load3(d.glo), load3(d.ghi), blo, bhi, plo, phi, cen);
+    V3 glo = load3(d.glo), ghi = load3(d.ghi);
+    if (g.groupBox && d.group < g.nGroups) {
+        const float *b = g.groupBox + (size_t) d.group * 6; glo = load3(b); ghi = load3(b + 3);
+        store3(d.glo, glo); store3(d.ghi, ghi);
+    }
+    V3 blo, bhi, plo, phi, cen; instanceBoxes(x, glo, ghi, blo, bhi, plo, phi, cen);
     const uint32_t slot = g.leafSlot[i];
     store3(g.leafBox + (size_t) slot * 6, plo); store3(g.leafBox + (size_t) slot * 6 + 3, phi);
 }

@@ -151,6 +151,7 @@ void MIPathTracerHIP::setMaterials(const mi_material *m, uint32_t n) { editAll("
 void MIPathTracerHIP::setEmitters(const mi_emitter *e, uint32_t n) { editAll("MIPathTracerHIP::setEmitters", [&](mi_scene *s) { return mi_scene_update_emitters(s, e, n); }); }
 void MIPathTracerHIP::setEnvmapTransform(const float *toWorld, float scale) { editAll("MIPathTracerHIP::setEnvmapTransform", [&](mi_scene *s) { return mi_scene_update_envmap_transform(s, toWorld, scale); }); }
 void MIPathTracerHIP::setInstances(const mi_instance *instances, uint32_t n) { editAll("MIPathTracerHIP::setInstances", [&](mi_scene *s) { return mi_scene_update_instances(s, instances, n); }); }
+void MIPathTracerHIP::setGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *instances, uint32_t nInstances) { editAll("MIPathTracerHIP::setGeometry", [&](mi_scene *s) { return mi_scene_update_geometry(s, pos, nrm, nVerts, instances, nInstances); }); }
 void MIPathTracerHIP::setVertices(const float *pos, const float *nrm, uint32_t nVerts) { editAll("MIPathTracerHIP::setVertices", [&](mi_scene *s) { return mi_scene_update_vertices(s, pos, nrm, nVerts); }); }
 
 const char *MIPathTracerHIP::getRealtimeStatistics() {
@@ -214,6 +215,7 @@ int mi_host_set_materials(void *h, const mi_material *m, uint32_t n) { HOST_EDIT
 int mi_host_set_emitters(void *h, const mi_emitter *e, uint32_t n) { HOST_EDIT(setEmitters(e, n)) }
 int mi_host_set_envmap_transform(void *h, const float *toWorld, float scale) { HOST_EDIT(setEnvmapTransform(toWorld, scale)) }
 int mi_host_set_instances(void *h, const mi_instance *instances, uint32_t n) { HOST_EDIT(setInstances(instances, n)) }
+int mi_host_set_geometry(void *h, const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *instances, uint32_t nInstances) { HOST_EDIT(setGeometry(pos, nrm, nVerts, instances, nInstances)) }
 int mi_host_set_vertices(void *h, const float *pos, const float *nrm, uint32_t nVerts) { HOST_EDIT(setVertices(pos, nrm, nVerts)) }
 void mi_host_cancel(void *h) { ((mi355::MIPathTracerHIP *) h)->cancel(); }
 const char *mi_host_statistics(void *h) { return ((mi355::MIPathTracerHIP *) h)->getRealtimeStatistics(); }

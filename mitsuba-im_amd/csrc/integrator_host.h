@@ -59,6 +59,7 @@ public:
     void setEmitters(const mi_emitter *emitters, uint32_t n);
     void setEnvmapTransform(const float *toWorld16, float scale);
     void setInstances(const mi_instance *instances, uint32_t n);   // mi_scene_update_instances: new transforms of the committed instances, scene-level tree refit on every device
+    void setGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *instances, uint32_t nInstances);   // mi_scene_update_geometry: vertices (group members included) and / or instance transforms, every tree refitted on every device
     void setVertices(const float *pos, const float *nrm, uint32_t nVerts);   // mi_scene_update_vertices: new positions (and normals) of the committed vertices, tree refit on every device
     float getLowerSampleBound() const { return 1.0f; }
     const char *getRealtimeStatistics();

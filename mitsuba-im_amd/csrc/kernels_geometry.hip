@@ -1,5 +1,5 @@
-// kernels_geometry.hip -- mi_scene_update_vertices and mi_scene_update_instances on the device: the per-triangle records, the instance records and the refit of the
-// existing tree (DESIGN.md §3 "In-place edits").
+// kernels_geometry.hip -- mi_scene_update_vertices, mi_scene_update_instances and mi_scene_update_geometry on the device: the per-triangle records, the instance
+// records and the refit of the existing trees (DESIGN.md §3 "In-place edits").
 //
 // All kernels are thin: the arithmetic is geometry_records.h, shared with commitHost() and SceneHost::refreshHostGeometry(), so that an edited scene holds, bit for
 // bit, the records a fresh commit of the new vertices would hold.  Compiled like every other unit: -ffp-contract=off, correctly rounded divide and square root.
@@ -8,9 +8,11 @@
 //                   48-B Wald record twice (leaf slot, packet-exact table), the geometric words of the TriShade line, the UV tangents and the 24-B padded leaf box.
 //                   Memory bound: ~36 B gathered + 128 B read-modify-write + ~170 B written per triangle; no LDS, no cross-lane traffic.
 //   k_instance_records   one thread per instance: reads its new to_world / to_object (96 B from the staging array), rewrites those 96 of the 128 B of its InstanceD
-//                   and the 24-B padded box of its leaf record (the 8 transformed corners of the group box, which the record itself carries).  No LDS, no cross-lane
-//                   traffic, no atomics; k_refit over the scene-level tree follows on the same stream.
-//   k_refit         one thread per node of ONE level (all of its inner children belong to lower levels, refitted by earlier launches on the same stream): unions
+//                   and the 24-B padded box of its leaf record (the 8 transformed corners of the group box, which the record itself carries).  A geometry edit hands it
+//                   the groups' new boxes (24 B per group, a handful of cache lines shared by all lanes): the record's glo / ghi are then rewritten from the box of its
+//                   own `group` first.  No LDS, no cross-lane traffic, no atomics; k_refit follows on the same stream.
+//   k_refit         one thread per node of ONE level (all of its inner children belong to lower levels, refitted by earlier launches on the same stream; a geometry
+//                   edit puts the nodes of equal height of the scene-level tree and of every group tree into one level -- no tree reads another's nodes): unions
 //                   the child boxes and rewrites the node's child boxes -- for a 4-wide node org, the three steps and the quantised bytes by the builder's rule.
 //                   No atomics and no synchronisation between workgroups: the launch order is the only dependency, the result is deterministic.
 #include <hip/hip_runtime.h>

@@ -84,6 +84,16 @@ void SceneHost::buildSceneBox(const float *extra, uint32_t n) {
     store3(aabbLo, lo); store3(aabbHi, hi);
 }
 
+// kd-tree box of every shape group = union of the member shapes' AABBs in shape order (ShapeKDTree::addShape, skdtree.cpp:68-77), enlarged like the kd-tree root
+void SceneHost::buildGroupBoxes() {
+    const float inf = std::numeric_limits<float>::infinity();
+    uint32_t ng = 0; for (const mi_shape &sh : shapes) ng = std::max(ng, sh.group);
+    std::vector<V3> glo(ng, mk(inf, inf, inf)), ghi(ng, mk(-inf, -inf, -inf));
+    for (const mi_shape &sh : shapes) { if (!sh.group) continue; const uint32_t g = sh.group - 1; for (uint32_t v = 0; v < sh.vert_count; ++v) { V3 p = load3(&pos[(size_t) (sh.first_vert + v) * 3]); glo[g] = vmin(glo[g], p); ghi[g] = vmax(ghi[g], p); } }
+    groupBoxes.assign((size_t) ng * 6, 0.0f);
+    for (uint32_t g = 0; g < ng; ++g) { enlargeBox(glo[g], ghi[g]); store3(&groupBoxes[(size_t) g * 6], glo[g]); store3(&groupBoxes[(size_t) g * 6 + 3], ghi[g]); }
+}
+
 struct BuildNode { V3 lo, hi; int left = -1, right = -1, first = 0, count = 0; };
 struct Builder {
     std::vector<BuildNode> nodes; std::vector<uint32_t> order; const std::vector<V3> *tlo, *thi, *cen;
@@ -157,7 +167,7 @@ static inline int32_t leafCode(int first, int count) { return ~(int32_t) (first 
 void SceneHost::commitHost() {
     ++treeBuilds;
     // a new tree: whatever the vertex or instance edits of the previous one derived (slot tables, level order, box scratch, the stale marks) describes a tree that no longer exists
-    geoPrepared = geoStale = instStale = false; leafSlotOfPrim.clear(); leafSlotOfInstance.clear(); refitOrder.clear(); refitLevelStart.clear(); leafBoxes.clear(); nodeBoxes.clear();
+    geoPrepared = geoStale = instStale = false; leafSlotOfPrim.clear(); leafSlotOfInstance.clear(); refitOrder.clear(); refitLevelStart.clear(); refitOrderAll.clear(); refitLevelStartAll.clear(); leafBoxes.clear(); nodeBoxes.clear();
     const uint32_t nt = (uint32_t) (idx.size() / 3), na = (uint32_t) analytic.size(), ni = (uint32_t) instances.size(), np = nt + na + ni;
     nTris = nt;
     auto vert = [&](uint32_t i) { return mk(pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]); };
@@ -202,12 +212,11 @@ void SceneHost::commitHost() {
     }
     // --- kd-tree boxes of the shape groups and of the scene = union of the member shapes' AABBs (ShapeKDTree::addShape, skdtree.cpp:68-77),
     //     enlarged like the kd-tree root (gkdtree.h:1213-1220); instance boxes = the 8 transformed corners of the group box (instance.cpp:46-64)
-    const float inf = std::numeric_limits<float>::infinity();
     uint32_t ng = 0; for (const mi_shape &sh : shapes) ng = std::max(ng, sh.group);
-    std::vector<V3> glo(ng + 1, mk(inf, inf, inf)), ghi(ng + 1, mk(-inf, -inf, -inf));      // slot ng (the scene level) is used by the member lists below; the scene's box is buildSceneBox()
-    auto slotOf = [&](const mi_shape &sh) { return sh.group ? sh.group - 1 : ng; };
-    for (const mi_shape &sh : shapes) { if (!sh.group) continue; uint32_t g = slotOf(sh); for (uint32_t v = 0; v < sh.vert_count; ++v) { V3 p = vert(sh.first_vert + v); glo[g] = vmin(glo[g], p); ghi[g] = vmax(ghi[g], p); } }
-    for (uint32_t g = 0; g < ng; ++g) enlargeBox(glo[g], ghi[g]);
+    auto slotOf = [&](const mi_shape &sh) { return sh.group ? sh.group - 1 : ng; };      // slot ng (the scene level) is used by the member lists below; the scene's box is buildSceneBox()
+    buildGroupBoxes();      // shared with the geometry edit
+    std::vector<V3> glo(ng), ghi(ng);
+    for (uint32_t g = 0; g < ng; ++g) { glo[g] = load3(&groupBoxes[(size_t) g * 6]); ghi[g] = load3(&groupBoxes[(size_t) g * 6 + 3]); }
     instancesD.assign(ni, InstanceD{});
     std::vector<float> instBoxes((size_t) ni * 6);
     for (uint32_t i = 0; i < ni; ++i) {
@@ -336,7 +345,7 @@ void SceneHost::commitHost() {
         }
         nodes.swap(re);
     }
-    std::vector<int> groupRoot(ng, 0);
+    groupRoot.assign(ng, 0);
     for (uint32_t g = 0; g < ng; ++g) groupRoot[g] = emitTree(members[g]);
     for (uint32_t i = 0; i < ni; ++i) instancesD[i].root = groupRoot[instances[i].group];
     // traversal stack need: scene tree + one return marker + the deepest group tree
@@ -680,7 +689,8 @@ int SceneHost::updateEnvmapTransform(const float *toWorld16, float scale, std::s
 // What a vertex or an instance edit needs beyond the committed tables, derived once at the first edit: where each triangle's and each instance's leaf record sits, the
 // padded boxes of the leaf records that the edit's kernel does not write (analytic shapes; on a scene with instances, where only instances move, also the triangles;
 // the never-hit record of unused 4-wide slots stays empty), and the order in which the existing nodes are refitted -- by height, height 0 = every child is a leaf,
-// so that a node comes after all of its inner children.  The walk starts at node 0 and an instance is a leaf, so the order covers the scene-level tree only.
+// so that a node comes after all of its inner children.  The walk starts at node 0 and an instance is a leaf, so that order (refitOrder) covers the scene-level tree
+// only; a second order (refitOrderAll, for mi_scene_update_geometry) repeats the walk from every group root and covers every tree.
 void SceneHost::prepareGeometryEdit() {
     const uint32_t nt = nTris; const float inf = std::numeric_limits<float>::infinity();
     leafSlotOfPrim.assign(nt, 0u); leafSlotOfInstance.assign(instances.size(), 0u); leafBoxes.assign(tris.size() * 6, 0.0f);
@@ -711,20 +721,28 @@ void SceneHost::prepareGeometryEdit() {
             height[n] = h; return h;
         } } walk{nodes, height, wideBvh};
     int top = nn ? walk.of(0) : -1;
-    refitLevelStart.assign((size_t) top + 2, 0u); refitOrder.clear();
-    for (size_t i = 0; i < nn; ++i) if (height[i] >= 0) ++refitLevelStart[(size_t) height[i] + 1];
-    for (size_t l = 1; l < refitLevelStart.size(); ++l) refitLevelStart[l] += refitLevelStart[l - 1];
-    refitOrder.resize(refitLevelStart.back());
-    { std::vector<uint32_t> fill(refitLevelStart.begin(), refitLevelStart.end() - 1); for (size_t i = 0; i < nn; ++i) if (height[i] >= 0) refitOrder[fill[(size_t) height[i]]++] = (uint32_t) i; }
+    auto byHeight = [&](std::vector<uint32_t> &order, std::vector<uint32_t> &levelStart) {      // counting sort of the nodes walked so far
+        levelStart.assign((size_t) top + 2, 0u); order.clear();
+        for (size_t i = 0; i < nn; ++i) if (height[i] >= 0) ++levelStart[(size_t) height[i] + 1];
+        for (size_t l = 1; l < levelStart.size(); ++l) levelStart[l] += levelStart[l - 1];
+        order.resize(levelStart.back());
+        std::vector<uint32_t> fill(levelStart.begin(), levelStart.end() - 1); for (size_t i = 0; i < nn; ++i) if (height[i] >= 0) order[fill[(size_t) height[i]]++] = (uint32_t) i;
+    };
+    byHeight(refitOrder, refitLevelStart);
+    // the geometry edit's order: the group trees as well, each walked from its own root.  The trees are disjoint, and an instance's leaf box comes from the group box
+    // (a vertex min / max), not from the group tree's root, so nodes of equal height share a level whatever tree they belong to.
+    for (int root : groupRoot) if (root >= 0 && (size_t) root < nn && height[root] < 0) top = std::max(top, walk.of(root));
+    byHeight(refitOrderAll, refitLevelStartAll);
     nodeBoxes.assign(nn * 6, 0.0f);
     geoPrepared = true;
 }
-int SceneHost::checkVertices(const float *posIn, const float *nrmIn, uint32_t nVerts, std::string &msg) const {
-    const std::string who = "mi_scene_update_vertices: ";
+int SceneHost::checkVertices(const float *posIn, const float *nrmIn, uint32_t nVerts, std::string &msg) const { return checkVerticesAs("mi_scene_update_vertices: ", false, posIn, nrmIn, nVerts, msg); }
+int SceneHost::checkVerticesAs(const std::string &who, bool groupsAllowed, const float *posIn, const float *nrmIn, uint32_t nVerts, std::string &msg) const {
     if (!posIn) { msg = who + "null argument"; return MI_ERR_INVALID; }
     if (!committed) { msg = who + "scene not committed"; return MI_ERR_INVALID; }
-    if (!instances.empty()) { msg = who + "instance 0 (of shape group " + std::to_string(instances[0].group) + "): group boxes, instance boxes and the two-level tree are not refitted; commit a new scene"; return MI_ERR_UNSUPPORTED; }
-    for (size_t i = 0; i < shapes.size(); ++i) if (shapes[i].group) { msg = who + "shape " + std::to_string(i) + " is a member of shape group " + std::to_string(shapes[i].group - 1) + " (instances): group boxes are not refitted; commit a new scene"; return MI_ERR_UNSUPPORTED; }
+    // mi_scene_update_vertices refits neither group boxes nor group trees; mi_scene_update_geometry does (groupsAllowed)
+    if (!groupsAllowed && !instances.empty()) { msg = who + "instance 0 (of shape group " + std::to_string(instances[0].group) + "): group boxes, instance boxes and the two-level tree are not refitted; commit a new scene"; return MI_ERR_UNSUPPORTED; }
+    if (!groupsAllowed) for (size_t i = 0; i < shapes.size(); ++i) if (shapes[i].group) { msg = who + "shape " + std::to_string(i) + " is a member of shape group " + std::to_string(shapes[i].group - 1) + " (instances): group boxes are not refitted; commit a new scene"; return MI_ERR_UNSUPPORTED; }
     if ((size_t) nVerts * 3 != pos.size() || !nTris) { msg = who + "the vertex count changes (" + std::to_string(pos.size() / 3) + " -> " + std::to_string(nVerts) + "); an update moves the committed vertices, commit a new scene"; return MI_ERR_INVALID; }
     if (nrmIn && nrm.empty()) { msg = who + "vertex normals given, but the scene was committed without normals"; return MI_ERR_INVALID; }
     if (!nrmIn && !nrm.empty()) { msg = who + "the scene was committed with vertex normals: new normals are required"; return MI_ERR_INVALID; }
@@ -748,8 +766,8 @@ void SceneHost::applyVertices(const float *posIn, const float *nrmIn, uint32_t n
     geoStale = true; ++revision;      // tris, shade, triuv, packetExact, nodes: refreshHostGeometry() before anything reads them
 }
 // ------------------------------------------------------------------------------------------------ instance edits (mi_scene_update_instances)
-int SceneHost::checkInstances(const mi_instance *in, uint32_t n, std::string &msg) const {
-    const std::string who = "mi_scene_update_instances: ";
+int SceneHost::checkInstances(const mi_instance *in, uint32_t n, std::string &msg) const { return checkInstancesAs("mi_scene_update_instances: ", in, n, msg); }
+int SceneHost::checkInstancesAs(const std::string &who, const mi_instance *in, uint32_t n, std::string &msg) const {
     if (!in) { msg = who + "null argument"; return MI_ERR_INVALID; }
     if (!committed) { msg = who + "scene not committed"; return MI_ERR_INVALID; }
     if (instances.empty()) { msg = who + "the scene has no instances"; return MI_ERR_INVALID; }
@@ -772,7 +790,7 @@ void SceneHost::applyInstances(const mi_instance *in, uint32_t n) {
     // the scene box takes the unpadded instance boxes in instance order, as commitHost() does: the same sequence of min / max, down to the sign of a zero
     std::vector<float> instBoxes((size_t) n * 6);
     for (uint32_t i = 0; i < n; ++i) {
-        const InstanceD &d0 = instancesD[i]; V3 blo, bhi, plo, phi, cen; instanceBoxes(in[i].to_world, load3(d0.glo), load3(d0.ghi), blo, bhi, plo, phi, cen);
+        const float *gb = &groupBoxes[(size_t) in[i].group * 6]; V3 blo, bhi, plo, phi, cen; instanceBoxes(in[i].to_world, load3(gb), load3(gb + 3), blo, bhi, plo, phi, cen);      // the group boxes of the current vertices (instancesD may be stale after a geometry edit)
         store3(&instBoxes[(size_t) i * 6], blo); store3(&instBoxes[(size_t) i * 6 + 3], bhi);
     }
     buildSceneBox(instBoxes.data(), n); buildBoundingSpheres();
@@ -780,25 +798,61 @@ void SceneHost::applyInstances(const mi_instance *in, uint32_t n) {
     syncCameraD(); syncEmittersD();
     instStale = true; ++revision;      // instancesD, nodes: refreshHostGeometry() before anything reads them
 }
-// The host mirrors of the per-triangle records, of the instance records and of the tree after vertex / instance edits: the same two steps the device runs
-// (geometry_records.h), in the same order.
+// ------------------------------------------------------------------------------------------------ geometry edits (mi_scene_update_geometry)
+int SceneHost::checkGeometry(const float *posIn, const float *nrmIn, uint32_t nVerts, const mi_instance *in, uint32_t nInstances, std::string &msg) const {
+    const std::string who = "mi_scene_update_geometry: ";
+    if (!posIn && !in) { msg = who + "null argument: neither vertices nor instances given"; return MI_ERR_INVALID; }
+    if (!committed) { msg = who + "scene not committed"; return MI_ERR_INVALID; }
+    if (!posIn && (nrmIn || nVerts)) { msg = who + "null argument: normals or a vertex count without positions"; return MI_ERR_INVALID; }
+    if (posIn) { const int rc = checkVerticesAs(who, true, posIn, nrmIn, nVerts, msg); if (rc) return rc; }
+    if (in) { const int rc = checkInstancesAs(who, in, nInstances, msg); if (rc) return rc; }
+    else if (nInstances) { msg = who + "null argument: an instance count without instances"; return MI_ERR_INVALID; }
+    return MI_OK;
+}
+int SceneHost::updateGeometry(const float *posIn, const float *nrmIn, uint32_t nVerts, const mi_instance *in, uint32_t nInstances, std::string &msg) {
+    { const int rc = checkGeometry(posIn, nrmIn, nVerts, in, nInstances, msg); if (rc) return rc; }
+    applyGeometry(posIn, nrmIn, nVerts, in, nInstances); return MI_OK;
+}
+void SceneHost::applyGeometry(const float *posIn, const float *nrmIn, uint32_t nVerts, const mi_instance *in, uint32_t nInstances) {
+    if (!geoPrepared) prepareGeometryEdit();      // reads topology, leaf slots and the boxes of records that never move: valid whatever was edited before
+    if (posIn) { pos.assign(posIn, posIn + (size_t) nVerts * 3); if (nrmIn) nrm.assign(nrmIn, nrmIn + (size_t) nVerts * 3); }
+    if (in) instances.assign(in, in + nInstances);
+    // group boxes, then the unpadded instance boxes in instance order, then the scene box: the commit's own pieces in the commit's order
+    buildGroupBoxes();
+    const uint32_t ni = (uint32_t) instances.size(); std::vector<float> instBoxes((size_t) ni * 6);
+    for (uint32_t i = 0; i < ni; ++i) {
+        const uint32_t g = instances[i].group; V3 blo, bhi, plo, phi, cen;
+        instanceBoxes(instances[i].to_world, load3(&groupBoxes[(size_t) g * 6]), load3(&groupBoxes[(size_t) g * 6 + 3]), blo, bhi, plo, phi, cen);
+        store3(&instBoxes[(size_t) i * 6], blo); store3(&instBoxes[(size_t) i * 6 + 3], bhi);
+    }
+    buildSceneBox(instBoxes.data(), ni);
+    buildEmitterTables();      // scene-level mesh lights may move (group members cannot be emitters)
+    buildBoundingSpheres();
+    for (int i = 0; i < 3; ++i) { d.aabb_lo[i] = aabbLo[i]; d.aabb_hi[i] = aabbHi[i]; }
+    syncCameraD(); syncEmittersD();
+    if (!ni) { buildPacketTables(); for (int i = 0; i < 3; ++i) d.packet_gk[i] = packetGK[i]; d.packet_scale = packetScale; }      // as applyVertices
+    if (posIn) geoStale = true;      // tris, shade, triuv, packetExact, every tree
+    if (ni) instStale = true;        // instancesD (glo / ghi follow the vertices, the matrices the instances), the scene-level tree
+    ++revision;
+}
+// The host mirrors of the per-triangle records, of the instance records and of the trees after vertex / instance / geometry edits, in any interleaving: the steps the
+// device runs (geometry_records.h), in the device's order, from the CURRENT inputs -- triangle records, group boxes into the instance records, instance records, then
+// the refit: over every tree when vertices moved, over the scene level alone otherwise.
 void SceneHost::refreshHostGeometry() {
+    if (!geoStale && !instStale) return;
+    GeoEditTables g{}; g.pos = pos.data(); g.nrm = nrm.empty() ? nullptr : nrm.data(); g.shade = shade.data(); g.triuv = triuv.empty() ? nullptr : triuv.data();
+    g.tris = tris.data(); g.packetExact = packetExact.data(); g.leafSlot = leafSlotOfPrim.data(); g.leafBox = leafBoxes.data(); g.nodes = nodes.data(); g.nodeBox = nodeBoxes.data();
+    g.nTris = nTris; g.nPacketExact = (uint32_t) std::min<size_t>(packetExact.size(), nTris); g.wide = wideBvh ? 1u : 0u;
+    if (geoStale) for (uint32_t t = 0; t < nTris; ++t) geoTriRecord(g, t);
     if (instStale) {
         std::vector<float> xf((size_t) instances.size() * 24);
         for (size_t i = 0; i < instances.size(); ++i) { std::memcpy(&xf[i * 24], instances[i].to_world, 48); std::memcpy(&xf[i * 24 + 12], instances[i].to_object, 48); }
         InstEditTables it{}; it.xf = xf.data(); it.inst = instancesD.data(); it.leafSlot = leafSlotOfInstance.data(); it.leafBox = leafBoxes.data(); it.n = (uint32_t) instancesD.size();
+        it.groupBox = groupBoxes.data(); it.nGroups = (uint32_t) (groupBoxes.size() / 6);      // of the current vertices: the committed ones' unless a geometry edit moved them
         for (uint32_t i = 0; i < it.n; ++i) geoInstanceRecord(it, i);
-        GeoEditTables g{}; g.leafBox = leafBoxes.data(); g.nodes = nodes.data(); g.nodeBox = nodeBoxes.data(); g.wide = wideBvh ? 1u : 0u;
-        for (uint32_t n : refitOrder) geoRefitNode(g, n);
-        instStale = false;
     }
-    if (!geoStale) return;
-    GeoEditTables g{}; g.pos = pos.data(); g.nrm = nrm.empty() ? nullptr : nrm.data(); g.shade = shade.data(); g.triuv = triuv.empty() ? nullptr : triuv.data();
-    g.tris = tris.data(); g.packetExact = packetExact.data(); g.leafSlot = leafSlotOfPrim.data(); g.leafBox = leafBoxes.data(); g.nodes = nodes.data(); g.nodeBox = nodeBoxes.data();
-    g.nTris = nTris; g.nPacketExact = (uint32_t) std::min<size_t>(packetExact.size(), nTris); g.wide = wideBvh ? 1u : 0u;
-    for (uint32_t t = 0; t < nTris; ++t) geoTriRecord(g, t);
-    for (uint32_t n : refitOrder) geoRefitNode(g, n);
-    geoStale = false;
+    for (uint32_t n : (geoStale ? refitOrderAll : refitOrder)) geoRefitNode(g, n);
+    geoStale = instStale = false;
 }
 
 int validateMaterials(const mi_material *m, uint32_t n, std::string &msg) {

@@ -75,13 +75,26 @@ struct SceneHost {
     int updateInstances(const mi_instance *in, uint32_t n, std::string &msg);      // = checkInstances, then applyInstances
     int checkInstances(const mi_instance *in, uint32_t n, std::string &msg) const;   // every refusal; changes nothing
     void applyInstances(const mi_instance *in, uint32_t n);                            // checked arguments only
-    void prepareGeometryEdit();         // first edit: leafSlotOfPrim / leafSlotOfInstance, leafBoxes of the records that do not move, refitOrder / refitLevelStart
+    // Geometry edit (mi_scene_update_geometry): one frame of an animation -- new positions (and normals) for the whole vertex array, shape-group members included, and / or
+    // new transforms for every instance.  Replaces pos / nrm / instances, the group boxes, the scene box and the small tables at once; the per-triangle mirrors, instancesD
+    // (glo / ghi included) and `nodes` -- scene level AND group trees -- become STALE until refreshHostGeometry() repeats the device's steps.
+    int updateGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *in, uint32_t nInstances, std::string &msg);      // = checkGeometry, then applyGeometry
+    int checkGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *in, uint32_t nInstances, std::string &msg) const;   // every refusal; changes nothing
+    void applyGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *in, uint32_t nInstances);                            // checked arguments only; a null part stays
+    int checkVerticesAs(const std::string &who, bool groupsAllowed, const float *pos, const float *nrm, uint32_t nVerts, std::string &msg) const;      // the rules of checkVertices under another caller's name
+    int checkInstancesAs(const std::string &who, const mi_instance *in, uint32_t n, std::string &msg) const;
+    void buildGroupBoxes();             // groupBoxes: per shape group the union of its member shapes' vertices in shape order, enlarged like a kd-tree root (commitHost() and the geometry edit)
+    std::vector<float> groupBoxes;      // 6 floats (lo, hi) per shape group
+    std::vector<int> groupRoot;         // root node of every group's tree in `nodes`
+    void prepareGeometryEdit();         // first edit: leafSlotOfPrim / leafSlotOfInstance, leafBoxes of the records that do not move, refitOrder / refitLevelStart (scene level), refitOrderAll / refitLevelStartAll (+ the group trees)
     void refreshHostGeometry();
     std::vector<uint32_t> leafSlotOfInstance;   // instance -> its MI_K_INSTANCE record in `tris`
     std::vector<uint32_t> leafSlotOfPrim, refitOrder, refitLevelStart;   // triangle -> its record in `tris`; node indices sorted by height (0 = all children are leaves), level l = refitOrder[refitLevelStart[l] .. refitLevelStart[l + 1])
-    std::vector<float> leafBoxes, nodeBoxes;   // padded box (lo, hi) per leaf record; exact union of the child boxes per node
+    std::vector<uint32_t> refitOrderAll, refitLevelStartAll;   // the same over the scene-level tree and every group tree: nodes of equal height share a level, no tree reads another tree's nodes
+    std::vector<float> leafBoxes, nodeBoxes;   // padded box (lo, hi) per leaf record; exact union of the child boxes per node (a group tree's: valid after its first refit only)
     bool geoPrepared = false, geoStale = false, instStale = false;
     void *dPos = nullptr, *dLeafSlot = nullptr, *dLeafBox = nullptr, *dNodeBox = nullptr, *dRefitOrder = nullptr;   // device side of a vertex edit, allocated at the first one
+    void *dRefitOrderAll = nullptr, *dGroupBox = nullptr;   // device side of a geometry edit (with all of the above), allocated at the first one: refitOrderAll, the group boxes of the current edit
     void *dInstXf = nullptr, *dLeafSlotInst = nullptr;   // device side of an instance edit (with dLeafBox, dNodeBox, dRefitOrder), allocated at the first one: the 24-float transform pairs, leafSlotOfInstance
     ~SceneHost() { release(); }
 };

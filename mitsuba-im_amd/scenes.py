@@ -709,10 +709,11 @@ def cbox_materials(width=96, height=96, spp=16, sampler=SAMPLER_SOBOL, max_depth
                         seed=seed, strict_normals=strict_normals, hide_emitters=hide_emitters, name="cbox_materials", analytic=b.resolve_analytic())
 
 
-def instanced_garden(width=96, height=64, spp=16, sampler=SAMPLER_SOBOL, max_depth=6, rr_depth=4, seed=0, n_side=4, smooth=True):
+def instanced_garden(width=96, height=64, spp=16, sampler=SAMPLER_SOBOL, max_depth=6, rr_depth=4, seed=0, n_side=4, smooth=True, bush_levels=2):
     """`shapegroup` + `instance`: two shape groups -- a smooth-shaded "bush" (octahedral blob with vertex normals) and a
     face-normal "crate" with a rough-conductor lid -- placed n_side x n_side times with rotation, non-uniform scale and shear-free tilts,
-    over a mesh floor, lit by an area light and a constant sky."""
+    over a mesh floor, lit by an area light and a constant sky.  bush_levels: subdivisions of the bush's octahedron (8 * 4^levels triangles; 4 gives a 2048-triangle
+    group, the smallest whose tree has a level wider than one 256-thread workgroup)."""
     b = _Builder()
     ground = b.bsdf(reflectance=(0.45, 0.5, 0.4)); leaf = b.bsdf(reflectance=(0.2, 0.55, 0.15), twosided=True); wood = b.bsdf(reflectance=(0.5, 0.33, 0.18))
     eta, k = CONDUCTOR_IOR["Cu"]; lid = b.bsdf(kind=BSDF_ROUGHCONDUCTOR, alpha=0.12, distr=DISTR_GGX, eta=eta, k=k)
@@ -725,7 +726,7 @@ def instanced_garden(width=96, height=64, spp=16, sampler=SAMPLER_SOBOL, max_dep
     P = [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
     F = [(0, 2, 4), (2, 1, 4), (1, 3, 4), (3, 0, 4), (2, 0, 5), (1, 2, 5), (3, 1, 5), (0, 3, 5)]
     pts = [np.asarray(p, np.float64) for p in P]; faces = list(F)
-    for _ in range(2):
+    for _ in range(bush_levels):
         nf = []; cache = {}
         def mid(i, j):
             key = (min(i, j), max(i, j))
