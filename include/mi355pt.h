@@ -199,6 +199,11 @@ int mi_scene_set_envmap(mi_scene *s, const float *rgb, uint32_t w, uint32_t h, c
 int mi_scene_set_envmap_filter(mi_scene *s, int32_t texture);
 /* PerspectiveCameraImpl: m_sampleToCamera, world transform, clip planes (src/sensors/perspective.cpp:126-178) */
 int mi_scene_set_camera(mi_scene *s, const float *sample_to_camera16, const float *to_world16, float near_clip, float far_clip);
+/* Thin lens on top of the perspective camera (src/sensors/thinlens.cpp:324-361): aperture radius in world units and the distance of the focal plane along the camera's
+ * z axis.  Every sample then draws an aperture point -- the sampler's next 2-D value after the pixel offset (src/librender/integrator.cpp:172-175): Sobol dimensions 2 / 3 --
+ * and every later draw of the path moves by two dimensions.  Before mi_scene_commit; radius 0 removes the lens (the pinhole, the default; focus_distance is then ignored).
+ * MI_ERR_INVALID: null scene, a negative or non-finite radius, a non-positive or non-finite focus distance with a positive radius. */
+int mi_scene_set_lens(mi_scene *s, float aperture_radius, float focus_distance);
 /* Film crop size + reconstruction filter (src/librender/film.cpp:92; src/rfilters/<name>.cpp): kind 0 box(radius), 1 gaussian(stddev), 2 tent,
  * 3 mitchell (B in `radius`, C in `stddev`), 4 catmullrom, 5 lanczos (lobes in `radius`) */
 int mi_scene_set_film(mi_scene *s, uint32_t width, uint32_t height, uint32_t filter_kind, float radius, float stddev);
@@ -218,6 +223,10 @@ int mi_scene_clone(mi_scene *s, uint32_t device, mi_scene **out);
  *    scene: its next run traces the edited scene -- after mi_render_clear; a run that would add to a film holding samples of the earlier scene returns MI_ERR_INVALID.
  *    A replica (mi_scene_clone) is a scene of its own and is updated by its owner. */
 int mi_scene_update_camera(mi_scene *s, const float *sample_to_camera16, const float *to_world16, float near_clip, float far_clip);
+/* Focus pull / aperture change on a committed lens scene: both values in place, nothing else is recomputed or sent.  The checks of mi_scene_set_lens apply (messages
+ * start with "mi_scene_update_lens: "); turning a lens on (scene committed without one) or off (radius 0 on a lens scene) changes the sample layout of every path:
+ * MI_ERR_UNSUPPORTED, the scene is left as it was. */
+int mi_scene_update_lens(mi_scene *s, float aperture_radius, float focus_distance);
 int mi_scene_update_materials(mi_scene *s, const mi_material *materials, uint32_t n);
 int mi_scene_update_emitters(mi_scene *s, const mi_emitter *emitters, uint32_t n);
 int mi_scene_update_envmap_transform(mi_scene *s, const float *to_world16, float scale);   /* envmap scenes only */
@@ -332,6 +341,11 @@ int mi_render_field_film_size(mi_render *r, int layout, uint32_t *height, uint32
 int mi_render_read_fields(mi_render *r, int layout, float *host_out);
 /* Debug / parity: the fields of individual (px, py, sampleIndex) triples, batched as mi_render_samples: generate, one extend, the field stage (no shading); out[n * 3F] */
 int mi_render_field_samples(mi_render *r, const uint32_t *pairs, uint64_t n, float *out);
+/* Debug / parity: what a shading stage recomputes for the sensor rays of individual (px, py, sampleIndex) triples from the path state in the queues, batched as
+ * mi_render_samples (generate only): out8 = the path's aperture sample ((0.5, 0.5) without a lens), then the rx / ry directions scaled by 1 / sqrt(spp).  A parity hook, not a
+ * product call.  Its kernel looks Sobol values up in the render's GLOBAL nibble tables from st0.y / st0.z, as k_env_primary does; the shade kernels call the same functions on
+ * their LDS copy of the tables -- that path is checked through renders (tests/test_gpu_thinlens.py), not here. */
+int mi_render_debug_sensor_differentials(mi_render *r, const uint32_t *pairs, uint64_t n, float *out8);
 int mi_render_set_profiling(mi_render *r, int enabled);   /* per-stage HIP-event timing: events are recorded between the stage launches of the first stream, nothing is serialised (off by default) */
 
 /* bool Scene::rayIntersect(const Ray &ray, Intersection &its) for a batch of rays (include/mitsuba/render/scene.h:187-243): rays8 = (o.xyz, mint, d.xyz, maxt) per
@@ -375,7 +389,10 @@ int mi_debug_intersect_fused(mi_scene *s, const float *rays8, uint64_t n, int an
 int mi_debug_geometry_bytes(mi_scene *s, uint32_t what, uint64_t *bytes);
 int mi_debug_read_geometry(mi_scene *s, uint32_t what, void *out, uint64_t bytes);
 int mi_debug_sobol(mi_scene *s, const uint32_t *px_py_k, uint64_t n, uint32_t ndims, uint64_t *out_index, float *out_values);
-int mi_debug_camera_rays(mi_scene *s, const float *sample_pos2, uint64_t n, float *out_rays8);
+int mi_debug_camera_rays(mi_scene *s, const float *sample_pos2, uint64_t n, float *out_rays8);   /* on a lens scene: the aperture sample (0.5, 0.5), the reference's default when none is drawn */
+/* The sensor ray with its differentials, unscaled (RayDifferential::scaleDifferential not applied): out14 = origin, mint, direction, maxt, rx direction, ry direction per
+ * ray; aperture2 = the aperture sample of every ray, ignored (may be NULL) on a scene without a lens, which returns mi_debug_camera_rays' ray + the perspective differentials */
+int mi_debug_camera_rays_lens(mi_scene *s, const float *sample_pos2, const float *aperture2, uint64_t n, float *out14);
 int mi_debug_libm(int fn, const float *x, const float *y, uint64_t n, float *out);   /* the device restatements of glibc's routines (libm_glibc.h) as the kernels call them:
                                       fn 0 expf(x), 1 logf(x), 2 powf(x, y), 3 tanf(x), 4 atanf(x), 5 atan2f(x, y), 6 acosf(x); y may be NULL for the one-argument routines */
 int mi_debug_sincosf(const float *x, uint64_t n, float *out_sin_cos2);   /* the device restatement of glibc's sincosf (warps): out[2i] = sin, out[2i+1] = cos */

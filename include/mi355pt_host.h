@@ -24,6 +24,7 @@ int mi_host_render(void *integrator, float *targetRGBA, const int *continu, cons
 /* in-place edits (mi_scene_update_* of mi355pt.h) of the scene given to mi_host_preprocess and of every replica, between two mi_host_render calls; 0 = applied,
  * otherwise refused (message in mi_host_last_error) and nothing changed */
 int mi_host_set_camera(void *integrator, const float *sample_to_camera16, const float *to_world16, float near_clip, float far_clip);
+int mi_host_set_lens(void *integrator, float aperture_radius, float focus_distance);   /* mi_scene_update_lens on the borrowed scene and every replica */
 int mi_host_set_materials(void *integrator, const mi_material *materials, uint32_t n);
 int mi_host_set_emitters(void *integrator, const mi_emitter *emitters, uint32_t n);
 int mi_host_set_envmap_transform(void *integrator, const float *to_world16, float scale);

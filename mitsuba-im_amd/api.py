@@ -88,12 +88,12 @@ class MiFusedDebugInfo(C.Structure):
 
 
 EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_scene_create", "mi_scene_destroy", "mi_scene_set_triangles",
-           "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_film",
-           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
+           "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_lens", "mi_scene_set_film",
+           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
-           "mi_render_set_profiling", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_geometry_bytes", "mi_debug_read_geometry"]
+           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_geometry_bytes", "mi_debug_read_geometry"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
-                "mi_host_set_camera", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
+                "mi_host_set_camera", "mi_host_set_lens", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
 
 
 def build(force=False):
@@ -126,11 +126,13 @@ class Lib:
         L.mi_scene_set_envmap.argtypes = [vp, vp, u32, u32, vp, f32]
         L.mi_scene_set_envmap_filter.argtypes = [vp, C.c_int32]
         L.mi_scene_set_camera.argtypes = [vp, vp, vp, f32, f32]
+        L.mi_scene_set_lens.argtypes = [vp, f32, f32]
         L.mi_scene_set_film.argtypes = [vp, u32, u32, u32, f32, f32]
         L.mi_scene_commit.argtypes = [vp, u32]
         L.mi_scene_clone.argtypes = [vp, u32, C.POINTER(vp)]
         L.mi_scene_ray_intersect.argtypes = [vp, vp, u64, vp]
         L.mi_scene_update_camera.argtypes = [vp, vp, vp, f32, f32]
+        L.mi_scene_update_lens.argtypes = [vp, f32, f32]
         L.mi_scene_update_materials.argtypes = [vp, vp, u32]
         L.mi_scene_update_emitters.argtypes = [vp, vp, u32]
         L.mi_scene_update_envmap_transform.argtypes = [vp, vp, f32]
@@ -155,11 +157,13 @@ class Lib:
         L.mi_render_read_fields.argtypes = [vp, i32, vp]
         L.mi_render_field_samples.argtypes = [vp, vp, u64, vp]
         L.mi_render_set_profiling.argtypes = [vp, i32]
+        L.mi_render_debug_sensor_differentials.argtypes = [vp, vp, u64, vp]
         L.mi_debug_intersect.argtypes = [vp, vp, u64, i32, vp]
         L.mi_debug_intersect_inst.argtypes = [vp, vp, u64, i32, vp, vp]
         L.mi_debug_intersect_fused.argtypes = [vp, vp, u64, i32, vp, u32, u32, u32, u32, vp, C.POINTER(MiFusedDebugInfo)]
         L.mi_debug_sobol.argtypes = [vp, vp, u64, u32, vp, vp]
         L.mi_debug_camera_rays.argtypes = [vp, vp, u64, vp]
+        L.mi_debug_camera_rays_lens.argtypes = [vp, vp, vp, u64, vp]
         L.mi_debug_sincosf.argtypes = [vp, u64, vp]
         L.mi_debug_libm.argtypes = [i32, vp, vp, u64, vp]
         L.mi_debug_geometry_bytes.argtypes = [vp, u32, C.POINTER(u64)]
@@ -293,6 +297,8 @@ class Scene:
                 L.check(L.L.mi_scene_set_envmap_filter(h, int(sc.env_texture) - 1))
         s2c = np.ascontiguousarray(sc.sample_to_camera, np.float32); c2w = np.ascontiguousarray(sc.cam_to_world, np.float32)
         L.check(L.L.mi_scene_set_camera(h, _p(s2c), _p(c2w), sc.near, sc.far))
+        if float(sc.get("aperture_radius", 0.0) or 0.0) != 0.0:      # thin lens (scenes.py: aperture_radius / focus_distance; 0 = the pinhole)
+            L.check(L.L.mi_scene_set_lens(h, float(sc.aperture_radius), float(sc.get("focus_distance", 0.0) or 0.0)))
         L.check(L.L.mi_scene_set_film(h, sc.width, sc.height, sc.filter, sc.filter_radius, sc.filter_stddev))
         L.check(L.L.mi_scene_commit(h, device))
 
@@ -315,6 +321,11 @@ class Scene:
         s2c = np.ascontiguousarray(sample_to_camera, np.float32).reshape(4, 4); c2w = np.ascontiguousarray(cam_to_world, np.float32).reshape(4, 4)
         self.L.check(self.L.L.mi_scene_update_camera(self.h, _p(s2c), _p(c2w), float(near), float(far)))
         self.sc.sample_to_camera = s2c; self.sc.cam_to_world = c2w; self.sc.near = float(near); self.sc.far = float(far)
+
+    def update_lens(self, aperture_radius, focus_distance):
+        """Focus pull / aperture change of a lens scene: two scalars in place.  Turning a lens on or off is refused (MiError code 3): it changes every path's sample layout."""
+        self.L.check(self.L.L.mi_scene_update_lens(self.h, float(aperture_radius), float(focus_distance)))
+        self.sc.aperture_radius = float(aperture_radius); self.sc.focus_distance = float(focus_distance)
 
     def update_materials(self, bsdfs):
         """bsdfs: the full list of dict records, as in the scene description; values may change, structure may not (MiError code 3 names the first offending record)."""
@@ -414,9 +425,18 @@ class Scene:
         a = np.ascontiguousarray(px_py_k, np.uint32).reshape(-1, 3); idx = np.zeros(len(a), np.uint64); vals = np.zeros((len(a), ndims), np.float32)
         self.L.check(self.L.L.mi_debug_sobol(self.h, _p(a), len(a), ndims, _p(idx), _p(vals))); return idx, vals
 
-    def camera_rays(self, pos2):
-        a = np.ascontiguousarray(pos2, np.float32).reshape(-1, 2); out = np.zeros((len(a), 8), np.float32)
-        self.L.check(self.L.L.mi_debug_camera_rays(self.h, _p(a), len(a), _p(out))); return out
+    def camera_rays(self, pos2, aperture2=None, differentials=False):
+        """Sensor rays (o, mint, d, maxt) at film positions pos2.  aperture2: the aperture sample of every ray of a lens scene (None: (0.5, 0.5), the reference's default
+        when none is drawn; ignored without a lens).  differentials: six more floats per ray, the unscaled rx / ry directions."""
+        a = np.ascontiguousarray(pos2, np.float32).reshape(-1, 2)
+        if aperture2 is None and not differentials:
+            out = np.zeros((len(a), 8), np.float32)
+            self.L.check(self.L.L.mi_debug_camera_rays(self.h, _p(a), len(a), _p(out))); return out
+        ap = np.full((len(a), 2), 0.5, np.float32) if aperture2 is None else np.ascontiguousarray(aperture2, np.float32).reshape(-1, 2)
+        if len(ap) != len(a): raise ValueError("camera_rays: one aperture sample per film position")
+        out = np.zeros((len(a), 14), np.float32)
+        self.L.check(self.L.L.mi_debug_camera_rays_lens(self.h, _p(a), _p(ap), len(a), _p(out)))
+        return out if differentials else np.ascontiguousarray(out[:, :8])
 
 
 class Render:
@@ -496,6 +516,11 @@ class Render:
         a = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 3); out = np.zeros((len(a), 3), np.float32)
         self.L.check(self.L.L.mi_render_samples(self.h, _p(a), len(a), _p(out))); return out
 
+    def sensor_differentials(self, pairs):
+        """What the shading stages recompute for the sensor rays of (px, py, sampleIndex) triples from the path state -> [n, 8]: aperture sample, scaled rx / ry directions."""
+        a = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 3); out = np.zeros((len(a), 8), np.float32)
+        self.L.check(self.L.L.mi_render_debug_sensor_differentials(self.h, _p(a), len(a), _p(out))); return out
+
     def merge_film(self, other):
         """self += other (raw film sums, field planes included, ray counters): both renders idle, same film, same field list."""
         self.L.check(self.L.L.mi_render_merge_film(self.h, other.h))
@@ -545,6 +570,13 @@ class HostIntegrator:
         if self.L.mi_host_set_camera(self.h, _p(s2c), _p(c2w), float(near), float(far)) != 0:
             raise RuntimeError(self.L.mi_host_last_error().decode())
         sc = self.scene.sc; sc.sample_to_camera = s2c; sc.cam_to_world = c2w; sc.near = float(near); sc.far = float(far)
+
+    def set_lens(self, aperture_radius, focus_distance):
+        """MIPathTracerHIP::setLens: mi_scene_update_lens on the borrowed scene and on every replica, between two render() calls."""
+        self.L.mi_host_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float]
+        if self.L.mi_host_set_lens(self.h, float(aperture_radius), float(focus_distance)) != 0:
+            raise RuntimeError(self.L.mi_host_last_error().decode())
+        self.scene.sc.aperture_radius = float(aperture_radius); self.scene.sc.focus_distance = float(focus_distance)
 
     def set_vertices(self, pos, nrm=None):
         """MIPathTracerHIP::setVertices: mi_scene_update_vertices on the borrowed scene and on every replica, between two render() calls."""

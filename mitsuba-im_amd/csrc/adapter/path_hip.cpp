@@ -627,7 +627,7 @@ struct CameraRecord {
     float s2c[16], c2w[16], nearClip, farClip; Vector2i cropSize;
     // rebuild m_sampleToCamera exactly as PerspectiveCameraImpl::configure does (perspective.cpp:150-157); it is a protected member
     void of(const Sensor *sensor) {
-        if (!sensor->getClass()->derivesFrom(MTS_CLASS(PerspectiveCamera))) SLog(EError, "path_hip: only the perspective camera is implemented");
+        if (!sensor->getClass()->derivesFrom(MTS_CLASS(PerspectiveCamera))) SLog(EError, "path_hip: only the perspective camera is implemented in the plugin (a thinlens sensor renders through the C-ABI: mi_scene_set_lens, or python -m mitsuba-im_amd.render)");
         const PerspectiveCamera *cam = static_cast<const PerspectiveCamera *>(sensor);
         const Film *film = sensor->getFilm();
         const Vector2i &filmSize = film->getSize(), &crop = film->getCropSize(); const Point2i &cropOffset = film->getCropOffset();

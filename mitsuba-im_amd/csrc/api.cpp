@@ -44,6 +44,8 @@ void mi_launch_debug_fused(const DScene &, const Queues &, int, uint32_t, uint32
 uint32_t mi_fused_lds_stack(void);
 void mi_launch_debug_sobol(const DScene &, const uint32_t *, uint64_t, uint32_t, unsigned long long *, float *, hipStream_t);
 void mi_launch_debug_camera(const DScene &, const float *, uint64_t, float *, hipStream_t);
+void mi_launch_debug_camera_lens(const DScene &, const float *, const float *, uint64_t, float *, hipStream_t);
+void mi_launch_debug_sensor_differentials(const DScene &, const RenderConst &, const Queues &, uint64_t, float *, hipStream_t);
 void mi_launch_debug_sincosf(const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_libm(int, const float *, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_field_film(const DScene &, const FieldArgs &, const Queues &, const BatchDesc &, float *, float *, hipStream_t);
@@ -237,6 +239,12 @@ int mi_scene_set_envmap(mi_scene *s, const float *rgb, uint32_t w, uint32_t h, c
 int mi_scene_set_camera(mi_scene *s, const float *s2c, const float *c2w, float nearClip, float farClip) {
     if (!s || !s2c || !c2w) return fail(MI_ERR_INVALID, "mi_scene_set_camera: null argument");
     memcpy(s->h.s2c, s2c, 64); memcpy(s->h.c2w, c2w, 64); s->h.nearClip = nearClip; s->h.farClip = farClip; s->h.haveCamera = true; s->h.committed = false;
+    return MI_OK;
+}
+int mi_scene_set_lens(mi_scene *s, float apertureRadius, float focusDistance) {
+    if (!s) return fail(MI_ERR_INVALID, "mi_scene_set_lens: null scene");
+    std::string msg; if (const int rc = mi::validateLens("mi_scene_set_lens", apertureRadius, focusDistance, msg)) return fail(rc, msg);
+    s->h.lensRadius = apertureRadius; s->h.focusDistance = apertureRadius != 0.0f ? focusDistance : 0.0f; s->h.committed = false;
     return MI_OK;
 }
 int mi_scene_set_film(mi_scene *s, uint32_t w, uint32_t h, uint32_t kind, float radius, float stddev) {
@@ -451,6 +459,13 @@ int mi_scene_update_camera(mi_scene *s, const float *s2c, const float *c2w, floa
     UPDATE_ENTER("mi_scene_update_camera");
     std::string msg; const int rc = s->h.updateCamera(s2c, c2w, nearClip, farClip, msg); if (rc) return fail(rc, msg);
     return MI_OK;      // the camera lives in the scene record alone: renders pick it up with their next run
+}
+int mi_scene_update_lens(mi_scene *s, float apertureRadius, float focusDistance) {
+    if (!s) return fail(MI_ERR_INVALID, "mi_scene_update_lens: null scene");
+    std::string msg; if (const int bad = mi::validateLens("mi_scene_update_lens", apertureRadius, focusDistance, msg)) return fail(bad, msg);      // value checks first: they need no scene state
+    UPDATE_ENTER("mi_scene_update_lens");
+    const int rc = s->h.updateLens(apertureRadius, focusDistance, msg); if (rc) return fail(rc, msg);
+    return MI_OK;      // like the camera, the lens lives in the scene record alone
 }
 int mi_scene_update_materials(mi_scene *s, const mi_material *m, uint32_t n) {
     if (!s || !m || !n) return fail(MI_ERR_INVALID, "mi_scene_update_materials: null argument");
@@ -787,15 +802,19 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         int depth = p->max_depth < 0 ? 250 : p->max_depth;
         int perBounce = 5; for (const mi_material &m : s->h.materials) if (m.type == MI_BSDF_ROUGHDIELECTRIC) perBounce = 6;
         if (vol) perBounce += 2;      // + the one or two draws of HomogeneousMedium::sampleDistance per iteration
-        if (p->max_depth > 0 && (uint32_t) (3 + perBounce * depth) > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! You may have to reduce the 'maxDepth' parameter of your integrator.");
+        const int lensDims = s->h.lensRadius != 0.0f ? 2 : 0;      // the aperture sample: dimensions 2 / 3 (k_generate), every later draw moves by two
+        if (lensDims && (uint32_t) (3 + lensDims) > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! The thin lens draws Sobol dimensions 2 and 3.");
+        if (p->max_depth > 0 && (uint32_t) (3 + lensDims + perBounce * depth) > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! You may have to reduce the 'maxDepth' parameter of your integrator.");
         if (p->max_depth < 0) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: maxDepth = -1 with the Sobol sampler needs more dimensions than are loaded");
+        // the state word st0.w carries the dimension in 8 bits: with the shipped 128-dimension tables the bound above is the tighter one, larger caller-supplied tables end here
+        if (p->max_depth > 0 && 3 + lensDims + perBounce * depth > 256) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the path state numbers a path's Sobol dimensions with 8 bits; maxDepth x draws per bounce exceeds 256 (reduce maxDepth)");
     }
     if (p->sampler == MI_SAMPLER_INDEPENDENT && p->max_depth > 0) {
         // the build-defined independent stream numbers a path's draws with 8 bits: a path that could draw more than 256 values would re-read
         // its own stream from call 0 -- refused by name rather than silently correlated (unbounded depth keeps the documented period)
         int perBounce = 5; for (const mi_material &m : s->h.materials) if (m.type == MI_BSDF_ROUGHDIELECTRIC) perBounce = 6;
         if (vol) perBounce += 2;
-        if (2 + perBounce * p->max_depth > 256) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the independent sampler stream numbers 256 draws per path; maxDepth x draws per bounce exceeds that (use the Sobol sampler or a smaller maxDepth)");
+        if (2 + (s->h.lensRadius != 0.0f ? 2 : 0) + perBounce * p->max_depth > 256) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the independent sampler stream numbers 256 draws per path; maxDepth x draws per bounce exceeds that (use the Sobol sampler or a smaller maxDepth)");
     }
     HIPCHK(hipSetDevice(s->h.device));
     mi_render *r = new mi_render(); r->scene = s; r->p = *p;
@@ -824,7 +843,7 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         if (vol) perBounceDims += 2;
         uint32_t sppBits = 0; while ((1ull << sppBits) < p->spp) ++sppBits;
         const uint32_t bits = (s->h.logRes > 1 ? 2 * s->h.logRes : 0) + sppBits + 1;
-        const uint32_t nibs = std::max<uint32_t>(8, (bits + 3) / 4), dims      /* at least the eight nibbles of the low index word (pt_device.h sobolBitsNib unrolls them) */ = std::min<uint32_t>(s->h.d.sobol_dims, (uint32_t) (4 + perBounceDims * p->max_depth));
+        const uint32_t nibs = std::max<uint32_t>(8, (bits + 3) / 4), dims      /* at least the eight nibbles of the low index word (pt_device.h sobolBitsNib unrolls them) */ = std::min<uint32_t>(s->h.d.sobol_dims, (uint32_t) (4 + (s->h.lensRadius != 0.0f ? 2 : 0) + perBounceDims * p->max_depth));
         std::vector<uint32_t> nib((size_t) dims * nibs * 16);
         for (uint32_t dmn = 0; dmn < dims; ++dmn) for (uint32_t n = 0; n < nibs; ++n) for (uint32_t v = 0; v < 16; ++v) {
             uint32_t x = 0; for (uint32_t b = 0; b < 4; ++b) if (((v >> b) & 1u) && 4 * n + b < MI_SOBOL_SIZE) x ^= g_sobolM32[(size_t) dmn * MI_SOBOL_SIZE + 4 * n + b];
@@ -907,6 +926,29 @@ int mi_render_clear(mi_render *r) {
     HIPCHK(hipStreamSynchronize(r->stream)); r->samplesTotal = 0; r->mergedRays = r->mergedShadow = r->mergedPathLen = r->mergedSamples = 0; r->filmRev = r->scene->h.revision; r->cancel.store(0); return MI_OK;
 }
 void mi_render_cancel(mi_render *r) { if (r) r->cancel.store(1); }
+// Debug / parity: generate the listed paths, then read back what a shading stage would recompute for their sensor rays (k_debug_sensor_differentials)
+int mi_render_debug_sensor_differentials(mi_render *r, const uint32_t *pairs, uint64_t n, float *out) {
+    if (!r || !pairs || !out || !n) return fail(MI_ERR_INVALID, "mi_render_debug_sensor_differentials: null argument");
+    const mi::SceneHost &h = r->scene->h; HIPCHK(hipSetDevice(h.device));
+    for (uint64_t i = 0; i < n; ++i) if (pairs[i * 3] >= h.width || pairs[i * 3 + 1] >= h.height) return fail(MI_ERR_INVALID, "mi_render_debug_sensor_differentials: pixel outside the film");
+    RunGuard running; { const int rc = beginRun(r, running, false, "mi_render_debug_sensor_differentials"); if (rc) return rc; }
+    if (n > r->poolPaths) { int rc = allocPool(r, n); if (rc) return rc; }
+    if (!r->q.counters) return fail(MI_ERR_DEVICE, "mi_render_debug_sensor_differentials: no path pool");
+    uint32_t *dList = nullptr; float *dOut = nullptr;
+    HIPCHK(hipMalloc((void **) &dList, n * 12));
+    if (hipMalloc((void **) &dOut, n * 32) != hipSuccess) { (void) hipFree(dList); return fail(MI_ERR_DEVICE, "mi_render_debug_sensor_differentials: out of device memory"); }
+    BatchDesc bd{}; bd.tile = mi_tile{0, 0, h.width, h.height}; bd.n_pix = (uint32_t) n; bd.n_planes = 1; bd.sample_begin = 0; bd.n_paths = n; bd.list = dList; bd.row_stride = 1;
+    hipError_t e = hipMemcpy(dList, pairs, n * 12, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        mi_launch_generate(r->sc, r->rc, r->q, bd, r->grid, r->stream);
+        mi_launch_debug_sensor_differentials(r->sc, r->rc, r->q, n, dOut, r->stream);
+        e = hipStreamSynchronize(r->stream); if (e == hipSuccess) e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, dOut, n * 32, hipMemcpyDeviceToHost);
+    (void) hipFree(dList); (void) hipFree(dOut);
+    if (e != hipSuccess) return fail(MI_ERR_DEVICE, std::string("mi_render_debug_sensor_differentials: ") + hipGetErrorString(e));
+    return MI_OK;
+}
 int mi_render_set_profiling(mi_render *r, int enabled) { if (!r) return fail(MI_ERR_INVALID, "null"); r->profiling = enabled != 0; return MI_OK; }
 
 static void mark(mi_render *r, int tag, size_t &used, hipStream_t st = nullptr) {
@@ -1370,6 +1412,14 @@ int mi_debug_camera_rays(mi_scene *s, const float *pos, uint64_t n, float *out) 
     if (!s || !s->h.committed || !pos || !out || !n) return fail(MI_ERR_INVALID, "mi_debug_camera_rays: bad argument");
     HIPCHK(hipSetDevice(s->h.device));
     return withBuffers(pos, n * 8, out, n * 32, [&](void *i, void *o) { mi_launch_debug_camera(s->h.d, (const float *) i, n, (float *) o, nullptr); });
+}
+
+int mi_debug_camera_rays_lens(mi_scene *s, const float *pos, const float *aperture, uint64_t n, float *out) {
+    if (!s || !s->h.committed || !pos || !out || !n || (s->h.lensRadius != 0.0f && !aperture)) return fail(MI_ERR_INVALID, "mi_debug_camera_rays_lens: bad argument");
+    HIPCHK(hipSetDevice(s->h.device));
+    const bool lens = s->h.lensRadius != 0.0f;
+    std::vector<float> in(n * 4, 0.5f); memcpy(in.data(), pos, n * 8); if (lens) memcpy(in.data() + n * 2, aperture, n * 8);
+    return withBuffers(in.data(), n * 16, out, n * 56, [&](void *i, void *o) { mi_launch_debug_camera_lens(s->h.d, (const float *) i, (const float *) i + n * 2, n, (float *) o, nullptr); });
 }
 
 }  // extern "C"

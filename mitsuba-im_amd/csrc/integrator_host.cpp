@@ -147,6 +147,7 @@ template <typename F> void MIPathTracerHIP::editAll(const char *what, F edit) {
     for (mi_scene *rs : m_replicaScenes) check(edit(rs), what);
 }
 void MIPathTracerHIP::setCamera(const float *s2c, const float *c2w, float nearClip, float farClip) { editAll("MIPathTracerHIP::setCamera", [&](mi_scene *s) { return mi_scene_update_camera(s, s2c, c2w, nearClip, farClip); }); }
+void MIPathTracerHIP::setLens(float apertureRadius, float focusDistance) { editAll("MIPathTracerHIP::setLens", [&](mi_scene *s) { return mi_scene_update_lens(s, apertureRadius, focusDistance); }); }
 void MIPathTracerHIP::setMaterials(const mi_material *m, uint32_t n) { editAll("MIPathTracerHIP::setMaterials", [&](mi_scene *s) { return mi_scene_update_materials(s, m, n); }); }
 void MIPathTracerHIP::setEmitters(const mi_emitter *e, uint32_t n) { editAll("MIPathTracerHIP::setEmitters", [&](mi_scene *s) { return mi_scene_update_emitters(s, e, n); }); }
 void MIPathTracerHIP::setEnvmapTransform(const float *toWorld, float scale) { editAll("MIPathTracerHIP::setEnvmapTransform", [&](mi_scene *s) { return mi_scene_update_envmap_transform(s, toWorld, scale); }); }
@@ -211,6 +212,7 @@ int mi_host_render(void *h, float *target, const int *continu, const int *abortF
 }
 #define HOST_EDIT(call) try { ((mi355::MIPathTracerHIP *) h)->call; return 0; } catch (const std::exception &e) { g_hostErr = e.what(); return 1; }
 int mi_host_set_camera(void *h, const float *s2c, const float *c2w, float nearClip, float farClip) { HOST_EDIT(setCamera(s2c, c2w, nearClip, farClip)) }
+int mi_host_set_lens(void *h, float apertureRadius, float focusDistance) { HOST_EDIT(setLens(apertureRadius, focusDistance)) }
 int mi_host_set_materials(void *h, const mi_material *m, uint32_t n) { HOST_EDIT(setMaterials(m, n)) }
 int mi_host_set_emitters(void *h, const mi_emitter *e, uint32_t n) { HOST_EDIT(setEmitters(e, n)) }
 int mi_host_set_envmap_transform(void *h, const float *toWorld, float scale) { HOST_EDIT(setEnvmapTransform(toWorld, scale)) }

@@ -55,6 +55,7 @@ public:
     // In-place edits of the borrowed scene and of every replica scene (mi_scene_update_*): valid between render() calls, no preprocess() needed afterwards.
     // Each throws std::runtime_error with the library's message when the edit is refused; the scenes are then unchanged.
     void setCamera(const float *sampleToCamera16, const float *toWorld16, float nearClip, float farClip);
+    void setLens(float apertureRadius, float focusDistance);
     void setMaterials(const mi_material *materials, uint32_t n);
     void setEmitters(const mi_emitter *emitters, uint32_t n);
     void setEnvmapTransform(const float *toWorld16, float scale);

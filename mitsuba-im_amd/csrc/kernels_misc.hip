@@ -4,6 +4,8 @@
 // ---------------------------------------------------------------------------------------------- generate
 // One camera sample per path: src/librender/integrator.cpp:166-181 (pixel offset + sensor ray), sampler set-up
 // src/samplers/sobol.cpp:171-216.  Path q of the batch = (plane q / npix, tile pixel q % npix).
+// LENS: the scene has a thin lens (DScene::lens_radius != 0; chosen at launch) -- the pinhole instantiation holds no lens code at all.
+template <bool LENS>
 __global__ __launch_bounds__(WG) void k_generate(DScene sc, RenderConst rc, Queues q, BatchDesc bd) {
     const uint32_t tid = threadIdx.x;
     for (uint32_t seg = blockIdx.x; seg < q.n_seg; seg += gridDim.x) {
@@ -39,7 +41,13 @@ __global__ __launch_bounds__(WG) void k_generate(DScene sc, RenderConst rc, Queu
             next2D(ss, 0, SobolTab{nullptr, 0, 0}, jx, jy);
         }
         float sx = (float) (int) px + jx, sy = (float) (int) py + jy;
-        v3 o, d; float mint, maxt; cameraRay(sc, sx, sy, o, d, mint, maxt);
+        v3 o, d; float mint, maxt;
+        if (LENS) {      // thin lens: the aperture sample is the sampler's next 2-D value (integrator.cpp:174-175) -- Sobol dimensions 2 / 3, the path starts at 4
+            float ax, ay;
+            if (rc.sampler == 1) { lensSampleOfPath(1u, SobolTab{rc.sobol_nib, rc.nib_count, rc.sobol_scramble}, ss.a, ss.b, ax, ay); ss.dim = 4; }
+            else next2D(ss, 0, SobolTab{nullptr, 0, 0}, ax, ay);
+            lensRay(sc, sx, sy, ax, ay, o, d, mint, maxt);
+        } else cameraRay(sc, sx, sy, o, d, mint, maxt);
         const uint64_t slot = segBase + i;
         q.rayO[0][slot] = make_float4(o.x, o.y, o.z, mint);
         q.rayD[0][slot] = make_float4(d.x, d.y, d.z, maxt);
@@ -63,9 +71,9 @@ __global__ __launch_bounds__(WG) void k_env_primary(DScene sc, RenderConst rc, Q
         const uint32_t n = q.count[buf][seg]; const uint64_t segBase = (uint64_t) seg * q.cap;
         for (uint32_t i = threadIdx.x; i < n; i += WG) {
             if (__float_as_uint(q.hit[segBase + i].w) != 0xFFFFFFFFu) continue;
-            const float4 rd = q.rayD[buf][segBase + i]; const uint32_t pid = q.st0[buf][segBase + i].x;
+            const float4 rd = q.rayD[buf][segBase + i]; const uint4 s0 = q.st0[buf][segBase + i]; const uint32_t pid = s0.x;
             const v3 d = V(rd.x, rd.y, rd.z); const float2 sp = q.pos[pid];
-            v3 rxd, ryd; cameraDifferentials(sc, rc.inv_sqrt_spp, sp.x, sp.y, d, rxd, ryd);
+            v3 rxd, ryd; sensorDifferentials(sc, rc, SobolTab{rc.sobol_nib, rc.nib_count, rc.sobol_scramble}, s0.y, s0.z, sp.x, sp.y, d, rxd, ryd);
             const v3 v = mat3(sc.env_to_local, d);
             const float uvx = atan2f(v.x, -v.z) * MI_INV_TWOPI, uvy = acosf(minf(1.0f, maxf(-1.0f, v.y))) * MI_INV_PI;
             const v3 dvdx = mat3(sc.env_to_local, rxd) - v, dvdy = mat3(sc.env_to_local, ryd) - v;
@@ -173,8 +181,34 @@ __global__ void k_debug_libm(int fn, const float *x, const float *y, uint64_t n,
 __global__ void k_debug_camera(DScene sc, const float *pos, uint64_t n, float *out) {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    v3 o, d; float mint, maxt; cameraRay(sc, pos[i * 2], pos[i * 2 + 1], o, d, mint, maxt);
+    v3 o, d; float mint, maxt;
+    if (sc.lens_radius != 0.0f) lensRay(sc, pos[i * 2], pos[i * 2 + 1], 0.5f, 0.5f, o, d, mint, maxt);      // no aperture sample drawn: the reference's default (integrator.cpp:152)
+    else cameraRay(sc, pos[i * 2], pos[i * 2 + 1], o, d, mint, maxt);
     float *r = out + i * 8; r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = mint; r[4] = d.x; r[5] = d.y; r[6] = d.z; r[7] = maxt;
+}
+// the sensor ray with its differentials, unscaled (invSqrtSpp = 1): origin, mint, direction, maxt, rx direction, ry direction; `aperture` is read on lens scenes only
+__global__ void k_debug_camera_lens(DScene sc, const float *pos, const float *aperture, uint64_t n, float *out) {
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float sx = pos[i * 2], sy = pos[i * 2 + 1];
+    v3 o, d, rx, ry; float mint, maxt;
+    if (sc.lens_radius != 0.0f) {
+        const float ax = aperture[i * 2], ay = aperture[i * 2 + 1];
+        lensRay(sc, sx, sy, ax, ay, o, d, mint, maxt); lensDifferentials(sc, 1.0f, sx, sy, ax, ay, d, rx, ry);
+    } else { cameraRay(sc, sx, sy, o, d, mint, maxt); cameraDifferentials(sc, 1.0f, sx, sy, d, rx, ry); }
+    float *r = out + i * 14; r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = mint; r[4] = d.x; r[5] = d.y; r[6] = d.z; r[7] = maxt;
+    r[8] = rx.x; r[9] = rx.y; r[10] = rx.z; r[11] = ry.x; r[12] = ry.y; r[13] = ry.z;
+}
+// What the shading stages recompute for a sensor ray, from the state k_generate left in the queues (slot = path id in list mode): the aperture sample of the path
+// (lensSampleOfPath on st0.y / st0.z; (0.5, 0.5) without a lens) and the scaled differentials sensorDifferentials returns to its five callers.  out: 8 floats per path.
+__global__ void k_debug_sensor_differentials(DScene sc, RenderConst rc, Queues q, uint64_t n, float *out) {
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 s0 = q.st0[0][i]; const float4 rd = q.rayD[0][i]; const float2 sp = q.pos[s0.x];
+    const SobolTab st{rc.sobol_nib, rc.nib_count, rc.sobol_scramble};
+    float ax = 0.5f, ay = 0.5f; if (sc.lens_radius != 0.0f) lensSampleOfPath(rc.sampler, st, s0.y, s0.z, ax, ay);
+    v3 rxd, ryd; sensorDifferentials(sc, rc, st, s0.y, s0.z, sp.x, sp.y, V(rd.x, rd.y, rd.z), rxd, ryd);
+    float *r = out + i * 8; r[0] = ax; r[1] = ay; r[2] = rxd.x; r[3] = rxd.y; r[4] = rxd.z; r[5] = ryd.x; r[6] = ryd.y; r[7] = ryd.z;
 }
 
 
@@ -192,7 +226,10 @@ __global__ void k_patch_material_flags(TriShade *shade, uint32_t nTris, const ui
 
 // ---------------------------------------------------------------------------------------------- launch wrappers (used by api.cpp)
 extern "C" {
-void mi_launch_generate(const DScene &sc, const RenderConst &rc, const Queues &q, const BatchDesc &bd, uint32_t grid, hipStream_t st) { hipLaunchKernelGGL(k_generate, dim3(grid), dim3(WG), 0, st, sc, rc, q, bd); }
+void mi_launch_generate(const DScene &sc, const RenderConst &rc, const Queues &q, const BatchDesc &bd, uint32_t grid, hipStream_t st) {
+    if (sc.lens_radius != 0.0f) hipLaunchKernelGGL(k_generate<true>, dim3(grid), dim3(WG), 0, st, sc, rc, q, bd);
+    else hipLaunchKernelGGL(k_generate<false>, dim3(grid), dim3(WG), 0, st, sc, rc, q, bd);
+}
 void mi_launch_env_primary(const DScene &sc, const RenderConst &rc, const Queues &q, int buf, uint32_t grid, hipStream_t st) { hipLaunchKernelGGL(k_env_primary, dim3(grid), dim3(WG), 0, st, sc, rc, q, buf); }
 void mi_launch_film(const DScene &sc, const Queues &q, const BatchDesc &bd, float *film, float *spill, hipStream_t st) { hipLaunchKernelGGL(k_film, dim3((bd.n_pix + WG - 1) / WG), dim3(WG), 0, st, sc, q, bd, film, spill); }
 void mi_launch_film_layout(const float *film, const float *spill, float *out, int W, int H, int border, int layout, hipStream_t st) {
@@ -204,6 +241,8 @@ void mi_launch_debug_sobol(const DScene &sc, const uint32_t *in, uint64_t n, uin
 void mi_launch_debug_sincosf(const float *in, uint64_t n, float *out, hipStream_t st) { hipLaunchKernelGGL(k_debug_sincosf, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, in, n, out); }
 void mi_launch_debug_libm(int fn, const float *x, const float *y, uint64_t n, float *out, hipStream_t st) { hipLaunchKernelGGL(k_debug_libm, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, fn, x, y, n, out); }
 void mi_launch_debug_camera(const DScene &sc, const float *pos, uint64_t n, float *out, hipStream_t st) { hipLaunchKernelGGL(k_debug_camera, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, sc, pos, n, out); }
+void mi_launch_debug_camera_lens(const DScene &sc, const float *pos, const float *aperture, uint64_t n, float *out, hipStream_t st) { hipLaunchKernelGGL(k_debug_camera_lens, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, sc, pos, aperture, n, out); }
+void mi_launch_debug_sensor_differentials(const DScene &sc, const RenderConst &rc, const Queues &q, uint64_t n, float *out, hipStream_t st) { hipLaunchKernelGGL(k_debug_sensor_differentials, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, sc, rc, q, n, out); }
 void mi_launch_patch_material_flags(TriShade *shade, uint32_t nTris, const uint32_t *matFlags, uint32_t nMaterials, hipStream_t st) {
     const unsigned grid = (unsigned) std::min<uint64_t>(((uint64_t) nTris + 255) / 256, 2048);      // at most 8 workgroups per CU, the loop strides over the rest
     if (grid) hipLaunchKernelGGL(k_patch_material_flags, dim3(grid), dim3(256), 0, st, shade, nTris, matFlags, nMaterials);

@@ -402,6 +402,45 @@ DEV void cameraDifferentials(const DScene &sc, float invSqrtSpp, float sx, float
     v3 ry = V(c[0] * b.x + c[1] * b.y + c[2] * b.z, c[4] * b.x + c[5] * b.y + c[6] * b.z, c[8] * b.x + c[9] * b.y + c[10] * b.z);
     rxd = d + (rx - d) * invSqrtSpp; ryd = d + (ry - d) * invSqrtSpp;
 }
+// ---- thin lens (src/sensors/thinlens.cpp:324-361 ThinLens::sampleRayDifferential).  (ax, ay) is the aperture sample: the sampler's 2-D value right after the
+// pixel offset (src/librender/integrator.cpp:172-175).  Same operations in the same order as the reference, so a strict build of it rounds alike.
+DEV v3 lensNearP(const DScene &sc, float sx, float sy) {
+    const float *m = sc.s2c;
+    float px = sx * sc.inv_res_x, py = sy * sc.inv_res_y, pz = 0.0f;
+    float x = m[0] * px + m[1] * py + m[2] * pz + m[3], y = m[4] * px + m[5] * py + m[6] * pz + m[7], z = m[8] * px + m[9] * py + m[10] * pz + m[11], w = m[12] * px + m[13] * py + m[14] * pz + m[15];
+    v3 nearP = V(x, y, z);
+    if (w != 1.0f) { float r = 1.0f / w; nearP = nearP * r; }
+    return nearP;
+}
+DEV v3 lensAperture(const DScene &sc, float ax, float ay) { float tx, ty; diskConcentric(ax, ay, tx, ty); return V(tx * sc.lens_radius, ty * sc.lens_radius, 0.0f); }
+DEV void lensRay(const DScene &sc, float sx, float sy, float ax, float ay, v3 &o, v3 &d, float &mint, float &maxt) {
+    const v3 apertureP = lensAperture(sc, ax, ay), nearP = lensNearP(sc, sx, sy);
+    const float fDist = sc.focus_distance / nearP.z;
+    const v3 dl = normalize(nearP * fDist - apertureP);
+    const float invZ = 1.0f / dl.z;
+    mint = sc.near_clip * invZ; maxt = sc.far_clip * invZ;
+    o = xfPoint(sc.c2w, apertureP); d = xfVector(sc.c2w, dl);
+}
+// its differentials: rxOrigin = ryOrigin = the ray's origin (thinlens.cpp:355; scaleDifferential leaves o + (o - o) * amount = o), so computePartials' common origin holds
+DEV void lensDifferentials(const DScene &sc, float invSqrtSpp, float sx, float sy, float ax, float ay, v3 d, v3 &rxd, v3 &ryd) {
+    const v3 apertureP = lensAperture(sc, ax, ay), nearP = lensNearP(sc, sx, sy);
+    const float fDist = sc.focus_distance / nearP.z;
+    const v3 rx = xfVector(sc.c2w, normalize((nearP + ld3(sc.cam_dx)) * fDist - apertureP)), ry = xfVector(sc.c2w, normalize((nearP + ld3(sc.cam_dy)) * fDist - apertureP));
+    rxd = d + (rx - d) * invSqrtSpp; ryd = d + (ry - d) * invSqrtSpp;
+}
+// The aperture sample of a path, evaluated again from its sampler state (the queues do not carry it): Sobol dimensions 2 / 3 of the path's index, or draw 1 of its
+// counter-based stream -- the values k_generate drew.  Needed at depth 1 only, by textured hits and filtered sky lookups.
+template <typename P>
+DEV void lensSampleOfPath(uint32_t kind, SobolTabT<P> st, uint32_t a, uint32_t b, float &ax, float &ay) {
+    if (kind == 1) { ax = sobolSampleNib(st, a, b, 2); ay = sobolSampleNib(st, a, b, 3); }
+    else { const uint64_t r = sampleTEA(a, (b << 8) | 1u); ax = bitsToFloat((uint32_t) r); ay = bitsToFloat((uint32_t) (r >> 32)); }
+}
+// differentials of the sensor ray of path (a, b) at film position (sx, sy): the perspective camera's, or the lens's (uniform branch per launch)
+template <typename P>
+DEV void sensorDifferentials(const DScene &sc, const RenderConst &rc, SobolTabT<P> st, uint32_t a, uint32_t b, float sx, float sy, v3 d, v3 &rxd, v3 &ryd) {
+    if (sc.lens_radius != 0.0f) { float ax, ay; lensSampleOfPath(rc.sampler, st, a, b, ax, ay); lensDifferentials(sc, rc.inv_sqrt_spp, sx, sy, ax, ay, d, rxd, ryd); }
+    else cameraDifferentials(sc, rc.inv_sqrt_spp, sx, sy, d, rxd, ryd);
+}
 // Checkerboard::eval (src/textures/checkerboard.cpp:68-76), GridTexture::eval (src/textures/gridtexture.cpp:63-77) under Texture2D::eval
 // (src/librender/texture.cpp:112-121; these textures do not filter: usesRayDifferentials() = false)
 DEV v3 textureEval(const TextureD &t, float u, float v) {

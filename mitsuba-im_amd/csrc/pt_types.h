@@ -135,6 +135,7 @@ struct DScene {
     float aabb_lo[3], aabb_hi[3];         // kd-tree root box of the reference incl. its enlargement (gkdtree.h:1213-1220)
     float s2c[16], c2w[16];               // sampleToCamera, cameraToWorld
     float near_clip, far_clip, inv_res_x, inv_res_y;
+    float lens_radius, focus_distance;    // ThinLens::m_apertureRadius / ProjectiveCamera::m_focusDistance (src/sensors/thinlens.cpp); lens_radius == 0: no lens (the perspective camera)
     uint32_t width, height;
     // film
     const float *filter_values;           // [MI_FILTER_RES + 1], global memory (indexed per lane)

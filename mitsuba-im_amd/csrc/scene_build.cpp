@@ -607,6 +607,7 @@ void SceneHost::buildEnvTransform() {
 // d.cam_dx / d.cam_dy: PerspectiveCameraImpl::m_dx / m_dy (perspective.cpp:159-163)
 void SceneHost::syncCameraD() {
     memcpy(d.s2c, s2c, 64); memcpy(d.c2w, c2w, 64); d.near_clip = nearClip; d.far_clip = farClip;
+    d.lens_radius = lensRadius; d.focus_distance = lensRadius != 0.0f ? focusDistance : 0.0f;
     const float *m = s2c; const float irx = 1.0f / (float) width, iry = 1.0f / (float) height;
     auto pt = [&](float px, float py, float *o) {
         float x = m[0] * px + m[1] * py + m[2] * 0.0f + m[3], y = m[4] * px + m[5] * py + m[6] * 0.0f + m[7], z = m[8] * px + m[9] * py + m[10] * 0.0f + m[11], w = m[12] * px + m[13] * py + m[14] * 0.0f + m[15];
@@ -630,6 +631,23 @@ int SceneHost::updateCamera(const float *s2cIn, const float *c2wIn, float nearIn
     if (!committed) { msg = "mi_scene_update_camera: scene not committed"; return MI_ERR_INVALID; }
     memcpy(s2c, s2cIn, 64); memcpy(c2w, c2wIn, 64); nearClip = nearIn; farClip = farIn;
     buildBoundingSpheres();      // the environment emitters' sphere includes the sensor position
+    syncCameraD(); ++revision;
+    return MI_OK;
+}
+int validateLens(const char *who, float apertureRadius, float focusDistance, std::string &msg) {
+    if (!std::isfinite(apertureRadius) || apertureRadius < 0.0f) { msg = std::string(who) + ": the aperture radius must be finite and >= 0"; return MI_ERR_INVALID; }
+    if (apertureRadius > 0.0f && (!std::isfinite(focusDistance) || !(focusDistance > 0.0f))) { msg = std::string(who) + ": the focus distance must be finite and > 0 when the aperture radius is positive"; return MI_ERR_INVALID; }
+    return MI_OK;
+}
+// The lens lives in the scene record alone, like the camera: syncCameraD() is all an edit recomputes.
+int SceneHost::updateLens(float apertureRadius, float focusDistanceIn, std::string &msg) {
+    if (!committed) { msg = "mi_scene_update_lens: scene not committed"; return MI_ERR_INVALID; }
+    if (const int rc = validateLens("mi_scene_update_lens", apertureRadius, focusDistanceIn, msg)) return rc;
+    if ((apertureRadius != 0.0f) != (lensRadius != 0.0f)) {
+        msg = std::string("mi_scene_update_lens: the scene was committed ") + (lensRadius != 0.0f ? "with" : "without") + " a lens; turning it " + (lensRadius != 0.0f ? "off" : "on") + " changes the sample layout of every path, commit a new scene";
+        return MI_ERR_UNSUPPORTED;
+    }
+    lensRadius = apertureRadius; focusDistance = apertureRadius != 0.0f ? focusDistanceIn : 0.0f;
     syncCameraD(); ++revision;
     return MI_OK;
 }

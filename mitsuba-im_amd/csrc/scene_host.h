@@ -16,6 +16,7 @@ struct SceneHost {
     std::vector<MediumD> mediaD; std::vector<uint32_t> primMedia;   // derived: device records; per primitive (interior + 1) | (exterior + 1) << 16
     void *dMedia = nullptr, *dPrimMedia = nullptr;
     float s2c[16] = {0}, c2w[16] = {0}; float nearClip = 0, farClip = 0; bool haveCamera = false;
+    float lensRadius = 0, focusDistance = 0;   // mi_scene_set_lens: thin lens (src/sensors/thinlens.cpp); radius 0 = none
     uint32_t width = 0, height = 0, filterKind = 0; float filterRadius = 0.5f, filterStddev = 0.5f; bool haveFilm = false;
     std::vector<float> envRGB; uint32_t envW = 0, envH = 0; float envToWorld[16] = {0}, envScale = 1.0f;
     // derived on the host (scene_build.cpp)
@@ -55,12 +56,13 @@ struct SceneHost {
     void buildEnvTransform();           // envToWorld3, envToLocal3
     void buildSceneBox(const float *extraBoxes, uint32_t n);   // aabbLo / aabbHi from the vertices, the analytic shapes and n further boxes (lo, hi: the instances)
     void buildPacketTables();           // packetScale, packetGroups, packetGK
-    void syncCameraD();                 // d.s2c, d.c2w, clip planes, cam_dx / cam_dy, env bounding sphere
+    void syncCameraD();                 // d.s2c, d.c2w, clip planes, cam_dx / cam_dy, lens radius / focus distance, env bounding sphere
     void syncEmittersD();               // d.emitter_norm
     void syncEnvD();                    // d.env_to_world, d.env_to_local, d.env_scale
     // The edits.  Each returns MI_OK or an error code with `msg` set and then leaves the scene as it was; on success the host tables above and `d` are those of a
     // fresh commit with the new inputs, `revision` has advanced, and the caller re-sends the small device tables (api.cpp).
     int updateCamera(const float *s2c16, const float *c2w16, float nearClip, float farClip, std::string &msg);
+    int updateLens(float apertureRadius, float focusDistance, std::string &msg);      // values only: a lens appearing or vanishing changes every path's sample layout
     int updateMaterials(const mi_material *m, uint32_t n, std::string &msg, bool *flagsChanged);
     int updateEmitters(const mi_emitter *e, uint32_t n, std::string &msg);
     int updateEnvmapTransform(const float *toWorld16, float scale, std::string &msg);
@@ -103,5 +105,7 @@ struct SceneHost {
 // value checks of mi_scene_set_materials / mi_scene_set_emitters, shared with the in-place updates (scene_build.cpp)
 int validateMaterials(const mi_material *m, uint32_t n, std::string &msg);
 int validateEmitters(const mi_emitter *e, uint32_t n, std::string &msg);
+// value checks of mi_scene_set_lens / mi_scene_update_lens; `who` starts the message
+int validateLens(const char *who, float apertureRadius, float focusDistance, std::string &msg);
 
 }  // namespace mi

@@ -16,6 +16,10 @@ upload -- and is written to `<output>_000.<ext>`, `<output>_001.<ext>`, ...
 `--spin N [--spin-axis x|y|z]` renders N frames in which every instance of a shape group is turned by 360 k / N degrees (frame k) about the axis through its own placed
 origin.  One commit again; every frame is an in-place instance edit (Scene.update_instances: the instance records and a refit of the scene-level tree on the device),
 a clear and a run, written like the orbit's frames.  A scene without instances ends with a message.
+
+`--focus-pull N --focus-from A --focus-to B` renders N frames of a `thinlens` scene with the focus distance going from A to B in equal steps (either end defaults to
+the scene's own focusDistance; the aperture stays).  One commit; every frame is an in-place lens edit (Scene.update_lens: two scalars), a clear and a run, written
+like the orbit's frames.  With `--orbit N` (the same N) every frame takes its camera and its focus distance.  A scene without a thinlens sensor ends with a message.
 """
 import argparse
 import sys
@@ -95,6 +99,11 @@ def spin_instances(sc, n, axis="y"):
     return out
 
 
+def focus_distances(n, a, b):
+    """The n focus distances of a pull from a to b: equal steps, frame 0 = a exactly, frame n - 1 = b exactly."""
+    return [float(a)] if n == 1 else [float(a) if f == 0 else float(b) if f == n - 1 else float(a + (b - a) * f / (n - 1)) for f in range(n)]
+
+
 def write_outputs(sc, render, out, rgb=None, fields=None):
     """the developed film (and, for a multichannel scene, the field groups) of `render` -> `out`; False (message printed) when the format cannot hold them"""
     if rgb is None:
@@ -125,6 +134,9 @@ def main(argv=None):
     ap.add_argument("--orbit-axis", choices=["x", "y", "z"], default="y")
     ap.add_argument("--spin", type=int, default=0, metavar="N", help="N frames with every instance turned about its own origin: one commit, one in-place instance edit per frame")
     ap.add_argument("--spin-axis", choices=["x", "y", "z"], default="y")
+    ap.add_argument("--focus-pull", type=int, default=0, metavar="N", help="N frames of a thinlens scene with the focus distance going from --focus-from to --focus-to: one commit, one in-place lens edit per frame")
+    ap.add_argument("--focus-from", type=float, default=None, metavar="A")
+    ap.add_argument("--focus-to", type=float, default=None, metavar="B")
     a = ap.parse_args(argv)
     params = {}
     for d in a.defines:
@@ -135,6 +147,10 @@ def main(argv=None):
         raise SystemExit("--orbit expects a frame count >= 1")
     if a.spin < 0 or (a.spin and a.orbit):
         raise SystemExit("--spin expects a frame count >= 1 and cannot be combined with --orbit")
+    if a.focus_pull < 0 or (a.focus_pull and a.spin) or (a.focus_pull and a.orbit and a.orbit != a.focus_pull):
+        raise SystemExit("--focus-pull expects a frame count >= 1, cannot be combined with --spin, and with --orbit both take the same frame count")
+    if not a.focus_pull and (a.focus_from is not None or a.focus_to is not None):
+        raise SystemExit("--focus-from / --focus-to belong to --focus-pull N")
     try:
         t0 = time.perf_counter()
         sc = xml_scene.load_scene(a.scene, params, sampler=a.sampler)
@@ -144,11 +160,33 @@ def main(argv=None):
         if a.spin and not (sc.get("instances") or []):
             print(f"error: {a.scene}: --spin turns the instances of shape groups, and this scene has none", file=sys.stderr)
             return 1
+        if a.focus_pull:
+            if not float(sc.get("aperture_radius", 0.0) or 0.0):
+                print(f"error: {a.scene}: --focus-pull moves the focal plane of a thinlens sensor, and this scene's sensor has no lens", file=sys.stderr)
+                return 1
+            pull = focus_distances(a.focus_pull, sc.focus_distance if a.focus_from is None else a.focus_from, sc.focus_distance if a.focus_to is None else a.focus_to)
+            if not all(np.isfinite(d) and d > 0 for d in pull):
+                print("error: --focus-from / --focus-to expect positive distances", file=sys.stderr)
+                return 1
         t1 = time.perf_counter()
         scene = Scene(sc, device=a.device)
         render = Render(scene, device=a.device)
         t2 = time.perf_counter()
         n = sc.width * sc.height * sc.spp
+        if a.focus_pull:
+            stem, ext = out.rsplit(".", 1); frame_s = []
+            cams = orbit_cameras(sc, a.orbit, a.orbit_axis) if a.orbit else [None] * a.focus_pull
+            for f, (dist, c2w) in enumerate(zip(pull, cams)):
+                tf = time.perf_counter()
+                if c2w is not None: scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far)
+                scene.update_lens(sc.aperture_radius, dist); render.clear(); render.run()
+                frame_s.append(time.perf_counter() - tf)
+                if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}"):
+                    return 1
+            rev, builds = scene.revision(); mean = sum(frame_s) / len(frame_s)
+            print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s once ({builds} tree build, {rev} edits), "
+                  f"{a.focus_pull} frames, focus {pull[0]:g} .. {pull[-1]:g}, render {mean:.3f} s per frame ({n / mean / 1e6:.1f} Msamples/s) -> {stem}_000.{ext} .. {stem}_{a.focus_pull - 1:03d}.{ext}")
+            return 0
         if a.orbit:
             stem, ext = out.rsplit(".", 1); frame_s = []
             for f, c2w in enumerate(orbit_cameras(sc, a.orbit, a.orbit_axis)):

@@ -317,6 +317,13 @@ def set_crop_window(sc, full_width, full_height, offset_x, offset_y):
     return sc
 
 
+def with_lens(sc, aperture_radius, focus_distance):
+    """The scene description with a thin lens: world-space aperture radius, distance of the focal plane along the camera axis.  Returns sc."""
+    if not (aperture_radius >= 0) or (aperture_radius > 0 and not (focus_distance > 0)): raise ValueError("with_lens: aperture radius >= 0 and, with a lens, focus distance > 0")
+    sc.aperture_radius = float(f32(aperture_radius)); sc.focus_distance = float(f32(focus_distance)) if aperture_radius > 0 else 0.0
+    return sc
+
+
 def finish_scene(verts, tris, shapes, bsdfs, emitters, cam_to_world, xfov, near, far, width, height,
                  spp, sampler, max_depth, rr_depth=5, filter_kind=FILTER_BOX, seed=0,
                  normals=None, uvs=None, strict_normals=False, hide_emitters=False, envmap=None,
@@ -341,6 +348,7 @@ def finish_scene(verts, tris, shapes, bsdfs, emitters, cam_to_world, xfov, near,
     sc.strict_normals = int(strict_normals); sc.hide_emitters = int(hide_emitters)
     sc.sampler = sampler; sc.spp = int(spp); sc.seed = int(seed)
     sc.envmap = envmap          # None or dict(rgb[h,w,3] f32, to_world[4,4], scale)
+    sc.aperture_radius = 0.0; sc.focus_distance = 0.0   # thin lens (src/sensors/thinlens.cpp) on top of the perspective camera; radius 0 = none (with_lens)
     sc.fields = []              # field channels next to the radiance (the reference's multichannel + field integrators): names out of api.FIELD_NAMES or (name, undefined) pairs
     textures = list(textures or [])
     sc.env_texture = 0                              # index + 1 of the texture record holding the environment map's MIP pyramid (camera-ray lookups, envmap.cpp:398-411)
@@ -1559,6 +1567,8 @@ VEACH_MICROFACETS_2 = [
 # binary container for the oracle-side harness
 # ---------------------------------------------------------------------------------------------
 def save_scene(sc, path):
+    if float(sc.get("aperture_radius", 0.0) or 0.0) != 0.0:
+        raise ValueError("save_scene: the MISCENE2 container has no field for a thin lens (aperture_radius / focus_distance); only perspective-camera scenes can be written")
     with open(path, "wb") as f:
         f.write(b"MISCENE2")
         has_n = int(sc.nrm is not None); has_uv = int(sc.uv is not None)

@@ -8,6 +8,7 @@ substitution, <include>, <ref>, <integer> <float> <boolean> <string> <point> <ve
 <texture> <emitter>.  Plugins understood = the ones the hot path implements:
     integrator  path
     sensor      perspective                                  (src/librender/sensor.cpp:225-305 fov / fovAxis / focalLength)
+                thinlens                                     (src/sensors/thinlens.cpp: + apertureRadius, focusDistance)
     sampler     independent, sobol
     film        hdrfilm / ldrfilm / mfilm (size + reconstruction filter; the file-format options do not concern the path)
     rfilter     box, tent, gaussian, mitchell, catmullrom, lanczos
@@ -975,8 +976,8 @@ class _SceneBuilder:
         if len(sensors) != 1:
             raise SceneError("exactly one <sensor> is expected (the reference builds a default camera from the scene bounds; give one explicitly)")
         sen = sensors[0][1]
-        if sen.type != "perspective":
-            raise SceneError(f"sensor \"{sen.type}\" is not supported (perspective)")
+        if sen.type not in ("perspective", "thinlens"):
+            raise SceneError(f"sensor \"{sen.type}\" is not supported (perspective, thinlens)")
         film = sen.child("film"); smp = sen.child("sampler")
         width = int(film.get("width", 768)) if film is not None else 768
         height = int(film.get("height", 576)) if film is not None else 576
@@ -1061,8 +1062,21 @@ class _SceneBuilder:
         lin = cam[:3, :3].astype(np.float64)
         if not np.allclose(lin.T @ lin, np.eye(3), atol=1e-3):
             raise SceneError("Scale factors in the camera-to-world transformation are not allowed!")      # perspective.cpp:116-118
-        for k in ("shutterOpen", "shutterClose", "focusDistance"):
+        for k in ("shutterOpen", "shutterClose"):
             sen.get(k)
+        focus = sen.get("focusDistance", far)            # ProjectiveCamera: m_focusDistance defaults to the far plane (src/librender/sensor.cpp:161); the pinhole ignores it
+        aperture = 0.0
+        if sen.type == "thinlens":                       # src/sensors/thinlens.cpp:124-143; the scale check above is the perspective camera's
+            if not sen.has("apertureRadius"):
+                raise SceneError('<sensor type="thinlens">: property "apertureRadius" has not been specified!')      # props.getFloat without a default
+            aperture = float(f32(sen.get("apertureRadius")))
+            if aperture == 0:
+                aperture = float(f32(1e-4))              # "Can't have a zero aperture radius -- setting to Epsilon" (thinlens.cpp:134-138)
+            # (the reference takes a negative radius as it comes -- a mirrored aperture disk; mi_scene_set_lens refuses it, so it is refused here by name rather than at commit)
+            if not (aperture > 0 and math.isfinite(aperture)):
+                raise SceneError('<sensor type="thinlens">: apertureRadius must be positive and finite')
+            if not (focus > 0 and math.isfinite(focus)):
+                raise SceneError('<sensor type="thinlens">: focusDistance must be positive and finite')
         sm = sen.children_of("medium")
         if len(sm) > 1:
             raise SceneError("a sensor takes one medium")
@@ -1106,6 +1120,8 @@ class _SceneBuilder:
                             integrator=integrators[integ.type])
         if sc.integrator != S.INTEGRATOR_PATH and not self.media:
             pass                                        # a volumetric integrator over a scene without media is legal (it renders what `path` renders)
+        if aperture:
+            S.with_lens(sc, aperture, focus)
         if crop is not None:
             S.set_crop_window(sc, full_w, full_h, crop[0], crop[1])
         if f_radius is not None:
@@ -1194,7 +1210,9 @@ def export_scene(sc, directory, name=None, mesh_format="serialized"):
               "lanczos": f'<integer name="lobes" value="{int(sc.filter_radius)}"/>'}.get(filt, "")
     smp = "sobol" if sc.sampler == S.SAMPLER_SOBOL else "independent"
     seed = f'<integer name="{"seed" if smp == "independent" else "scramble"}" value="{sc.seed}"/>' if sc.seed else ""
-    out.append(f'\t<sensor type="perspective"><float name="fov" value="{fmt([sc.xfov])}"/><string name="fovAxis" value="x"/>'
+    lens = float(sc.get("aperture_radius", 0.0) or 0.0)
+    lens_props = f'<float name="apertureRadius" value="{fmt([lens])}"/><float name="focusDistance" value="{fmt([sc.focus_distance])}"/>' if lens else ""
+    out.append(f'\t<sensor type="{"thinlens" if lens else "perspective"}"><float name="fov" value="{fmt([sc.xfov])}"/><string name="fovAxis" value="x"/>{lens_props}'
                f'<float name="nearClip" value="{fmt([sc.near])}"/><float name="farClip" value="{fmt([sc.far])}"/>{mat("toWorld", sc.cam_to_world)}\n'
                f'\t\t<sampler type="{smp}"><integer name="sampleCount" value="{sc.spp}"/>{seed}</sampler>\n'
                f'\t\t<film type="hdrfilm">' + (f'<integer name="width" value="{sc.crop[0]}"/><integer name="height" value="{sc.crop[1]}"/><integer name="cropOffsetX" value="{sc.crop[2]}"/>'
