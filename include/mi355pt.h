@@ -396,6 +396,23 @@ int mi_debug_camera_rays_lens(mi_scene *s, const float *sample_pos2, const float
 int mi_debug_libm(int fn, const float *x, const float *y, uint64_t n, float *out);   /* the device restatements of glibc's routines (libm_glibc.h) as the kernels call them:
                                       fn 0 expf(x), 1 logf(x), 2 powf(x, y), 3 tanf(x), 4 atanf(x), 5 atan2f(x, y), 6 acosf(x); y may be NULL for the one-argument routines */
 int mi_debug_sincosf(const float *x, uint64_t n, float *out_sin_cos2);   /* the device restatement of glibc's sincosf (warps): out[2i] = sin, out[2i+1] = cos */
+/* The shape of a path pool.  A pool of `paths` paths is cut into n_seg segments of cap slots (cap a multiple of 64; segment s holds the paths s * cap ..); the shade stages
+ * give every segment to one wave, which walks it in chunks of 64.  The rule, a pure host function (no device, no environment): n_seg = the override, else 16384, or -- on a
+ * scene with rough conductors -- paths / 1024 kept within [16384, 2^18]; never more than ceil(paths / 64) segments (and never fewer than one); the volumetric integrators
+ * keep a segment at <= 65472 slots (their stages pack two per-segment record counts into 16 bits each) by raising n_seg to ceil(paths / 65472); cap = ceil(paths / n_seg)
+ * rounded up to a multiple of 64; the three stage grids = min(n_seg, override or the default 4096 / 768 (512 with rough conductors) / 4096).  An override of 0 means unset
+ * (so do MI355PT_SEGMENTS and MI355PT_GRID_EXTEND / _SHADE / _SHADOW when they are 0, negative or no number).  A pool of 2^28 slots or more is refused: MI_ERR_INVALID. */
+typedef struct { uint32_t segments, grid_extend, grid_shade, grid_shadow; } mi_pool_overrides;
+typedef struct { uint32_t n_seg, cap, grid_extend, grid_shade, grid_shadow; } mi_pool_shape;
+int mi_debug_pool_shape(uint64_t paths, int has_roughconductor, uint32_t integrator, const mi_pool_overrides *overrides /* NULL: none */, mi_pool_shape *out);
+/* The pools of a render as they are now.  Known from mi_render_create on: n_pools = the pools / streams the render owns (MI355PT_STREAMS; a job of fewer batches uses
+ * fewer of them: 3 batches on a render of 4 pools run on 3), lds_tables = this render stages the scene tables in LDS, has_roughconductor / integrator = what the rule above
+ * is given.  Zero until the first run / samples call allocates the pools: n_seg, cap, the three stage grids and pool_paths (a pool only grows, so a smaller job reports
+ * the shape it runs in).  Of the last launch of the path integrator's shade stage (zero before it, and for the volumetric integrators): shade_table_bytes = the dynamic
+ * LDS it asked for in front of the order list (Sobol tables, scene tables), sorted = it read its segments through the class-sorted order list, which takes a scene with
+ * rough conductors, cap <= 8192 and shade_table_bytes rounded up to 16 + 8 * cap + 16 <= 65536. */
+typedef struct { uint32_t n_seg, cap, n_pools, grid_extend, grid_shade, grid_shadow, lds_tables, sorted, has_roughconductor, integrator, shade_table_bytes, pad; uint64_t pool_paths; } mi_pool_info;
+int mi_render_debug_pool_info(mi_render *r, mi_pool_info *out);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,20 @@ def normalize_fields(fields):
     return out
 
 
+class MiPoolOverrides(C.Structure):
+    """0 = unset (the library's default rule)"""
+    _fields_ = [("segments", C.c_uint32), ("grid_extend", C.c_uint32), ("grid_shade", C.c_uint32), ("grid_shadow", C.c_uint32)]
+
+
+class MiPoolShape(C.Structure):
+    _fields_ = [("n_seg", C.c_uint32), ("cap", C.c_uint32), ("grid_extend", C.c_uint32), ("grid_shade", C.c_uint32), ("grid_shadow", C.c_uint32)]
+
+
+class MiPoolInfo(C.Structure):
+    _fields_ = [("n_seg", C.c_uint32), ("cap", C.c_uint32), ("n_pools", C.c_uint32), ("grid_extend", C.c_uint32), ("grid_shade", C.c_uint32), ("grid_shadow", C.c_uint32),
+                ("lds_tables", C.c_uint32), ("sorted", C.c_uint32), ("has_roughconductor", C.c_uint32), ("integrator", C.c_uint32), ("shade_table_bytes", C.c_uint32), ("pad", C.c_uint32), ("pool_paths", C.c_uint64)]
+
+
 class MiFusedDebugInfo(C.Structure):
     _fields_ = [("wide", C.c_uint32), ("bvh_depth", C.c_uint32), ("bvh_stack_direct", C.c_uint32), ("max_stack_seen", C.c_uint32), ("rays_counted", C.c_uint64)]
 
@@ -91,7 +105,7 @@ EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_s
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_lens", "mi_scene_set_film",
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
-           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_geometry_bytes", "mi_debug_read_geometry"]
+           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
                 "mi_host_set_camera", "mi_host_set_lens", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
 
@@ -168,6 +182,8 @@ class Lib:
         L.mi_debug_libm.argtypes = [i32, vp, vp, u64, vp]
         L.mi_debug_geometry_bytes.argtypes = [vp, u32, C.POINTER(u64)]
         L.mi_debug_read_geometry.argtypes = [vp, u32, vp, u64]
+        L.mi_debug_pool_shape.argtypes = [u64, i32, u32, C.POINTER(MiPoolOverrides), C.POINTER(MiPoolShape)]
+        L.mi_render_debug_pool_info.argtypes = [vp, C.POINTER(MiPoolInfo)]
 
     def check(self, rc):
         if rc != 0:
@@ -199,6 +215,14 @@ def load_sobol_tables(L, path=SOBOL_PATH):
 
 def _p(a):
     return None if a is None else a.ctypes.data
+
+
+def pool_shape(paths, has_roughconductor=False, integrator=0, segments=0, grid_extend=0, grid_shade=0, grid_shadow=0):
+    """The shape a path pool of `paths` paths gets (mi_debug_pool_shape: host arithmetic, no device): dict of n_seg, cap and the three stage grids; the overrides are
+    what MI355PT_SEGMENTS / MI355PT_GRID_* would set, 0 = unset.  A pool of 2^28 slots or more raises MiError (code 1)."""
+    L = lib(); ov = MiPoolOverrides(segments, grid_extend, grid_shade, grid_shadow); out = MiPoolShape()
+    L.check(L.L.mi_debug_pool_shape(paths, int(bool(has_roughconductor)), int(integrator), C.byref(ov), C.byref(out)))
+    return {k: getattr(out, k) for k, _ in MiPoolShape._fields_}
 
 
 def device_sincosf(x):
@@ -524,6 +548,13 @@ class Render:
     def merge_film(self, other):
         """self += other (raw film sums, field planes included, ray counters): both renders idle, same film, same field list."""
         self.L.check(self.L.L.mi_render_merge_film(self.h, other.h))
+
+    def pool_info(self):
+        """The path pools as they are now (read-only): n_pools (the pools the render owns), lds_tables, has_roughconductor and integrator from creation on; n_seg, cap, the
+        three stage grids and pool_paths once a run has allocated the pools; shade_table_bytes (dynamic LDS in front of the order list) and sorted (the segments were
+        read through the class-sorted order list) of the last shade launch of the path integrator."""
+        s = MiPoolInfo(); self.L.check(self.L.L.mi_render_debug_pool_info(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in MiPoolInfo._fields_ if k != "pad"}
 
     def stats(self):
         s = MiStats(); self.L.check(self.L.L.mi_render_stats(self.h, C.byref(s)))

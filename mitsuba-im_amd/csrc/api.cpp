@@ -61,12 +61,13 @@ void mi_launch_instance_records(const mi::InstEditTables &, hipStream_t);
 // (Round 2 experiment, removed: two launches per bounce -- diffuse hits through the diffuse-only kernel, the rest through the full kernel -- measured SLOWER
 // than one launch of the full kernel over the class-sorted list, 1579 vs 1675 Msamples/s on the Veach scene: a wave of diffuse hits already skips the other
 // BSDFs' code at run time, and the stage runs at two waves per SIMD either way)
-static void mi_launch_shade(const DScene &scIn, bool ldsTables, const RenderConst &rc, const Queues &q, int buf, uint32_t grid, hipStream_t st) {
+static bool mi_launch_shade(const DScene &scIn, bool ldsTables, const RenderConst &rc, const Queues &q, int buf, uint32_t grid, hipStream_t st, uint32_t *tableBytes = nullptr) {
     DScene sc = scIn; sc.small_tables = ldsTables ? 1u : 0u;
     size_t lds = rc.sampler == 1 ? (size_t) rc.nib_dims * rc.nib_count * 64 : 16;
     const bool env = sc.env_index >= 0;
     if (sc.small_tables) lds += 16 + 4 * ((size_t) sc.n_tris * (4 * MI_SHADE_WORDS) + sc.n_materials * 16 + sc.n_emitters * 12 + ((sc.n_emitters + 4) & ~3u) + sc.area_cdf_len);
     RenderConst rcl = rc; rcl.order_offset_words = 0;
+    if (tableBytes) *tableBytes = (uint32_t) lds;      // dynamic LDS in front of the order list (mi_render_debug_pool_info)
     if (sc.has_roughconductor && q.cap <= 8192u) {      // path-order list: only where it still fits the 64 KB a launch may request (else unsorted shading)
         const uint32_t off = (uint32_t) ((lds + 15) / 16 * 4); const size_t total = (size_t) off * 4 + (size_t) q.cap * 2 * 4 + 16;
         if (total <= 64 * 1024) { rcl.order_offset_words = off; lds = total; }
@@ -74,6 +75,7 @@ static void mi_launch_shade(const DScene &scIn, bool ldsTables, const RenderCons
     if (!sc.has_roughconductor) (env ? mi_launch_shade_d_env : mi_launch_shade_d)(sc, rcl, q, buf, grid, lds, st);
     else if (sc.has_adapters & 1u) (env ? mi_launch_shade_rcw_env : mi_launch_shade_rcw)(sc, rcl, q, buf, grid, lds, st);      // mixturebsdf / bumpmap / normalmap present
     else (env ? mi_launch_shade_rc_env : mi_launch_shade_rc)(sc, rcl, q, buf, grid, lds, st);
+    return rcl.order_offset_words != 0 && q.cap <= 0xFFFFu;      // shade.h doSort: the segments were read through the class-sorted order list
 }
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -95,6 +97,8 @@ struct mi_render {
     bool profiling = false; std::vector<hipEvent_t> evPool; std::vector<int> evTag;   // tag: 0 generate/film, 1 extend, 2 shade, 3 shadow
     mi_stats stats{};
     uint64_t samplesTotal = 0, launchesAll = 0; uint64_t mergedRays = 0, mergedShadow = 0, mergedPathLen = 0, mergedSamples = 0;   // counters of replicas merged into this film
+    uint32_t lastTableBytes = 0;   // dynamic LDS the last shade launch of the path integrator asked for in front of the order list
+    bool lastSorted = false;  // the last shade launch read its segments through the class-sorted order list (mi_render_debug_pool_info)
     bool ldsTables = false;   // this render stages the scene tables in LDS (scene eligible and everything fits 64 KB together with the Sobol tables and the order list)
     uint32_t *pollHost = nullptr; size_t pollWords = 0; hipEvent_t pollEv = nullptr;   // unbounded depth: pinned landing buffer + event for the survivor-count poll
     uint32_t *dNib = nullptr; void *dSobolTabs = nullptr;   // dSobolTabs: the three look_up tables of k_generate (frame, px, py), one allocation
@@ -706,21 +710,35 @@ static int allocQ(std::vector<void *> &allocs, void **p, size_t bytes) {
 #define ALLOC(ptr, type, count) do { void *p_ = nullptr; int rc_ = allocQ(allocs, &p_, sizeof(type) * (size_t) (count)); if (rc_) return rc_; ptr = (type *) p_; } while (0)
 
 static void freePoolQ(Queues &Q, std::vector<void *> &allocs) { for (void *p : allocs) (void) hipFree(p); allocs.clear(); Q = Queues{}; }      // no dangling queue pointer survives
+// The shape of a path pool (include/mi355pt.h): pure host arithmetic, exported so that tests can state the shape they mean to run at.
+// segments (each owned by one wave in the shade stage): 16384, or -- where the shade stage sorts a segment's paths by material class and its
+// index list must fit LDS -- as many as keep a segment at ~1000 slots (C3 at 64 M paths: 1916 Msamples/s with 16384 segments, 1983 with 65536)
+extern "C" int mi_debug_pool_shape(uint64_t paths, int hasRC, uint32_t integrator, const mi_pool_overrides *ov, mi_pool_shape *out) {
+    if (!out) return fail(MI_ERR_INVALID, "mi_debug_pool_shape: null argument");
+    const mi_pool_overrides none{}; if (!ov) ov = &none;
+    uint64_t grid = ov->segments ? ov->segments : hasRC ? std::min<uint64_t>(std::max<uint64_t>(16384u, paths / 1024u), 1u << 18) : 16384u;
+    const uint64_t minGrid = (paths + 63) / 64; if (grid > minGrid) grid = std::max<uint64_t>(minGrid, 1);
+    if (integrator != MI_INTEGRATOR_PATH && (paths + grid - 1) / grid > 65472u) grid = (paths + 65471u) / 65472u;      // the volumetric stages count two kinds of shadow records per segment in 16 bits each
+    uint64_t cap = (paths + grid - 1) / grid; cap = (cap + 63) / 64 * 64;
+    if (cap * grid >= (1ull << 28)) return fail(MI_ERR_INVALID, "mi_render_run: a path pool holds fewer than 2^28 slots (the stages address the queues through 32-bit byte offsets); lower planes_per_batch");
+    out->n_seg = (uint32_t) grid; out->cap = (uint32_t) cap;
+    // workgroups launched per stage (each walks segments b, b + grid, ...): sized to the stage's occupancy on 256 CUs
+    out->grid_extend = (uint32_t) std::min<uint64_t>(grid, ov->grid_extend ? ov->grid_extend : 4096u);
+    out->grid_shade = (uint32_t) std::min<uint64_t>(grid, ov->grid_shade ? ov->grid_shade : hasRC ? 512u : 768u);      // 3 workgroups per CU since the diffuse kernels hold 4 waves per SIMD (C2: 512 -> 2970, 640 -> 3022, 768 -> 3078, 896 -> 2890 Msamples/s); the 2-wave microfacet kernels stay at 2
+    out->grid_shadow = (uint32_t) std::min<uint64_t>(grid, ov->grid_shadow ? ov->grid_shadow : 4096u);
+    return MI_OK;
+}
 // allocates the queues of ONE pool into an empty Q (freePoolQ first); on failure the caller releases whatever was allocated
 static int allocPoolQ(mi_render *r, uint64_t paths, Queues &Q, std::vector<void *> &allocs) {
-    auto envU = [](const char *name, uint32_t dflt) { const char *v = getenv(name); return v && v[0] ? (uint32_t) atoi(v) : dflt; };
-    // segments of the path pool (each owned by one wave in the shade stage): 16384, or -- where the shade stage sorts a segment's paths by material class and its
-    // index list must fit LDS -- as many as keep a segment at ~1000 slots (C3 at 64 M paths: 1916 Msamples/s with 16384 segments, 1983 with 65536)
-    uint32_t grid = envU("MI355PT_SEGMENTS", r->scene->h.d.has_roughconductor ? (uint32_t) std::min<uint64_t>(std::max<uint64_t>(16384u, paths / 1024u), 1u << 18) : 16384u);
-    uint64_t minGrid = (paths + 63) / 64; if (grid > minGrid) grid = (uint32_t) std::max<uint64_t>(minGrid, 1);
-    if (r->rc.integrator != MI_INTEGRATOR_PATH && (paths + grid - 1) / grid > 65472u) grid = (uint32_t) ((paths + 65471u) / 65472u);      // the volumetric stages count two kinds of shadow records per segment in 16 bits each
-    uint64_t cap = (paths + grid - 1) / grid; cap = (cap + 63) / 64 * 64;
-    r->grid = grid; Q.cap = (uint32_t) cap; Q.n_seg = grid;
-    // workgroups launched per stage (each walks segments b, b + grid, ...): sized to the stage's occupancy on 256 CUs
-    r->gridExtend = std::min(grid, envU("MI355PT_GRID_EXTEND", 4096u)); r->gridShade = std::min(grid, envU("MI355PT_GRID_SHADE", r->scene->h.d.has_roughconductor ? 512u : 768u));      // 3 workgroups per CU since the diffuse kernels hold 4 waves per SIMD (C2: 512 -> 2970, 640 -> 3022, 768 -> 3078, 896 -> 2890 Msamples/s); the 2-wave microfacet kernels stay at 2
-    r->gridShadow = std::min(grid, envU("MI355PT_GRID_SHADOW", 4096u));
+    // MI355PT_SEGMENTS / MI355PT_GRID_*: 0, a negative value or no number at all count as unset (a segment count of 0 would divide by zero below)
+    auto envU = [](const char *name) -> uint32_t { const char *v = getenv(name); const long long x = v ? atoll(v) : 0; return x > 0 ? (uint32_t) std::min<long long>(x, 0xFFFFFFFFll) : 0u; };
+    const mi_pool_overrides ov{envU("MI355PT_SEGMENTS"), envU("MI355PT_GRID_EXTEND"), envU("MI355PT_GRID_SHADE"), envU("MI355PT_GRID_SHADOW")};
+    mi_pool_shape g{};
+    { const int rc = mi_debug_pool_shape(paths, r->scene->h.d.has_roughconductor ? 1 : 0, r->rc.integrator, &ov, &g); if (rc) return rc; }
+    const uint32_t grid = g.n_seg; const uint64_t cap = g.cap;
+    r->grid = grid; Q.cap = g.cap; Q.n_seg = grid;
+    r->gridExtend = g.grid_extend; r->gridShade = g.grid_shade; r->gridShadow = g.grid_shadow;
     const uint64_t slots = cap * grid;
-    if (slots >= (1ull << 28)) return fail(MI_ERR_INVALID, "mi_render_run: a path pool holds fewer than 2^28 slots (the stages address the queues through 32-bit byte offsets); lower planes_per_batch");
     {   // MI355PT_POOL_LIMIT (bytes per pool; tests): behave as if the card had no more room than this -- mi_render_run then falls back to smaller batches
         const char *lim = getenv("MI355PT_POOL_LIMIT");
         if (lim && atoll(lim) > 0 && slots * 224ull > (uint64_t) atoll(lim)) return fail(MI_ERR_DEVICE, "mi_render_run: path pool larger than MI355PT_POOL_LIMIT");
@@ -949,6 +967,12 @@ int mi_render_debug_sensor_differentials(mi_render *r, const uint32_t *pairs, ui
     if (e != hipSuccess) return fail(MI_ERR_DEVICE, std::string("mi_render_debug_sensor_differentials: ") + hipGetErrorString(e));
     return MI_OK;
 }
+int mi_render_debug_pool_info(mi_render *r, mi_pool_info *out) {
+    if (!r || !out) return fail(MI_ERR_INVALID, "mi_render_debug_pool_info: null argument");
+    *out = mi_pool_info{}; out->n_pools = (uint32_t) r->nStreams; out->lds_tables = r->ldsTables ? 1u : 0u; out->sorted = r->lastSorted ? 1u : 0u; out->has_roughconductor = r->scene->h.d.has_roughconductor ? 1u : 0u; out->integrator = r->rc.integrator; out->shade_table_bytes = r->lastTableBytes; out->pool_paths = r->poolPaths;
+    if (r->poolPaths) { out->n_seg = r->q.n_seg; out->cap = r->q.cap; out->grid_extend = r->gridExtend; out->grid_shade = r->gridShade; out->grid_shadow = r->gridShadow; }
+    return MI_OK;
+}
 int mi_render_set_profiling(mi_render *r, int enabled) { if (!r) return fail(MI_ERR_INVALID, "null"); r->profiling = enabled != 0; return MI_OK; }
 
 static void mark(mi_render *r, int tag, size_t &used, hipStream_t st = nullptr) {
@@ -983,7 +1007,7 @@ static int traceBatch(mi_render *r, const BatchDesc &bd, const uint32_t *list, s
             if (depth < maxDepth || (depth == 1 && r->rc.opacity)) { mark(r, 3, evUsed, st); (mis ? mi_launch_shadow_volmis : mi_launch_shadow_vol)(sc, Q, r->gridShadow, st); }      // (depth 1 with EOpacity: the alpha walks)
         } else {
         if (depth == 1 && sc.env_texture && !r->rc.hide_emitters) mi_launch_env_primary(sc, r->rc, Q, buf, r->gridExtend, st);   // camera rays that see the sky: filtered lookup (envmap.cpp:398-411)
-        mark(r, 2, evUsed, st); mi_launch_shade(sc, r->ldsTables, r->rc, Q, buf, r->gridShade, st);
+        mark(r, 2, evUsed, st); r->lastSorted = mi_launch_shade(sc, r->ldsTables, r->rc, Q, buf, r->gridShade, st, &r->lastTableBytes);
         if (depth < maxDepth) { mark(r, 3, evUsed, st); if (fused && 2 * depth + 1 < MI_TICKETS) mi_launch_shadow_fused(sc, Q, Q.ticket + 2 * depth + 1, st); else mi_launch_shadow(sc, Q, r->gridShadow, st); }
         }
         buf ^= 1;
