@@ -395,6 +395,19 @@ int mi_debug_camera_rays(mi_scene *s, const float *sample_pos2, uint64_t n, floa
 int mi_debug_camera_rays_lens(mi_scene *s, const float *sample_pos2, const float *aperture2, uint64_t n, float *out14);
 int mi_debug_libm(int fn, const float *x, const float *y, uint64_t n, float *out);   /* the device restatements of glibc's routines (libm_glibc.h) as the kernels call them:
                                       fn 0 expf(x), 1 logf(x), 2 powf(x, y), 3 tanf(x), 4 atanf(x), 5 atan2f(x, y), 6 acosf(x); y may be NULL for the one-argument routines */
+/* The BSDF routines one call at a time.  Record `material` is resolved as the shade stage resolves the material of an untextured hit (a coating / roughcoating record with
+ * its nested record) and queried through the widest instantiation of the stage's own sample / eval / pdf functions (every BSDF type and wrapper, tables in global memory).
+ * mode 0 = BSDF::sample(bRec, pdf, sample): wi3, uv2 = the 2-D sample, extra1 = the value handed out if the sampled BSDF asks its sampler for one more (BSDF::EUsesSampler);
+ *          wo3 is ignored (may be NULL); out11 = weight rgb, pdf, wo xyz, eta, sampled component is a Dirac delta (0 / 1), is ENull (0 / 1), extra value drawn (0 / 1).
+ * mode 1 = BSDF::eval + BSDF::pdf (all components, solid angle): wi3, wo3; uv2 / extra1 are ignored (may be NULL); out4 = value rgb, pdf.
+ * Records whose evaluation needs a hit record are refused by name with MI_ERR_UNSUPPORTED: mask (its logic is inline in the shade stage), bumpmap, normalmap, a record with
+ * a bound texture, and a coating / mixturebsdf / blendbsdf over one of them. */
+int mi_debug_bsdf(mi_scene *s, uint32_t material, int mode, const float *wi3, const float *wo3, const float *uv2, const float *extra1, uint64_t n, float *out);
+/* The texture routines one call at a time: record `texture` of mi_scene_set_textures at uv2.  Bitmaps: scale and offset as the shade stage applies them; partials4 = (dudx,
+ * dvdx, dudy, dvdy) per lookup selects the filtered lookup of a camera hit (TMIPMap::eval under the record's filter), NULL the level-0 lookup of every later bounce
+ * (bilinear, or the nearest texel under the nearest filter).  Procedural textures ignore the partials.  The EWA loops run over the footprint's bounding box: the caller
+ * keeps footprints bounded. */
+int mi_debug_texture(mi_scene *s, uint32_t texture, const float *uv2, const float *partials4, uint64_t n, float *out3);
 int mi_debug_sincosf(const float *x, uint64_t n, float *out_sin_cos2);   /* the device restatement of glibc's sincosf (warps): out[2i] = sin, out[2i+1] = cos */
 /* The shape of a path pool.  A pool of `paths` paths is cut into n_seg segments of cap slots (cap a multiple of 64; segment s holds the paths s * cap ..); the shade stages
  * give every segment to one wave, which walks it in chunks of 64.  The rule, a pure host function (no device, no environment): n_seg = the override, else 16384, or -- on a

@@ -105,7 +105,7 @@ EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_s
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_lens", "mi_scene_set_film",
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
-           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
+           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
                 "mi_host_set_camera", "mi_host_set_lens", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
 
@@ -180,6 +180,8 @@ class Lib:
         L.mi_debug_camera_rays_lens.argtypes = [vp, vp, vp, u64, vp]
         L.mi_debug_sincosf.argtypes = [vp, u64, vp]
         L.mi_debug_libm.argtypes = [i32, vp, vp, u64, vp]
+        L.mi_debug_bsdf.argtypes = [vp, u32, i32, vp, vp, vp, vp, u64, vp]
+        L.mi_debug_texture.argtypes = [vp, u32, vp, vp, u64, vp]
         L.mi_debug_geometry_bytes.argtypes = [vp, u32, C.POINTER(u64)]
         L.mi_debug_read_geometry.argtypes = [vp, u32, vp, u64]
         L.mi_debug_pool_shape.argtypes = [u64, i32, u32, C.POINTER(MiPoolOverrides), C.POINTER(MiPoolShape)]
@@ -448,6 +450,28 @@ class Scene:
     def sobol(self, px_py_k, ndims):
         a = np.ascontiguousarray(px_py_k, np.uint32).reshape(-1, 3); idx = np.zeros(len(a), np.uint64); vals = np.zeros((len(a), ndims), np.float32)
         self.L.check(self.L.L.mi_debug_sobol(self.h, _p(a), len(a), ndims, _p(idx), _p(vals))); return idx, vals
+
+    def bsdf_units(self, material, wi, wo=None, uv=None, extra=None):
+        """The device's BSDF routines on chosen inputs (mi_debug_bsdf), one call per row.  With `wo`: BSDF::eval + pdf -> [n, 4] = value rgb, pdf.  Without: BSDF::sample
+        with the 2-D sample `uv` and the value `extra` for a BSDF that asks its sampler for one more (default 0.5) -> [n, 11] = weight rgb, pdf, wo xyz, eta, delta flag,
+        null flag, extra-drawn flag.  Records that need a hit record (mask, bumpmap, normalmap, textured ones) raise MiError code 3 naming the kind."""
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3); n = len(wi)
+        if wo is not None:
+            wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3); out = np.zeros((n, 4), np.float32)
+            if len(wo) != n: raise ValueError("bsdf_units: one wo per wi")
+            self.L.check(self.L.L.mi_debug_bsdf(self.h, int(material), 1, _p(wi), _p(wo), None, None, n, _p(out))); return out
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2); ex = np.full(n, 0.5, np.float32) if extra is None else np.ascontiguousarray(extra, np.float32).reshape(-1)
+        if len(uv) != n or len(ex) != n: raise ValueError("bsdf_units: one sample and one extra value per wi")
+        out = np.zeros((n, 11), np.float32)
+        self.L.check(self.L.L.mi_debug_bsdf(self.h, int(material), 0, _p(wi), None, _p(uv), _p(ex), n, _p(out))); return out
+
+    def texture_units(self, texture, uv, partials=None):
+        """The device's texture routines on chosen inputs (mi_debug_texture): record `texture` at uv [n, 2]; partials [n, 4] = (dudx, dvdx, dudy, dvdy) for the filtered
+        lookup of a camera hit, None for the level-0 lookup of later bounces -> [n, 3]."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2); n = len(uv); out = np.zeros((n, 3), np.float32)
+        pa = None if partials is None else np.ascontiguousarray(partials, np.float32).reshape(-1, 4)
+        if pa is not None and len(pa) != n: raise ValueError("texture_units: one set of partials per lookup")
+        self.L.check(self.L.L.mi_debug_texture(self.h, int(texture), _p(uv), _p(pa), n, _p(out))); return out
 
     def camera_rays(self, pos2, aperture2=None, differentials=False):
         """Sensor rays (o, mint, d, maxt) at film positions pos2.  aperture2: the aperture sample of every ray of a lens scene (None: (0.5, 0.5), the reference's default

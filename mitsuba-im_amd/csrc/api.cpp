@@ -48,6 +48,8 @@ void mi_launch_debug_camera_lens(const DScene &, const float *, const float *, u
 void mi_launch_debug_sensor_differentials(const DScene &, const RenderConst &, const Queues &, uint64_t, float *, hipStream_t);
 void mi_launch_debug_sincosf(const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_libm(int, const float *, const float *, uint64_t, float *, hipStream_t);
+void mi_launch_debug_bsdf(const DScene &, int, int, const float *, uint64_t, float *, hipStream_t);
+void mi_launch_debug_texture(const DScene &, uint32_t, const float *, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_field_film(const DScene &, const FieldArgs &, const Queues &, const BatchDesc &, float *, float *, hipStream_t);
 void mi_launch_field_samples(const DScene &, const FieldArgs &, const Queues &, uint64_t, float *, hipStream_t);
 void mi_launch_field_layout(const float *, const float *, float *, int, int, int, int, int, hipStream_t);
@@ -1431,6 +1433,49 @@ int mi_debug_libm(int fn, const float *x, const float *y, uint64_t n, float *out
     if (!x || !out || !n || fn < 0 || fn > 6 || ((fn == 2 || fn == 5) && !y)) return fail(MI_ERR_INVALID, "mi_debug_libm: bad argument");
     std::vector<float> xy(2 * n); memcpy(xy.data(), x, n * 4); if (y) memcpy(xy.data() + n, y, n * 4);
     return withBuffers(xy.data(), n * 8, out, n * 4, [&](void *i, void *o) { mi_launch_debug_libm(fn, (const float *) i, y ? (const float *) i + n : nullptr, n, (float *) o, nullptr); });
+}
+// Unit entry points over the BSDF and texture routines (kernels_units.hip).  A record whose evaluation needs a hit record is refused by name: the mask's logic is
+// inline in the shade stage, bumpmap / normalmap perturb a hit's frame, a bound texture is looked up at a hit's uv.
+static const char *unitNeedsHit(const mi::SceneHost &h, uint32_t material, int depth = 0) {
+    if (material >= h.materials.size() || depth > 4) return "a record out of range";
+    const mi_material &m = h.materials[material];
+    if (m.type == MI_BSDF_MASK) return "mask";
+    if (m.type == MI_BSDF_BUMPMAP) return "bumpmap";
+    if (m.type == MI_BSDF_NORMALMAP) return "normalmap";
+    if ((m.flags >> 8) & 0xFFFFu) return "a record with a bound texture";
+    if (m.type == MI_BSDF_COATING || m.type == MI_BSDF_ROUGHCOATING) return unitNeedsHit(h, m.distr, depth + 1);
+    if (m.type == MI_BSDF_MIXTURE) {
+        for (uint32_t i = 0; i < m.distr && i < 4; ++i) if (const char *r = unitNeedsHit(h, (uint32_t) (i < 3 ? m.reflectance[i] : m.eta[0]), depth + 1)) return r;
+    }
+    if (m.type == MI_BSDF_BLEND) {
+        for (uint32_t i = 0; i < 2; ++i) if (const char *r = unitNeedsHit(h, (uint32_t) m.eta[i], depth + 1)) return r;
+    }
+    return nullptr;
+}
+int mi_debug_bsdf(mi_scene *s, uint32_t material, int mode, const float *wi, const float *wo, const float *uv, const float *extra, uint64_t n, float *out) {
+    if (!s || !s->h.committed || !wi || !out || !n || mode < 0 || mode > 1 || (mode == 0 && (!uv || !extra)) || (mode == 1 && !wo)) return fail(MI_ERR_INVALID, "mi_debug_bsdf: bad argument");
+    if (material >= s->h.materials.size()) return fail(MI_ERR_INVALID, "mi_debug_bsdf: material " + std::to_string(material) + " of " + std::to_string(s->h.materials.size()));
+    if (const char *why = unitNeedsHit(s->h, material)) return fail(MI_ERR_UNSUPPORTED, "mi_debug_bsdf: material " + std::to_string(material) + " is or holds " + why + ", which needs a hit record");
+    HIPCHK(hipSetDevice(s->h.device));
+    std::vector<float> in(n * 9, 0.0f);
+    for (uint64_t i = 0; i < n; ++i) {
+        float *p = &in[i * 9]; memcpy(p, wi + 3 * i, 12);
+        if (wo) memcpy(p + 3, wo + 3 * i, 12);
+        if (uv) memcpy(p + 6, uv + 2 * i, 8);
+        if (extra) p[8] = extra[i];
+    }
+    const int per = mode == 0 ? 11 : 4; std::vector<float> raw(n * 12);
+    int rc = withBuffers(in.data(), n * 36, raw.data(), n * 48, [&](void *i, void *o) { mi_launch_debug_bsdf(s->h.d, (int) material, mode, (const float *) i, n, (float *) o, nullptr); });
+    if (rc) return rc;
+    for (uint64_t i = 0; i < n; ++i) memcpy(out + i * per, &raw[i * 12], per * 4);
+    return MI_OK;
+}
+int mi_debug_texture(mi_scene *s, uint32_t texture, const float *uv, const float *partials, uint64_t n, float *out) {
+    if (!s || !s->h.committed || !uv || !out || !n) return fail(MI_ERR_INVALID, "mi_debug_texture: bad argument");
+    if (texture >= s->h.textures.size() || !s->h.d.textures) return fail(MI_ERR_INVALID, "mi_debug_texture: texture " + std::to_string(texture) + " of " + std::to_string(s->h.textures.size()));
+    HIPCHK(hipSetDevice(s->h.device));
+    std::vector<float> in(n * 6, 0.0f); memcpy(in.data(), uv, n * 8); if (partials) memcpy(in.data() + n * 2, partials, n * 16);
+    return withBuffers(in.data(), n * 24, out, n * 12, [&](void *i, void *o) { mi_launch_debug_texture(s->h.d, texture, (const float *) i, partials ? (const float *) i + n * 2 : nullptr, n, (float *) o, nullptr); });
 }
 int mi_debug_camera_rays(mi_scene *s, const float *pos, uint64_t n, float *out) {
     if (!s || !s->h.committed || !pos || !out || !n) return fail(MI_ERR_INVALID, "mi_debug_camera_rays: bad argument");

@@ -102,6 +102,9 @@ def lib():
         L.orc_sample_emitter_direct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.orc_bsdf_sample.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.orc_bsdf_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_bsdf_sample_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        L.orc_texture_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+        L.orc_texture_last_info.argtypes = [C.c_void_p]
         L.orc_filter_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_sfmt_sequence.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
         L.orc_sfmt_floats.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
@@ -236,6 +239,37 @@ class Oracle:
         film = np.zeros((sc.height + 2 * b, sc.width + 2 * b, 5), np.float32); counters = np.zeros(3, np.uint64)
         lib().orc_render_image(self.h, s0, s1, y0, y1, threads, _ptr(film), _ptr(counters))
         return film, counters
+
+    # unit entry points on arrays (one C call per row)
+    def bsdf_sample_units(self, material, wi, uv, extra=None):
+        """orc_bsdf_sample_ex per row -> [n, 10] = weight rgb, pdf, wo xyz, eta, component code (0 smooth, 1 delta, 2 null), extra value drawn."""
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3); uv = np.asarray(uv, np.float32).reshape(-1, 2); n = len(wi)
+        ex = np.full(n, 0.5, np.float32) if extra is None else np.asarray(extra, np.float32).reshape(-1)
+        out = np.zeros((n, 10), np.float32); f = lib().orc_bsdf_sample_ex; h = self.h; pw = wi.ctypes.data; po = out.ctypes.data; us = uv.tolist(); es = ex.tolist()
+        for i in range(n):
+            f(h, material, pw + 12 * i, us[i][0], us[i][1], es[i], po + 40 * i)
+        return out
+
+    def bsdf_eval_units(self, material, wi, wo):
+        """orc_bsdf_eval per row -> [n, 4] = value rgb, pdf."""
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3); wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3); n = len(wi)
+        out = np.zeros((n, 4), np.float32); f = lib().orc_bsdf_eval; h = self.h; pw = wi.ctypes.data; pv = wo.ctypes.data; po = out.ctypes.data
+        for i in range(n):
+            f(h, material, pw + 12 * i, pv + 12 * i, po + 16 * i)
+        return out
+
+    TEXTURE_BRANCHES = {"nearest": 1, "bilinear": 2, "trilinear": 4, "degenerate": 8, "level_negative": 16, "ewa_clamped": 32, "ewa_unclamped": 64, "ewa_to_bilinear": 128,
+                        "level_past_pyramid": 256, "ewa_zero_denominator": 512}
+
+    def texture_units(self, texture, uv, partials=None, info=False):
+        """orc_texture_eval per row -> [n, 3]; info: also orc_texture_last_info per row -> int32 [n, 3] = branch bits (TEXTURE_BRANCHES), integer level, EWA texels."""
+        uv = np.asarray(uv, np.float32).reshape(-1, 2); n = len(uv); pa = None if partials is None else np.ascontiguousarray(partials, np.float32).reshape(-1, 4)
+        out = np.zeros((n, 3), np.float32); inf = np.zeros((n, 3), np.int32); L = lib(); f = L.orc_texture_eval; g = L.orc_texture_last_info; h = self.h
+        us = uv.tolist(); po = out.ctypes.data; pp = pa.ctypes.data if pa is not None else None; pi = inf.ctypes.data
+        for i in range(n):
+            f(h, texture, us[i][0], us[i][1], pp + 16 * i if pp is not None else None, po + 12 * i)
+            if info: g(pi + 12 * i)
+        return (out, inf) if info else out
 
     def camera_ray(self, sx, sy):
         o = np.zeros(8, np.float32); lib().orc_camera_ray(self.h, sx, sy, _ptr(o)); return o

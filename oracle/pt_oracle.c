@@ -1470,7 +1470,7 @@ static float bsdf_pdf(const orc_material *m, v3 wi, v3 wo) {
 }
 /* *delta = the sampled component is a Dirac delta (bRec.sampledType & BSDF::EDelta, path.cpp:259-260) */
 /* sp: the path's sampler, used by BSDFs with EUsesSampler (may be NULL for the unit entry point: then `extra_unit` stands in) */
-static float g_extra_unit = 0.5f;
+static float g_extra_unit = 0.5f; static int g_extra_drawn = 0;      /* orc_bsdf_sample_ex sets the value and reads back whether it was drawn */
 static v3 bsdf_sample(const orc_material *m, v3 wi, float u, float v, v3 *wo, float *pdf, float *eta, int *delta, sampler_t *sp) {
     int flipped = 0; *delta = 0;
     if ((m->flags & BSDF_FLAG_TWOSIDED) && wi.z < 0) { wi.z = -wi.z; flipped = 1; }
@@ -1480,7 +1480,7 @@ static v3 bsdf_sample(const orc_material *m, v3 wi, float u, float v, v3 *wo, fl
         case BSDF_CONDUCTOR: w = conductor_sample(m, wi, wo, pdf, eta, delta); break;
         case BSDF_DIELECTRIC: w = dielectric_sample(m, wi, u, wo, pdf, eta, delta); break;
         case BSDF_PLASTIC: w = plastic_sample(m, wi, u, v, wo, pdf, eta, delta); break;
-        case BSDF_ROUGHDIELECTRIC: w = rd_sample(m, wi, u, v, sp ? next1D(sp) : g_extra_unit, wo, pdf, eta); break;
+        case BSDF_ROUGHDIELECTRIC: w = rd_sample(m, wi, u, v, sp ? next1D(sp) : (g_extra_drawn = 1, g_extra_unit), wo, pdf, eta); break;
         case BSDF_DIFFTRANS: w = dt_sample(m, wi, u, v, wo, pdf, eta); break;
         case BSDF_ROUGHPLASTIC: w = rp_sample(m, wi, u, v, wo, pdf, eta); break;
         case BSDF_ROUGHDIFFUSE: w = roughdiffuse_sample(m, wi, u, v, wo, pdf, eta); break;
@@ -1506,6 +1506,15 @@ static v3 sm_sample(const smat_t *sm, v3 wi, float u, float v, v3 *wo, float *pd
 void orc_bsdf_sample(const orc_scene *s, uint32_t mi, const float *wi, float u, float v, float *o) {
     v3 wo = V(0, 0, 0); float pdf = 0, eta = 0; int delta; const smat_t sm = resolve_material(s, mi, NULL, 0, V(0, 0, 0), NULL, NULL); v3 w = sm_sample(&sm, V(wi[0], wi[1], wi[2]), u, v, &wo, &pdf, &eta, &delta, NULL);
     o[0] = w.x; o[1] = w.y; o[2] = w.z; o[3] = pdf; o[4] = wo.x; o[5] = wo.y; o[6] = wo.z; o[7] = eta;
+}
+/* orc_bsdf_sample with the extra sampler value (BSDF::EUsesSampler: roughdielectric) as an argument; out10 = weight rgb, pdf, wo xyz, eta, the code of the sampled
+ * component (0 smooth, 1 Dirac delta, 2 ENull) and whether the extra value was drawn.  Not reentrant (the unit entry points are called from one thread) */
+void orc_bsdf_sample_ex(const orc_scene *s, uint32_t mi, const float *wi, float u, float v, float extra, float *o) {
+    v3 wo = V(0, 0, 0); float pdf = 0, eta = 0; int delta = 0; const smat_t sm = resolve_material(s, mi, NULL, 0, V(0, 0, 0), NULL, NULL);
+    g_extra_unit = extra; g_extra_drawn = 0;
+    v3 w = sm_sample(&sm, V(wi[0], wi[1], wi[2]), u, v, &wo, &pdf, &eta, &delta, NULL);
+    g_extra_unit = 0.5f;
+    o[0] = w.x; o[1] = w.y; o[2] = w.z; o[3] = pdf; o[4] = wo.x; o[5] = wo.y; o[6] = wo.z; o[7] = eta; o[8] = (float) delta; o[9] = (float) g_extra_drawn;
 }
 void orc_bsdf_eval(const orc_scene *s, uint32_t mi, const float *wi, const float *wo, float *o) {
     const smat_t sm = resolve_material(s, mi, NULL, 0, V(0, 0, 0), NULL, NULL);
@@ -1775,6 +1784,11 @@ void orc_sample_emitter_direct(const orc_scene *s, const float *rp, const float 
 /* ---- bitmap textures: TMIPMap (include/mitsuba/render/mipmap.h): evalTexel :504-560, evalBox :562-566, evalBilinear :572-596, eval :625-705,
  * evalEWA :746-818; the pyramid itself is input data (the reference resamples with Bitmap::resample; fixtures come from oracle/_ref/harness mipmap) */
 static inline int imod(int a, int b) { int r = a % b; return r < 0 ? r + b : r; }
+/* what the last lookup of this thread did (orc_texture_last_info): the branches of mip_eval / mip_ewa as bits, the integer level, the iterations of the EWA loops.
+ * Set where the branches are taken, not classified a second time */
+enum { TEXI_NEAREST = 1, TEXI_BILINEAR = 2, TEXI_TRILINEAR = 4, TEXI_DEGENERATE = 8, TEXI_LEVEL_NEGATIVE = 16, TEXI_EWA_CLAMPED = 32, TEXI_EWA_UNCLAMPED = 64,
+       TEXI_EWA_TO_BILINEAR = 128, TEXI_LEVEL_PAST_PYRAMID = 256, TEXI_EWA_ZERO_DENOMINATOR = 512 };
+static _Thread_local struct { uint32_t branches; int32_t level; uint32_t texels; } g_tex_info;
 static v3 mip_texel(const orc_scene *s, const orc_texture *t, int level, int x, int y) {
     const uint32_t *L = &s->tex_levels[(t->first_level + (uint32_t) level) * 3]; const int w = (int) L[0], h = (int) L[1];
     if (x < 0 || x >= w) switch (t->wrap_u) {
@@ -1799,7 +1813,7 @@ static v3 mip_box(const orc_scene *s, const orc_texture *t, int level, float u, 
 }
 static v3 mip_bilinear(const orc_scene *s, const orc_texture *t, int level, float uvx, float uvy) {
     if (!isfinite(uvx) || !isfinite(uvy)) return V(0, 0, 0);
-    if (level >= (int) t->n_levels) return mip_box(s, t, (int) t->n_levels - 1, uvx, uvy);
+    if (level >= (int) t->n_levels) { g_tex_info.branches |= TEXI_LEVEL_PAST_PYRAMID; return mip_box(s, t, (int) t->n_levels - 1, uvx, uvy); }
     const uint32_t *L = &s->tex_levels[(t->first_level + (uint32_t) level) * 3];
     float u = uvx * (float) (int) L[0] - 0.5f, v = uvy * (float) (int) L[1] - 0.5f;
     int xPos = (int) floorf(u), yPos = (int) floorf(v);
@@ -1812,7 +1826,7 @@ static v3 mip_bilinear(const orc_scene *s, const orc_texture *t, int level, floa
 }
 static v3 mip_ewa(const orc_scene *s, const orc_texture *t, int level, float uvx, float uvy, float A, float B, float C) {
     if (!isfinite(A + B + C + uvx + uvy)) return V(0, 0, 0);
-    if (level >= (int) t->n_levels) return mip_box(s, t, (int) t->n_levels - 1, uvx, uvy);
+    if (level >= (int) t->n_levels) { g_tex_info.branches |= TEXI_LEVEL_PAST_PYRAMID; return mip_box(s, t, (int) t->n_levels - 1, uvx, uvy); }
     const uint32_t *L = &s->tex_levels[(t->first_level + (uint32_t) level) * 3], *L0 = &s->tex_levels[t->first_level * 3];
     float u = uvx * (float) (int) L[0] - 0.5f, v = uvy * (float) (int) L[1] - 0.5f;
     const float rx = (float) (int) L[0] / (float) (int) L0[0], ry = (float) (int) L[1] / (float) (int) L0[1];     /* m_sizeRatio[level] */
@@ -1825,6 +1839,7 @@ static v3 mip_ewa(const orc_scene *s, const orc_texture *t, int level, float uvx
         const float vv = (float) vt - v;
         float q = As * uu0 * uu0 + (Bs * uu0 + Cs * vv) * vv, dq = As * (2 * uu0 + 1) + Bs * vv;
         for (int ut = u0; ut <= u1; ++ut) {
+            ++g_tex_info.texels;
             if (q < 64.0f) {
                 uint32_t qi = (uint32_t) q;
                 if (qi < 64) { const float weight = s->mip_lut[(int) q]; result = add(result, scale(mip_texel(s, t, level, ut, vt), weight)); denominator += weight; }
@@ -1832,7 +1847,7 @@ static v3 mip_ewa(const orc_scene *s, const orc_texture *t, int level, float uvx
             q += dq; dq += ddq;
         }
     }
-    if (denominator == 0) return mip_bilinear(s, t, level, uvx, uvy);
+    if (denominator == 0) { g_tex_info.branches |= TEXI_EWA_ZERO_DENOMINATOR; return mip_bilinear(s, t, level, uvx, uvy); }
     { float r = 1.0f / denominator; return scale(result, r); }
 }
 static float hypot2f(float a, float b) {                       /* src/libcore/math.cpp:74-86 */
@@ -1844,8 +1859,8 @@ static float hypot2f(float a, float b) {                       /* src/libcore/ma
 }
 static inline float mi_log2(float v) { const float invLn2 = 1.0f / logf(2.0f); return (float) log((double) v) * invLn2; }   /* math.cpp:103-106 */
 static v3 mip_eval(const orc_scene *s, const orc_texture *t, float uvx, float uvy, float d0x, float d0y, float d1x, float d1y) {
-    if (t->filter == 0) return mip_box(s, t, 0, uvx, uvy);
-    if (t->filter == 1) return mip_bilinear(s, t, 0, uvx, uvy);
+    if (t->filter == 0) { g_tex_info.branches |= TEXI_NEAREST; return mip_box(s, t, 0, uvx, uvy); }
+    if (t->filter == 1) { g_tex_info.branches |= TEXI_BILINEAR; return mip_bilinear(s, t, 0, uvx, uvy); }
     const uint32_t *L0 = &s->tex_levels[t->first_level * 3]; const float sx = (float) (int) L0[0], sy = (float) (int) L0[1];
     float du0 = d0x * sx, dv0 = d0y * sy, du1 = d1x * sx, dv1 = d1y * sy;
     float A = dv0 * dv0 + dv1 * dv1, B = -2.0f * (du0 * dv0 + du1 * dv1), C = du0 * du0 + du1 * du1, F = A * C - B * B * 0.25f;
@@ -1853,10 +1868,12 @@ static v3 mip_eval(const orc_scene *s, const orc_texture *t, float uvx, float uv
           majorRadius = Aprime != 0 ? sqrtf(F / Aprime) : 0, minorRadius = Cprime != 0 ? sqrtf(F / Cprime) : 0;
     if (t->filter == 2 || !(minorRadius > 0) || !(majorRadius > 0) || F < 0) {
         float level = mi_log2(maxf(majorRadius, EPSILON)); int ilevel = (int) floorf(level);
-        if (ilevel < 0) return mip_bilinear(s, t, 0, uvx, uvy);
+        g_tex_info.branches |= t->filter == 2 ? TEXI_TRILINEAR : TEXI_DEGENERATE; g_tex_info.level = ilevel;
+        if (ilevel < 0) { g_tex_info.branches |= TEXI_LEVEL_NEGATIVE; return mip_bilinear(s, t, 0, uvx, uvy); }
         float a = level - (float) ilevel;
         return add(scale(mip_bilinear(s, t, ilevel, uvx, uvy), 1.0f - a), scale(mip_bilinear(s, t, ilevel + 1, uvx, uvy), a));
     }
+    g_tex_info.branches |= minorRadius * t->max_anisotropy < majorRadius ? TEXI_EWA_CLAMPED : TEXI_EWA_UNCLAMPED;
     if (minorRadius * t->max_anisotropy < majorRadius) {
         minorRadius = majorRadius / t->max_anisotropy;
         float theta = 0.5f * atanf(B / (A - C)), sinTheta = sinf(theta), cosTheta = cosf(theta);
@@ -1865,7 +1882,8 @@ static v3 mip_eval(const orc_scene *s, const orc_texture *t, float uvx, float uv
     }
     float sc = 1.0f / F; A *= sc; B *= sc; C *= sc;
     float level = maxf(0.0f, mi_log2(minorRadius)); int ilevel = (int) level; float a = level - (float) ilevel;
-    if (majorRadius < 1 || !(A > 0 && C > 0)) return mip_bilinear(s, t, ilevel, uvx, uvy);
+    g_tex_info.level = ilevel;
+    if (majorRadius < 1 || !(A > 0 && C > 0)) { g_tex_info.branches |= TEXI_EWA_TO_BILINEAR; return mip_bilinear(s, t, ilevel, uvx, uvy); }
     return add(scale(mip_ewa(s, t, ilevel, uvx, uvy, A, B, C), 1.0f - a), scale(mip_ewa(s, t, ilevel + 1, uvx, uvy, A, B, C), a));
 }
 /* Intersection::computePartials (src/librender/intersection.cpp:5-76) for a hit of the CAMERA ray (rx/ry: its differentials, common origin o) */
@@ -1909,6 +1927,15 @@ static v3 texture_eval(const orc_scene *s, const orc_texture *t, float u, float 
     }
     return first ? V(t->color0[0], t->color0[1], t->color0[2]) : V(t->color1[0], t->color1[1], t->color1[2]);
 }
+/* texture_eval of record `texture` at (u, v); partials = {dudx, dvdx, dudy, dvdy} or NULL (the lookup of every hit but the camera ray's) */
+void orc_texture_eval(const orc_scene *s, uint32_t texture, float u, float v, const float *partials, float *out3) {
+    g_tex_info.branches = 0; g_tex_info.level = 0; g_tex_info.texels = 0;
+    v3 c = texture_eval(s, &s->textures[texture], u, v, partials); out3[0] = c.x; out3[1] = c.y; out3[2] = c.z;
+}
+/* what the calling thread's last orc_texture_eval did: out[0] = the branches taken (bits: 1 nearest, 2 bilinear, 4 trilinear by filter, 8 trilinear because the footprint
+ * was degenerate, 16 level < 0, 32 EWA clamped, 64 EWA unclamped, 128 EWA falling to bilinear, 256 level past the pyramid, 512 EWA zero denominator), out[1] = the integer
+ * level, out[2] = iterations of the EWA loops (texels visited) */
+void orc_texture_last_info(int32_t *out) { out[0] = (int32_t) g_tex_info.branches; out[1] = g_tex_info.level; out[2] = (int32_t) g_tex_info.texels; }
 /* ---- mask: src/bsdfs/mask.cpp:104-229.  A material record of type 9 puts an opacity (its `reflectance`, constant or textured) in front of the nested material
  * record `distr`: eval = nested * opacity, pdf = nested * luminance(opacity); sample picks the nested BSDF with probability prob = luminance(opacity) (sample.x
  * rescaled) or passes straight through (wo = -wi, an ENull component: the path stays "unscattered").  Its component list holds EBackSide -> refN = 0. */

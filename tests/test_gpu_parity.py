@@ -531,14 +531,14 @@ def test_texture_coordinates_and_procedural_textures(mi, oracle, golden_scenes):
 def test_bitmap_textures(mi, oracle, golden_scenes):
     """`bitmap` textures: MIP pyramid as input data, EWA (anisotropic footprints on the floor, clamped anisotropy), trilinear, bilinear and
     nearest lookups, repeat / mirror / clamp / zero / one wrapping; the camera hit filters with Intersection::computePartials, later bounces read
-    level 0.  log / atan / sin / cos of the level selection come from the device math library -> tolerance-pinned."""
+    level 0.  log / atan / sin / cos of the level selection are glibc's routines restated on the device (csrc/libm_glibc.h): bit share >= 0.9999 (measured 1.0000)."""
     name = "bitmap_room"; sc = golden_scenes[name]; gs = mi.Scene(sc); orc = oracle.Oracle(sc); r = mi.Render(gs)
     gd = np.load(os.path.join(GOLDEN, name + "_samples.npz"))
     rng = np.random.default_rng(48); n = 20000
     pairs = np.stack([rng.integers(0, sc.width, n), rng.integers(0, sc.height, n), rng.integers(0, sc.spp, n)], 1).astype(np.uint32)
     ref = orc.render_samples(pairs)["li"]; got = r.samples(pairs)
     err = np.abs(got - ref).max(1) / (np.abs(ref).max(1) + 1e-6)
-    assert (err < 1e-4).mean() > 0.998 and np.median(err) < 1e-6 and (bits(got) == bits(ref)).all(1).mean() > 0.6
+    assert (err < 1e-4).mean() > 0.998 and np.median(err) < 1e-6 and bit_share(got, ref, "bitmap_textures") >= 0.9999
     got = r.samples(gd["pairs"]); err = np.abs(got - gd["li"]).max(1) / (np.abs(gd["li"]).max(1) + 1e-6)      # the reference's own Li
     assert (err < 2e-4).mean() > 0.998 and np.median(err) < 1e-6
     r.run(); film = r.read_film(0); st = r.stats(); ofilm, cnt = orc.render_image(threads=4)
@@ -957,7 +957,7 @@ def test_bsdf_adapters(mi, oracle, golden_scenes, name):
     pairs = np.stack([rng.integers(0, sc.width, n), rng.integers(0, sc.height, n), rng.integers(0, sc.spp, n)], 1).astype(np.uint32)
     ref = orc.render_samples(pairs)["li"]; got = r.samples(pairs)
     err = np.abs(got - ref).max(1) / (np.abs(ref).max(1) + 1e-6)
-    assert (bits(got) == bits(ref)).all(1).mean() > 0.6 and (err < 1e-4).mean() > 0.995 and np.median(err) < 1e-7, ((bits(got) == bits(ref)).all(1).mean(), (err < 1e-4).mean())
+    assert bit_share(got, ref, "bsdf_adapters " + name) >= 0.9999 and (err < 1e-4).mean() > 0.995 and np.median(err) < 1e-7, (err < 1e-4).mean()
     got = r.samples(gd["pairs"])
     err = np.abs(got - gd["li"]).max(1) / (np.abs(gd["li"]).max(1) + 1e-6)            # the reference as shipped (-ffast-math)
     assert (err < 1e-4).mean() > 0.99 and np.median(err) < 1e-6
