@@ -16,6 +16,10 @@ void *mi_host_create(int maxDepth, int rrDepth, int strictNormals, int hideEmitt
 void *mi_host_create_devices(int maxDepth, int rrDepth, int strictNormals, int hideEmitters, int sampler, uint32_t spp, uint64_t seed, const uint32_t *devices, uint32_t n_devices, uint32_t planes_per_batch);
 /* everything at once: `integrator` = MI_INTEGRATOR_PATH / _VOLPATH_SIMPLE / _VOLPATH (the plugin's `integrator` property), preview_interval_ms < 0 = the default (100 ms) */
 void *mi_host_create_ex(int maxDepth, int rrDepth, int strictNormals, int hideEmitters, int sampler, uint32_t spp, uint64_t seed, const uint32_t *devices, uint32_t n_devices, uint32_t planes_per_batch, int integrator, double preview_interval_ms);
+/* integrator = MI_INTEGRATOR_DIRECT: emitterSamples / bsdfSamples of direct.cpp:96-107; NULL with the reference's assertion when both are 0.
+   The host mirror keeps each count in 16 bits (mi355::Properties, integrator_host.h): at most 65535 each, NULL with "at most 65535 emitter / BSDF samples" beyond that --
+   narrower than mi_render_params, whose two fields are uint32_t */
+void *mi_host_create_direct(int strictNormals, int hideEmitters, int sampler, uint32_t spp, uint64_t seed, const uint32_t *devices, uint32_t n_devices, uint32_t planes_per_batch, uint32_t emitterSamples, uint32_t bsdfSamples, double preview_interval_ms);
 void mi_host_destroy(void *integrator);
 int mi_host_preprocess(void *integrator, mi_scene *scene);
 /* Controls = {continu, abort, interrupt}: returns 0 done, -1 *abort set, -2 *continu cleared, otherwise progress()'s non-zero value;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +15,7 @@
 #include "geometry_records.h"
 #include "queues.h"
 #include "fields.h"
+#include "direct_const.h"
 
 extern "C" {
 void mi_launch_generate(const DScene &, const RenderConst &, const Queues &, const BatchDesc &, uint32_t, hipStream_t);
@@ -34,6 +36,11 @@ void mi_launch_shadow_vol(const DScene &, const Queues &, uint32_t, hipStream_t)
 void mi_launch_shade_volmis(const DScene &, const RenderConst &, const Queues &, int, uint32_t, size_t, hipStream_t);
 void mi_launch_shadow_volmis(const DScene &, const Queues &, uint32_t, hipStream_t);
 void mi_launch_film(const DScene &, const Queues &, const BatchDesc &, float *, float *, hipStream_t);
+void mi_launch_direct_d(const DScene &, const RenderConst &, const DirectConst &, const Queues &, const BatchDesc &, int, uint32_t, size_t, hipStream_t);
+void mi_launch_direct_d_env(const DScene &, const RenderConst &, const DirectConst &, const Queues &, const BatchDesc &, int, uint32_t, size_t, hipStream_t);
+void mi_launch_direct_rc(const DScene &, const RenderConst &, const DirectConst &, const Queues &, const BatchDesc &, int, uint32_t, size_t, hipStream_t);
+void mi_launch_direct_rc_env(const DScene &, const RenderConst &, const DirectConst &, const Queues &, const BatchDesc &, int, uint32_t, size_t, hipStream_t);
+void mi_launch_direct_hit(const DScene &, const RenderConst &, const DirectConst &, const Queues &, uint32_t, hipStream_t);
 void mi_launch_env_primary(const DScene &, const RenderConst &, const Queues &, int, uint32_t, hipStream_t);
 void mi_launch_film_layout(const float *, const float *, float *, int, int, int, int, hipStream_t);
 void mi_launch_gather_samples(const Queues &, const uint32_t *, uint64_t, float *, hipStream_t);
@@ -79,6 +86,8 @@ static bool mi_launch_shade(const DScene &scIn, bool ldsTables, const RenderCons
     else (env ? mi_launch_shade_rc_env : mi_launch_shade_rc)(sc, rcl, q, buf, grid, lds, st);
     return rcl.order_offset_words != 0 && q.cap <= 0xFFFFu;      // shade.h doSort: the segments were read through the class-sorted order list
 }
+// volpath_simple / volpath: the integrators whose stages walk media (kernels_vol.hip, kernels_volmis.hip); path and direct share the pool layout and the traversal stages
+static inline bool isVolumetric(uint32_t integrator) { return integrator == MI_INTEGRATOR_VOLPATH_SIMPLE || integrator == MI_INTEGRATOR_VOLPATH; }
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(MI_ERR_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
@@ -112,6 +121,8 @@ struct mi_render {
     // field kernel of the batch last traced on that pool has finished (chains consecutive batches across the streams, as filmDone chains k_film); lastFieldPool: pool of the previous batch of this run
     uint32_t nFields = 0; mi_field fields[MI_MAX_FIELDS] = {}; FieldArgs fa{}; float *fieldFilm = nullptr, *fieldSpill = nullptr, *fieldTmp = nullptr; size_t fieldFloats = 0; int32_t *dTriShape = nullptr;
     hipEvent_t fieldDone[kMaxPools] = {}; int lastFieldPool = -1; bool fieldChain = false;
+    // direct integrator (direct.h): its constants, and per pool the hit array (+ instance indices) of the BSDF rays in buffer 1 -- Queues::hit keeps the camera hits for the whole batch
+    DirectConst dc{}; float4 *hitB[kMaxPools] = {}; int32_t *hitInstB[kMaxPools] = {};
     uint64_t sceneRev = 0, filmRev = 0;   // scene revision `sc` was copied from / the samples in the film (and the field film) were traced at
     Queues &pool(int i) { return i ? qx[i - 1] : q; }
     hipStream_t poolStream(int i) { return i ? streamx[i - 1] : stream; }
@@ -696,7 +707,7 @@ static int beginRun(mi_render *r, RunGuard &g, bool film, const char *who) {
     if (film && (r->samplesTotal || r->mergedSamples) && r->filmRev != s->h.revision)
         return fail(MI_ERR_INVALID, std::string(who) + ": the film holds samples of the scene before its last update; call mi_render_clear first");
     if (r->sceneRev != s->h.revision) {
-        r->sc = s->h.d; if (r->rc.integrator != MI_INTEGRATOR_PATH) r->sc.packet_n = 0;
+        r->sc = s->h.d; if (isVolumetric(r->rc.integrator)) r->sc.packet_n = 0;
         r->rc.alpha_dist = alphaDistOf(s->h);
         if (r->nFields) (void) worldToCamera(s->h, r->fa.w2c);
         r->sceneRev = s->h.revision;
@@ -720,7 +731,7 @@ extern "C" int mi_debug_pool_shape(uint64_t paths, int hasRC, uint32_t integrato
     const mi_pool_overrides none{}; if (!ov) ov = &none;
     uint64_t grid = ov->segments ? ov->segments : hasRC ? std::min<uint64_t>(std::max<uint64_t>(16384u, paths / 1024u), 1u << 18) : 16384u;
     const uint64_t minGrid = (paths + 63) / 64; if (grid > minGrid) grid = std::max<uint64_t>(minGrid, 1);
-    if (integrator != MI_INTEGRATOR_PATH && (paths + grid - 1) / grid > 65472u) grid = (paths + 65471u) / 65472u;      // the volumetric stages count two kinds of shadow records per segment in 16 bits each
+    if (isVolumetric(integrator) && (paths + grid - 1) / grid > 65472u) grid = (paths + 65471u) / 65472u;      // the volumetric stages count two kinds of shadow records per segment in 16 bits each
     uint64_t cap = (paths + grid - 1) / grid; cap = (cap + 63) / 64 * 64;
     if (cap * grid >= (1ull << 28)) return fail(MI_ERR_INVALID, "mi_render_run: a path pool holds fewer than 2^28 slots (the stages address the queues through 32-bit byte offsets); lower planes_per_batch");
     out->n_seg = (uint32_t) grid; out->cap = (uint32_t) cap;
@@ -753,9 +764,13 @@ static int allocPoolQ(mi_render *r, uint64_t paths, Queues &Q, std::vector<void 
     }
     if (r->scene->h.d.n_instances) ALLOC(Q.hitInst, int32_t, slots); else Q.hitInst = nullptr;
     // shadow records: 48 B; the volumetric integrators add throughput and BSDF / phase value (80 B); volpath leaves up to two records per path and pass (kernels_volmis.hip)
-    const uint64_t shSlots = r->rc.integrator != MI_INTEGRATOR_PATH ? slots * 2 : slots;
+    const uint64_t shSlots = isVolumetric(r->rc.integrator) ? slots * 2 : slots;
     ALLOC(Q.hit, float4, slots); ALLOC(Q.shO, float4, shSlots); ALLOC(Q.shD, float4, shSlots); ALLOC(Q.shC, float4, shSlots);
-    if (r->rc.integrator != MI_INTEGRATOR_PATH) { ALLOC(Q.shT, float4, shSlots); ALLOC(Q.shX, float4, shSlots); } else { Q.shT = nullptr; Q.shX = nullptr; }
+    if (isVolumetric(r->rc.integrator)) { ALLOC(Q.shT, float4, shSlots); ALLOC(Q.shX, float4, shSlots); } else { Q.shT = nullptr; Q.shX = nullptr; }
+    if (r->rc.integrator == MI_INTEGRATOR_DIRECT) {      // the BSDF rays of a pass are extended into a hit array of their own (direct.h)
+        const int pi = &Q == &r->q ? 0 : (int) (&Q - r->qx) + 1;
+        ALLOC(r->hitB[pi], float4, slots); if (r->scene->h.d.n_instances) ALLOC(r->hitInstB[pi], int32_t, slots); else r->hitInstB[pi] = nullptr;
+    }
     ALLOC(Q.acc, float4, slots); ALLOC(Q.pos, float2, slots); ALLOC(Q.shCount, uint32_t, grid);
     ALLOC(Q.counters, unsigned long long, 4);
     ALLOC(Q.ticket, uint32_t, MI_TICKETS);
@@ -799,9 +814,38 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
     if (p->max_depth <= 0 && p->max_depth != -1) return fail(MI_ERR_INVALID, "'maxDepth' must be set to -1 (infinite) or a value greater than zero!");   // :224-225
     if (p->max_depth > 250) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: maxDepth > 250");
     if (p->sampler > 1) return fail(MI_ERR_INVALID, "mi_render_create: unknown sampler");
-    if (p->integrator != MI_INTEGRATOR_PATH && (s->h.d.has_adapters & 4u)) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: `coating`, `roughcoating` and `blendbsdf` are implemented for the path integrator only");
-    if (p->integrator > MI_INTEGRATOR_VOLPATH) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: integrators path (0), volpath_simple (1) and volpath (2) are implemented");
-    const bool vol = p->integrator != MI_INTEGRATOR_PATH;
+    if (isVolumetric(p->integrator) && (s->h.d.has_adapters & 4u)) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: `coating`, `roughcoating` and `blendbsdf` are implemented for the path integrator only");
+    if (p->integrator > MI_INTEGRATOR_DIRECT) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: integrators path (0), volpath_simple (1), volpath (2) and direct (3) are implemented");
+    const bool vol = isVolumetric(p->integrator), direct = p->integrator == MI_INTEGRATOR_DIRECT;
+    DirectConst dc{}; uint32_t directDims = 0, directFrames = 0;      // Sobol' dimensions / look_up frames a direct render can touch
+    if (direct) {      // MIDirectIntegrator (direct.cpp:93-144); what its kernels (direct.h) are not built for is refused by name
+        if (s->h.d.has_adapters & 1u) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the direct integrator does not implement `mixturebsdf`, `bumpmap`, `normalmap`, `coating`, `roughcoating` and `blendbsdf` (use the path integrator with maxDepth = 2)");
+        if (!s->h.media.empty()) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the direct integrator does not support participating media (direct.cpp:181-182)");
+        for (const mi_material &m : s->h.materials) if (m.type == MI_BSDF_NULL) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the direct integrator does not support `null` boundaries (index-matched medium transitions, direct.cpp:181-182)");
+        const uint32_t N = p->emitter_samples, M = p->bsdf_samples;
+        if (N == 0 && M == 0) return fail(MI_ERR_INVALID, "Assertion 'm_emitterSamples + m_bsdfSamples > 0' failed: emitterSamples and bsdfSamples must not both be 0");      // direct.cpp:107
+        const uint32_t S = std::max(std::max(N, M), 1u);
+        if ((uint64_t) std::max(p->spp, 1u) * S > (1ull << 22)) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: direct integrator: spp x max(emitterSamples, bsdfSamples) beyond 2^22 (the sample arrays number their Sobol' points m x S + j in 32 bits, and the look_up tables hold one entry per point)");
+        dc.n_em = N; dc.n_bs = M; dc.weight_lum = 1.0f / (float) N; dc.weight_bsdf = 1.0f / (float) M; dc.frac_lum = (float) N / (float) (N + M); dc.frac_bsdf = (float) M / (float) (N + M);
+        const bool lens = s->h.lensRadius != 0.0f;
+        if (p->sampler == MI_SAMPLER_SOBOL) {      // sobol.cpp:171-250: arrays from dimension 5, two each, emitter side first; next2D / next1D skip the reserved range
+            const uint32_t arrays = (N > 1 ? 1u : 0u) + (M > 1 ? 1u : 0u), arrayEnd = 5u + 2u * arrays; uint32_t dim = lens ? 4u : 2u;
+            auto own2D = [&]() { if (dim + 1 >= 5u && dim < arrayEnd) dim = arrayEnd; const uint32_t d0 = dim; dim += 2; return d0; };
+            if (N > 1) dc.em_array = 5u; else dc.em_dim = own2D();
+            if (M > 1) dc.bs_array = 5u + (N > 1 ? 2u : 0u); else dc.bs_dim = own2D();
+            dc.extra_dim = dim; dc.array_end = arrayEnd;
+            bool usesSampler = false; for (const mi_material &m : s->h.materials) if (m.type == MI_BSDF_ROUGHDIELECTRIC) usesSampler = true;
+            if (usesSampler) for (uint32_t j = 0; j < std::max(M, 1u); ++j) { if (dim >= 5u && dim < arrayEnd) dim = arrayEnd; ++dim; }      // one next1D per BSDF sub-sample at the most
+            directDims = std::max(dim, arrayEnd); directFrames = std::max(p->spp, 1u) * (arrays ? S : 1u);
+            if (arrays && s->h.logRes < 1) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: direct integrator: Sobol' sample arrays need a film of at least 2 x 2 pixels (sobol::look_up of a 1 x 1 film reads outside its tables)");
+        } else {      // the build-defined stream: own requests and EUsesSampler draws count upwards as in `path`, array elements downwards from call 255
+            uint32_t c = lens ? 2u : 1u, top = 256u;
+            if (N > 1) { dc.em_array = top - 1u; top -= N; } else dc.em_dim = c++;
+            if (M > 1) { dc.bs_array = top - 1u; top -= M; } else dc.bs_dim = c++;
+            dc.extra_dim = c; dc.array_end = 0;
+            if ((uint64_t) c + M > top || N > 255u || M > 255u) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: direct integrator: the independent sampler stream numbers 256 draws per sample; emitterSamples + 2 x bsdfSamples + the camera's draws exceed that (use the Sobol sampler or fewer shading samples)");
+        }
+    }
     if (vol) {       // what the volumetric stages (kernels_vol.hip) are built for
         // a bumpmap / normalmap over a `null` / `thindielectric` has an ENull lobe the transmittance walks would have to evaluate in a perturbed frame (the reference reads an unset shading frame there); plain records, `mask` and `mixturebsdf` are seen through (surfaceNullEval)
         auto nullLobe = [&](uint32_t i) { return i < s->h.materials.size() && (s->h.materials[i].type == MI_BSDF_NULL || s->h.materials[i].type == MI_BSDF_THINDIELECTRIC); };
@@ -824,12 +868,16 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         if (vol) perBounce += 2;      // + the one or two draws of HomogeneousMedium::sampleDistance per iteration
         const int lensDims = s->h.lensRadius != 0.0f ? 2 : 0;      // the aperture sample: dimensions 2 / 3 (k_generate), every later draw moves by two
         if (lensDims && (uint32_t) (3 + lensDims) > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! The thin lens draws Sobol dimensions 2 and 3.");
+        if (direct) {      // maxDepth plays no part: the dimensions of direct.cpp's requests (computed above)
+            if (directDims > s->h.d.sobol_dims || directDims > 256u) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! You may have to reduce 'bsdfSamples' (a roughdielectric draws one more dimension per BSDF sample).");
+        } else {
         if (p->max_depth > 0 && (uint32_t) (3 + lensDims + perBounce * depth) > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! You may have to reduce the 'maxDepth' parameter of your integrator.");
         if (p->max_depth < 0) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: maxDepth = -1 with the Sobol sampler needs more dimensions than are loaded");
         // the state word st0.w carries the dimension in 8 bits: with the shipped 128-dimension tables the bound above is the tighter one, larger caller-supplied tables end here
         if (p->max_depth > 0 && 3 + lensDims + perBounce * depth > 256) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the path state numbers a path's Sobol dimensions with 8 bits; maxDepth x draws per bounce exceeds 256 (reduce maxDepth)");
+        }
     }
-    if (p->sampler == MI_SAMPLER_INDEPENDENT && p->max_depth > 0) {
+    if (p->sampler == MI_SAMPLER_INDEPENDENT && p->max_depth > 0 && !direct) {
         // the build-defined independent stream numbers a path's draws with 8 bits: a path that could draw more than 256 values would re-read
         // its own stream from call 0 -- refused by name rather than silently correlated (unbounded depth keeps the documented period)
         int perBounce = 5; for (const mi_material &m : s->h.materials) if (m.type == MI_BSDF_ROUGHDIELECTRIC) perBounce = 6;
@@ -837,7 +885,9 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         if (2 + (s->h.lensRadius != 0.0f ? 2 : 0) + perBounce * p->max_depth > 256) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the independent sampler stream numbers 256 draws per path; maxDepth x draws per bounce exceeds that (use the Sobol sampler or a smaller maxDepth)");
     }
     HIPCHK(hipSetDevice(s->h.device));
-    mi_render *r = new mi_render(); r->scene = s; r->p = *p;
+    mi_render *r = new mi_render(); r->scene = s;
+    memcpy(&r->p, p, offsetof(mi_render_params, emitter_samples));      // the two trailing fields exist in a caller's struct only where it asks for the direct integrator
+    if (direct) { r->p.emitter_samples = p->emitter_samples; r->p.bsdf_samples = p->bsdf_samples; r->dc = dc; }
     r->sc = s->h.d; r->sceneRev = r->filmRev = s->h.revision; if (vol) r->sc.packet_n = 0;      // packet or tree is decided per render: volpath / volpath_simple on a <= 64-triangle scene without media walk its tree
     struct Guard { mi_render *r; ~Guard() { if (r) mi_render_destroy(r); } } guard{r};      // every early return below releases what was created so far
     r->rc.max_depth = p->max_depth; r->rc.rr_depth = p->rr_depth; r->rc.strict_normals = p->strict_normals; r->rc.hide_emitters = p->hide_emitters; r->rc.opacity = p->opacity;
@@ -861,9 +911,9 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         // fold the direction matrices into 4-bit lookup tables for the dimensions / index bits this render can touch
         int perBounceDims = 5; for (const mi_material &m : s->h.materials) if (m.type == MI_BSDF_ROUGHDIELECTRIC) perBounceDims = 6;
         if (vol) perBounceDims += 2;
-        uint32_t sppBits = 0; while ((1ull << sppBits) < p->spp) ++sppBits;
+        uint32_t sppBits = 0; while ((1ull << sppBits) < (direct ? directFrames : p->spp)) ++sppBits;      // (direct: the array elements' frames m x S + j)
         const uint32_t bits = (s->h.logRes > 1 ? 2 * s->h.logRes : 0) + sppBits + 1;
-        const uint32_t nibs = std::max<uint32_t>(8, (bits + 3) / 4), dims      /* at least the eight nibbles of the low index word (pt_device.h sobolBitsNib unrolls them) */ = std::min<uint32_t>(s->h.d.sobol_dims, (uint32_t) (4 + (s->h.lensRadius != 0.0f ? 2 : 0) + perBounceDims * p->max_depth));
+        const uint32_t nibs = std::max<uint32_t>(8, (bits + 3) / 4), dims      /* at least the eight nibbles of the low index word (pt_device.h sobolBitsNib unrolls them) */ = std::min<uint32_t>(s->h.d.sobol_dims, direct ? std::max(directDims, 4u) : (uint32_t) (4 + (s->h.lensRadius != 0.0f ? 2 : 0) + perBounceDims * p->max_depth));
         std::vector<uint32_t> nib((size_t) dims * nibs * 16);
         for (uint32_t dmn = 0; dmn < dims; ++dmn) for (uint32_t n = 0; n < nibs; ++n) for (uint32_t v = 0; v < 16; ++v) {
             uint32_t x = 0; for (uint32_t b = 0; b < 4; ++b) if (((v >> b) & 1u) && 4 * n + b < MI_SOBOL_SIZE) x ^= g_sobolM32[(size_t) dmn * MI_SOBOL_SIZE + 4 * n + b];
@@ -878,11 +928,11 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         // into the sample afterwards (k_generate), so the tables do not depend on it.
         const uint32_t m = s->h.logRes;
         if (m > 1) {
-            if (2 * m + sppBits > 52 || p->spp > (1u << 22)) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: Sobol index beyond 52 bits (film resolution x sample count)");
+            if (2 * m + sppBits > 52 || p->spp > (1u << 22) || (direct && directFrames > (1u << 22))) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: Sobol index beyond 52 bits (film resolution x sample count)");
             const uint64_t *vdc = g_sobolVdc.data() + (size_t) (m - 1) * MI_SOBOL_SIZE, *vdi = g_sobolVdcInv.data() + (size_t) (m - 1) * MI_SOBOL_SIZE;
             auto mulVec = [&](const uint64_t *cols, uint64_t b) { uint64_t x = 0; for (uint32_t c = 0; b; b >>= 1, ++c) if (b & 1) x ^= cols[c]; return x; };
             auto dimBits = [&](uint32_t dmn, uint64_t index) { uint32_t x = 0; for (uint32_t c = 0; index; index >>= 1, ++c) if (index & 1) x ^= g_sobolM32[(size_t) dmn * MI_SOBOL_SIZE + c]; return x; };
-            const size_t res = (size_t) 1 << m, nF = std::max<uint32_t>(p->spp, 1u);
+            const size_t res = (size_t) 1 << m, nF = direct ? directFrames : std::max<uint32_t>(p->spp, 1u);
             std::vector<uint32_t> tab((nF + 2 * res) * 4);
             auto put = [&](size_t e, uint64_t idx) { tab[e * 4] = (uint32_t) idx; tab[e * 4 + 1] = (uint32_t) (idx >> 32); tab[e * 4 + 2] = dimBits(0, idx); tab[e * 4 + 3] = dimBits(1, idx); };
             for (size_t f = 0; f < nF; ++f) put(f, ((uint64_t) f << (2 * m)) ^ mulVec(vdi, mulVec(vdc, f)));
@@ -983,10 +1033,56 @@ static void mark(mi_render *r, int tag, size_t &used, hipStream_t st = nullptr) 
     (void) hipEventRecord(r->evPool[used], r->stream); r->evTag[used] = tag; ++used;
 }
 
+// One pass of the direct integrator over the camera-hit queue (direct.h): emitter sub-sample j (bsdfPass = 0) or BSDF sub-sample j.  Dynamic LDS as mi_launch_shade,
+// without the order list (a pass runs one half of the shade stage's code; its segments are read in queue order).
+static void launchDirectPass(mi_render *r, const Queues &q, const BatchDesc &bd, int bsdfPass, uint32_t j, hipStream_t st) {
+    DScene sc = r->sc; sc.small_tables = r->ldsTables ? 1u : 0u;
+    size_t lds = r->rc.sampler == 1 ? (size_t) r->rc.nib_dims * r->rc.nib_count * 64 : 16;
+    if (sc.small_tables) lds += 16 + 4 * ((size_t) sc.n_tris * (4 * MI_SHADE_WORDS) + sc.n_materials * 16 + sc.n_emitters * 12 + ((sc.n_emitters + 4) & ~3u) + sc.area_cdf_len);
+    DirectConst dc = r->dc; dc.pass = j; const bool env = sc.env_index >= 0;
+    if (!sc.has_roughconductor) (env ? mi_launch_direct_d_env : mi_launch_direct_d)(sc, r->rc, dc, q, bd, bsdfPass, r->gridShade, lds, st);
+    else (env ? mi_launch_direct_rc_env : mi_launch_direct_rc)(sc, r->rc, dc, q, bd, bsdfPass, r->gridShade, lds, st);
+}
+// trace one batch of the direct integrator: one camera hit, then N emitter passes and M BSDF passes over it (direct.h; direct.cpp:146-309)
+static int traceBatchDirect(mi_render *r, const BatchDesc &bd, size_t &evUsed, int pool) {
+    const DScene &sc = r->sc; hipStream_t st = r->poolStream(pool); Queues &Q = r->pool(pool);
+    Queues QB = Q; QB.hit = r->hitB[pool]; QB.hitInst = r->hitInstB[pool];      // the BSDF rays' view of the pool: buffer 1 with a hit array of its own
+    mark(r, 0, evUsed, st);
+    const bool fused = mi_fused_walk(sc); uint32_t ticket = 2;      // every fused traversal launch of the batch takes a zeroed ticket word; beyond MI_TICKETS launches the while-while kernels
+    if (fused) HIPCHK(hipMemsetAsync(Q.ticket, 0, MI_TICKETS * sizeof(uint32_t), st));
+    mi_launch_generate(sc, r->rc, Q, bd, r->grid, st);
+    mark(r, 1, evUsed, st);
+    if (fused) mi_launch_extend_fused(sc, Q, 0, Q.ticket + ticket++, st); else mi_launch_extend(sc, Q, 0, r->gridExtend, st);
+    ++r->launchesAll;
+    if (r->nFields && !bd.list) {      // field channels of the film samples, as in traceBatch
+        mark(r, 0, evUsed, st);
+        if (r->fieldChain && r->lastFieldPool >= 0 && r->lastFieldPool != pool) HIPCHK(hipStreamWaitEvent(st, r->fieldDone[r->lastFieldPool], 0));
+        mi_launch_field_film(sc, r->fa, Q, bd, r->fieldFilm, r->fieldSpill, st);
+        if (r->fieldChain) { HIPCHK(hipEventRecord(r->fieldDone[pool], st)); r->lastFieldPool = pool; }
+    }
+    if (sc.env_texture && !r->rc.hide_emitters) mi_launch_env_primary(sc, r->rc, Q, 0, r->gridExtend, st);
+    const uint32_t N = r->dc.n_em, M = r->dc.n_bs;
+    for (uint32_t j = 0; j < std::max(N, 1u); ++j) {      // (N = 0: one launch for Le, the environment and the alpha rule)
+        mark(r, 2, evUsed, st); launchDirectPass(r, Q, bd, 0, j, st);
+        if (N) { mark(r, 3, evUsed, st); if (fused && ticket < MI_TICKETS) mi_launch_shadow_fused(sc, Q, Q.ticket + ticket++, st); else mi_launch_shadow(sc, Q, r->gridShadow, st); }
+    }
+    for (uint32_t j = 0; j < M; ++j) {
+        mark(r, 2, evUsed, st); launchDirectPass(r, Q, bd, 1, j, st);
+        mark(r, 1, evUsed, st);
+        if (fused && ticket < MI_TICKETS) mi_launch_extend_fused(sc, QB, 1, Q.ticket + ticket++, st); else mi_launch_extend(sc, QB, 1, r->gridExtend, st);
+        ++r->launchesAll;
+        mark(r, 2, evUsed, st); mi_launch_direct_hit(sc, r->rc, r->dc, QB, r->gridExtend, st);
+    }
+    mark(r, 0, evUsed, st);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
+
 // trace one batch: paths = tile pixels x planes (or an explicit list), all bounces
 static int traceBatch(mi_render *r, const BatchDesc &bd, const uint32_t *list, size_t &evUsed, int pool = 0) {
     const DScene &sc = r->sc; hipStream_t st = r->poolStream(pool); Queues &Q = r->pool(pool);
     (void) list;
+    if (r->rc.integrator == MI_INTEGRATOR_DIRECT) return traceBatchDirect(r, bd, evUsed, pool);
     mark(r, 0, evUsed, st);
     const bool fused = r->rc.integrator == MI_INTEGRATOR_PATH && mi_fused_walk(sc);      // trace_fused.h: persistent waves fetch segments through per-launch tickets
     if (fused) HIPCHK(hipMemsetAsync(Q.ticket, 0, MI_TICKETS * sizeof(uint32_t), st));
@@ -1275,7 +1371,7 @@ int mi_render_field_samples(mi_render *r, const uint32_t *pairs, uint64_t n, flo
     hipError_t e = hipMemcpy(dList, pairs, n * 12, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(keep, Q.counters, 32, hipMemcpyDeviceToHost);      // like mi_render_samples, the parity entry point leaves the ray counters untouched
     if (e == hipSuccess) {
-        const bool fused = r->rc.integrator == MI_INTEGRATOR_PATH && mi_fused_walk(sc);
+        const bool fused = !isVolumetric(r->rc.integrator) && mi_fused_walk(sc);
         if (fused) e = hipMemsetAsync(Q.ticket, 0, MI_TICKETS * sizeof(uint32_t), st);
         if (e == hipSuccess) {
             mi_launch_generate(sc, r->rc, Q, bd, r->grid, st);

@@ -36,6 +36,8 @@ MIPathTracerHIP::MIPathTracerHIP(const Properties &props) : m_props(props) {
     if (m_props.rrDepth <= 0) throw std::runtime_error("'rrDepth' must be set to a value greater than zero!");                          // integrator.cpp:221-222
     if (m_props.maxDepth <= 0 && m_props.maxDepth != -1)
         throw std::runtime_error("'maxDepth' must be set to -1 (infinite) or a value greater than zero!");                            // integrator.cpp:224-225
+    if (m_props.integrator == MI_INTEGRATOR_DIRECT && m_props.emitterSamples + m_props.bsdfSamples == 0)
+        throw std::runtime_error("Assertion 'm_emitterSamples + m_bsdfSamples > 0' failed");                                          // direct.cpp:107
 }
 MIPathTracerHIP::~MIPathTracerHIP() { releaseReplicas(); if (m_render) mi_render_destroy(m_render); }
 void MIPathTracerHIP::releaseReplicas() {
@@ -52,7 +54,7 @@ bool MIPathTracerHIP::preprocess(mi_scene *scene) {
     mi_render_params p{};
     p.max_depth = m_props.maxDepth; p.rr_depth = m_props.rrDepth; p.strict_normals = m_props.strictNormals; p.hide_emitters = m_props.hideEmitters;
     p.sampler = (uint32_t) m_props.sampler; p.spp = m_props.sampleCount; p.seed = m_props.seed; p.device = m_props.device; p.planes_per_batch = m_props.planesPerBatch; p.opacity = m_props.opacity ? 1 : 0;
-    p.integrator = (uint32_t) m_props.integrator;
+    p.integrator = (uint32_t) m_props.integrator; p.emitter_samples = m_props.emitterSamples; p.bsdf_samples = m_props.bsdfSamples;
     check(mi_render_create(scene, &p, &m_render), "MIPathTracerHIP::preprocess");
     // `devices`: every further entry gets a replica of the scene and a render handle of its own; film rows are interleaved over the replicas
     for (size_t i = 1; i < m_props.devices.size(); ++i) {
@@ -181,6 +183,17 @@ void *mi_host_create_ex(int maxDepth, int rrDepth, int strictNormals, int hideEm
     try {
         mi355::Properties pr; pr.maxDepth = maxDepth; pr.rrDepth = rrDepth; pr.strictNormals = strictNormals != 0; pr.hideEmitters = hideEmitters != 0;
         pr.sampler = sampler; pr.sampleCount = spp; pr.seed = seed; pr.planesPerBatch = planes; pr.integrator = integrator; if (previewIntervalMs >= 0) pr.previewIntervalMs = previewIntervalMs;
+        if (devices && nDevices) { pr.devices.assign(devices, devices + nDevices); pr.device = devices[0]; }
+        return new mi355::MIPathTracerHIP(pr);
+    } catch (const std::exception &e) { g_hostErr = e.what(); return nullptr; }
+}
+void *mi_host_create_direct(int strictNormals, int hideEmitters, int sampler, uint32_t spp, uint64_t seed, const uint32_t *devices, uint32_t nDevices, uint32_t planes, uint32_t emitterSamples, uint32_t bsdfSamples, double previewIntervalMs) {
+    try {
+        mi355::Properties pr; pr.strictNormals = strictNormals != 0; pr.hideEmitters = hideEmitters != 0;
+        pr.sampler = sampler; pr.sampleCount = spp; pr.seed = seed; pr.planesPerBatch = planes; pr.integrator = MI_INTEGRATOR_DIRECT;
+        if (emitterSamples > 0xFFFFu || bsdfSamples > 0xFFFFu) throw std::runtime_error("mi_host_create_direct: at most 65535 emitter / BSDF samples");
+        pr.emitterSamples = (uint16_t) emitterSamples; pr.bsdfSamples = (uint16_t) bsdfSamples;
+        if (previewIntervalMs >= 0) pr.previewIntervalMs = previewIntervalMs;
         if (devices && nDevices) { pr.devices.assign(devices, devices + nDevices); pr.device = devices[0]; }
         return new mi355::MIPathTracerHIP(pr);
     } catch (const std::exception &e) { g_hostErr = e.what(); return nullptr; }

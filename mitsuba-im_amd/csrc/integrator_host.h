@@ -30,6 +30,10 @@ struct Properties {                 // the subset of mitsuba::Properties this in
     int integrator = MI_INTEGRATOR_PATH;   // build-specific: MI_INTEGRATOR_VOLPATH_SIMPLE / MI_INTEGRATOR_VOLPATH = the loops of volpath_simple / volpath over the scene's participating media
     double previewIntervalMs = 100.0;   // build-specific: the responsive face copies the film into its target at most this often between submissions (always after the last one); 0 = after every submission
     bool opacity = true;   // RadianceQueryRecord::EOpacity: the responsive drivers always request it (integrator.cpp:474)
+    // integrator = MI_INTEGRATOR_DIRECT only: MIDirectIntegrator's properties (direct.cpp:96-107; `shadingSamples` sets both, default 1).  They sit in what was the tail padding of
+    // this record (16 bits each, at most 65535): its size and the offset of every earlier field stay as they were, so a path_hip.so built against the earlier header keeps working
+    // with this library (it never asks for `direct`, the only case in which the two are read)
+    uint16_t emitterSamples = 1, bsdfSamples = 1;
 };
 
 class Interrupt;
@@ -75,5 +79,7 @@ private:
     struct Workers; std::unique_ptr<Workers> m_workers;   // one persistent host thread per replica (multi-device renders)
     std::atomic<int> m_cancel{0};   // set by cancel(), reset at the start of render(): a cancel between two batches or two mi_render_run calls is never lost
 };
+
+static_assert(sizeof(Properties) == 88, "mi355::Properties is part of the plugin boundary: append within the tail padding or version the constructor");
 
 }  // namespace mi355
