@@ -50,6 +50,7 @@ typedef struct { float sigma_a[3], sigma_s[3]; uint32_t strategy; float sampling
 #define MI_INTEGRATOR_VOLPATH_SIMPLE 1  /* SimpleVolumetricPathTracer, src/integrators/path/volpath_simple.cpp */
 #define MI_INTEGRATOR_VOLPATH 2         /* VolumetricPathTracer, src/integrators/path/volpath.cpp: multiple importance sampling, emitters found through index-matched boundaries */
 #define MI_INTEGRATOR_DIRECT 3          /* MIDirectIntegrator, src/integrators/direct/direct.cpp: one camera hit, emitter_samples emitter + bsdf_samples BSDF samples, power heuristic */
+#define MI_INTEGRATOR_AO 4              /* AmbientOcclusionIntegrator, src/integrators/direct/ao.cpp: one camera hit, shading_samples cosine-distributed any-hit rays of length ray_length */
 
 #define MI_BSDF_DIFFUSE 0         /* src/bsdfs/diffuse.cpp: reflectance                                                              */
 #define MI_BSDF_ROUGHCONDUCTOR 1  /* src/bsdfs/roughconductor.cpp + microfacet.h: alpha (alphaU), distr, eta, k, specular; flags: sampleVisible, anisotropic */
@@ -150,9 +151,12 @@ typedef struct {
                                     the responsive drivers and films with an alpha channel); 0: alpha = 1 (classic film without alpha, integrator.cpp:160-161) */
     uint32_t integrator;         /* MI_INTEGRATOR_PATH (0, default), MI_INTEGRATOR_VOLPATH_SIMPLE or MI_INTEGRATOR_VOLPATH: the same loop over participating media (mi_scene_set_media);
                                     MI_INTEGRATOR_DIRECT: direct illumination (no media, no mixturebsdf / bumpmap / normalmap / coating / roughcoating / blendbsdf / null records; max_depth and
-                                    rr_depth are validated and otherwise ignored); anything else: MI_ERR_UNSUPPORTED.  (Round 1 had `fast_math` here; one set of kernels ships: strict IEEE arithmetic) */
+                                    rr_depth are validated and otherwise ignored); MI_INTEGRATOR_AO: ambient occlusion (reads no BSDF, emitter or medium: every scene is accepted; max_depth, rr_depth, strict_normals
+                                    and hide_emitters play no part); anything else: MI_ERR_UNSUPPORTED.  (Round 1 had `fast_math` here; one set of kernels ships: strict IEEE arithmetic) */
     uint32_t emitter_samples;    /* MI_INTEGRATOR_DIRECT only (not read otherwise: callers of the other integrators may pass the struct without these two fields): */
     uint32_t bsdf_samples;       /* `emitterSamples` / `bsdfSamples` of direct.cpp:96-107 (`shadingSamples` sets both); either may be 0, not both */
+    uint32_t shading_samples;    /* MI_INTEGRATOR_AO only (not read otherwise: callers of the other integrators may pass the struct without these two fields): */
+    float ray_length;            /* `shadingSamples` (>= 1) / `rayLength` of ao.cpp:72-80; ray_length < 0: automatic, half the radius of the scene's bounding sphere */
 } mi_render_params;
 
 typedef struct { uint32_t x0, y0, x1, y1; } mi_tile;   /* pixel rectangle [x0,x1) x [y0,y1) in GLOBAL film coordinates */

@@ -20,6 +20,9 @@ void *mi_host_create_ex(int maxDepth, int rrDepth, int strictNormals, int hideEm
    The host mirror keeps each count in 16 bits (mi355::Properties, integrator_host.h): at most 65535 each, NULL with "at most 65535 emitter / BSDF samples" beyond that --
    narrower than mi_render_params, whose two fields are uint32_t */
 void *mi_host_create_direct(int strictNormals, int hideEmitters, int sampler, uint32_t spp, uint64_t seed, const uint32_t *devices, uint32_t n_devices, uint32_t planes_per_batch, uint32_t emitterSamples, uint32_t bsdfSamples, double preview_interval_ms);
+/* integrator = MI_INTEGRATOR_AO: shadingSamples / rayLength of ao.cpp:40-48 (rayLength < 0: automatic, half the radius of the scene's bounding sphere); NULL when
+   shadingSamples is 0.  maxDepth, rrDepth, strictNormals and hideEmitters play no part in this integrator and are not asked for */
+void *mi_host_create_ao(int sampler, uint32_t spp, uint64_t seed, const uint32_t *devices, uint32_t n_devices, uint32_t planes_per_batch, uint32_t shadingSamples, float rayLength, double preview_interval_ms);
 void mi_host_destroy(void *integrator);
 int mi_host_preprocess(void *integrator, mi_scene *scene);
 /* Controls = {continu, abort, interrupt}: returns 0 done, -1 *abort set, -2 *continu cleared, otherwise progress()'s non-zero value;

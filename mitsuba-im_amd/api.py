@@ -49,7 +49,8 @@ class MiInstance(C.Structure):
 
 class MiRenderParams(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("rr_depth", C.c_int32), ("strict_normals", C.c_uint32), ("hide_emitters", C.c_uint32),
-                ("sampler", C.c_uint32), ("spp", C.c_uint32), ("seed", C.c_uint64), ("device", C.c_uint32), ("planes_per_batch", C.c_uint32), ("opacity", C.c_uint32), ("integrator", C.c_uint32), ("emitter_samples", C.c_uint32), ("bsdf_samples", C.c_uint32)]
+                ("sampler", C.c_uint32), ("spp", C.c_uint32), ("seed", C.c_uint64), ("device", C.c_uint32), ("planes_per_batch", C.c_uint32), ("opacity", C.c_uint32), ("integrator", C.c_uint32), ("emitter_samples", C.c_uint32), ("bsdf_samples", C.c_uint32),
+                ("shading_samples", C.c_uint32), ("ray_length", C.c_float)]
 
 
 class MiTile(C.Structure):
@@ -106,7 +107,7 @@ EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_s
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
            "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
-HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_create_direct", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
+HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_create_direct", "mi_host_create_ao", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
                 "mi_host_set_camera", "mi_host_set_lens", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
 
 
@@ -491,17 +492,22 @@ class Render:
     """mi_render handle: the integrator instance (MonteCarloIntegrator properties + sampler)."""
 
     def __init__(self, scene, max_depth=None, rr_depth=None, sampler=None, spp=None, seed=None, device=0, planes_per_batch=0,
-                 strict_normals=None, hide_emitters=None, opacity=False, integrator=None, fields=None, emitter_samples=None, bsdf_samples=None):
+                 strict_normals=None, hide_emitters=None, opacity=False, integrator=None, fields=None, emitter_samples=None, bsdf_samples=None,
+                 shading_samples=None, ray_length=None):
         sc = scene.sc; L = scene.L; self.L = L; self.scene = scene
         # integrator = INTEGRATOR_DIRECT: emitterSamples / bsdfSamples of direct.cpp:96-107 (the scene description's keys, default 1 each); not read by the other integrators
         if emitter_samples is None: emitter_samples = sc.get("emitter_samples", 1)
         if bsdf_samples is None: bsdf_samples = sc.get("bsdf_samples", 1)
+        # integrator = INTEGRATOR_AO: shadingSamples / rayLength of ao.cpp:40-48 (the scene description's keys, default 1 and -1 = automatic); not read by the other integrators
+        if shading_samples is None: shading_samples = sc.get("shading_samples", 1)
+        if ray_length is None: ray_length = sc.get("ray_length", -1.0)
         p = MiRenderParams(sc.max_depth if max_depth is None else max_depth, sc.rr_depth if rr_depth is None else rr_depth,
                            sc.strict_normals if strict_normals is None else int(strict_normals),
                            sc.hide_emitters if hide_emitters is None else int(hide_emitters),
                            sc.sampler if sampler is None else sampler, sc.spp if spp is None else spp,
                            sc.seed if seed is None else seed, device, planes_per_batch, int(opacity), int(sc.get("integrator", 0) or 0) if integrator is None else int(integrator),
-                           1 if emitter_samples is None else int(emitter_samples), 1 if bsdf_samples is None else int(bsdf_samples))
+                           1 if emitter_samples is None else int(emitter_samples), 1 if bsdf_samples is None else int(bsdf_samples),
+                           1 if shading_samples is None else int(shading_samples), -1.0 if ray_length is None else float(ray_length))
         self.params = p
         h = C.c_void_p(); L.check(L.L.mi_render_create(scene.h, C.byref(p), C.byref(h))); self.h = h
         self.field_names = []
@@ -595,7 +601,7 @@ class HostIntegrator:
     film and a progress callback between submissions (src/mitsuba/im_render.cpp:103-222).  devices = HIP devices the film rows are spread over (entries may repeat)."""
     _CB = C.CFUNCTYPE(C.c_int, C.c_double, C.c_void_p)
 
-    def __init__(self, scene, spp=None, devices=(0,), planes_per_batch=0, integrator=None, preview_interval_ms=-1.0, max_depth=None, emitter_samples=None, bsdf_samples=None):
+    def __init__(self, scene, spp=None, devices=(0,), planes_per_batch=0, integrator=None, preview_interval_ms=-1.0, max_depth=None, emitter_samples=None, bsdf_samples=None, shading_samples=None, ray_length=None):
         L = scene.L.L; self.L = L; self.scene = scene; sc = scene.sc
         L.mi_host_create_ex.restype = C.c_void_p; L.mi_host_last_error.restype = C.c_char_p; L.mi_host_statistics.restype = C.c_char_p
         L.mi_host_create_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int, C.c_double]
@@ -609,6 +615,11 @@ class HostIntegrator:
             L.mi_host_create_direct.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double]
             n_em = sc.get("emitter_samples", 1) if emitter_samples is None else emitter_samples; n_bs = sc.get("bsdf_samples", 1) if bsdf_samples is None else bsdf_samples
             self.h = L.mi_host_create_direct(sc.strict_normals, sc.hide_emitters, sc.sampler, self.spp, sc.seed, dev, len(devices), planes_per_batch, int(n_em), int(n_bs), float(preview_interval_ms))
+        elif integ == 4:      # INTEGRATOR_AO: its own properties (ao.cpp:40-48), the scene description's keys unless given
+            L.mi_host_create_ao.restype = C.c_void_p
+            L.mi_host_create_ao.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_double]
+            n_sh = sc.get("shading_samples", 1) if shading_samples is None else shading_samples; length = sc.get("ray_length", -1.0) if ray_length is None else ray_length
+            self.h = L.mi_host_create_ao(sc.sampler, self.spp, sc.seed, dev, len(devices), planes_per_batch, int(n_sh), float(length), float(preview_interval_ms))
         else:
             self.h = L.mi_host_create_ex(sc.max_depth if max_depth is None else max_depth, sc.rr_depth, sc.strict_normals, sc.hide_emitters, sc.sampler, self.spp, sc.seed, dev, len(devices),
                                          planes_per_batch, integ, float(preview_interval_ms))

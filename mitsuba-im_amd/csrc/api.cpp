@@ -16,6 +16,7 @@
 #include "queues.h"
 #include "fields.h"
 #include "direct_const.h"
+#include "ao_const.h"
 
 extern "C" {
 void mi_launch_generate(const DScene &, const RenderConst &, const Queues &, const BatchDesc &, uint32_t, hipStream_t);
@@ -41,6 +42,8 @@ void mi_launch_direct_d_env(const DScene &, const RenderConst &, const DirectCon
 void mi_launch_direct_rc(const DScene &, const RenderConst &, const DirectConst &, const Queues &, const BatchDesc &, int, uint32_t, size_t, hipStream_t);
 void mi_launch_direct_rc_env(const DScene &, const RenderConst &, const DirectConst &, const Queues &, const BatchDesc &, int, uint32_t, size_t, hipStream_t);
 void mi_launch_direct_hit(const DScene &, const RenderConst &, const DirectConst &, const Queues &, uint32_t, hipStream_t);
+void mi_launch_ao(const DScene &, const RenderConst &, const AoConst &, const Queues &, const BatchDesc &, uint32_t, size_t, hipStream_t);
+void mi_launch_ao_resolve(const Queues &, float, uint32_t, hipStream_t);
 void mi_launch_env_primary(const DScene &, const RenderConst &, const Queues &, int, uint32_t, hipStream_t);
 void mi_launch_film_layout(const float *, const float *, float *, int, int, int, int, hipStream_t);
 void mi_launch_gather_samples(const Queues &, const uint32_t *, uint64_t, float *, hipStream_t);
@@ -123,6 +126,7 @@ struct mi_render {
     hipEvent_t fieldDone[kMaxPools] = {}; int lastFieldPool = -1; bool fieldChain = false;
     // direct integrator (direct.h): its constants, and per pool the hit array (+ instance indices) of the BSDF rays in buffer 1 -- Queues::hit keeps the camera hits for the whole batch
     DirectConst dc{}; float4 *hitB[kMaxPools] = {}; int32_t *hitInstB[kMaxPools] = {};
+    AoConst ac{};   // ambient-occlusion integrator (ao.h): its constants; ray_length follows the scene under the automatic length (beginRun)
     uint64_t sceneRev = 0, filmRev = 0;   // scene revision `sc` was copied from / the samples in the film (and the field film) were traced at
     Queues &pool(int i) { return i ? qx[i - 1] : q; }
     hipStream_t poolStream(int i) { return i ? streamx[i - 1] : stream; }
@@ -681,6 +685,9 @@ static float alphaDistOf(const mi::SceneHost &h) {
     float c[3], d2 = 0; for (int i = 0; i < 3; ++i) { c[i] = (hi[i] + lo[i]) * 0.5f; const float d = c[i] - hi[i]; d2 += d * d; }
     (void) c; return std::sqrt(d2) * 2;
 }
+// AmbientOcclusionIntegrator::preprocess (ao.cpp:77-80): a negative rayLength becomes scene->getAABB().getBSphere().radius * 0.5f -- the sphere above, whose radius
+// alphaDistOf hands out times 2 (both scalings by powers of two: exact)
+static float aoRayLengthOf(const mi::SceneHost &h, float asked) { return asked < 0 ? alphaDistOf(h) * 0.25f : asked; }
 // inverse of the sensor's (affine) world transform in double precision, rounded to float (the relPosition field); false: not invertible
 static bool worldToCamera(const mi::SceneHost &h, float *w2c) {
     double m[3][3], t[3]; for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) m[i][j] = h.c2w[i * 4 + j]; t[i] = h.c2w[i * 4 + 3]; }
@@ -709,6 +716,7 @@ static int beginRun(mi_render *r, RunGuard &g, bool film, const char *who) {
     if (r->sceneRev != s->h.revision) {
         r->sc = s->h.d; if (isVolumetric(r->rc.integrator)) r->sc.packet_n = 0;
         r->rc.alpha_dist = alphaDistOf(s->h);
+        if (r->rc.integrator == MI_INTEGRATOR_AO) r->ac.ray_length = aoRayLengthOf(s->h, r->p.ray_length);
         if (r->nFields) (void) worldToCamera(s->h, r->fa.w2c);
         r->sceneRev = s->h.revision;
     }
@@ -815,9 +823,26 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
     if (p->max_depth > 250) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: maxDepth > 250");
     if (p->sampler > 1) return fail(MI_ERR_INVALID, "mi_render_create: unknown sampler");
     if (isVolumetric(p->integrator) && (s->h.d.has_adapters & 4u)) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: `coating`, `roughcoating` and `blendbsdf` are implemented for the path integrator only");
-    if (p->integrator > MI_INTEGRATOR_DIRECT) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: integrators path (0), volpath_simple (1), volpath (2) and direct (3) are implemented");
-    const bool vol = isVolumetric(p->integrator), direct = p->integrator == MI_INTEGRATOR_DIRECT;
-    DirectConst dc{}; uint32_t directDims = 0, directFrames = 0;      // Sobol' dimensions / look_up frames a direct render can touch
+    if (p->integrator > MI_INTEGRATOR_AO) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: integrators path (0), volpath_simple (1), volpath (2), direct (3) and ao (4) are implemented");
+    const bool vol = isVolumetric(p->integrator), direct = p->integrator == MI_INTEGRATOR_DIRECT, ao = p->integrator == MI_INTEGRATOR_AO, oneHit = direct || ao;      // oneHit: one camera hit with sample arrays, their sampler layout
+    DirectConst dc{}; AoConst ac{}; uint32_t directDims = 0, directFrames = 0;      // Sobol' dimensions / look_up frames a direct / ao render can touch
+    if (ao) {      // AmbientOcclusionIntegrator (ao.cpp:38-82).  No BSDF, emitter or medium is read: every scene is accepted
+        const uint32_t N = p->shading_samples; const bool lens = s->h.lensRadius != 0.0f;
+        if (N == 0) return fail(MI_ERR_INVALID, "mi_render_create: ao integrator: shadingSamples must be at least 1 (ao.cpp:122 divides by it)");
+        if ((uint64_t) std::max(p->spp, 1u) * N > (1ull << 22)) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: ao integrator: spp x shadingSamples beyond 2^22 (the sample array numbers its Sobol' points m x N + j in 32 bits, and the look_up tables hold one entry per point)");
+        if (!(p->ray_length == p->ray_length)) return fail(MI_ERR_INVALID, "mi_render_create: ao integrator: rayLength is not a number");
+        if (p->opacity && !s->h.media.empty()) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: ao integrator: `opacity` on a scene with participating media needs the transmittance walk of records.inl:124-135, which this integrator does not have");
+        ac.n = N; ac.recip = 1.0f / (float) N; ac.ray_length = aoRayLengthOf(s->h, p->ray_length);
+        if (p->sampler == MI_SAMPLER_SOBOL) {      // sobol.cpp:171-250: the one array at dimensions 5 / 6; else next2D after the pixel offset / the aperture sample, skipping dimension 4
+            if (N > 1) { ac.array = 5u; directDims = 7u; } else { ac.own_dim = lens ? 5u : 2u; directDims = ac.own_dim + 2u; }
+            directFrames = std::max(p->spp, 1u) * N;
+            if (N > 1 && s->h.logRes < 1) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: ao integrator: Sobol' sample arrays need a film of at least 2 x 2 pixels (sobol::look_up of a 1 x 1 film reads outside its tables)");
+        } else {      // the build-defined stream: the own request is the next call after the camera's, array elements count down from call 255
+            const uint32_t c = lens ? 2u : 1u;
+            if (N > 1) ac.array = 255u; else ac.own_dim = c;
+            if (N > 1 && (uint64_t) c + N > 256u) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: ao integrator: the independent sampler stream numbers 256 draws per sample; shadingSamples + the camera's draws exceed that (use the Sobol sampler or fewer shading samples)");
+        }
+    }
     if (direct) {      // MIDirectIntegrator (direct.cpp:93-144); what its kernels (direct.h) are not built for is refused by name
         if (s->h.d.has_adapters & 1u) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the direct integrator does not implement `mixturebsdf`, `bumpmap`, `normalmap`, `coating`, `roughcoating` and `blendbsdf` (use the path integrator with maxDepth = 2)");
         if (!s->h.media.empty()) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the direct integrator does not support participating media (direct.cpp:181-182)");
@@ -868,7 +893,8 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         if (vol) perBounce += 2;      // + the one or two draws of HomogeneousMedium::sampleDistance per iteration
         const int lensDims = s->h.lensRadius != 0.0f ? 2 : 0;      // the aperture sample: dimensions 2 / 3 (k_generate), every later draw moves by two
         if (lensDims && (uint32_t) (3 + lensDims) > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! The thin lens draws Sobol dimensions 2 and 3.");
-        if (direct) {      // maxDepth plays no part: the dimensions of direct.cpp's requests (computed above)
+        if (oneHit) {      // maxDepth plays no part: the dimensions of direct.cpp's / ao.cpp's requests (computed above)
+            if (ao && directDims > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! The ao integrator's sample array draws Sobol dimensions 5 and 6 (7 dimensions are needed when shadingSamples > 1).");
             if (directDims > s->h.d.sobol_dims || directDims > 256u) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! You may have to reduce 'bsdfSamples' (a roughdielectric draws one more dimension per BSDF sample).");
         } else {
         if (p->max_depth > 0 && (uint32_t) (3 + lensDims + perBounce * depth) > s->h.d.sobol_dims) return fail(MI_ERR_INVALID, "Lookup dimension exceeds the direction number table size! You may have to reduce the 'maxDepth' parameter of your integrator.");
@@ -877,7 +903,7 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         if (p->max_depth > 0 && 3 + lensDims + perBounce * depth > 256) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: the path state numbers a path's Sobol dimensions with 8 bits; maxDepth x draws per bounce exceeds 256 (reduce maxDepth)");
         }
     }
-    if (p->sampler == MI_SAMPLER_INDEPENDENT && p->max_depth > 0 && !direct) {
+    if (p->sampler == MI_SAMPLER_INDEPENDENT && p->max_depth > 0 && !oneHit) {
         // the build-defined independent stream numbers a path's draws with 8 bits: a path that could draw more than 256 values would re-read
         // its own stream from call 0 -- refused by name rather than silently correlated (unbounded depth keeps the documented period)
         int perBounce = 5; for (const mi_material &m : s->h.materials) if (m.type == MI_BSDF_ROUGHDIELECTRIC) perBounce = 6;
@@ -888,6 +914,7 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
     mi_render *r = new mi_render(); r->scene = s;
     memcpy(&r->p, p, offsetof(mi_render_params, emitter_samples));      // the two trailing fields exist in a caller's struct only where it asks for the direct integrator
     if (direct) { r->p.emitter_samples = p->emitter_samples; r->p.bsdf_samples = p->bsdf_samples; r->dc = dc; }
+    if (ao) { r->p.shading_samples = p->shading_samples; r->p.ray_length = p->ray_length; r->ac = ac; }      // (read only here: the other integrators' callers may pass the shorter struct)
     r->sc = s->h.d; r->sceneRev = r->filmRev = s->h.revision; if (vol) r->sc.packet_n = 0;      // packet or tree is decided per render: volpath / volpath_simple on a <= 64-triangle scene without media walk its tree
     struct Guard { mi_render *r; ~Guard() { if (r) mi_render_destroy(r); } } guard{r};      // every early return below releases what was created so far
     r->rc.max_depth = p->max_depth; r->rc.rr_depth = p->rr_depth; r->rc.strict_normals = p->strict_normals; r->rc.hide_emitters = p->hide_emitters; r->rc.opacity = p->opacity;
@@ -911,9 +938,9 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         // fold the direction matrices into 4-bit lookup tables for the dimensions / index bits this render can touch
         int perBounceDims = 5; for (const mi_material &m : s->h.materials) if (m.type == MI_BSDF_ROUGHDIELECTRIC) perBounceDims = 6;
         if (vol) perBounceDims += 2;
-        uint32_t sppBits = 0; while ((1ull << sppBits) < (direct ? directFrames : p->spp)) ++sppBits;      // (direct: the array elements' frames m x S + j)
+        uint32_t sppBits = 0; while ((1ull << sppBits) < (oneHit ? directFrames : p->spp)) ++sppBits;      // (direct, ao: the array elements' frames m x S + j)
         const uint32_t bits = (s->h.logRes > 1 ? 2 * s->h.logRes : 0) + sppBits + 1;
-        const uint32_t nibs = std::max<uint32_t>(8, (bits + 3) / 4), dims      /* at least the eight nibbles of the low index word (pt_device.h sobolBitsNib unrolls them) */ = std::min<uint32_t>(s->h.d.sobol_dims, direct ? std::max(directDims, 4u) : (uint32_t) (4 + (s->h.lensRadius != 0.0f ? 2 : 0) + perBounceDims * p->max_depth));
+        const uint32_t nibs = std::max<uint32_t>(8, (bits + 3) / 4), dims      /* at least the eight nibbles of the low index word (pt_device.h sobolBitsNib unrolls them) */ = std::min<uint32_t>(s->h.d.sobol_dims, oneHit ? std::max(directDims, 4u) : (uint32_t) (4 + (s->h.lensRadius != 0.0f ? 2 : 0) + perBounceDims * p->max_depth));
         std::vector<uint32_t> nib((size_t) dims * nibs * 16);
         for (uint32_t dmn = 0; dmn < dims; ++dmn) for (uint32_t n = 0; n < nibs; ++n) for (uint32_t v = 0; v < 16; ++v) {
             uint32_t x = 0; for (uint32_t b = 0; b < 4; ++b) if (((v >> b) & 1u) && 4 * n + b < MI_SOBOL_SIZE) x ^= g_sobolM32[(size_t) dmn * MI_SOBOL_SIZE + 4 * n + b];
@@ -928,11 +955,11 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
         // into the sample afterwards (k_generate), so the tables do not depend on it.
         const uint32_t m = s->h.logRes;
         if (m > 1) {
-            if (2 * m + sppBits > 52 || p->spp > (1u << 22) || (direct && directFrames > (1u << 22))) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: Sobol index beyond 52 bits (film resolution x sample count)");
+            if (2 * m + sppBits > 52 || p->spp > (1u << 22) || (oneHit && directFrames > (1u << 22))) return fail(MI_ERR_UNSUPPORTED, "mi_render_create: Sobol index beyond 52 bits (film resolution x sample count)");
             const uint64_t *vdc = g_sobolVdc.data() + (size_t) (m - 1) * MI_SOBOL_SIZE, *vdi = g_sobolVdcInv.data() + (size_t) (m - 1) * MI_SOBOL_SIZE;
             auto mulVec = [&](const uint64_t *cols, uint64_t b) { uint64_t x = 0; for (uint32_t c = 0; b; b >>= 1, ++c) if (b & 1) x ^= cols[c]; return x; };
             auto dimBits = [&](uint32_t dmn, uint64_t index) { uint32_t x = 0; for (uint32_t c = 0; index; index >>= 1, ++c) if (index & 1) x ^= g_sobolM32[(size_t) dmn * MI_SOBOL_SIZE + c]; return x; };
-            const size_t res = (size_t) 1 << m, nF = direct ? directFrames : std::max<uint32_t>(p->spp, 1u);
+            const size_t res = (size_t) 1 << m, nF = oneHit ? directFrames : std::max<uint32_t>(p->spp, 1u);
             std::vector<uint32_t> tab((nF + 2 * res) * 4);
             auto put = [&](size_t e, uint64_t idx) { tab[e * 4] = (uint32_t) idx; tab[e * 4 + 1] = (uint32_t) (idx >> 32); tab[e * 4 + 2] = dimBits(0, idx); tab[e * 4 + 3] = dimBits(1, idx); };
             for (size_t f = 0; f < nF; ++f) put(f, ((uint64_t) f << (2 * m)) ^ mulVec(vdi, mulVec(vdc, f)));
@@ -1077,12 +1104,45 @@ static int traceBatchDirect(mi_render *r, const BatchDesc &bd, size_t &evUsed, i
     HIPCHK(hipGetLastError());
     return MI_OK;
 }
+// trace one batch of the ambient-occlusion integrator: one camera hit, then N x (k_ao, shadow) over it and the resolve pass (ao.h; ao.cpp:84-125).  The camera-hit queue
+// stays put as in traceBatchDirect; no second hit array, no environment launch (a camera miss is 1 whatever the environment is)
+static int traceBatchAo(mi_render *r, const BatchDesc &bd, size_t &evUsed, int pool) {
+    const DScene &scR = r->sc; hipStream_t st = r->poolStream(pool); Queues &Q = r->pool(pool);
+    mark(r, 0, evUsed, st);
+    const bool fused = mi_fused_walk(scR); uint32_t ticket = 2;
+    if (fused) HIPCHK(hipMemsetAsync(Q.ticket, 0, MI_TICKETS * sizeof(uint32_t), st));
+    mi_launch_generate(scR, r->rc, Q, bd, r->grid, st);
+    mark(r, 1, evUsed, st);
+    if (fused) mi_launch_extend_fused(scR, Q, 0, Q.ticket + ticket++, st); else mi_launch_extend(scR, Q, 0, r->gridExtend, st);
+    ++r->launchesAll;
+    if (r->nFields && !bd.list) {      // field channels of the film samples, as in traceBatch
+        mark(r, 0, evUsed, st);
+        if (r->fieldChain && r->lastFieldPool >= 0 && r->lastFieldPool != pool) HIPCHK(hipStreamWaitEvent(st, r->fieldDone[r->lastFieldPool], 0));
+        mi_launch_field_film(scR, r->fa, Q, bd, r->fieldFilm, r->fieldSpill, st);
+        if (r->fieldChain) { HIPCHK(hipEventRecord(r->fieldDone[pool], st)); r->lastFieldPool = pool; }
+    }
+    // dynamic LDS of k_ao: the Sobol' nibble tables, then (small scenes) the shading records -- no material, emitter or CDF table
+    DScene sc = scR; sc.small_tables = r->ldsTables ? 1u : 0u;
+    size_t lds = r->rc.sampler == 1 ? (size_t) r->rc.nib_dims * r->rc.nib_count * 64 : 16;
+    if (sc.small_tables) lds += 16 + 4 * ((size_t) sc.n_tris * (4 * MI_SHADE_WORDS));
+    AoConst ac = r->ac;
+    for (uint32_t j = 0; j < ac.n; ++j) {
+        ac.pass = j;
+        mark(r, 2, evUsed, st); mi_launch_ao(sc, r->rc, ac, Q, bd, r->gridShade, lds, st);
+        mark(r, 3, evUsed, st); if (fused && ticket < MI_TICKETS) mi_launch_shadow_fused(scR, Q, Q.ticket + ticket++, st); else mi_launch_shadow(scR, Q, r->gridShadow, st);
+    }
+    if (ac.n > 1u) { mark(r, 2, evUsed, st); mi_launch_ao_resolve(Q, ac.recip, r->gridShadow, st); }      // (N = 1: the reciprocal is 1)
+    mark(r, 0, evUsed, st);
+    HIPCHK(hipGetLastError());
+    return MI_OK;
+}
 
 // trace one batch: paths = tile pixels x planes (or an explicit list), all bounces
 static int traceBatch(mi_render *r, const BatchDesc &bd, const uint32_t *list, size_t &evUsed, int pool = 0) {
     const DScene &sc = r->sc; hipStream_t st = r->poolStream(pool); Queues &Q = r->pool(pool);
     (void) list;
     if (r->rc.integrator == MI_INTEGRATOR_DIRECT) return traceBatchDirect(r, bd, evUsed, pool);
+    if (r->rc.integrator == MI_INTEGRATOR_AO) return traceBatchAo(r, bd, evUsed, pool);
     mark(r, 0, evUsed, st);
     const bool fused = r->rc.integrator == MI_INTEGRATOR_PATH && mi_fused_walk(sc);      // trace_fused.h: persistent waves fetch segments through per-launch tickets
     if (fused) HIPCHK(hipMemsetAsync(Q.ticket, 0, MI_TICKETS * sizeof(uint32_t), st));

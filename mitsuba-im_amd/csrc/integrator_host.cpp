@@ -55,6 +55,7 @@ bool MIPathTracerHIP::preprocess(mi_scene *scene) {
     p.max_depth = m_props.maxDepth; p.rr_depth = m_props.rrDepth; p.strict_normals = m_props.strictNormals; p.hide_emitters = m_props.hideEmitters;
     p.sampler = (uint32_t) m_props.sampler; p.spp = m_props.sampleCount; p.seed = m_props.seed; p.device = m_props.device; p.planes_per_batch = m_props.planesPerBatch; p.opacity = m_props.opacity ? 1 : 0;
     p.integrator = (uint32_t) m_props.integrator; p.emitter_samples = m_props.emitterSamples; p.bsdf_samples = m_props.bsdfSamples;
+    p.shading_samples = m_props.shadingSamples; p.ray_length = m_props.rayLength;
     check(mi_render_create(scene, &p, &m_render), "MIPathTracerHIP::preprocess");
     // `devices`: every further entry gets a replica of the scene and a render handle of its own; film rows are interleaved over the replicas
     for (size_t i = 1; i < m_props.devices.size(); ++i) {
@@ -193,6 +194,16 @@ void *mi_host_create_direct(int strictNormals, int hideEmitters, int sampler, ui
         pr.sampler = sampler; pr.sampleCount = spp; pr.seed = seed; pr.planesPerBatch = planes; pr.integrator = MI_INTEGRATOR_DIRECT;
         if (emitterSamples > 0xFFFFu || bsdfSamples > 0xFFFFu) throw std::runtime_error("mi_host_create_direct: at most 65535 emitter / BSDF samples");
         pr.emitterSamples = (uint16_t) emitterSamples; pr.bsdfSamples = (uint16_t) bsdfSamples;
+        if (previewIntervalMs >= 0) pr.previewIntervalMs = previewIntervalMs;
+        if (devices && nDevices) { pr.devices.assign(devices, devices + nDevices); pr.device = devices[0]; }
+        return new mi355::MIPathTracerHIP(pr);
+    } catch (const std::exception &e) { g_hostErr = e.what(); return nullptr; }
+}
+void *mi_host_create_ao(int sampler, uint32_t spp, uint64_t seed, const uint32_t *devices, uint32_t nDevices, uint32_t planes, uint32_t shadingSamples, float rayLength, double previewIntervalMs) {
+    try {
+        mi355::Properties pr; pr.sampler = sampler; pr.sampleCount = spp; pr.seed = seed; pr.planesPerBatch = planes; pr.integrator = MI_INTEGRATOR_AO;
+        if (shadingSamples == 0) throw std::runtime_error("mi_host_create_ao: shadingSamples must be at least 1 (ao.cpp:122 divides by it)");
+        pr.shadingSamples = shadingSamples; pr.rayLength = rayLength;
         if (previewIntervalMs >= 0) pr.previewIntervalMs = previewIntervalMs;
         if (devices && nDevices) { pr.devices.assign(devices, devices + nDevices); pr.device = devices[0]; }
         return new mi355::MIPathTracerHIP(pr);

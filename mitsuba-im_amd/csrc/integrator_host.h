@@ -23,11 +23,16 @@ class MIPathTracerHIP;
 
 struct Properties {                 // the subset of mitsuba::Properties this integrator queries
     int maxDepth = -1, rrDepth = 5; bool strictNormals = false, hideEmitters = false;
-    int sampler = MI_SAMPLER_SOBOL; uint32_t sampleCount = 4; uint64_t seed = 0;   // the scene's sampler (Sampler::getSampleCount, getProperties)
+    int sampler = MI_SAMPLER_SOBOL; uint32_t sampleCount = 4;                      // the scene's sampler (Sampler::getSampleCount, getProperties)
+    // integrator = MI_INTEGRATOR_AO only: AmbientOcclusionIntegrator's properties (ao.cpp:40-48; rayLength < 0 = automatic).  The two sit in what were the alignment holes in
+    // front of `seed` and of `previewIntervalMs` (4 bytes each): the record's size and the offset of every other field stay as they were, so a path_hip.so built against the
+    // earlier header keeps working with this library (it never asks for `ao`, the only case in which the two are read)
+    uint32_t shadingSamples = 1;
+    uint64_t seed = 0;
     uint32_t device = 0, planesPerBatch = 0;                                       // build-specific
     std::vector<uint32_t> devices;   // build-specific (SURVEY §8b `devices`): HIP devices to spread the film rows over; empty = {device}.  An entry may repeat (two
                                      // replicas on one GPU).  The scene handed to preprocess() lives on devices[0]; the others get clones (mi_scene_clone)
-    int integrator = MI_INTEGRATOR_PATH;   // build-specific: MI_INTEGRATOR_VOLPATH_SIMPLE / MI_INTEGRATOR_VOLPATH = the loops of volpath_simple / volpath over the scene's participating media
+    int integrator = MI_INTEGRATOR_PATH; float rayLength = -1.0f;   // (rayLength: see shadingSamples)  integrator, build-specific: MI_INTEGRATOR_VOLPATH_SIMPLE / MI_INTEGRATOR_VOLPATH = the loops of volpath_simple / volpath over the scene's participating media
     double previewIntervalMs = 100.0;   // build-specific: the responsive face copies the film into its target at most this often between submissions (always after the last one); 0 = after every submission
     bool opacity = true;   // RadianceQueryRecord::EOpacity: the responsive drivers always request it (integrator.cpp:474)
     // integrator = MI_INTEGRATOR_DIRECT only: MIDirectIntegrator's properties (direct.cpp:96-107; `shadingSamples` sets both, default 1).  They sit in what was the tail padding of

@@ -1,6 +1,6 @@
 """Command-line front end: render a Mitsuba XML scene on the MI355X path tracer (what `mitsuba scene.xml` does for the `path` integrator).
 
-    python -m mitsuba-im_amd.render scene.xml [-o out.exr|out.pfm|out.npy|out.png] [-D name=value ...] [--spp N] [--sampler sobol|independent] [--device K]
+    python -m mitsuba-im_amd.render scene.xml [-o out.exr|out.pfm|out.npy|out.png] [-D name=value ...] [--spp N] [--sampler sobol|independent] [--device K] [--ao N [--ao-length L]]
 
 The image written is the developed film (sum / weight, linear RGB, as HDRFilm::develop would hand to its writer); `.exr` (FLOAT channels, ZIP), `.pfm` and `.npy`
 keep the linear values; `.png` / `.jpg` get ldrfilm's default sRGB encoding (imageio.py).  There is no CPU fallback: without the HIP library / a GPU this exits with an error.
@@ -8,6 +8,9 @@ keep the linear values; `.png` / `.jpg` get ldrfilm's default sRGB encoding (ima
 A scene whose integrator is `multichannel` (one of path / volpath_simple / volpath plus `field` integrators) writes one OpenEXR file holding the radiance and one channel
 group per field, named by the film's `channelNames` (default: `color`, then the field kinds) and shaped by its `pixelFormat` list: `<name>.R/.G/.B` for `rgb`, `<name>.Y`
 for `luminance`.  Other output formats cannot hold the groups: an error that names `.exr`.
+
+`--ao N [--ao-length L]` renders any scene file with the ambient-occlusion integrator (`ao`: N shading samples, occlusion rays of length L, default automatic) in
+place of the file's own integrator; the field channels of a `multichannel` scene stay.  A scene file whose integrator is `ao` needs no option.
 
 `--orbit N [--orbit-axis x|y|z]` renders a turntable: N frames with the camera rotated in steps of 360 / N degrees about the axis through the centre of the scene's
 box.  The scene is committed once; every frame is an in-place camera edit of the committed scene (Scene.update_camera), a clear and a run -- no tree build, no
@@ -104,6 +107,15 @@ def focus_distances(n, a, b):
     return [float(a)] if n == 1 else [float(a) if f == 0 else float(b) if f == n - 1 else float(a + (b - a) * f / (n - 1)) for f in range(n)]
 
 
+def use_ao(sc, shading_samples, ray_length=-1.0):
+    """`--ao N [--ao-length L]`: the scene description with the ambient-occlusion integrator in place of its own (its field list, sampler and film stay)."""
+    from .scenes import INTEGRATOR_AO
+    if shading_samples < 1:
+        raise ValueError("--ao expects a number of shading samples >= 1")
+    sc.integrator = INTEGRATOR_AO; sc.shading_samples = int(shading_samples); sc.ray_length = float(ray_length)
+    return sc
+
+
 def write_outputs(sc, render, out, rgb=None, fields=None):
     """the developed film (and, for a multichannel scene, the field groups) of `render` -> `out`; False (message printed) when the format cannot hold them"""
     if rgb is None:
@@ -130,6 +142,8 @@ def main(argv=None):
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--sampler", choices=["sobol", "independent"], default=None, help="replace the scene's sampler plugin (keeps its sampleCount)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--ao", type=int, default=0, metavar="N", help="render with the ambient-occlusion integrator (N shading samples) in place of the scene's own integrator")
+    ap.add_argument("--ao-length", type=float, default=None, metavar="L", help="length of the occlusion rays of --ao (default: automatic, half the radius of the scene's bounding sphere)")
     ap.add_argument("--orbit", type=int, default=0, metavar="N", help="turntable of N frames about the scene box's centre: one commit, one in-place camera edit per frame")
     ap.add_argument("--orbit-axis", choices=["x", "y", "z"], default="y")
     ap.add_argument("--spin", type=int, default=0, metavar="N", help="N frames with every instance turned about its own origin: one commit, one in-place instance edit per frame")
@@ -143,6 +157,8 @@ def main(argv=None):
         if "=" not in d:
             raise SystemExit(f"-D expects name=value, got {d!r}")
         k, v = d.split("=", 1); params[k] = v
+    if a.ao < 0 or (a.ao_length is not None and not a.ao):
+        raise SystemExit("--ao expects a number of shading samples >= 1; --ao-length belongs to --ao N")
     if a.orbit < 0:
         raise SystemExit("--orbit expects a frame count >= 1")
     if a.spin < 0 or (a.spin and a.orbit):
@@ -156,6 +172,8 @@ def main(argv=None):
         sc = xml_scene.load_scene(a.scene, params, sampler=a.sampler)
         if a.spp is not None:
             sc.spp = a.spp
+        if a.ao:
+            use_ao(sc, a.ao, -1.0 if a.ao_length is None else a.ao_length)
         out = a.output or (a.scene.rsplit(".", 1)[0] + ".exr")          # hdrfilm's default fileFormat (src/films/hdrfilm.cpp: openexr)
         if a.spin and not (sc.get("instances") or []):
             print(f"error: {a.scene}: --spin turns the instances of shape groups, and this scene has none", file=sys.stderr)

@@ -113,6 +113,7 @@ INTEGRATOR_PATH = 0            # src/integrators/path/path.cpp
 INTEGRATOR_VOLPATH_SIMPLE = 1  # src/integrators/path/volpath_simple.cpp
 INTEGRATOR_VOLPATH = 2         # src/integrators/path/volpath.cpp (multiple importance sampling, emitters found through index-matched boundaries)
 INTEGRATOR_DIRECT = 3          # src/integrators/direct/direct.cpp (scene keys emitter_samples / bsdf_samples, default 1 each)
+INTEGRATOR_AO = 4              # src/integrators/direct/ao.cpp (scene keys shading_samples, default 1, and ray_length, default -1 = automatic)
 MEDIUM_BALANCE, MEDIUM_SINGLE, MEDIUM_MANUAL = 0, 1, 2      # HomogeneousMedium sampling strategies (homogeneous.cpp:192-226; `maximum` is not built)
 PHASE_ISOTROPIC, PHASE_HG = 0, 1
 

@@ -6,7 +6,7 @@ What is read (reference: src/librender/scenehandler.cpp:104-140 tag table, :300-
 substitution, <include>, <ref>, <integer> <float> <boolean> <string> <point> <vector> <rgb> <srgb> <spectrum> <blackbody>, <transform> with
 <translate> <rotate> <scale> <matrix> <lookat>, and the plugin tags <integrator> <sensor> <sampler> <film> <rfilter> <shape> <bsdf>
 <texture> <emitter>.  Plugins understood = the ones the hot path implements:
-    integrator  path, volpath_simple, volpath, direct (shadingSamples / emitterSamples / bsdfSamples), multichannel + field
+    integrator  path, volpath_simple, volpath, direct (shadingSamples / emitterSamples / bsdfSamples), ao (shadingSamples / rayLength), multichannel + field
     sensor      perspective                                  (src/librender/sensor.cpp:225-305 fov / fovAxis / focalLength)
                 thinlens                                     (src/sensors/thinlens.cpp: + apertureRadius, focusDistance)
     sampler     independent, sobol
@@ -943,19 +943,19 @@ class _SceneBuilder:
         integ = root.child("integrator")
         if integ is None:
             raise SceneError("the scene has no <integrator> (the reference would insert a direct-illumination integrator, which is not this path)")
-        integrators = {"path": S.INTEGRATOR_PATH, "volpath_simple": S.INTEGRATOR_VOLPATH_SIMPLE, "volpath": S.INTEGRATOR_VOLPATH, "direct": S.INTEGRATOR_DIRECT}
+        integrators = {"path": S.INTEGRATOR_PATH, "volpath_simple": S.INTEGRATOR_VOLPATH_SIMPLE, "volpath": S.INTEGRATOR_VOLPATH, "direct": S.INTEGRATOR_DIRECT, "ao": S.INTEGRATOR_AO}
         fields = []; n_nested = 1
         if integ.type == "field":
-            raise SceneError("a <integrator type=\"field\"> at the root is not supported: nest it in <integrator type=\"multichannel\"> next to a path, volpath_simple, volpath or direct integrator")
+            raise SceneError("a <integrator type=\"field\"> at the root is not supported: nest it in <integrator type=\"multichannel\"> next to a path, volpath_simple, volpath or direct integrator, or an ao integrator")
         if integ.type == "multichannel":
             # src/integrators/misc/multichannel.cpp: every nested integrator sees the same sensor ray and intersection; here: exactly one radiance integrator plus any
             # number of `field` integrators (src/integrators/misc/field.cpp), in document order = the order of the film's pixelFormat / channelNames lists
             nested = [c for _, c in integ.children_of("integrator")]; radiance = [c for c in nested if c.type != "field"]
             for c in radiance:
                 if c.type not in integrators:
-                    raise SceneError(f"integrator \"{c.type}\" is not supported: this framework implements path, volpath_simple, volpath and direct")
+                    raise SceneError(f"integrator \"{c.type}\" is not supported: this framework implements path, volpath_simple, volpath and direct, and ao")
             if len(radiance) != 1:
-                raise SceneError(f"<integrator type=\"multichannel\"> must hold exactly one radiance integrator (path, volpath_simple, volpath or direct) next to its field integrators, found {len(radiance)}")
+                raise SceneError(f"<integrator type=\"multichannel\"> must hold exactly one radiance integrator (path, volpath_simple, volpath or direct, or ao) next to its field integrators, found {len(radiance)}")
             if nested[0] is not radiance[0]:
                 raise SceneError("<integrator type=\"multichannel\">: the radiance integrator must come first (the film's first channel group is the radiance)")
             from .api import FIELD_NAMES
@@ -968,7 +968,7 @@ class _SceneBuilder:
                 c.check_all_used(); fields.append((fname, undef))
             integ.check_all_used(); n_nested = len(nested); integ = radiance[0]
         if integ.type not in integrators:
-            raise SceneError(f"integrator \"{integ.type}\" is not supported: this framework implements path, volpath_simple, volpath and direct")
+            raise SceneError(f"integrator \"{integ.type}\" is not supported: this framework implements path, volpath_simple, volpath and direct, and ao")
         emitter_samples = bsdf_samples = 1
         if integ.type == "direct":                      # src/integrators/direct/direct.cpp:93-108: shadingSamples sets both counts; no maxDepth / rrDepth (read as unknown properties)
             shading = int(integ.get("shadingSamples", 1))
@@ -976,9 +976,15 @@ class _SceneBuilder:
             if emitter_samples < 0 or bsdf_samples < 0 or emitter_samples + bsdf_samples == 0:
                 raise SceneError("<integrator type=\"direct\">: emitterSamples + bsdfSamples must be greater than zero (and neither negative)")
             max_depth, rr_depth = 2, 5                  # what one camera hit + one more segment is in the path tracer's terms; the direct kernels ignore both
+        elif integ.type == "ao":                        # src/integrators/direct/ao.cpp:40-48: shadingSamples, rayLength (negative: automatic) and nothing else
+            shading_samples, ray_length = int(integ.get("shadingSamples", 1)), float(integ.get("rayLength", -1.0))
+            if shading_samples < 1:
+                raise SceneError("<integrator type=\"ao\">: shadingSamples must be at least 1 (the reference divides by it)")
+            max_depth, rr_depth = 2, 5                  # valid values for the render parameters; the ao kernels ignore both
         else:
             max_depth, rr_depth = int(integ.get("maxDepth", -1)), int(integ.get("rrDepth", 5))
-        strict, hide = bool(integ.get("strictNormals", False)), bool(integ.get("hideEmitters", False))
+        # (ao.cpp reads neither: there they are unknown properties)
+        strict, hide = (False, False) if integ.type == "ao" else (bool(integ.get("strictNormals", False)), bool(integ.get("hideEmitters", False)))
         integ.check_all_used()
         sensors = root.children_of("sensor")
         if len(sensors) != 1:
@@ -1130,6 +1136,8 @@ class _SceneBuilder:
             if self.media:
                 raise SceneError("<integrator type=\"direct\"> does not support participating media (src/integrators/direct/direct.cpp:181-182): use volpath_simple or volpath")
             sc.emitter_samples, sc.bsdf_samples = emitter_samples, bsdf_samples
+        elif sc.integrator == S.INTEGRATOR_AO:
+            sc.shading_samples, sc.ray_length = shading_samples, ray_length
         elif sc.integrator != S.INTEGRATOR_PATH and not self.media:
             pass                                        # a volumetric integrator over a scene without media is legal (it renders what `path` renders)
         if aperture:
@@ -1193,10 +1201,12 @@ def export_scene(sc, directory, name=None, mesh_format="serialized"):
     rgb = lambda n, v: f'<rgb name="{n}" value="{fmt(v).replace(" ", ", ")}"/>'
     mat = lambda n, m: f'<transform name="{n}"><matrix value="{fmt(m)}"/></transform>'
     out = ['<?xml version="1.0" encoding="utf-8"?>', '<scene version="0.5.0">']
-    integ_name = {S.INTEGRATOR_PATH: "path", S.INTEGRATOR_VOLPATH_SIMPLE: "volpath_simple", S.INTEGRATOR_VOLPATH: "volpath", S.INTEGRATOR_DIRECT: "direct"}[sc.get("integrator", 0) or 0]
+    integ_name = {S.INTEGRATOR_PATH: "path", S.INTEGRATOR_VOLPATH_SIMPLE: "volpath_simple", S.INTEGRATOR_VOLPATH: "volpath", S.INTEGRATOR_DIRECT: "direct", S.INTEGRATOR_AO: "ao"}[sc.get("integrator", 0) or 0]
     if integ_name == "direct":
         radiance_xml = (f'<integrator type="direct"><integer name="emitterSamples" value="{int(sc.get("emitter_samples", 1))}"/><integer name="bsdfSamples" value="{int(sc.get("bsdf_samples", 1))}"/>'
                         f'<boolean name="strictNormals" value="{str(bool(sc.strict_normals)).lower()}"/><boolean name="hideEmitters" value="{str(bool(sc.hide_emitters)).lower()}"/></integrator>')
+    elif integ_name == "ao":
+        radiance_xml = f'<integrator type="ao"><integer name="shadingSamples" value="{int(sc.get("shading_samples", 1))}"/><float name="rayLength" value="{fmt([sc.get("ray_length", -1.0)])}"/></integrator>'
     else:
         radiance_xml = (f'<integrator type="{integ_name}"><integer name="maxDepth" value="{sc.max_depth}"/><integer name="rrDepth" value="{sc.rr_depth}"/>'
                         f'<boolean name="strictNormals" value="{str(bool(sc.strict_normals)).lower()}"/><boolean name="hideEmitters" value="{str(bool(sc.hide_emitters)).lower()}"/></integrator>')
