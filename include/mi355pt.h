@@ -311,6 +311,23 @@ int mi_render_merge_film(mi_render *dst, mi_render *src);
 int mi_render_samples(mi_render *r, const uint32_t *pairs, uint64_t n, float *out_li);
 int mi_render_stats(mi_render *r, mi_stats *out);
 
+/* -- adaptive sampling: replaces the `adaptive` integrator wrapped around `path` / `volpath_simple` / `volpath` (src/integrators/misc/adaptive.cpp:202-319).
+ *    Pixel p takes its samples k = 0, 1, 2, ... in order (the values mi_render_samples gives at (px, py, k)); each goes through ImageBlock::put (a rejected sample
+ *    counts with luminance 0) and the online variance of :278-282; the pixel stops at max_sample_factor x spp samples, or, from spp samples on, as soon as
+ *    sqrtf(variance / n) x quantile <= max_error x max(mean, average_luminance x 0.01f).  Its footprint enters the film scaled by 1.0f / n (:307-317), so the film's weights
+ *    are those of ONE sample per pixel.  All float32, one rounding per operation: the count map equals a sequential model bit for bit whatever round_samples,
+ *    planes_per_batch and the pool shape are.  Two deviations from the reference: quantile = |approx_erfinv(-1 + p_value)| x SQRT_TWO (the reference omits the absolute
+ *    value and with it stops every pixel at spp); average_luminance <= 0 asks for the estimate over min(10000, W x H) pixels (i x W x H) / N at sample index 2^24 - 1.
+ *    Independent sampler only (adaptive.cpp:150-152), spp >= 8 (:210-212), integrators path / volpath_simple / volpath, no field channels. */
+typedef struct { float max_error, p_value; int32_t max_sample_factor; uint32_t round_samples; float average_luminance; uint32_t pad[3]; } mi_adaptive_params;   /* max_sample_factor < 0: no cap but the stream's 2^24 - 2; round_samples: sample indices per round, 0 = spp */
+typedef struct { uint64_t samples_used, samples_traced; uint32_t rounds, pixels_at_cap, min_count, max_count; float average_luminance, quantile; } mi_adaptive_stats;   /* of the last adaptive run: used = sum of the counts, traced = used + the samples of a round that followed a pixel's stop */
+int mi_render_set_adaptive(mi_render *r, const mi_adaptive_params *p);       /* NULL: off; only while the film is clear */
+/* One adaptive render of `tile` into a CLEAR film; there is one adaptive run per mi_render_clear, and mi_render_run / mi_render_run_rows / mi_render_merge_film refuse a
+ * film that holds one.  Rounds of round_samples sample indices over the compacted list of active pixels; the cancel flag is observed before every batch. */
+int mi_render_run_adaptive(mi_render *r, mi_tile tile);
+int mi_render_read_sample_counts(mi_render *r, uint32_t *out /* H x W, 0 = not rendered */);
+int mi_render_adaptive_stats(mi_render *r, mi_adaptive_stats *out);
+
 /* -- field channels: replaces the `multichannel` integrator with nested `field` integrators (src/integrators/misc/multichannel.cpp:164-221,
  *    src/integrators/misc/field.cpp:124-177).  Every sample of the radiance film also puts the data of its first camera hit into a field film, at the same film
  *    position through the same reconstruction filter; the radiance film is what it is without fields.  Kinds in the order of field.cpp's EField; each field is three

@@ -63,6 +63,15 @@ class MiStats(C.Structure):
                 ("extend_launches", C.c_uint64), ("extend_rays", C.c_uint64), ("extend_launches_all", C.c_uint64)]
 
 
+class MiAdaptiveParams(C.Structure):
+    _fields_ = [("max_error", C.c_float), ("p_value", C.c_float), ("max_sample_factor", C.c_int32), ("round_samples", C.c_uint32), ("average_luminance", C.c_float), ("pad", C.c_uint32 * 3)]
+
+
+class MiAdaptiveStats(C.Structure):
+    _fields_ = [("samples_used", C.c_uint64), ("samples_traced", C.c_uint64), ("rounds", C.c_uint32), ("pixels_at_cap", C.c_uint32), ("min_count", C.c_uint32), ("max_count", C.c_uint32),
+                ("average_luminance", C.c_float), ("quantile", C.c_float)]
+
+
 class MiField(C.Structure):
     _fields_ = [("field", C.c_uint32), ("undefined", C.c_float * 3)]
 
@@ -105,6 +114,7 @@ class MiFusedDebugInfo(C.Structure):
 EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_scene_create", "mi_scene_destroy", "mi_scene_set_triangles",
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_lens", "mi_scene_set_film",
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
+           "mi_render_set_adaptive", "mi_render_run_adaptive", "mi_render_read_sample_counts", "mi_render_adaptive_stats",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
            "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_create_direct", "mi_host_create_ao", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
@@ -167,6 +177,10 @@ class Lib:
         L.mi_render_read_film_device.argtypes = [vp, i32, vp]
         L.mi_render_samples.argtypes = [vp, vp, u64, vp]
         L.mi_render_stats.argtypes = [vp, C.POINTER(MiStats)]
+        L.mi_render_set_adaptive.argtypes = [vp, C.POINTER(MiAdaptiveParams)]
+        L.mi_render_run_adaptive.argtypes = [vp, MiTile]
+        L.mi_render_read_sample_counts.argtypes = [vp, vp]
+        L.mi_render_adaptive_stats.argtypes = [vp, C.POINTER(MiAdaptiveStats)]
         L.mi_render_set_fields.argtypes = [vp, vp, u32]
         L.mi_render_field_film_size.argtypes = [vp, i32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.mi_render_read_fields.argtypes = [vp, i32, vp]
@@ -513,6 +527,34 @@ class Render:
         self.field_names = []
         if fields is None: fields = sc.get("fields")          # the scene description's own list (scene files with a `multichannel` integrator); [] = none
         if fields: self.set_fields(fields)
+        ad = sc.get("adaptive")                               # the scene description's own parameters (scene files with an `adaptive` integrator); None = uniform sampling
+        if ad: self.set_adaptive(**ad)
+
+    def set_adaptive(self, max_error=0.05, p_value=0.05, max_sample_factor=32, round_samples=0, average_luminance=0.0):
+        """Per-pixel error control (the reference's `adaptive` integrator over path / volpath_simple / volpath): run_adaptive() then gives every pixel samples until the
+        half width of its confidence interval is at most max_error x max(mean luminance, 1 % of average_luminance), or max_sample_factor x spp samples are spent
+        (negative: no cap).  round_samples: sample indices traced per round (0 = spp); average_luminance <= 0: estimated.  Only while the film is clear;
+        max_error=None turns it off."""
+        if max_error is None:
+            self.L.check(self.L.L.mi_render_set_adaptive(self.h, None)); return
+        p = MiAdaptiveParams(float(max_error), float(p_value), int(max_sample_factor), int(round_samples), float(average_luminance))
+        self.L.check(self.L.L.mi_render_set_adaptive(self.h, C.byref(p)))
+
+    def run_adaptive(self, tile=None):
+        """One adaptive render of the tile (default: the film) into a clear film; one per clear()."""
+        sc = self.scene.sc
+        t = MiTile(0, 0, sc.width, sc.height) if tile is None else MiTile(*tile)
+        self.L.check(self.L.L.mi_render_run_adaptive(self.h, t))
+
+    def sample_counts(self):
+        """H x W uint32: the samples each pixel took in the adaptive run (0 = not rendered)."""
+        sc = self.scene.sc; out = np.zeros((sc.height, sc.width), np.uint32)
+        self.L.check(self.L.L.mi_render_read_sample_counts(self.h, _p(out))); return out
+
+    def adaptive_stats(self):
+        """Of the last adaptive run: samples_used (sum of the counts), samples_traced, rounds, pixels_at_cap, min_count, max_count, average_luminance, quantile."""
+        s = MiAdaptiveStats(); self.L.check(self.L.L.mi_render_adaptive_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in MiAdaptiveStats._fields_}
 
     def set_fields(self, fields):
         """Field channels of the first camera hit (the reference's `multichannel` + `field` integrators): names out of FIELD_NAMES, or (name, undefined) with a float or an
@@ -603,6 +645,8 @@ class HostIntegrator:
 
     def __init__(self, scene, spp=None, devices=(0,), planes_per_batch=0, integrator=None, preview_interval_ms=-1.0, max_depth=None, emitter_samples=None, bsdf_samples=None, shading_samples=None, ray_length=None):
         L = scene.L.L; self.L = L; self.scene = scene; sc = scene.sc
+        if sc.get("adaptive"):      # never rendered uniformly without saying so
+            raise MiError(3, "HostIntegrator: the host mirror does not offer adaptive sampling (the scene description holds `adaptive` parameters); use Render.run_adaptive")
         L.mi_host_create_ex.restype = C.c_void_p; L.mi_host_last_error.restype = C.c_char_p; L.mi_host_statistics.restype = C.c_char_p
         L.mi_host_create_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int, C.c_double]
         L.mi_host_preprocess.argtypes = [C.c_void_p, C.c_void_p]; L.mi_host_destroy.argtypes = [C.c_void_p]; L.mi_host_statistics.argtypes = [C.c_void_p]

@@ -17,6 +17,7 @@
 #include "fields.h"
 #include "direct_const.h"
 #include "ao_const.h"
+#include "adaptive.h"
 
 extern "C" {
 void mi_launch_generate(const DScene &, const RenderConst &, const Queues &, const BatchDesc &, uint32_t, hipStream_t);
@@ -67,6 +68,10 @@ void mi_launch_patch_material_flags(TriShade *, uint32_t, const uint32_t *, uint
 void mi_launch_tri_records(const mi::GeoEditTables &, hipStream_t);
 void mi_launch_refit_level(const mi::GeoEditTables &, const uint32_t *, uint32_t, uint32_t, uint32_t, hipStream_t);
 void mi_launch_instance_records(const mi::InstEditTables &, hipStream_t);
+void mi_launch_adapt_tile(uint32_t *, mi_tile, uint32_t, uint32_t, hipStream_t);
+void mi_launch_adapt_list(const uint32_t *, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
+void mi_launch_adapt_accumulate(const DScene &, const Queues &, const AdaptArgs &, const uint32_t *, uint32_t, uint32_t, float *, float *, hipStream_t);
+void mi_launch_adapt_compact(const uint32_t *, uint32_t, const uint32_t *, uint32_t *, uint32_t *, uint32_t *, hipStream_t);
 }
 
 // Shading stage dispatch.  Dynamic LDS: Sobol nibble tables + (small scenes) the scene tables + (scenes with non-diffuse BSDFs) the per-wave path-order list.
@@ -127,6 +132,10 @@ struct mi_render {
     // direct integrator (direct.h): its constants, and per pool the hit array (+ instance indices) of the BSDF rays in buffer 1 -- Queues::hit keeps the camera hits for the whole batch
     DirectConst dc{}; float4 *hitB[kMaxPools] = {}; int32_t *hitInstB[kMaxPools] = {};
     AoConst ac{};   // ambient-occlusion integrator (ao.h): its constants; ray_length follows the scene under the automatic length (beginRun)
+    // adaptive sampling (adaptive.h; mi_render_set_adaptive): nothing below is allocated before the first adaptive run.  adaptFilm: the film holds an adaptive run (weights of one
+    // sample per pixel: no other run or merge may add to it).  adActive: the active list of this round and the next; adList[pool]: the triple list of the batch on that pool
+    bool adaptOn = false, adaptFilm = false; mi_adaptive_params ap{}; mi_adaptive_stats as{}; AdaptArgs ad{}; float adQuantile = 0;
+    uint32_t *adActive[2] = {}, *adWave = nullptr, *adNNext = nullptr, *adHostN = nullptr, *adList[kMaxPools] = {}; uint64_t adListPaths = 0; uint32_t adPix = 0;
     uint64_t sceneRev = 0, filmRev = 0;   // scene revision `sc` was copied from / the samples in the film (and the field film) were traced at
     Queues &pool(int i) { return i ? qx[i - 1] : q; }
     hipStream_t poolStream(int i) { return i ? streamx[i - 1] : stream; }
@@ -991,6 +1000,7 @@ static void releaseFields(mi_render *r) {
     for (hipEvent_t &e : r->fieldDone) if (e) { (void) hipEventDestroy(e); e = nullptr; }
     r->fieldFilm = r->fieldSpill = r->fieldTmp = nullptr; r->dTriShape = nullptr; r->fieldFloats = 0; r->nFields = 0; r->fa = FieldArgs{};
 }
+static void releaseAdaptive(mi_render *r);
 void mi_render_destroy(mi_render *r) {
     if (!r) return;
     (void) hipSetDevice(r->scene->h.device);
@@ -1004,6 +1014,7 @@ void mi_render_destroy(mi_render *r) {
     if (r->layoutTmp) (void) hipFree(r->layoutTmp);
     if (r->mergeTmp) (void) hipFree(r->mergeTmp);
     releaseFields(r);
+    releaseAdaptive(r);
     if (r->dNib) (void) hipFree(r->dNib);
     if (r->pollHost) (void) hipHostFree(r->pollHost);
     if (r->pollEv) (void) hipEventDestroy(r->pollEv);
@@ -1020,6 +1031,7 @@ int mi_render_clear(mi_render *r) {
     if (r->nFields) { HIPCHK(hipMemsetAsync(r->fieldFilm, 0, r->fieldFloats * 4, r->stream)); HIPCHK(hipMemsetAsync(r->fieldSpill, 0, r->fieldFloats * 4, r->stream)); }
     if (r->q.counters) HIPCHK(hipMemsetAsync(r->q.counters, 0, 32, r->stream));
     for (Queues &Q : r->qx) if (Q.counters) HIPCHK(hipMemsetAsync(Q.counters, 0, 32, r->stream));
+    r->adaptFilm = false; r->as = mi_adaptive_stats{};      // adaptive state and counts are zeroed when the next adaptive run starts
     HIPCHK(hipStreamSynchronize(r->stream)); r->samplesTotal = 0; r->mergedRays = r->mergedShadow = r->mergedPathLen = r->mergedSamples = 0; r->filmRev = r->scene->h.revision; r->cancel.store(0); return MI_OK;
 }
 void mi_render_cancel(mi_render *r) { if (r) r->cancel.store(1); }
@@ -1188,6 +1200,7 @@ int mi_render_run(mi_render *r, mi_tile tile, uint32_t s0, uint32_t s1) { return
 int mi_render_run_rows(mi_render *r, mi_tile tile, uint32_t rowStride, uint32_t s0, uint32_t s1) {
     if (!r) return fail(MI_ERR_INVALID, "mi_render_run: null");
     if (rowStride == 0) return fail(MI_ERR_INVALID, "mi_render_run_rows: row stride must be >= 1");
+    if (r->adaptFilm) return fail(MI_ERR_INVALID, "mi_render_run: the film holds an adaptive run (weights of one sample per pixel); call mi_render_clear first");
     const mi::SceneHost &h = r->scene->h;
     if (tile.x1 <= tile.x0 || tile.y1 <= tile.y0 || tile.x1 > h.width || tile.y1 > h.height) return fail(MI_ERR_INVALID, "mi_render_run: tile outside the film");
     if (s1 < s0 || s1 > r->p.spp) return fail(MI_ERR_INVALID, "mi_render_run: sample range outside [0, spp]");
@@ -1288,6 +1301,7 @@ int mi_render_read_film(mi_render *r, int layout, float *host) {
 // without peer access: staged through the host.  Both renders must be idle.  The host mirror calls this along a reduction tree (integrator_host.cpp).
 int mi_render_merge_film(mi_render *dst, mi_render *src) {
     if (!dst || !src || dst == src) return fail(MI_ERR_INVALID, "mi_render_merge_film: two different render handles are needed");
+    if (dst->adaptFilm || src->adaptFilm) return fail(MI_ERR_INVALID, "mi_render_merge_film: a film that holds an adaptive run (weights of one sample per pixel) cannot be merged");
     if (dst->filmFloats != src->filmFloats) return fail(MI_ERR_INVALID, "mi_render_merge_film: the two renders have different films");
     if (dst->nFields != src->nFields || memcmp(dst->fields, src->fields, sizeof(mi_field) * dst->nFields)) return fail(MI_ERR_INVALID, "mi_render_merge_film: the two renders hold different field lists (mi_render_set_fields)");
     const int dd = dst->scene->h.device, sd = src->scene->h.device; const size_t n = dst->filmFloats;
@@ -1353,6 +1367,179 @@ int mi_render_samples(mi_render *r, const uint32_t *pairs, uint64_t n, float *ou
     if (!rc) { hipError_t e = hipMemcpy(outLi, dOut, n * 12, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = fail(MI_ERR_DEVICE, hipGetErrorString(e)); }
     (void) hipFree(dList); (void) hipFree(dOut); (void) hipFree(dSlots);
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------ adaptive sampling (adaptive.h, kernels_adaptive.hip)
+// approx_erfinv of adaptive.cpp:26-60 (M. Giles' single-precision polynomial): its constants and operation order are part of the arithmetic contract, like the BSDF numerics
+static float approxErfinv(float x) {
+    float w = -std::log((1.0f - x) * (1.0f + x)), p;
+    if (w < 5.000000f) {
+        w = w - 2.500000f;
+        p = 2.81022636e-08f; p = 3.43273939e-07f + p * w; p = -3.5233877e-06f + p * w; p = -4.39150654e-06f + p * w; p = 0.00021858087f + p * w;
+        p = -0.00125372503f + p * w; p = -0.00417768164f + p * w; p = 0.246640727f + p * w; p = 1.50140941f + p * w;
+    } else {
+        w = sqrtf(w) - 3.000000f;
+        p = -0.000200214257f; p = 0.000100950558f + p * w; p = 0.00134934322f + p * w; p = -0.00367342844f + p * w; p = 0.00573950773f + p * w;
+        p = -0.0076224613f + p * w; p = 0.00943887047f + p * w; p = 1.00167406f + p * w; p = 2.83297682f + p * w;
+    }
+    return p * x;
+}
+static const uint32_t kAdaptLastIndex = (1u << 24) - 1u;      // last index of the independent stream: kept for the luminance estimate, never reached by a render
+static bool filmHoldsSamples(const mi_render *r) { return r->samplesTotal || r->mergedSamples || r->adaptFilm; }
+static void releaseAdaptive(mi_render *r) {
+    void *ps[] = {r->ad.fp, r->ad.ms, r->ad.n, r->ad.counts, r->adActive[0], r->adActive[1], r->adWave, r->adNNext};
+    for (void *p : ps) if (p) (void) hipFree(p);
+    for (uint32_t *&l : r->adList) { if (l) (void) hipFree(l); l = nullptr; }
+    if (r->adHostN) (void) hipHostFree(r->adHostN);
+    r->ad = AdaptArgs{}; r->adActive[0] = r->adActive[1] = r->adWave = r->adNNext = r->adHostN = nullptr; r->adListPaths = 0; r->adPix = 0;
+}
+int mi_render_set_adaptive(mi_render *r, const mi_adaptive_params *p) {
+    if (!r) return fail(MI_ERR_INVALID, "mi_render_set_adaptive: null render");
+    if (filmHoldsSamples(r)) return fail(MI_ERR_INVALID, "mi_render_set_adaptive: the film holds samples (set the adaptive parameters after mi_render_create or mi_render_clear)");
+    if (!p) { r->adaptOn = false; return MI_OK; }
+    if (r->p.sampler != MI_SAMPLER_INDEPENDENT) return fail(MI_ERR_UNSUPPORTED, "The error-controlling integrator should only be used in conjunction with the independent sampler");      // adaptive.cpp:150-152
+    if (r->p.spp < 8) return fail(MI_ERR_INVALID, "Starting the adaptive integrator with less than 8 samples per pixel does not make much sense -- giving up.");      // :210-212
+    if (r->p.integrator == MI_INTEGRATOR_DIRECT || r->p.integrator == MI_INTEGRATOR_AO)
+        return fail(MI_ERR_UNSUPPORTED, "mi_render_set_adaptive: adaptive sampling over the direct and ao integrators is not implemented (their adaptive queries renumber the sample arrays, direct.cpp:192, ao.cpp:102); use path, volpath_simple or volpath");
+    if (r->nFields) return fail(MI_ERR_UNSUPPORTED, "mi_render_set_adaptive: field channels are set on this render (mi_render_set_fields); adaptive sampling does not fill a field film");
+    if (p->max_sample_factor == 0) return fail(MI_ERR_INVALID, "mi_render_set_adaptive: max_sample_factor must not be 0 (negative: no cap, positive: at most max_sample_factor x spp samples per pixel)");
+    if (!(p->max_error >= 0)) return fail(MI_ERR_INVALID, "mi_render_set_adaptive: max_error must be >= 0");
+    if (!(p->p_value > 0 && p->p_value < 1)) return fail(MI_ERR_INVALID, "mi_render_set_adaptive: p_value must lie in (0, 1)");
+    if (p->max_sample_factor > 0 && (uint64_t) p->max_sample_factor * r->p.spp >= kAdaptLastIndex)
+        return fail(MI_ERR_INVALID, "mi_render_set_adaptive: max_sample_factor x spp reaches the end of the independent stream (2^24 - 1 samples per pixel; the last index is kept for the luminance estimate)");
+    r->ap = *p; r->adaptOn = true;
+    r->adQuantile = std::fabs(approxErfinv(-1 + p->p_value)) * 1.41421356237309504880f;      // the reference omits the absolute value: its quantile is negative (include/mi355pt.h)
+    return MI_OK;
+}
+int mi_render_read_sample_counts(mi_render *r, uint32_t *out) {
+    if (!r || !out) return fail(MI_ERR_INVALID, "mi_render_read_sample_counts: null argument");
+    const mi::SceneHost &h = r->scene->h; const size_t n = (size_t) h.width * h.height;
+    if (!r->ad.counts || !r->adaptFilm) { memset(out, 0, n * 4); return MI_OK; }      // nothing rendered adaptively since the last clear
+    HIPCHK(hipSetDevice(h.device)); HIPCHK(hipMemcpy(out, r->ad.counts, n * 4, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+int mi_render_adaptive_stats(mi_render *r, mi_adaptive_stats *out) {
+    if (!r || !out) return fail(MI_ERR_INVALID, "mi_render_adaptive_stats: null argument");
+    *out = r->as; return MI_OK;
+}
+int mi_render_run_adaptive(mi_render *r, mi_tile tile) {
+    if (!r) return fail(MI_ERR_INVALID, "mi_render_run_adaptive: null render");
+    if (!r->adaptOn) return fail(MI_ERR_INVALID, "mi_render_run_adaptive: no adaptive parameters are set (mi_render_set_adaptive)");
+    const mi::SceneHost &h = r->scene->h;
+    if (tile.x1 <= tile.x0 || tile.y1 <= tile.y0 || tile.x1 > h.width || tile.y1 > h.height) return fail(MI_ERR_INVALID, "mi_render_run_adaptive: tile outside the film");
+    if (filmHoldsSamples(r)) return fail(MI_ERR_INVALID, "mi_render_run_adaptive: the film holds samples; an adaptive run needs a clear film (one adaptive run per mi_render_clear)");
+    if (r->nFields) return fail(MI_ERR_UNSUPPORTED, "mi_render_run_adaptive: field channels are set on this render (mi_render_set_fields)");
+    HIPCHK(hipSetDevice(h.device));
+    const uint32_t spp = r->p.spp, R = r->ap.round_samples ? r->ap.round_samples : spp;
+    const uint32_t cap = r->ap.max_sample_factor > 0 ? (uint32_t) r->ap.max_sample_factor * spp : kAdaptLastIndex - 1u;
+    const uint32_t nPixFilm = h.width * h.height, npix = (tile.x1 - tile.x0) * (tile.y1 - tile.y0);
+    const int hb = (int) std::floor(h.filterRadiusEff + 0.5f), side = 2 * hb + 1;
+    // footprint, state and count buffers: allocated at the first adaptive run, freed with the render
+    if (!r->ad.fp) {
+        const uint64_t fpBytes = (uint64_t) nPixFilm * side * side * 5u * 4u, bytes = fpBytes + (uint64_t) nPixFilm * (8u + 4u + 4u + 4u + 4u) + MI_ADAPT_RANGES * 4u + 4u;
+        const char *lim = getenv("MI355PT_POOL_LIMIT");
+        if (lim && atoll(lim) > 0 && bytes > (uint64_t) atoll(lim)) return fail(MI_ERR_DEVICE, "mi_render_run_adaptive: the footprint, state and count buffers (" + std::to_string(bytes) + " bytes) are larger than MI355PT_POOL_LIMIT");
+        size_t freeB = 0, totalB = 0; HIPCHK(hipMemGetInfo(&freeB, &totalB));
+        if (bytes > freeB) return fail(MI_ERR_DEVICE, "mi_render_run_adaptive: the footprint, state and count buffers (" + std::to_string(bytes) + " bytes) are larger than the free device memory");
+        hipError_t e = hipMalloc((void **) &r->ad.fp, fpBytes);
+        if (e == hipSuccess) e = hipMalloc((void **) &r->ad.ms, (size_t) nPixFilm * 8);
+        if (e == hipSuccess) e = hipMalloc((void **) &r->ad.n, (size_t) nPixFilm * 4);
+        if (e == hipSuccess) e = hipMalloc((void **) &r->ad.counts, (size_t) nPixFilm * 4);
+        if (e == hipSuccess) e = hipMalloc((void **) &r->adActive[0], (size_t) nPixFilm * 4);
+        if (e == hipSuccess) e = hipMalloc((void **) &r->adActive[1], (size_t) nPixFilm * 4);
+        if (e == hipSuccess) e = hipMalloc((void **) &r->adWave, MI_ADAPT_RANGES * 4);
+        if (e == hipSuccess) e = hipMalloc((void **) &r->adNNext, 4);
+        if (e == hipSuccess) e = hipHostMalloc((void **) &r->adHostN, 4, hipHostMallocDefault);
+        if (e != hipSuccess) { (void) hipGetLastError(); releaseAdaptive(r); return fail(MI_ERR_DEVICE, std::string("mi_render_run_adaptive: cannot allocate the footprint, state and count buffers: ") + hipGetErrorString(e)); }
+        r->adPix = nPixFilm;
+    }
+    // average luminance: given, or the estimate over N = min(10000, W x H) pixels at the stream's last sample index, through the route of mi_render_samples (taken again
+    // at every run: the scene may have been edited); summed in double in index order
+    float avgLum = r->ap.average_luminance;
+    if (!(avgLum > 0)) {
+        const uint64_t wh = nPixFilm, N = std::min<uint64_t>(10000u, wh);
+        std::vector<uint32_t> pairs(N * 3); std::vector<float> li(N * 3);
+        for (uint64_t i = 0; i < N; ++i) { const uint64_t p = i * wh / N; pairs[i * 3] = (uint32_t) (p % h.width); pairs[i * 3 + 1] = (uint32_t) (p / h.width); pairs[i * 3 + 2] = kAdaptLastIndex; }
+        { const int rc = mi_render_samples(r, pairs.data(), N, li.data()); if (rc) return rc; }
+        double sum = 0; for (uint64_t i = 0; i < N; ++i) sum += (double) (li[i * 3] * 0.212671f + li[i * 3 + 1] * 0.715160f + li[i * 3 + 2] * 0.072169f);
+        avgLum = (float) (sum / (double) N);
+    }
+    RunGuard running; { const int rc = beginRun(r, running, true, "mi_render_run_adaptive"); if (rc) return rc; }
+    // batches: a round of R sample indices over nAct pixels is cut into batches of `planes` indices that fit the pool, as mi_render_run_rows cuts the planes of a tile
+    uint32_t planes = r->p.planes_per_batch;
+    if (!planes) { const char *v = getenv("MI355PT_BATCH_PATHS"); const uint64_t target = v && atoll(v) > 0 ? (uint64_t) atoll(v) : (uint64_t) (64u << 20); planes = (uint32_t) std::max<uint64_t>(1, target / npix); }
+    planes = std::min(planes, std::min(R, cap));
+    if (!r->p.planes_per_batch && planes < R && R <= cap) { const uint32_t ns = (uint32_t) r->nStreams; uint32_t nb = (R + planes - 1) / planes; nb = (nb + ns - 1) / ns * ns; planes = (R + nb - 1) / nb; }
+    uint64_t need = (uint64_t) npix * planes;
+    if (need > 0xFFFFFF00ull) return fail(MI_ERR_INVALID, "mi_render_run_adaptive: batch larger than 2^32 paths");
+    while (need > r->poolPaths) {
+        int rc = allocPool(r, need);
+        if (!rc) break;
+        (void) hipGetLastError(); r->poolPaths = 0;
+        if (r->p.planes_per_batch || planes <= 1) return rc;
+        planes = (planes + 1) / 2; need = (uint64_t) npix * planes;
+    }
+    const int nPools = r->nStreams;
+    if (need > r->adListPaths || !r->adList[nPools - 1]) {
+        for (uint32_t *&l : r->adList) { if (l) (void) hipFree(l); l = nullptr; }
+        r->adListPaths = 0;
+        for (int i = 0; i < nPools; ++i) HIPCHK(hipMalloc((void **) &r->adList[i], need * 12));
+        r->adListPaths = need;
+    }
+    r->ad.n_pix = nPixFilm; r->ad.hb = hb; r->ad.spp = spp; r->ad.cap = cap; r->ad.max_error = r->ap.max_error; r->ad.quantile = r->adQuantile; r->ad.lum_floor = avgLum * 0.01f;
+    r->as = mi_adaptive_stats{}; r->as.average_luminance = avgLum; r->as.quantile = r->adQuantile;
+    r->adaptFilm = true;      // from here on the film is an adaptive one, whether the run completes or not
+    HIPCHK(hipMemsetAsync(r->ad.fp, 0, (size_t) nPixFilm * side * side * 5u * 4u, r->stream)); HIPCHK(hipMemsetAsync(r->ad.ms, 0, (size_t) nPixFilm * 8, r->stream));
+    HIPCHK(hipMemsetAsync(r->ad.n, 0, (size_t) nPixFilm * 4, r->stream)); HIPCHK(hipMemsetAsync(r->ad.counts, 0, (size_t) nPixFilm * 4, r->stream));
+    mi_launch_adapt_tile(r->adActive[0], tile, h.width, npix, r->stream);
+    size_t evUsed = 0; r->launchesAll = 0;
+    HIPCHK(hipEventRecord(r->evBegin, r->stream));
+    if (nPools > 1) HIPCHK(hipEventRecord(r->joinEv[0], r->stream));
+    for (int i = 1; i < nPools; ++i) HIPCHK(hipStreamWaitEvent(r->poolStream(i), r->joinEv[0], 0));
+    uint32_t nAct = npix, begin = 0; int cur = 0, batch = 0, lastPool = -1; uint64_t traced = 0; uint32_t rounds = 0;
+    while (nAct) {
+        const uint32_t roundLen = std::min(R, cap - begin);      // (begin < cap while a pixel is active: every pixel stops at cap)
+        for (uint32_t s = 0; s < roundLen; s += planes, ++batch) {
+            if (r->cancel.exchange(0)) { HIPCHK(hipDeviceSynchronize()); return fail(MI_CANCELLED, "render cancelled"); }
+            const int pool = batch % nPools; hipStream_t st = r->poolStream(pool);
+            BatchDesc bd{}; bd.tile = mi_tile{0, 0, h.width, h.height}; bd.n_pix = nAct; bd.n_planes = std::min(planes, roundLen - s); bd.sample_begin = begin + s;
+            bd.n_paths = (uint64_t) nAct * bd.n_planes; bd.list = r->adList[pool]; bd.row_stride = 1;
+            mi_launch_adapt_list(r->adActive[cur], nAct, bd.n_paths, bd.sample_begin, h.width, r->adList[pool], st);
+            { const int rc = traceBatch(r, bd, bd.list, evUsed, pool); if (rc) return rc; }
+            // a pixel's state and footprint are plain read-modify-writes in sample order: the accumulate kernels run in batch order, chained as filmDone chains k_film
+            if (nPools > 1 && lastPool >= 0 && lastPool != pool) HIPCHK(hipStreamWaitEvent(st, r->filmDone[lastPool], 0));
+            mi_launch_adapt_accumulate(h.d, r->pool(pool), r->ad, r->adActive[cur], nAct, bd.n_planes, r->film, r->spill, st);
+            if (nPools > 1) { HIPCHK(hipEventRecord(r->filmDone[pool], st)); lastPool = pool; }
+            mark(r, 0, evUsed, st);
+            r->samplesTotal += bd.n_paths; traced += bd.n_paths;
+        }
+        // the next active list, behind the round's last accumulate kernel (which waited for all before it); one 4-byte read-back sizes the next round
+        hipStream_t st = r->poolStream(lastPool < 0 ? 0 : lastPool);
+        mi_launch_adapt_compact(r->adActive[cur], nAct, r->ad.counts, r->adWave, r->adActive[cur ^ 1], r->adNNext, st);
+        HIPCHK(hipMemcpyAsync(r->adHostN, r->adNNext, 4, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipGetLastError());
+        if (*r->adHostN > nAct) return fail(MI_ERR_DEVICE, "mi_render_run_adaptive: the compaction returned more pixels than it was given");
+        nAct = *r->adHostN; cur ^= 1; begin += roundLen; ++rounds;
+    }
+    for (int i = 1; i < nPools; ++i) { HIPCHK(hipEventRecord(r->joinEv[i], r->poolStream(i))); HIPCHK(hipStreamWaitEvent(r->stream, r->joinEv[i], 0)); }
+    mark(r, 0, evUsed);
+    HIPCHK(hipEventRecord(r->evEnd, r->stream));
+    HIPCHK(hipStreamSynchronize(r->stream));
+    HIPCHK(hipGetLastError());
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r->evBegin, r->evEnd)); r->stats.render_ms = ms;
+    r->stats.extend_ms = r->stats.shade_ms = r->stats.shadow_ms = r->stats.other_ms = 0; r->stats.extend_launches = 0;
+    if (r->profiling) {
+        for (size_t i = 0; i + 1 < evUsed; ++i) {
+            float t = 0; if (hipEventElapsedTime(&t, r->evPool[i], r->evPool[i + 1]) != hipSuccess) continue;
+            switch (r->evTag[i]) { case 1: r->stats.extend_ms += t; r->stats.extend_launches++; break; case 2: r->stats.shade_ms += t; break; case 3: r->stats.shadow_ms += t; break; default: r->stats.other_ms += t; }
+        }
+    }
+    std::vector<uint32_t> counts(nPixFilm); HIPCHK(hipMemcpy(counts.data(), r->ad.counts, (size_t) nPixFilm * 4, hipMemcpyDeviceToHost));
+    r->as.samples_traced = traced; r->as.rounds = rounds; r->as.min_count = 0xFFFFFFFFu;
+    for (uint32_t y = tile.y0; y < tile.y1; ++y) for (uint32_t x = tile.x0; x < tile.x1; ++x) {
+        const uint32_t c = counts[(size_t) y * h.width + x];
+        r->as.samples_used += c; r->as.min_count = std::min(r->as.min_count, c); r->as.max_count = std::max(r->as.max_count, c); if (c == cap) ++r->as.pixels_at_cap;
+    }
+    return MI_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ field channels (kernels_field.hip)

@@ -12,6 +12,12 @@ for `luminance`.  Other output formats cannot hold the groups: an error that nam
 `--ao N [--ao-length L]` renders any scene file with the ambient-occlusion integrator (`ao`: N shading samples, occlusion rays of length L, default automatic) in
 place of the file's own integrator; the field channels of a `multichannel` scene stay.  A scene file whose integrator is `ao` needs no option.
 
+`--adaptive [MAXERROR] [--max-sample-factor N]` wraps the file's `path` / `volpath_simple` / `volpath` integrator in per-pixel error control (the reference's `adaptive`
+integrator: every pixel takes samples until the half width of its confidence interval is at most MAXERROR x its mean luminance, default 0.05, or N x spp samples are
+spent, default 32); a scene file whose integrator is `adaptive` needs no option.  The independent sampler and a sample count of at least 8 are required.
+`--sample-counts out.npy` writes the H x W map of samples per pixel (`out_000.npy`, ... for frames).  Both work with `--orbit`, `--spin` and `--focus-pull`: clear, edit,
+adaptive run per frame.
+
 `--orbit N [--orbit-axis x|y|z]` renders a turntable: N frames with the camera rotated in steps of 360 / N degrees about the axis through the centre of the scene's
 box.  The scene is committed once; every frame is an in-place camera edit of the committed scene (Scene.update_camera), a clear and a run -- no tree build, no
 upload -- and is written to `<output>_000.<ext>`, `<output>_001.<ext>`, ...
@@ -116,6 +122,25 @@ def use_ao(sc, shading_samples, ray_length=-1.0):
     return sc
 
 
+def use_adaptive(sc, max_error=0.05, max_sample_factor=None):
+    """`--adaptive [MAXERROR] [--max-sample-factor N]`: the scene description with per-pixel error control around its path / volpath_simple / volpath integrator.  A scene
+    file that holds an `adaptive` integrator keeps its own pValue (and whatever of the two is not given here)."""
+    from .scenes import INTEGRATOR_DIRECT, INTEGRATOR_AO
+    if (sc.get("integrator", 0) or 0) in (INTEGRATOR_DIRECT, INTEGRATOR_AO):
+        raise ValueError("--adaptive wraps a path, volpath_simple or volpath integrator; direct and ao are not supported underneath")
+    if sc.get("fields"):
+        raise ValueError("--adaptive cannot be combined with the field channels of a multichannel scene")
+    if max_error is not None and not max_error >= 0:
+        raise ValueError("--adaptive expects a maximum relative error >= 0")
+    if max_sample_factor is not None and max_sample_factor == 0:
+        raise ValueError("--max-sample-factor must not be 0 (negative: no limit)")
+    ad = dict(sc.get("adaptive") or dict(max_error=0.05, p_value=0.05, max_sample_factor=32))
+    if max_error is not None: ad["max_error"] = float(max_error)
+    if max_sample_factor is not None: ad["max_sample_factor"] = int(max_sample_factor)
+    sc.adaptive = ad
+    return sc
+
+
 def write_outputs(sc, render, out, rgb=None, fields=None):
     """the developed film (and, for a multichannel scene, the field groups) of `render` -> `out`; False (message printed) when the format cannot hold them"""
     if rgb is None:
@@ -144,6 +169,9 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--ao", type=int, default=0, metavar="N", help="render with the ambient-occlusion integrator (N shading samples) in place of the scene's own integrator")
     ap.add_argument("--ao-length", type=float, default=None, metavar="L", help="length of the occlusion rays of --ao (default: automatic, half the radius of the scene's bounding sphere)")
+    ap.add_argument("--adaptive", type=float, nargs="?", const=0.05, default=None, metavar="MAXERROR", help="per-pixel error control around the scene's path / volpath integrator (maximum relative error, default 0.05)")
+    ap.add_argument("--max-sample-factor", type=int, default=None, metavar="N", help="with adaptive sampling: at most N x spp samples per pixel (negative: no limit; default 32)")
+    ap.add_argument("--sample-counts", default=None, metavar="out.npy", help="with adaptive sampling: write the H x W map of samples per pixel")
     ap.add_argument("--orbit", type=int, default=0, metavar="N", help="turntable of N frames about the scene box's centre: one commit, one in-place camera edit per frame")
     ap.add_argument("--orbit-axis", choices=["x", "y", "z"], default="y")
     ap.add_argument("--spin", type=int, default=0, metavar="N", help="N frames with every instance turned about its own origin: one commit, one in-place instance edit per frame")
@@ -159,6 +187,10 @@ def main(argv=None):
         k, v = d.split("=", 1); params[k] = v
     if a.ao < 0 or (a.ao_length is not None and not a.ao):
         raise SystemExit("--ao expects a number of shading samples >= 1; --ao-length belongs to --ao N")
+    if a.sample_counts is not None and not a.sample_counts.endswith(".npy"):
+        raise SystemExit("--sample-counts expects a .npy file name")
+    if a.adaptive is not None and a.ao:
+        raise SystemExit("--adaptive cannot be combined with --ao (adaptive sampling runs over path, volpath_simple or volpath)")
     if a.orbit < 0:
         raise SystemExit("--orbit expects a frame count >= 1")
     if a.spin < 0 or (a.spin and a.orbit):
@@ -174,6 +206,18 @@ def main(argv=None):
             sc.spp = a.spp
         if a.ao:
             use_ao(sc, a.ao, -1.0 if a.ao_length is None else a.ao_length)
+        if a.adaptive is not None or (a.max_sample_factor is not None and sc.get("adaptive")):
+            try:
+                use_adaptive(sc, a.adaptive, a.max_sample_factor)
+            except ValueError as e:
+                print(f"error: {e}", file=sys.stderr)
+                return 1
+        elif a.max_sample_factor is not None:
+            print("error: --max-sample-factor belongs to --adaptive (or to a scene file with an adaptive integrator)", file=sys.stderr)
+            return 1
+        if a.sample_counts is not None and not sc.get("adaptive"):
+            print("error: --sample-counts needs adaptive sampling (--adaptive, or a scene file with an adaptive integrator)", file=sys.stderr)
+            return 1
         out = a.output or (a.scene.rsplit(".", 1)[0] + ".exr")          # hdrfilm's default fileFormat (src/films/hdrfilm.cpp: openexr)
         if a.spin and not (sc.get("instances") or []):
             print(f"error: {a.scene}: --spin turns the instances of shape groups, and this scene has none", file=sys.stderr)
@@ -190,6 +234,16 @@ def main(argv=None):
         scene = Scene(sc, device=a.device)
         render = Render(scene, device=a.device)
         t2 = time.perf_counter()
+        frame_no = [0]
+
+        def go():      # one frame into the clear film: the adaptive run of a scene with adaptive parameters (api.Render picked them up), else every pixel's spp samples
+            if not sc.get("adaptive"):
+                return render.run()
+            render.run_adaptive()
+            if a.sample_counts is not None:
+                frames = a.orbit or a.spin or a.focus_pull
+                np.save(a.sample_counts[:-4] + f"_{frame_no[0]:03d}.npy" if frames else a.sample_counts, render.sample_counts())
+            frame_no[0] += 1
         n = sc.width * sc.height * sc.spp
         if a.focus_pull:
             stem, ext = out.rsplit(".", 1); frame_s = []
@@ -197,7 +251,7 @@ def main(argv=None):
             for f, (dist, c2w) in enumerate(zip(pull, cams)):
                 tf = time.perf_counter()
                 if c2w is not None: scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far)
-                scene.update_lens(sc.aperture_radius, dist); render.clear(); render.run()
+                scene.update_lens(sc.aperture_radius, dist); render.clear(); go()
                 frame_s.append(time.perf_counter() - tf)
                 if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}"):
                     return 1
@@ -209,7 +263,7 @@ def main(argv=None):
             stem, ext = out.rsplit(".", 1); frame_s = []
             for f, c2w in enumerate(orbit_cameras(sc, a.orbit, a.orbit_axis)):
                 tf = time.perf_counter()
-                scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far); render.clear(); render.run()
+                scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far); render.clear(); go()
                 frame_s.append(time.perf_counter() - tf)
                 if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}"):
                     return 1
@@ -221,7 +275,7 @@ def main(argv=None):
             stem, ext = out.rsplit(".", 1); frame_s = []
             for f, insts in enumerate(spin_instances(sc, a.spin, a.spin_axis)):
                 tf = time.perf_counter()
-                scene.update_instances(insts); render.clear(); render.run()
+                scene.update_instances(insts); render.clear(); go()
                 frame_s.append(time.perf_counter() - tf)
                 if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}"):
                     return 1
@@ -229,7 +283,7 @@ def main(argv=None):
             print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles, {len(insts)} instances; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s once ({builds} tree build, {rev} instance edits), "
                   f"{a.spin} frames, render {mean:.3f} s per frame ({n / mean / 1e6:.1f} Msamples/s) -> {stem}_000.{ext} .. {stem}_{a.spin - 1:03d}.{ext}")
             return 0
-        render.run()
+        go()
         rgb = render.read_film(2)
         fields = render.read_fields(2) if render.field_names else None
         t3 = time.perf_counter()
@@ -238,7 +292,11 @@ def main(argv=None):
         return 1
     if not write_outputs(sc, render, out, rgb, fields):
         return 1
-    print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s, "
+    spp_text = f"{sc.spp} spp"
+    if sc.get("adaptive"):      # the samples the adaptive run traced, and what it kept
+        st = render.adaptive_stats(); n = st["samples_traced"]
+        spp_text = f"adaptive from {sc.spp} spp ({st['min_count']} .. {st['max_count']} per pixel, mean {st['samples_used'] / (sc.width * sc.height):.1f}, {st['rounds']} rounds)"
+    print(f"{sc.name}: {sc.width}x{sc.height}, {spp_text}, {len(sc.idx)} triangles; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s, "
           f"render {t3 - t2:.3f} s ({n / (t3 - t2) / 1e6:.1f} Msamples/s) -> {out}")
     return 0
 

@@ -6,7 +6,7 @@ What is read (reference: src/librender/scenehandler.cpp:104-140 tag table, :300-
 substitution, <include>, <ref>, <integer> <float> <boolean> <string> <point> <vector> <rgb> <srgb> <spectrum> <blackbody>, <transform> with
 <translate> <rotate> <scale> <matrix> <lookat>, and the plugin tags <integrator> <sensor> <sampler> <film> <rfilter> <shape> <bsdf>
 <texture> <emitter>.  Plugins understood = the ones the hot path implements:
-    integrator  path, volpath_simple, volpath, direct (shadingSamples / emitterSamples / bsdfSamples), ao (shadingSamples / rayLength), multichannel + field
+    integrator  path, volpath_simple, volpath, direct (shadingSamples / emitterSamples / bsdfSamples), ao (shadingSamples / rayLength), multichannel + field, adaptive (maxError / pValue / maxSampleFactor around path, volpath_simple or volpath)
     sensor      perspective                                  (src/librender/sensor.cpp:225-305 fov / fovAxis / focalLength)
                 thinlens                                     (src/sensors/thinlens.cpp: + apertureRadius, focusDistance)
     sampler     independent, sobol
@@ -952,8 +952,10 @@ class _SceneBuilder:
             # number of `field` integrators (src/integrators/misc/field.cpp), in document order = the order of the film's pixelFormat / channelNames lists
             nested = [c for _, c in integ.children_of("integrator")]; radiance = [c for c in nested if c.type != "field"]
             for c in radiance:
+                if c.type == "adaptive":
+                    raise SceneError("<integrator type=\"adaptive\"> inside <integrator type=\"multichannel\"> is not supported: adaptive sampling does not fill a field film")
                 if c.type not in integrators:
-                    raise SceneError(f"integrator \"{c.type}\" is not supported: this framework implements path, volpath_simple, volpath and direct, and ao")
+                    raise SceneError(f"integrator \"{c.type}\" is not supported: this framework implements path, volpath_simple, volpath and direct, and ao, and adaptive around path, volpath_simple or volpath")
             if len(radiance) != 1:
                 raise SceneError(f"<integrator type=\"multichannel\"> must hold exactly one radiance integrator (path, volpath_simple, volpath or direct, or ao) next to its field integrators, found {len(radiance)}")
             if nested[0] is not radiance[0]:
@@ -967,8 +969,24 @@ class _SceneBuilder:
                 undef = (float(undef),) * 3 if np.ndim(undef) == 0 else tuple(float(x) for x in np.asarray(undef, f32).reshape(3))
                 c.check_all_used(); fields.append((fname, undef))
             integ.check_all_used(); n_nested = len(nested); integ = radiance[0]
+        adaptive = None
+        if integ.type == "adaptive":
+            # src/integrators/misc/adaptive.cpp:97-140: maxError, pValue, maxSampleFactor, verbose around exactly one sub-integrator; here path, volpath_simple or volpath
+            adaptive = dict(max_error=float(f32(integ.get("maxError", 0.05))), p_value=float(f32(integ.get("pValue", 0.05))), max_sample_factor=int(integ.get("maxSampleFactor", 32)))      # single precision, as the library takes them
+            integ.get("verbose", False)                 # accepted, nothing to log
+            nested = [c for _, c in integ.children_of("integrator")]
+            if len(nested) != 1:
+                raise SceneError(f"<integrator type=\"adaptive\"> must hold exactly one sub-integrator (path, volpath_simple or volpath), found {len(nested)}")
+            sub = nested[0]
+            if sub.type in ("direct", "ao", "multichannel", "adaptive", "field"):
+                raise SceneError(f"<integrator type=\"adaptive\"> over a \"{sub.type}\" integrator is not supported: adaptive sampling runs over path, volpath_simple or volpath")
+            if adaptive["max_sample_factor"] == 0:
+                raise SceneError("<integrator type=\"adaptive\">: maxSampleFactor must not be 0 (negative: no limit)")
+            if not adaptive["max_error"] >= 0 or not 0 < adaptive["p_value"] < 1:
+                raise SceneError("<integrator type=\"adaptive\">: maxError must be >= 0 and pValue must lie in (0, 1)")
+            integ.check_all_used(); integ = sub
         if integ.type not in integrators:
-            raise SceneError(f"integrator \"{integ.type}\" is not supported: this framework implements path, volpath_simple, volpath and direct, and ao")
+            raise SceneError(f"integrator \"{integ.type}\" is not supported: this framework implements path, volpath_simple, volpath and direct, and ao, and adaptive around path, volpath_simple or volpath")
         emitter_samples = bsdf_samples = 1
         if integ.type == "direct":                      # src/integrators/direct/direct.cpp:93-108: shadingSamples sets both counts; no maxDepth / rrDepth (read as unknown properties)
             shading = int(integ.get("shadingSamples", 1))
@@ -1038,8 +1056,13 @@ class _SceneBuilder:
             smp.check_all_used()
         elif self.sampler_override:
             sampler = S.SAMPLER_SOBOL if self.sampler_override == "sobol" else S.SAMPLER_INDEPENDENT
+        if adaptive is not None:
+            if sampler != S.SAMPLER_INDEPENDENT:
+                raise SceneError("The error-controlling integrator should only be used in conjunction with the independent sampler")      # adaptive.cpp:150-152
+            if spp < 8:
+                raise SceneError("Starting the adaptive integrator with less than 8 samples per pixel does not make much sense -- giving up. (sampleCount < 8)")      # adaptive.cpp:210-212
         full_w, full_h = width, height
-        aspect = width / height                          # the camera's aspect is the FULL film's (sensor.cpp: m_aspect = size.x / size.y)
+        aspect = width / height                         # the camera's aspect is the FULL film's (sensor.cpp: m_aspect = size.x / size.y)
         if crop is not None:
             width, height = crop[2], crop[3]
         if sen.has("fov") and sen.has("focalLength"):
@@ -1148,6 +1171,8 @@ class _SceneBuilder:
             sc.filter_radius = float(f_radius)
         if f_stddev is not None:
             sc.filter_stddev = float(f_stddev)
+        if adaptive is not None:
+            sc.adaptive = adaptive                      # max_error, p_value, max_sample_factor of an `adaptive` integrator: api.Render picks them up, render.py runs run_adaptive
         sc.fields = fields                              # [(kind, undefined rgb)] of a `multichannel` integrator; kept with the film's lists for render.py and export_scene
         if fields:
             sc.pixel_formats = pixel_formats if film is not None else ["rgb"] * n_nested
@@ -1210,8 +1235,14 @@ def export_scene(sc, directory, name=None, mesh_format="serialized"):
     else:
         radiance_xml = (f'<integrator type="{integ_name}"><integer name="maxDepth" value="{sc.max_depth}"/><integer name="rrDepth" value="{sc.rr_depth}"/>'
                         f'<boolean name="strictNormals" value="{str(bool(sc.strict_normals)).lower()}"/><boolean name="hideEmitters" value="{str(bool(sc.hide_emitters)).lower()}"/></integrator>')
+    ad = sc.get("adaptive")
+    if ad:                                                # the error-controlling wrapper around path / volpath_simple / volpath; round_samples and average_luminance are render options, not the file's
+        if integ_name in ("direct", "ao") or sc.get("fields"):
+            raise SceneError("export_scene: adaptive sampling runs over path, volpath_simple or volpath, without field channels")
+        radiance_xml = (f'<integrator type="adaptive"><float name="maxError" value="{fmt([ad.get("max_error", 0.05)])}"/><float name="pValue" value="{fmt([ad.get("p_value", 0.05)])}"/>'
+                        f'<integer name="maxSampleFactor" value="{int(ad.get("max_sample_factor", 32))}"/>{radiance_xml}</integrator>')
     fields = sc.get("fields") or []; film_lists = ""
-    if fields:                                            # multichannel: the radiance integrator first, then one field integrator per entry; the film's lists as they were read
+    if fields:                                         # multichannel: the radiance integrator first, then one field integrator per entry; the film's lists as they were read
         from .api import normalize_fields
         fields = normalize_fields(fields)
         radiance_xml = '<integrator type="multichannel">' + radiance_xml + "".join(
