@@ -366,6 +366,35 @@ int mi_render_field_film_size(mi_render *r, int layout, uint32_t *height, uint32
 int mi_render_read_fields(mi_render *r, int layout, float *host_out);
 /* Debug / parity: the fields of individual (px, py, sampleIndex) triples, batched as mi_render_samples: generate, one extend, the field stage (no shading); out[n * 3F] */
 int mi_render_field_samples(mi_render *r, const uint32_t *pairs, uint64_t n, float *out);
+
+/* -- denoiser: the edge-avoiding a-trous filter of Dammertz, Sewtz, Hanika and Lensch (HPG 2010) with albedo demodulation, guided by the field channels; on the device
+ *    (csrc/denoise.h, csrc/kernels_denoise.hip).  The reference has no such component.  All values are float32 and every operation is one rounding, in the order written,
+ *    so the result equals a sequential model bit for bit (tests/denoise_model.py).
+ *    Inputs: C, N, P = H x W x 3 colour, normal guide, position guide; A = H x W x 3 albedo (optional); iterations K in 0..8, sigma_color > 0, sigma_normal > 0,
+ *    sigma_position != 0, demodulate 0 / 1.
+ *      1. K = 0: the output is C bit for bit; nothing below runs (the resolved width returned is sigma_position if positive, else 0).
+ *      2. sigma_position < 0 (automatic): over the pixels of P whose three components are all finite take the box, d = its extent per axis; the resolved width is
+ *         |sigma_position| x sqrtf((d.x d.x + d.y d.y) + d.z d.z); no such pixel, or a diagonal of 0: the position term is off (kp = 0, resolved width 0).
+ *      3. demodulate: D = A > 1e-3f ? A : 1e-3f per component (a NaN albedo gives 1e-3f), c_0 = C / D; otherwise c_0 = C.
+ *      4. levels i = 0 .. K - 1, step s = 2^i: sc = sigma_color x 2^-i, kc = 1.0f / (sc sc), kn = 1.0f / (sigma_normal sigma_normal), kp = 1.0f / (sp sp) or 0.
+ *         Pixel p visits the taps q = p + s (dx, dy), dy = -2..2 outer, dx = -2..2 inner; taps outside the image are skipped.  h = (1/16, 1/4, 3/8, 1/4, 1/16).
+ *         d2(a) = (e.x e.x + e.y e.y) + e.z e.z with e = a(p) - a(q);  x = -((d2(c_i) kc + d2(N) kn) + d2(P) kp);  w = x >= -80.0f ? (h[dy] h[dx]) expf(x) : 0
+ *         (glibc's expf; a NaN x fails the comparison, which drops every non-finite colour or guide).  A tap with w = 0 is skipped; otherwise sw += w and
+ *         sum.k += w c_i(q).k for k = r, g, b.  c_{i+1}(p) = sw > 0 ? sum / sw : c_i(p): a pixel whose own colour or guides are non-finite keeps its value.
+ *      5. output: c_K x D when demodulated, else c_K.
+ *    Refused with MI_ERR_INVALID, the message naming the parameter: iterations > 8, a non-positive or non-finite sigma_color / sigma_normal, a zero or non-finite
+ *    sigma_position, demodulate without albedo, zero width or height, NULL pointers. */
+typedef struct { uint32_t iterations; float sigma_color, sigma_normal, sigma_position; uint32_t demodulate; uint32_t pad[3]; } mi_denoise_params;
+/* the filter on host arrays (H x W x 3 each; albedo may be NULL when demodulate is 0); resolved_sigma_position may be NULL */
+int mi_denoise_image(uint32_t device, uint32_t width, uint32_t height, const float *color, const float *normal, const float *position,
+                     const float *albedo, const mi_denoise_params *p, float *out, float *resolved_sigma_position);
+/* The filter on a render's own films, on the device: radiance = film layout 2, guides = the FIRST shNormal and the FIRST position entry of the render's field list,
+ * albedo (demodulate) = its first albedo entry, each as layout 2 of the field film develops it -- the fields' `undefined` values included, as they stand.  A missing
+ * field: MI_ERR_INVALID naming it (a film that holds an adaptive run has no field film and is refused by this rule).  The films are read, never written: rendering more
+ * samples and filtering again is allowed.  Scratch (two colour buffers and the packed guides, 72 B per pixel) is allocated at the first call and freed with the render; a
+ * request beyond MI355PT_POOL_LIMIT or the free device memory is MI_ERR_DEVICE naming it.  A render that never calls this launches, allocates and records nothing extra. */
+int mi_render_denoise(mi_render *r, const mi_denoise_params *p, float *host_out /* H x W x 3 */, float *resolved_sigma_position);
+int mi_render_denoise_device(mi_render *r, const mi_denoise_params *p, void *device_out, float *resolved_sigma_position);
 /* Debug / parity: what a shading stage recomputes for the sensor rays of individual (px, py, sampleIndex) triples from the path state in the queues, batched as
  * mi_render_samples (generate only): out8 = the path's aperture sample ((0.5, 0.5) without a lens), then the rx / ry directions scaled by 1 / sqrt(spp).  A parity hook, not a
  * product call.  Its kernel looks Sobol values up in the render's GLOBAL nibble tables from st0.y / st0.z, as k_env_primary does; the shade kernels call the same functions on

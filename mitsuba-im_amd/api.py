@@ -76,6 +76,10 @@ class MiField(C.Structure):
     _fields_ = [("field", C.c_uint32), ("undefined", C.c_float * 3)]
 
 
+class MiDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("demodulate", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
 # field kinds in the order of the reference's EField (src/integrators/misc/field.cpp:57-67) = MI_FIELD_* of include/mi355pt.h
 FIELD_NAMES = ("position", "relPosition", "distance", "geoNormal", "shNormal", "uv", "albedo", "shapeIndex", "primIndex")
 SCALAR_FIELDS = ("distance", "shapeIndex", "primIndex")      # the three values of these are equal
@@ -115,7 +119,7 @@ EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_s
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_lens", "mi_scene_set_film",
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_adaptive", "mi_render_run_adaptive", "mi_render_read_sample_counts", "mi_render_adaptive_stats",
-           "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
+           "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_denoise_image", "mi_render_denoise", "mi_render_denoise_device", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
            "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_create_direct", "mi_host_create_ao", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
                 "mi_host_set_camera", "mi_host_set_lens", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
@@ -185,6 +189,9 @@ class Lib:
         L.mi_render_field_film_size.argtypes = [vp, i32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.mi_render_read_fields.argtypes = [vp, i32, vp]
         L.mi_render_field_samples.argtypes = [vp, vp, u64, vp]
+        L.mi_denoise_image.argtypes = [u32, u32, u32, vp, vp, vp, vp, C.POINTER(MiDenoiseParams), vp, C.POINTER(f32)]
+        L.mi_render_denoise.argtypes = [vp, C.POINTER(MiDenoiseParams), vp, C.POINTER(f32)]
+        L.mi_render_denoise_device.argtypes = [vp, C.POINTER(MiDenoiseParams), vp, C.POINTER(f32)]
         L.mi_render_set_profiling.argtypes = [vp, i32]
         L.mi_render_debug_sensor_differentials.argtypes = [vp, vp, u64, vp]
         L.mi_debug_intersect.argtypes = [vp, vp, u64, i32, vp]
@@ -256,6 +263,27 @@ def device_libm(name, x, y=None):
     L = lib(); a = np.ascontiguousarray(x, np.float32).reshape(-1); out = np.zeros(len(a), np.float32)
     b = None if y is None else np.ascontiguousarray(y, np.float32).reshape(-1)
     L.check(L.L.mi_debug_libm(LIBM_FUNCTIONS[name], _p(a), _p(b) if b is not None else None, len(a), _p(out))); return out
+
+
+# starting values of the denoiser's widths (nobody has tuned them on real renders yet)
+DENOISE_DEFAULTS = dict(iterations=5, sigma_color=4.0, sigma_normal=0.3, sigma_position=-0.05)
+
+
+def denoise_image(color, normal, position, albedo=None, iterations=5, sigma_color=4.0, sigma_normal=0.3, sigma_position=-0.05, device=0):
+    """The edge-avoiding a-trous filter (mi_denoise_image, include/mi355pt.h) on H x W x 3 float32 arrays: `normal` and `position` guide it, `albedo` (optional)
+    demodulates the colour first.  sigma_position < 0: that fraction of the diagonal of the finite positions' box.  -> (out, resolved_sigma_position)."""
+    L = lib(); c = np.ascontiguousarray(color, np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("denoise_image: colour must be H x W x 3")
+    n = np.ascontiguousarray(normal, np.float32); p = np.ascontiguousarray(position, np.float32)
+    a = None if albedo is None else np.ascontiguousarray(albedo, np.float32)
+    for name, g in (("normal", n), ("position", p), ("albedo", a)):
+        if g is not None and g.shape != c.shape:
+            raise ValueError(f"denoise_image: {name} has shape {g.shape}, the colour {c.shape}")
+    prm = MiDenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position), 0 if a is None else 1)
+    out = np.zeros_like(c); res = C.c_float(0.0)
+    L.check(L.L.mi_denoise_image(int(device), c.shape[1], c.shape[0], _p(c), _p(n), _p(p), _p(a), C.byref(prm), _p(out), C.byref(res)))
+    return out, float(res.value)
 
 
 def pack_materials(bsdfs):
@@ -524,7 +552,7 @@ class Render:
                            1 if shading_samples is None else int(shading_samples), -1.0 if ray_length is None else float(ray_length))
         self.params = p
         h = C.c_void_p(); L.check(L.L.mi_render_create(scene.h, C.byref(p), C.byref(h))); self.h = h
-        self.field_names = []
+        self.field_names = []; self.last_denoise_sigma_position = None
         if fields is None: fields = sc.get("fields")          # the scene description's own list (scene files with a `multichannel` integrator); [] = none
         if fields: self.set_fields(fields)
         ad = sc.get("adaptive")                               # the scene description's own parameters (scene files with an `adaptive` integrator); None = uniform sampling
@@ -573,6 +601,19 @@ class Render:
         """layout 0: raw sums (H+2b) x (W+2b) x (3F+1), weight last; layout 2: developed H x W x 3F (field i in channels 3i .. 3i+2)."""
         h, w, c, _ = self.field_film_shape(layout); out = np.zeros((h, w, c), np.float32)
         self.L.check(self.L.L.mi_render_read_fields(self.h, layout, _p(out))); return out
+
+    def denoise(self, iterations=5, sigma_color=4.0, sigma_normal=0.3, sigma_position=-0.05, demodulate=None, device_ptr=None):
+        """The edge-avoiding a-trous filter on this render's own films, on the device (mi_render_denoise): radiance = read_film(2), guides = the first shNormal and the
+        first position field, albedo = the first albedo field.  demodulate=None: if the render holds an albedo field.  -> H x W x 3, or None with device_ptr (the
+        address of H x W x 3 floats on the render's device, which then holds the result).  The resolved position width is left in last_denoise_sigma_position."""
+        if demodulate is None: demodulate = "albedo" in self.field_names
+        prm = MiDenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position), int(bool(demodulate))); res = C.c_float(0.0)
+        if device_ptr is not None:
+            self.L.check(self.L.L.mi_render_denoise_device(self.h, C.byref(prm), C.c_void_p(device_ptr), C.byref(res))); out = None
+        else:
+            sc = self.scene.sc; out = np.zeros((sc.height, sc.width, 3), np.float32)
+            self.L.check(self.L.L.mi_render_denoise(self.h, C.byref(prm), _p(out), C.byref(res)))
+        self.last_denoise_sigma_position = float(res.value); return out
 
     def field_samples(self, pairs):
         """The fields of individual (px, py, sampleIndex) triples -> [n, F, 3]."""

@@ -18,6 +18,7 @@
 #include "direct_const.h"
 #include "ao_const.h"
 #include "adaptive.h"
+#include "denoise.h"
 
 extern "C" {
 void mi_launch_generate(const DScene &, const RenderConst &, const Queues &, const BatchDesc &, uint32_t, hipStream_t);
@@ -72,6 +73,10 @@ void mi_launch_adapt_tile(uint32_t *, mi_tile, uint32_t, uint32_t, hipStream_t);
 void mi_launch_adapt_list(const uint32_t *, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
 void mi_launch_adapt_accumulate(const DScene &, const Queues &, const AdaptArgs &, const uint32_t *, uint32_t, uint32_t, float *, float *, hipStream_t);
 void mi_launch_adapt_compact(const uint32_t *, uint32_t, const uint32_t *, uint32_t *, uint32_t *, uint32_t *, hipStream_t);
+void mi_launch_dn_prepare_render(const DenoiseBufs &, const DenoiseFilmSrc &, int, int, int, hipStream_t);
+void mi_launch_dn_prepare_image(const DenoiseBufs &, const float *, const float *, const float *, const float *, int, int, int, hipStream_t);
+void mi_launch_dn_bounds(const DenoiseBufs &, size_t, float, hipStream_t);
+void mi_launch_dn_level(const DenoiseBufs &, int, const DenoiseLevel &, bool, float *, hipStream_t);
 }
 
 // Shading stage dispatch.  Dynamic LDS: Sobol nibble tables + (small scenes) the scene tables + (scenes with non-diffuse BSDFs) the per-wave path-order list.
@@ -136,6 +141,7 @@ struct mi_render {
     // sample per pixel: no other run or merge may add to it).  adActive: the active list of this round and the next; adList[pool]: the triple list of the batch on that pool
     bool adaptOn = false, adaptFilm = false; mi_adaptive_params ap{}; mi_adaptive_stats as{}; AdaptArgs ad{}; float adQuantile = 0;
     uint32_t *adActive[2] = {}, *adWave = nullptr, *adNNext = nullptr, *adHostN = nullptr, *adList[kMaxPools] = {}; uint64_t adListPaths = 0; uint32_t adPix = 0;
+    void *dnMem = nullptr; DenoiseBufs dn{};   // denoiser scratch (denoise.h): two colour buffers + the packed guides, allocated at the first mi_render_denoise, freed with the render
     uint64_t sceneRev = 0, filmRev = 0;   // scene revision `sc` was copied from / the samples in the film (and the field film) were traced at
     Queues &pool(int i) { return i ? qx[i - 1] : q; }
     hipStream_t poolStream(int i) { return i ? streamx[i - 1] : stream; }
@@ -1015,6 +1021,7 @@ void mi_render_destroy(mi_render *r) {
     if (r->mergeTmp) (void) hipFree(r->mergeTmp);
     releaseFields(r);
     releaseAdaptive(r);
+    if (r->dnMem) (void) hipFree(r->dnMem);
     if (r->dNib) (void) hipFree(r->dNib);
     if (r->pollHost) (void) hipHostFree(r->pollHost);
     if (r->pollEv) (void) hipEventDestroy(r->pollEv);
@@ -1631,6 +1638,111 @@ int mi_render_field_samples(mi_render *r, const uint32_t *pairs, uint64_t n, flo
     if (e == hipSuccess) e = hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost);
     (void) hipFree(dList); (void) hipFree(dOut);
     if (e != hipSuccess) return fail(MI_ERR_DEVICE, std::string("mi_render_field_samples: ") + hipGetErrorString(e));
+    return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ denoiser (denoise.h, kernels_denoise.hip)
+}  // extern "C"
+static int dnCheckParams(const std::string &fn, const mi_denoise_params *p) {
+    if (p->iterations > 8) return fail(MI_ERR_INVALID, fn + ": iterations must be 0..8 (got " + std::to_string(p->iterations) + ")");
+    if (!(p->sigma_color > 0) || !std::isfinite(p->sigma_color)) return fail(MI_ERR_INVALID, fn + ": sigma_color must be positive and finite");
+    if (!(p->sigma_normal > 0) || !std::isfinite(p->sigma_normal)) return fail(MI_ERR_INVALID, fn + ": sigma_normal must be positive and finite");
+    if (p->sigma_position == 0 || !std::isfinite(p->sigma_position)) return fail(MI_ERR_INVALID, fn + ": sigma_position must be non-zero and finite (negative: a fraction of the position box's diagonal)");
+    if (p->demodulate > 1) return fail(MI_ERR_INVALID, fn + ": demodulate must be 0 or 1");
+    return MI_OK;
+}
+static int dnCheckSize(const std::string &fn, uint32_t width, uint32_t height) {
+    if (!width || !height) return fail(MI_ERR_INVALID, fn + ": zero width or height");
+    if (width > (1u << 24) || height > 65535u * MI_DN_TILE_H) return fail(MI_ERR_INVALID, fn + ": width above 2^24 or height above " + std::to_string(65535u * MI_DN_TILE_H));
+    return MI_OK;
+}
+// two colour buffers, the packed guides, the divisor and the partial boxes in ONE allocation
+static int dnAlloc(const std::string &fn, size_t n, void **mem, DenoiseBufs *b) {
+    const uint64_t bytes = (uint64_t) n * MI_DN_BYTES_PER_PIXEL + MI_DN_TAIL_FLOATS * 4u;
+    const char *lim = getenv("MI355PT_POOL_LIMIT");
+    if (lim && atoll(lim) > 0 && bytes > (uint64_t) atoll(lim)) return fail(MI_ERR_DEVICE, fn + ": the colour and guide buffers (" + std::to_string(bytes) + " bytes) are larger than MI355PT_POOL_LIMIT");
+    size_t freeB = 0, totalB = 0; HIPCHK(hipMemGetInfo(&freeB, &totalB));
+    if (bytes > freeB) return fail(MI_ERR_DEVICE, fn + ": the colour and guide buffers (" + std::to_string(bytes) + " bytes) are larger than the free device memory");
+    hipError_t e = hipMalloc(mem, bytes);
+    if (e != hipSuccess) { (void) hipGetLastError(); *mem = nullptr; return fail(MI_ERR_DEVICE, fn + ": cannot allocate the colour and guide buffers: " + hipGetErrorString(e)); }
+    char *base = (char *) *mem;
+    b->col[0] = (float4 *) base; b->col[1] = (float4 *) (base + n * 16); b->gA = (float4 *) (base + n * 32); b->dem = (float4 *) (base + n * 48);
+    b->gB = (float2 *) (base + n * 64); b->partial = (float *) (base + n * 72); b->res = b->partial + MI_DN_BOUNDS_BLOCKS * 6u;
+    return MI_OK;
+}
+// bounds (automatic width) and the levels over prepared records; iterations >= 1.  Synchronises `st`.
+static int dnFilter(const DenoiseBufs &b, uint32_t width, uint32_t height, const mi_denoise_params *p, int demod, float *devOut, float *resolved, hipStream_t st) {
+    const bool automatic = p->sigma_position < 0;
+    if (automatic) mi_launch_dn_bounds(b, (size_t) width * height, std::fabs(p->sigma_position), st);
+    DenoiseLevel L{}; L.w = (int) width; L.h = (int) height; L.demod = demod; L.res = automatic ? b.res : nullptr;
+    L.kn = 1.0f / (p->sigma_normal * p->sigma_normal); L.kp = automatic ? 0.0f : 1.0f / (p->sigma_position * p->sigma_position);
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        const float sc = std::ldexp(p->sigma_color, -(int) i);
+        L.step = 1 << i; L.kc = 1.0f / (sc * sc);
+        mi_launch_dn_level(b, (int) (i & 1u), L, i + 1 == p->iterations, devOut, st);
+    }
+    HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipGetLastError());
+    float sigma = p->sigma_position;
+    if (automatic) HIPCHK(hipMemcpy(&sigma, b.res, 4, hipMemcpyDeviceToHost));
+    if (resolved) *resolved = sigma;
+    return MI_OK;
+}
+extern "C" {
+int mi_denoise_image(uint32_t device, uint32_t width, uint32_t height, const float *color, const float *normal, const float *position, const float *albedo,
+                     const mi_denoise_params *p, float *out, float *resolved_sigma_position) {
+    const std::string fn = "mi_denoise_image";
+    if (!color || !normal || !position || !p || !out) return fail(MI_ERR_INVALID, fn + ": null argument (color, normal, position, params, out)");
+    { int rc = dnCheckSize(fn, width, height); if (rc) return rc; }
+    { int rc = dnCheckParams(fn, p); if (rc) return rc; }
+    if (p->demodulate && !albedo) return fail(MI_ERR_INVALID, fn + ": demodulate without albedo");
+    const size_t n = (size_t) width * height;
+    if (p->iterations == 0) { memcpy(out, color, n * 12); if (resolved_sigma_position) *resolved_sigma_position = p->sigma_position > 0 ? p->sigma_position : 0.0f; return MI_OK; }
+    HIPCHK(hipSetDevice((int) device));
+    struct Mem { void *scratch = nullptr, *io = nullptr; ~Mem() { if (scratch) (void) hipFree(scratch); if (io) (void) hipFree(io); } } mem;
+    DenoiseBufs b{};
+    { int rc = dnAlloc(fn, n, &mem.scratch, &b); if (rc) return rc; }
+    const int demod = p->demodulate ? 1 : 0, nIn = demod ? 4 : 3;
+    HIPCHK(hipMalloc(&mem.io, n * 12 * (size_t) (nIn + 1)));
+    float *d = (float *) mem.io, *dC = d, *dN = d + n * 3, *dP = d + n * 6, *dA = demod ? d + n * 9 : nullptr, *dOut = d + n * 3 * (size_t) nIn;
+    HIPCHK(hipMemcpy(dC, color, n * 12, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dN, normal, n * 12, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dP, position, n * 12, hipMemcpyHostToDevice));
+    if (demod) HIPCHK(hipMemcpy(dA, albedo, n * 12, hipMemcpyHostToDevice));
+    mi_launch_dn_prepare_image(b, dC, dN, dP, dA, (int) width, (int) height, demod, nullptr);
+    { int rc = dnFilter(b, width, height, p, demod, dOut, resolved_sigma_position, nullptr); if (rc) return rc; }
+    HIPCHK(hipMemcpy(out, dOut, n * 12, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+int mi_render_denoise_device(mi_render *r, const mi_denoise_params *p, void *device_out, float *resolved_sigma_position) {
+    const std::string fn = "mi_render_denoise";
+    if (!r || !p || !device_out) return fail(MI_ERR_INVALID, fn + ": null argument");
+    { int rc = dnCheckParams(fn, p); if (rc) return rc; }
+    const mi::SceneHost &h = r->scene->h;
+    { int rc = dnCheckSize(fn, h.width, h.height); if (rc) return rc; }
+    int fN = -1, fP = -1, fA = -1;      // the first entry of each kind
+    for (int i = (int) r->nFields - 1; i >= 0; --i) { if (r->fields[i].field == MI_FIELD_SH_NORMAL) fN = i; if (r->fields[i].field == MI_FIELD_POSITION) fP = i; if (r->fields[i].field == MI_FIELD_ALBEDO) fA = i; }
+    const char *why = r->adaptFilm ? "; a film that holds an adaptive run has no field film" : "";
+    if (fN < 0) return fail(MI_ERR_INVALID, fn + ": the render has no shNormal field (mi_render_set_fields" + why + ")");
+    if (fP < 0) return fail(MI_ERR_INVALID, fn + ": the render has no position field (mi_render_set_fields" + why + ")");
+    if (p->demodulate && fA < 0) return fail(MI_ERR_INVALID, fn + ": demodulate without albedo: the render has no albedo field (mi_render_set_fields)");
+    HIPCHK(hipSetDevice(h.device));
+    const int W = (int) h.width + 2 * h.border, H = (int) h.height + 2 * h.border;
+    if (p->iterations == 0) {      // the radiance as layout 2 develops it
+        mi_launch_film_layout(r->film, r->spill, (float *) device_out, W, H, h.border, 2, r->stream);
+        HIPCHK(hipStreamSynchronize(r->stream)); HIPCHK(hipGetLastError());
+        if (resolved_sigma_position) *resolved_sigma_position = p->sigma_position > 0 ? p->sigma_position : 0.0f;
+        return MI_OK;
+    }
+    const size_t n = (size_t) h.width * h.height;
+    if (!r->dnMem) { int rc = dnAlloc(fn, n, &r->dnMem, &r->dn); if (rc) return rc; }
+    DenoiseFilmSrc f{}; f.film = r->film; f.spill = r->spill; f.ffilm = r->fieldFilm; f.fspill = r->fieldSpill; f.W = W; f.H = H; f.border = h.border;
+    f.nv = 3 * (int) r->nFields; f.fN = fN; f.fP = fP; f.fA = fA;
+    const int demod = p->demodulate ? 1 : 0;
+    mi_launch_dn_prepare_render(r->dn, f, (int) h.width, (int) h.height, demod, r->stream);
+    return dnFilter(r->dn, h.width, h.height, p, demod, (float *) device_out, resolved_sigma_position, r->stream);
+}
+int mi_render_denoise(mi_render *r, const mi_denoise_params *p, float *host_out, float *resolved_sigma_position) {
+    if (!r || !p || !host_out) return fail(MI_ERR_INVALID, "mi_render_denoise: null argument");
+    int rc = mi_render_denoise_device(r, p, r->layoutTmp, resolved_sigma_position); if (rc) return rc;      // layoutTmp holds 5 floats per film pixel, border included
+    HIPCHK(hipMemcpy(host_out, r->layoutTmp, (size_t) r->scene->h.width * r->scene->h.height * 12, hipMemcpyDeviceToHost));
     return MI_OK;
 }
 

@@ -1,6 +1,7 @@
 """Command-line front end: render a Mitsuba XML scene on the MI355X path tracer (what `mitsuba scene.xml` does for the `path` integrator).
 
     python -m mitsuba-im_amd.render scene.xml [-o out.exr|out.pfm|out.npy|out.png] [-D name=value ...] [--spp N] [--sampler sobol|independent] [--device K] [--ao N [--ao-length L]]
+                                    [--denoise [ITERATIONS] [--denoise-sigma C N P] [--denoise-raw PATH]]
 
 The image written is the developed film (sum / weight, linear RGB, as HDRFilm::develop would hand to its writer); `.exr` (FLOAT channels, ZIP), `.pfm` and `.npy`
 keep the linear values; `.png` / `.jpg` get ldrfilm's default sRGB encoding (imageio.py).  There is no CPU fallback: without the HIP library / a GPU this exits with an error.
@@ -17,6 +18,14 @@ integrator: every pixel takes samples until the half width of its confidence int
 spent, default 32); a scene file whose integrator is `adaptive` needs no option.  The independent sampler and a sample count of at least 8 are required.
 `--sample-counts out.npy` writes the H x W map of samples per pixel (`out_000.npy`, ... for frames).  Both work with `--orbit`, `--spin` and `--focus-pull`: clear, edit,
 adaptive run per frame.
+
+`--denoise [ITERATIONS]` filters the radiance on the device before it is written: the edge-avoiding a-trous filter (api.Render.denoise; ITERATIONS levels, default 5)
+guided by the render's own `shNormal` and `position` field channels and demodulated by its `albedo` channel.  The option adds the three fields (undefined 0 0 0) to
+the render's field list unless the scene file's `multichannel` integrator already asks for them; the ones it added are not written, the scene file's own are written
+as before.  On a scene whose BSDFs have no albedo field (plastic, roughplastic, coatings, a mask over a bumpmap / normalmap) it filters without demodulation and says
+so.  `--denoise-sigma C N P` sets the colour, normal and position widths (P < 0: that fraction of the scene's extent); `--denoise-raw PATH` also writes the
+unfiltered radiance (`PATH_000.ext`, ... for frames).  Works with `--orbit`, `--spin` and `--focus-pull`: one filter call per frame on the same render.  Not with
+adaptive sampling, whose film has no field channels.
 
 `--orbit N [--orbit-axis x|y|z]` renders a turntable: N frames with the camera rotated in steps of 360 / N degrees about the axis through the centre of the scene's
 box.  The scene is committed once; every frame is an in-place camera edit of the committed scene (Scene.update_camera), a clear and a run -- no tree build, no
@@ -141,16 +150,45 @@ def use_adaptive(sc, max_error=0.05, max_sample_factor=None):
     return sc
 
 
-def write_outputs(sc, render, out, rgb=None, fields=None):
+def use_denoise(sc, render, iterations=5, sigmas=None, raw=None):
+    """`--denoise`: puts the guides the filter needs behind the scene's own field list (what the scene file asks for stays in front and is reused) and returns what
+    `developed` needs: the filter's arguments, the count of the scene's own fields and the path of the unfiltered image."""
+    from .api import normalize_fields, MiError, DENOISE_DEFAULTS
+    own = normalize_fields(sc.get("fields") or []); names = [n for n, _ in own]
+    guides = own + [(g, 0.0) for g in ("shNormal", "position") if g not in names]
+    widths = dict(DENOISE_DEFAULTS, iterations=int(iterations))
+    if sigmas is not None: widths.update(sigma_color=float(sigmas[0]), sigma_normal=float(sigmas[1]), sigma_position=float(sigmas[2]))
+    try:
+        render.set_fields(guides + ([] if "albedo" in names else [("albedo", 0.0)]))
+    except MiError as e:
+        if e.code != 3 or "albedo" in names: raise
+        print(f"{sc.name}: {e}; --denoise filters without albedo demodulation", file=sys.stderr)
+        render.set_fields(guides)
+    return dict(widths=widths, own=len(own), raw=raw)
+
+
+def developed(render, dn=None):
+    """(radiance, fields or None, field names, unfiltered radiance or None) of the film as it stands; `dn` (use_denoise): the radiance filtered on the device, and
+    only the scene's own fields"""
+    rgb = render.read_film(2); names = list(render.field_names); fields = render.read_fields(2) if names else None
+    if dn is None:
+        return rgb, fields, names, None
+    own = dn["own"]
+    return render.denoise(**dn["widths"]), (fields[..., :3 * own] if own else None), names[:own], rgb
+
+
+def write_outputs(sc, render, out, dev=None, dn=None, frame=None):
     """the developed film (and, for a multichannel scene, the field groups) of `render` -> `out`; False (message printed) when the format cannot hold them"""
-    if rgb is None:
-        rgb = render.read_film(2); fields = render.read_fields(2) if render.field_names else None
+    rgb, fields, names, raw = developed(render, dn) if dev is None else dev
+    if raw is not None and dn["raw"]:
+        stem, ext = dn["raw"].rsplit(".", 1)
+        write_image(dn["raw"] if frame is None else f"{stem}_{frame:03d}.{ext}", raw)
     if fields is not None:
         if not out.endswith(".exr"):
             print(f"error: {out}: a render with field channels holds several channel groups, which only the .exr output can store", file=sys.stderr)
             return False
         from . import imageio
-        planes, chan = field_channel_groups(sc, rgb, fields, render.field_names)
+        planes, chan = field_channel_groups(sc, rgb, fields, names)
         imageio.write_exr(out, planes, chan)
     else:
         write_image(out, rgb)
@@ -172,6 +210,9 @@ def main(argv=None):
     ap.add_argument("--adaptive", type=float, nargs="?", const=0.05, default=None, metavar="MAXERROR", help="per-pixel error control around the scene's path / volpath integrator (maximum relative error, default 0.05)")
     ap.add_argument("--max-sample-factor", type=int, default=None, metavar="N", help="with adaptive sampling: at most N x spp samples per pixel (negative: no limit; default 32)")
     ap.add_argument("--sample-counts", default=None, metavar="out.npy", help="with adaptive sampling: write the H x W map of samples per pixel")
+    ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS", help="filter the radiance on the device with the edge-avoiding a-trous filter, guided by the shNormal / position / albedo field channels (levels, default 5)")
+    ap.add_argument("--denoise-sigma", type=float, nargs=3, default=None, metavar=("C", "N", "P"), help="with --denoise: colour, normal and position widths (P < 0: that fraction of the scene's extent)")
+    ap.add_argument("--denoise-raw", default=None, metavar="PATH", help="with --denoise: also write the unfiltered radiance")
     ap.add_argument("--orbit", type=int, default=0, metavar="N", help="turntable of N frames about the scene box's centre: one commit, one in-place camera edit per frame")
     ap.add_argument("--orbit-axis", choices=["x", "y", "z"], default="y")
     ap.add_argument("--spin", type=int, default=0, metavar="N", help="N frames with every instance turned about its own origin: one commit, one in-place instance edit per frame")
@@ -191,6 +232,10 @@ def main(argv=None):
         raise SystemExit("--sample-counts expects a .npy file name")
     if a.adaptive is not None and a.ao:
         raise SystemExit("--adaptive cannot be combined with --ao (adaptive sampling runs over path, volpath_simple or volpath)")
+    if a.denoise is None and (a.denoise_sigma is not None or a.denoise_raw is not None):
+        raise SystemExit("--denoise-sigma / --denoise-raw belong to --denoise")
+    if a.denoise is not None and not 0 <= a.denoise <= 8:
+        raise SystemExit("--denoise expects 0 to 8 iterations")
     if a.orbit < 0:
         raise SystemExit("--orbit expects a frame count >= 1")
     if a.spin < 0 or (a.spin and a.orbit):
@@ -218,6 +263,9 @@ def main(argv=None):
         if a.sample_counts is not None and not sc.get("adaptive"):
             print("error: --sample-counts needs adaptive sampling (--adaptive, or a scene file with an adaptive integrator)", file=sys.stderr)
             return 1
+        if a.denoise is not None and sc.get("adaptive"):
+            print("error: --denoise cannot be combined with adaptive sampling (--adaptive, or a scene file with an adaptive integrator): an adaptive film has no field channels", file=sys.stderr)
+            return 1
         out = a.output or (a.scene.rsplit(".", 1)[0] + ".exr")          # hdrfilm's default fileFormat (src/films/hdrfilm.cpp: openexr)
         if a.spin and not (sc.get("instances") or []):
             print(f"error: {a.scene}: --spin turns the instances of shape groups, and this scene has none", file=sys.stderr)
@@ -233,6 +281,7 @@ def main(argv=None):
         t1 = time.perf_counter()
         scene = Scene(sc, device=a.device)
         render = Render(scene, device=a.device)
+        dn = use_denoise(sc, render, a.denoise, a.denoise_sigma, a.denoise_raw) if a.denoise is not None else None
         t2 = time.perf_counter()
         frame_no = [0]
 
@@ -253,7 +302,7 @@ def main(argv=None):
                 if c2w is not None: scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far)
                 scene.update_lens(sc.aperture_radius, dist); render.clear(); go()
                 frame_s.append(time.perf_counter() - tf)
-                if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}"):
+                if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}", dn=dn, frame=f):
                     return 1
             rev, builds = scene.revision(); mean = sum(frame_s) / len(frame_s)
             print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s once ({builds} tree build, {rev} edits), "
@@ -265,7 +314,7 @@ def main(argv=None):
                 tf = time.perf_counter()
                 scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far); render.clear(); go()
                 frame_s.append(time.perf_counter() - tf)
-                if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}"):
+                if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}", dn=dn, frame=f):
                     return 1
             rev, builds = scene.revision(); mean = sum(frame_s) / len(frame_s)
             print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s once ({builds} tree build, {rev} camera edits), "
@@ -277,20 +326,19 @@ def main(argv=None):
                 tf = time.perf_counter()
                 scene.update_instances(insts); render.clear(); go()
                 frame_s.append(time.perf_counter() - tf)
-                if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}"):
+                if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}", dn=dn, frame=f):
                     return 1
             rev, builds = scene.revision(); mean = sum(frame_s) / len(frame_s)
             print(f"{sc.name}: {sc.width}x{sc.height}, {sc.spp} spp, {len(sc.idx)} triangles, {len(insts)} instances; load {t1 - t0:.2f} s, upload+BVH {t2 - t1:.2f} s once ({builds} tree build, {rev} instance edits), "
                   f"{a.spin} frames, render {mean:.3f} s per frame ({n / mean / 1e6:.1f} Msamples/s) -> {stem}_000.{ext} .. {stem}_{a.spin - 1:03d}.{ext}")
             return 0
         go()
-        rgb = render.read_film(2)
-        fields = render.read_fields(2) if render.field_names else None
+        dev = developed(render, dn)
         t3 = time.perf_counter()
     except (xml_scene.SceneError, MiError, OSError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 1
-    if not write_outputs(sc, render, out, rgb, fields):
+    if not write_outputs(sc, render, out, dev, dn):
         return 1
     spp_text = f"{sc.spp} spp"
     if sc.get("adaptive"):      # the samples the adaptive run traced, and what it kept
