@@ -462,6 +462,28 @@ int mi_debug_bsdf(mi_scene *s, uint32_t material, int mode, const float *wi3, co
  * (bilinear, or the nearest texel under the nearest filter).  Procedural textures ignore the partials.  The EWA loops run over the footprint's bounding box: the caller
  * keeps footprints bounded. */
 int mi_debug_texture(mi_scene *s, uint32_t texture, const float *uv2, const float *partials4, uint64_t n, float *out3);
+/* Scene::sampleEmitterDirect one call at a time, through the widest instantiation the stages have (every emitter kind, analytic shapes, tables in global memory): ref3 =
+ * the reference point, refN3 = its normal ((0, 0, 0): a two-sided or medium vertex), uv2 = the 2-D sample.  raw = 1 is the volumetric integrators' form
+ * (Scene::sampleAttenuatedEmitterDirect): the value is not yet divided by the emitter-selection probability, which comes back as em_pdf.  No visibility test is made
+ * (the shadow queue does that).  out17 = value rgb, p xyz, d xyz, dist, pdf, n xyz, emitter index, !isOnSurface (0 / 1), em_pdf (raw only, else 0); the record starts
+ * out zero, and where the returned pdf is 0 everything but value and pdf is whatever the routine left there.  A scene without emitters: MI_ERR_INVALID. */
+int mi_debug_emitter_sample(mi_scene *s, const float *ref3, const float *refN3, const float *uv2, uint64_t n, int raw, float *out17);
+/* What a BSDF-sampled ray that finds emitter `emitter` evaluates: the ray left ref3 in direction d3 and met the emitter after dist1 at a point with shading normal n3;
+ * facing1 (0 / 1) = dot(d, refN) >= 0, evaluated where the reference normal was still known.  out8 =
+ *   area light:  Emitter::eval(n, -d) rgb, Scene::pdfEmitterDirect, 0 0 0 0
+ *   envmap:      evalEnvironment(d) rgb, EnvironmentMap::pdfDirect's solid-angle density, then the value rgb and density of the fused routine the shade stage calls
+ *                for both at once (ref, n, dist, facing are ignored)
+ *   constant:    evalEnvironment rgb, 0 0 0 0 0 (its density is one line inside the shade stage)
+ * A point, spot, directional or collimated emitter is refused by name (MI_ERR_UNSUPPORTED: no ray finds one); an index out of range is MI_ERR_INVALID. */
+int mi_debug_emitter_eval(mi_scene *s, uint32_t emitter, const float *ref3, const float *d3, const float *n3, const float *dist1, const float *facing1, uint64_t n, float *out8);
+/* The medium routines of the volumetric stages one call at a time, on record `medium` of mi_scene_set_media.  in10 / out12 per case:
+ *   mode 0  HomogeneousMedium::evalTransmittance over [mint, maxt]: in[6], in[7] (the rest ignored) -> transmittance rgb
+ *   mode 1  HomogeneousMedium::sampleDistance: o xyz, d xyz, mint, maxt, and the two values its sampler hands out (the second is drawn only by the balance strategy when the
+ *           medium is chosen) -> success (0 / 1), t, p xyz, transmittance rgb, pdfSuccess, pdfFailure, values drawn; t and p start out zero
+ *   mode 2  PhaseFunction::sample, then eval of its own result: wi xyz, the 2-D sample -> wo xyz, eval
+ *   mode 3  PhaseFunction::eval: wi xyz, wo xyz -> eval
+ * the rest of out12 is 0.  A medium index out of range or a mode outside 0..3: MI_ERR_INVALID. */
+int mi_debug_medium(mi_scene *s, uint32_t medium, int mode, const float *in10, uint64_t n, float *out12);
 int mi_debug_sincosf(const float *x, uint64_t n, float *out_sin_cos2);   /* the device restatement of glibc's sincosf (warps): out[2i] = sin, out[2i+1] = cos */
 /* The shape of a path pool.  A pool of `paths` paths is cut into n_seg segments of cap slots (cap a multiple of 64; segment s holds the paths s * cap ..); the shade stages
  * give every segment to one wave, which walks it in chunks of 64.  The rule, a pure host function (no device, no environment): n_seg = the override, else 16384, or -- on a

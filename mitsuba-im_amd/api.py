@@ -120,7 +120,7 @@ EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_s
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_adaptive", "mi_render_run_adaptive", "mi_render_read_sample_counts", "mi_render_adaptive_stats",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_denoise_image", "mi_render_denoise", "mi_render_denoise_device", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
-           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
+           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_emitter_sample", "mi_debug_emitter_eval", "mi_debug_medium", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_create_direct", "mi_host_create_ao", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
                 "mi_host_set_camera", "mi_host_set_lens", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
 
@@ -204,6 +204,9 @@ class Lib:
         L.mi_debug_libm.argtypes = [i32, vp, vp, u64, vp]
         L.mi_debug_bsdf.argtypes = [vp, u32, i32, vp, vp, vp, vp, u64, vp]
         L.mi_debug_texture.argtypes = [vp, u32, vp, vp, u64, vp]
+        L.mi_debug_emitter_sample.argtypes = [vp, vp, vp, vp, u64, i32, vp]
+        L.mi_debug_emitter_eval.argtypes = [vp, u32, vp, vp, vp, vp, vp, u64, vp]
+        L.mi_debug_medium.argtypes = [vp, u32, i32, vp, u64, vp]
         L.mi_debug_geometry_bytes.argtypes = [vp, u32, C.POINTER(u64)]
         L.mi_debug_read_geometry.argtypes = [vp, u32, vp, u64]
         L.mi_debug_pool_shape.argtypes = [u64, i32, u32, C.POINTER(MiPoolOverrides), C.POINTER(MiPoolShape)]
@@ -515,6 +518,32 @@ class Scene:
         pa = None if partials is None else np.ascontiguousarray(partials, np.float32).reshape(-1, 4)
         if pa is not None and len(pa) != n: raise ValueError("texture_units: one set of partials per lookup")
         self.L.check(self.L.L.mi_debug_texture(self.h, int(texture), _p(uv), _p(pa), n, _p(out))); return out
+
+    def emitter_sample_units(self, ref, ref_n, uv, raw=False):
+        """The device's Scene::sampleEmitterDirect on chosen inputs (mi_debug_emitter_sample), one call per row and no visibility test: ref [n, 3], ref_n [n, 3] (zero: a
+        two-sided or medium vertex), uv [n, 2] -> [n, 17] = value rgb, p, d, dist, pdf, n, emitter index, delta flag, em_pdf.  raw: the volumetric integrators' form
+        (the value not yet divided by the selection probability em_pdf; without raw em_pdf is 0)."""
+        ref = np.ascontiguousarray(ref, np.float32).reshape(-1, 3); rn = np.ascontiguousarray(ref_n, np.float32).reshape(-1, 3); uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        n = len(ref); out = np.zeros((n, 17), np.float32)
+        if len(rn) != n or len(uv) != n: raise ValueError("emitter_sample_units: one normal and one sample per reference point")
+        self.L.check(self.L.L.mi_debug_emitter_sample(self.h, _p(ref), _p(rn), _p(uv), n, int(bool(raw)), _p(out))); return out
+
+    def emitter_eval_units(self, emitter, ref, d, nrm, dist, facing):
+        """What a BSDF-sampled ray that finds emitter `emitter` evaluates (mi_debug_emitter_eval), one call per row -> [n, 8].  Area light: value rgb, pdfEmitterDirect.
+        Envmap: evalEnvironment rgb, its solid-angle density, then value rgb and density of the fused routine.  Constant: value rgb.  Delta lights raise MiError code 3."""
+        ref = np.ascontiguousarray(ref, np.float32).reshape(-1, 3); d = np.ascontiguousarray(d, np.float32).reshape(-1, 3); nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        dist = np.ascontiguousarray(dist, np.float32).reshape(-1); fc = np.ascontiguousarray(facing, np.float32).reshape(-1); n = len(ref); out = np.zeros((n, 8), np.float32)
+        if not (len(d) == len(nrm) == len(dist) == len(fc) == n): raise ValueError("emitter_eval_units: one direction, normal, distance and flag per reference point")
+        self.L.check(self.L.L.mi_debug_emitter_eval(self.h, int(emitter), _p(ref), _p(d), _p(nrm), _p(dist), _p(fc), n, _p(out))); return out
+
+    MEDIUM_MODES = {"transmittance": 0, "distance": 1, "phase_sample": 2, "phase_eval": 3}
+
+    def medium_units(self, medium, mode, inputs):
+        """The device's medium routines on chosen inputs (mi_debug_medium), one call per row of inputs [n, 10] -> [n, 12].  "transmittance": columns 6, 7 = mint, maxt ->
+        rgb.  "distance": o, d, mint, maxt and the two values drawn -> success, t, p, transmittance rgb, pdfSuccess, pdfFailure, values drawn.  "phase_sample": wi, the
+        2-D sample -> wo, the phase function's value for it.  "phase_eval": wi, wo -> value."""
+        a = np.ascontiguousarray(inputs, np.float32).reshape(-1, 10); out = np.zeros((len(a), 12), np.float32)
+        self.L.check(self.L.L.mi_debug_medium(self.h, int(medium), self.MEDIUM_MODES[mode], _p(a), len(a), _p(out))); return out
 
     def camera_rays(self, pos2, aperture2=None, differentials=False):
         """Sensor rays (o, mint, d, maxt) at film positions pos2.  aperture2: the aperture sample of every ray of a lens scene (None: (0.5, 0.5), the reference's default

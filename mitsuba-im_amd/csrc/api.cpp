@@ -62,6 +62,9 @@ void mi_launch_debug_sincosf(const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_libm(int, const float *, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_bsdf(const DScene &, int, int, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_texture(const DScene &, uint32_t, const float *, const float *, uint64_t, float *, hipStream_t);
+void mi_launch_debug_emitter_sample(const DScene &, int, const float *, uint64_t, float *, hipStream_t);
+void mi_launch_debug_emitter_eval(const DScene &, int, int, const float *, uint64_t, float *, hipStream_t);
+void mi_launch_debug_medium(const DScene &, uint32_t, int, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_field_film(const DScene &, const FieldArgs &, const Queues &, const BatchDesc &, float *, float *, hipStream_t);
 void mi_launch_field_samples(const DScene &, const FieldArgs &, const Queues &, uint64_t, float *, hipStream_t);
 void mi_launch_field_layout(const float *, const float *, float *, int, int, int, int, int, hipStream_t);
@@ -1931,6 +1934,36 @@ int mi_debug_texture(mi_scene *s, uint32_t texture, const float *uv, const float
     HIPCHK(hipSetDevice(s->h.device));
     std::vector<float> in(n * 6, 0.0f); memcpy(in.data(), uv, n * 8); if (partials) memcpy(in.data() + n * 2, partials, n * 16);
     return withBuffers(in.data(), n * 24, out, n * 12, [&](void *i, void *o) { mi_launch_debug_texture(s->h.d, texture, (const float *) i, partials ? (const float *) i + n * 2 : nullptr, n, (float *) o, nullptr); });
+}
+// Unit entry points over the emitter routines (kernels_units.hip): Scene::sampleEmitterDirect on chosen reference points and sample values, and what a BSDF-sampled
+// ray that finds an emitter evaluates.
+int mi_debug_emitter_sample(mi_scene *s, const float *ref, const float *refN, const float *uv, uint64_t n, int raw, float *out) {
+    if (!s || !s->h.committed || !ref || !refN || !uv || !out || !n || raw < 0 || raw > 1) return fail(MI_ERR_INVALID, "mi_debug_emitter_sample: bad argument");
+    if (s->h.emitters.empty()) return fail(MI_ERR_INVALID, "mi_debug_emitter_sample: the scene has no emitter");
+    HIPCHK(hipSetDevice(s->h.device));
+    std::vector<float> in(n * 8);
+    for (uint64_t i = 0; i < n; ++i) { float *p = &in[i * 8]; memcpy(p, ref + 3 * i, 12); memcpy(p + 3, refN + 3 * i, 12); memcpy(p + 6, uv + 2 * i, 8); }
+    return withBuffers(in.data(), n * 32, out, n * 68, [&](void *i, void *o) { mi_launch_debug_emitter_sample(s->h.d, raw, (const float *) i, n, (float *) o, nullptr); });
+}
+int mi_debug_emitter_eval(mi_scene *s, uint32_t emitter, const float *ref, const float *d, const float *nrm, const float *dist, const float *facing, uint64_t n, float *out) {
+    if (!s || !s->h.committed || !ref || !d || !nrm || !dist || !facing || !out || !n) return fail(MI_ERR_INVALID, "mi_debug_emitter_eval: bad argument");
+    if (emitter >= s->h.emitters.size()) return fail(MI_ERR_INVALID, "mi_debug_emitter_eval: emitter " + std::to_string(emitter) + " of " + std::to_string(s->h.emitters.size()));
+    const uint32_t type = s->h.emitters[emitter].type;
+    if (type != MI_EMITTER_AREA && type != MI_EMITTER_ENVMAP && type != MI_EMITTER_CONSTANT) {
+        const char *name = type == MI_EMITTER_POINT ? "point" : type == MI_EMITTER_SPOT ? "spot" : type == MI_EMITTER_DIRECTIONAL ? "directional" : type == MI_EMITTER_COLLIMATED ? "collimated" : "unknown";
+        return fail(MI_ERR_UNSUPPORTED, "mi_debug_emitter_eval: emitter " + std::to_string(emitter) + " is a " + name + " light, which no ray can find");
+    }
+    HIPCHK(hipSetDevice(s->h.device));
+    std::vector<float> in(n * 11);
+    for (uint64_t i = 0; i < n; ++i) { float *p = &in[i * 11]; memcpy(p, ref + 3 * i, 12); memcpy(p + 3, d + 3 * i, 12); memcpy(p + 6, nrm + 3 * i, 12); p[9] = dist[i]; p[10] = facing[i]; }
+    const int kind = type == MI_EMITTER_AREA ? 0 : type == MI_EMITTER_ENVMAP ? 1 : 2;
+    return withBuffers(in.data(), n * 44, out, n * 32, [&](void *i, void *o) { mi_launch_debug_emitter_eval(s->h.d, (int) emitter, kind, (const float *) i, n, (float *) o, nullptr); });
+}
+int mi_debug_medium(mi_scene *s, uint32_t medium, int mode, const float *in, uint64_t n, float *out) {
+    if (!s || !s->h.committed || !in || !out || !n || mode < 0 || mode > 3) return fail(MI_ERR_INVALID, "mi_debug_medium: bad argument");
+    if (medium >= s->h.media.size() || !s->h.d.media) return fail(MI_ERR_INVALID, "mi_debug_medium: medium " + std::to_string(medium) + " of " + std::to_string(s->h.media.size()));
+    HIPCHK(hipSetDevice(s->h.device));
+    return withBuffers(in, n * 40, out, n * 48, [&](void *i, void *o) { mi_launch_debug_medium(s->h.d, medium, mode, (const float *) i, n, (float *) o, nullptr); });
 }
 int mi_debug_camera_rays(mi_scene *s, const float *pos, uint64_t n, float *out) {
     if (!s || !s->h.committed || !pos || !out || !n) return fail(MI_ERR_INVALID, "mi_debug_camera_rays: bad argument");

@@ -1,4 +1,5 @@
-// kernels_units.hip -- unit-level parity entry points over the BSDF and texture routines of pt_device.h (mi_debug_bsdf, mi_debug_texture): one call of the
+// kernels_units.hip -- unit-level parity entry points over the BSDF, texture and emitter routines of pt_device.h (mi_debug_bsdf, mi_debug_texture, mi_debug_emitter_sample,
+// mi_debug_emitter_eval) and the medium routines of the volumetric stages (mi_debug_medium): one call of the
 // routine per thread on caller-supplied inputs, so that directions, sample values and footprints a camera-driven path almost never produces can be compared with the
 // oracle's orc_bsdf_sample_ex / orc_bsdf_eval / orc_texture_eval.  Nothing here restates a routine: the kernels call what the shade stage calls.
 #include "kernels_common.h"
@@ -44,11 +45,84 @@ __global__ __launch_bounds__(WG) void k_debug_texture(DScene sc, uint32_t textur
     out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
 }
 
+// One call of sampleEmitterDirect<true, true, false, RAW> per thread: every emitter kind, analytic shapes, tables in global memory -- the widest instantiation the stages
+// have.  in8 = ref xyz, refN xyz, u, v.  out17 = value rgb, p xyz, d xyz, dist, pdf, n xyz, emitter index, delta flag, em_pdf (RAW only).  The record starts out zero;
+// no visibility test (the shadow queue makes it).
+template <bool RAW>
+__global__ __launch_bounds__(WG) void k_debug_emitter_sample(DScene sc, const float *in, uint64_t n, float *out) {
+    const uint64_t i = (uint64_t) blockIdx.x * WG + threadIdx.x;
+    if (i >= n) return;
+    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const float *p = in + i * 8; float *o = out + i * 17;
+    Direct dr; dr.p = V(0, 0, 0); dr.n = V(0, 0, 0); dr.d = V(0, 0, 0); dr.dist = 0.0f; dr.pdf = 0.0f; dr.em_pdf = 0.0f; dr.emitter = 0; dr.delta = false;
+    const v3 value = sampleEmitterDirect<true, true, false, RAW>(sc, tb, V(p[0], p[1], p[2]), V(p[3], p[4], p[5]), p[6], p[7], dr);
+    o[0] = value.x; o[1] = value.y; o[2] = value.z; o[3] = dr.p.x; o[4] = dr.p.y; o[5] = dr.p.z; o[6] = dr.d.x; o[7] = dr.d.y; o[8] = dr.d.z; o[9] = dr.dist; o[10] = dr.pdf;
+    o[11] = dr.n.x; o[12] = dr.n.y; o[13] = dr.n.z; o[14] = (float) dr.emitter; o[15] = dr.delta ? 1.0f : 0.0f; o[16] = RAW ? dr.em_pdf : 0.0f;
+}
+
+// What a BSDF-sampled ray that finds emitter `emitter` evaluates.  in11 = ref xyz, d xyz, n xyz, dist, facingRef (0 / 1).  out8:
+// kind 0 (area light): emitterEval(tb, e, n, -d) rgb, pdfEmitterDirect<true>(..., facingRef), 0...
+// kind 1 (envmap): envEval(d) rgb, envPdfDirection(to_local d), then value rgb and density of envEvalAndPdf(d)
+// kind 2 (constant): envEval rgb, 0... (its density is one line inside the shade stage)
+__global__ __launch_bounds__(WG) void k_debug_emitter_eval(DScene sc, int emitter, int kind, const float *in, uint64_t n, float *out) {
+    const uint64_t i = (uint64_t) blockIdx.x * WG + threadIdx.x;
+    if (i >= n) return;
+    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const float *p = in + i * 11; float *o = out + i * 8;
+    const v3 ref = V(p[0], p[1], p[2]), d = V(p[3], p[4], p[5]), nrm = V(p[6], p[7], p[8]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = 0.0f;
+    if (kind == 0) {
+        const v3 e = emitterEval(tb, emitter, nrm, -d);
+        o[0] = e.x; o[1] = e.y; o[2] = e.z; o[3] = pdfEmitterDirect<true>(sc, tb, emitter, ref, d, nrm, p[9], p[10] != 0.0f);
+    } else {
+        const v3 e = envEval(sc, d); o[0] = e.x; o[1] = e.y; o[2] = e.z;
+        if (kind == 1) {
+            o[3] = envPdfDirection(sc, mat3(sc.env_to_local, d));
+            v3 value; float pdfSA; envEvalAndPdf(sc, d, value, pdfSA);
+            o[4] = value.x; o[5] = value.y; o[6] = value.z; o[7] = pdfSA;
+        }
+    }
+}
+
+// The medium routines of the volumetric stages, one call per thread.  in10 / out12 per case:
+// mode 0 mediumTransmittance over [mint, maxt]: in[6], in[7] -> transmittance rgb
+// mode 1 mediumSampleDistance: o xyz, d xyz, mint, maxt, the two values its draw source hands out -> success, t, p xyz, transmittance rgb, pdfSuccess, pdfFailure, values drawn
+// mode 2 phaseSample, then phaseEval of its own result: wi xyz, the 2-D sample -> wo xyz, eval;  mode 3 phaseEval: wi xyz, wo xyz -> eval
+__global__ __launch_bounds__(WG) void k_debug_medium(DScene sc, uint32_t medium, int mode, const float *in, uint64_t n, float *out) {
+    const uint64_t i = (uint64_t) blockIdx.x * WG + threadIdx.x;
+    if (i >= n) return;
+    const MediumD md = sc.media[medium]; const float *p = in + i * 10; float *o = out + i * 12;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[k] = 0.0f;
+    if (mode == 0) { const v3 t = mediumTransmittance(md, p[6], p[7]); o[0] = t.x; o[1] = t.y; o[2] = t.z; }
+    else if (mode == 1) {
+        int drawn = 0; const float r0 = p[8], r1 = p[9];
+        MediumRec r; r.t = 0.0f; r.p = V(0, 0, 0); r.transmittance = V(0, 0, 0); r.pdfSuccess = 0.0f; r.pdfFailure = 0.0f;
+        const bool ok = mediumSampleDistance(md, V(p[0], p[1], p[2]), V(p[3], p[4], p[5]), p[6], p[7], [&]() { return drawn++ == 0 ? r0 : r1; }, r);
+        o[0] = ok ? 1.0f : 0.0f; o[1] = r.t; o[2] = r.p.x; o[3] = r.p.y; o[4] = r.p.z; o[5] = r.transmittance.x; o[6] = r.transmittance.y; o[7] = r.transmittance.z;
+        o[8] = r.pdfSuccess; o[9] = r.pdfFailure; o[10] = (float) drawn;
+    } else if (mode == 2) {
+        const v3 wi = V(p[0], p[1], p[2]), wo = phaseSample(md, wi, p[3], p[4]);
+        o[0] = wo.x; o[1] = wo.y; o[2] = wo.z; o[3] = phaseEval(md, wi, wo);
+    } else o[0] = phaseEval(md, V(p[0], p[1], p[2]), V(p[3], p[4], p[5]));
+}
+
 extern "C" {
 void mi_launch_debug_bsdf(const DScene &sc, int material, int mode, const float *in, uint64_t n, float *out, hipStream_t st) {
     hipLaunchKernelGGL(k_debug_bsdf, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, sc, material, mode, in, n, out);
 }
 void mi_launch_debug_texture(const DScene &sc, uint32_t texture, const float *uv, const float *partials, uint64_t n, float *out, hipStream_t st) {
     hipLaunchKernelGGL(k_debug_texture, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, sc, texture, uv, partials, n, out);
+}
+void mi_launch_debug_emitter_sample(const DScene &sc, int raw, const float *in, uint64_t n, float *out, hipStream_t st) {
+    if (raw) hipLaunchKernelGGL(k_debug_emitter_sample<true>, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, sc, in, n, out);
+    else hipLaunchKernelGGL(k_debug_emitter_sample<false>, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, sc, in, n, out);
+}
+void mi_launch_debug_emitter_eval(const DScene &sc, int emitter, int kind, const float *in, uint64_t n, float *out, hipStream_t st) {
+    hipLaunchKernelGGL(k_debug_emitter_eval, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, sc, emitter, kind, in, n, out);
+}
+void mi_launch_debug_medium(const DScene &sc, uint32_t medium, int mode, const float *in, uint64_t n, float *out, hipStream_t st) {
+    hipLaunchKernelGGL(k_debug_medium, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, sc, medium, mode, in, n, out);
 }
 }

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(WG) void k_shade_vol(DScene sc, RenderConst rc, Que
                 if (!(depth <= rc.max_depth || rc.max_depth < 0)) { pathLen += (unsigned) depth; break; }
                 const bool others = (fl & VOL_OTHERS) != 0, emitted = (fl & VOL_EMITTED) != 0, scattered = (fl & VOL_SCATTERED) != 0;
                 MediumRec mRec; bool mediumEvent = false; MediumD md;
-                if (medium >= 0) { md = sc.media[medium]; mediumEvent = mediumSampleDistance(md, o, d, 0.0f, tHit, ss, rc.sampler, m32, mRec); }
+                if (medium >= 0) { md = sc.media[medium]; mediumEvent = mediumSampleDistance(md, o, d, 0.0f, tHit, [&]() { return next1D(ss, rc.sampler, m32); }, mRec); }
                 if (depth == 1 && rc.opacity && prim == 0xFFFFFFFFu) {      // records.inl:131-137: EOpacity on a sensor ray that hits nothing -- what the medium in front of the sensor absorbs / scatters, or 0
                     float al = 0.0f;
                     if (medium >= 0) { const v3 p2 = o + d * rc.alpha_dist, dd = p2 - o; const v3 tr = mediumTransmittance(md, 0.0f, sqrtf(dot(dd, dd))); al = 1 - ((0.0f + tr.x) + tr.y + tr.z) * (1.0f / 3); }

@@ -1986,13 +1986,14 @@ DEV v3 mediumTransmittance(const MediumD &m, float mint, float maxt) {
     const float negLength = mint - maxt;
     return V(m.sigma_t[0] != 0 ? miFastExp(m.sigma_t[0] * negLength) : 1.0f, m.sigma_t[1] != 0 ? miFastExp(m.sigma_t[1] * negLength) : 1.0f, m.sigma_t[2] != 0 ? miFastExp(m.sigma_t[2] * negLength) : 1.0f);
 }
-// HomogeneousMedium::sampleDistance (homogeneous.cpp:275-349), strategies balance / single / manual; draws one or two 1-D samples
-template <typename P>
-DEV bool mediumSampleDistance(const MediumD &m, v3 o, v3 d, float mint, float maxt, SamplerState &ss, uint32_t kind, SobolTabT<P> st, MediumRec &r) {
-    float rnd = next1D(ss, kind, st), sampled, density = m.sampling_density;
+// HomogeneousMedium::sampleDistance (homogeneous.cpp:275-349), strategies balance / single / manual; draws one or two 1-D samples from `draw` (the stages:
+// next1D of the path's sampler state; mi_debug_medium: the caller's values)
+template <typename Draw>
+DEV bool mediumSampleDistance(const MediumD &m, v3 o, v3 d, float mint, float maxt, Draw draw, MediumRec &r) {
+    float rnd = draw(), sampled, density = m.sampling_density;
     if (rnd < m.medium_sampling_weight) {
         rnd /= m.medium_sampling_weight;
-        if (m.strategy == 0u) { int ch = (int) (next1D(ss, kind, st) * 3); if (ch > 2) ch = 2; density = ch == 0 ? m.sigma_t[0] : (ch == 1 ? m.sigma_t[1] : m.sigma_t[2]); }
+        if (m.strategy == 0u) { int ch = (int) (draw() * 3); if (ch > 2) ch = 2; density = ch == 0 ? m.sigma_t[0] : (ch == 1 ? m.sigma_t[1] : m.sigma_t[2]); }
         sampled = -miFastLog(1 - rnd) / density;
     } else sampled = INFINITY;
     const float distSurf = maxt - mint; bool success = true;

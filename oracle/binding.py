@@ -105,6 +105,9 @@ def lib():
         L.orc_bsdf_sample_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]
         L.orc_texture_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         L.orc_texture_last_info.argtypes = [C.c_void_p]
+        L.orc_emitter_sample_units.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+        L.orc_emitter_eval_units.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p, C.c_void_p]
+        L.orc_medium_units.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.orc_filter_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_sfmt_sequence.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
         L.orc_sfmt_floats.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
@@ -270,6 +273,38 @@ class Oracle:
             f(h, texture, us[i][0], us[i][1], pp + 16 * i if pp is not None else None, po + 12 * i)
             if info: g(pi + 12 * i)
         return (out, inf) if info else out
+
+    EMITTER_BRANCHES = {"area_mesh": 1, "area_analytic": 2, "envmap": 4, "constant": 8, "point": 16, "spot": 32, "directional": 64, "collimated": 128,
+                        "sphere_cone": 1 << 8, "sphere_whole": 1 << 9, "spot_outside": 1 << 10, "spot_beam": 1 << 11, "spot_transition": 1 << 12, "directional_behind": 1 << 13,
+                        "constant_normal": 1 << 14, "constant_no_normal": 1 << 15, "constant_zero_value": 1 << 16, "env_zero_value": 1 << 17, "env_zero_pdf": 1 << 18,
+                        "env_missed_sphere": 1 << 19, "env_near": 1 << 20, "env_far": 1 << 21, "envpdf_non_finite": 1 << 22}
+
+    def emitter_sample_units(self, ref, ref_n, uv, raw=False):
+        """orc_emitter_sample_units (one C call for all rows) -> [n, 17] = value rgb, p, d, dist, pdf, n, emitter index, delta flag, em_pdf (raw only), and uint32 [n] =
+        the branches taken (EMITTER_BRANCHES)."""
+        ref = np.ascontiguousarray(ref, np.float32).reshape(-1, 3); rn = np.ascontiguousarray(ref_n, np.float32).reshape(-1, 3); uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        n = len(ref); assert len(rn) == n and len(uv) == n
+        out = np.zeros((n, 17), np.float32); br = np.zeros(n, np.uint32)
+        lib().orc_emitter_sample_units(self.h, _ptr(ref), _ptr(rn), _ptr(uv), n, int(bool(raw)), _ptr(out), _ptr(br)); return out, br
+
+    def emitter_eval_units(self, emitter, ref, d, nrm, dist, facing):
+        """orc_emitter_eval_units -> [n, 8] (area: value rgb, pdfEmitterDirect; envmap: value rgb, solid-angle density; constant: value rgb) and the branches taken."""
+        ref = np.ascontiguousarray(ref, np.float32).reshape(-1, 3); d = np.ascontiguousarray(d, np.float32).reshape(-1, 3); nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        dist = np.ascontiguousarray(dist, np.float32).reshape(-1); fc = np.ascontiguousarray(facing, np.float32).reshape(-1); n = len(ref)
+        assert len(d) == len(nrm) == len(dist) == len(fc) == n
+        out = np.zeros((n, 8), np.float32); br = np.zeros(n, np.uint32)
+        if lib().orc_emitter_eval_units(self.h, int(emitter), _ptr(ref), _ptr(d), _ptr(nrm), _ptr(dist), _ptr(fc), n, _ptr(out), _ptr(br)) != 0:
+            raise ValueError(f"oracle: emitter {emitter} is out of range or a light no ray finds")
+        return out, br
+
+    MEDIUM_BRANCHES = {"chosen": 1, "not_chosen": 2, "channel_0": 4, "channel_1": 8, "channel_2": 16, "success": 32, "p_equals_o": 64, "beyond": 128, "cut": 256}
+    MEDIUM_MODES = {"transmittance": 0, "distance": 1, "phase_sample": 2, "phase_eval": 3}
+
+    def medium_units(self, medium, mode, inputs):
+        """orc_medium_units: `mode` out of MEDIUM_MODES, inputs [n, 10] as laid out in pt_oracle.c -> [n, 12] and the branches taken (MEDIUM_BRANCHES; distance only)."""
+        a = np.ascontiguousarray(inputs, np.float32).reshape(-1, 10); n = len(a); out = np.zeros((n, 12), np.float32); br = np.zeros(n, np.uint32)
+        if lib().orc_medium_units(self.h, int(medium), self.MEDIUM_MODES[mode], _ptr(a), n, _ptr(out), _ptr(br)) != 0: raise ValueError(f"oracle: medium {medium} is out of range")
+        return out, br
 
     def camera_ray(self, sx, sy):
         o = np.zeros(8, np.float32); lib().orc_camera_ray(self.h, sx, sy, _ptr(o)); return o

@@ -133,6 +133,7 @@ typedef struct {
     uint32_t px, py; uint64_t sample_index, sobol_index; uint32_t dim;   /* sobol */
     uint32_t v0, call;                                                  /* independent */
     float *log; int nlog;
+    const float *replay;                                                /* kind 2 (orc_medium_units): the values come from the caller, `call` counts them */
 } sampler_t;
 
 static void sampler_begin(sampler_t *sp, const orc_scene *sc, uint32_t px, uint32_t py, uint64_t sample_index, float *log) {
@@ -150,6 +151,7 @@ static void sampler_begin(sampler_t *sp, const orc_scene *sc, uint32_t px, uint3
 static inline void slog(sampler_t *sp, float v) { if (sp->log && sp->nlog < 64) sp->log[sp->nlog] = v; sp->nlog++; }
 static float next1D(sampler_t *sp) {
     float v;
+    if (sp->kind == 2) return sp->replay[sp->call++];
     if (sp->kind == 1) {
         if (sp->dim >= 5 && sp->dim < 5) sp->dim = 5;          /* sobol.cpp:220-221 with start == end == 5: never taken */
         v = orc_sobol_sample(sp->sc, sp->sobol_index, sp->dim++);
@@ -160,6 +162,7 @@ static float next1D(sampler_t *sp) {
     slog(sp, v); return v;
 }
 static void next2D(sampler_t *sp, float *x, float *y) {
+    if (sp->kind == 2) { *x = sp->replay[sp->call++]; *y = sp->replay[sp->call++]; return; }
     if (sp->kind == 1) {
         if (sp->dim + 1 >= 5 && sp->dim < 5) sp->dim = 5;      /* sobol.cpp:233-235: a 2D request at dim 4 skips to 5 */
         if (sp->dim == 0 && sp->sobol_index != sp->sample_index) {  /* sobol.cpp:241-243 */
@@ -445,6 +448,13 @@ static void analytic_uv(const analytic_t *sh, float lx, float ly, v3 p_ray, floa
     }
     }
 }
+/* what the emitter routines did since the bits were last cleared (orc_emitter_sample_units / orc_emitter_eval_units hand them out per case): set where the branches are
+ * taken, not classified a second time */
+enum { EMI_AREA_MESH = 1, EMI_AREA_ANALYTIC = 2, EMI_ENVMAP = 4, EMI_CONSTANT = 8, EMI_POINT = 16, EMI_SPOT = 32, EMI_DIRECTIONAL = 64, EMI_COLLIMATED = 128,
+       EMI_SPHERE_CONE = 1 << 8, EMI_SPHERE_WHOLE = 1 << 9, EMI_SPOT_OUTSIDE = 1 << 10, EMI_SPOT_BEAM = 1 << 11, EMI_SPOT_TRANSITION = 1 << 12, EMI_DIRECTIONAL_BEHIND = 1 << 13,
+       EMI_CONSTANT_NORMAL = 1 << 14, EMI_CONSTANT_NO_NORMAL = 1 << 15, EMI_CONSTANT_ZERO_VALUE = 1 << 16, EMI_ENV_ZERO_VALUE = 1 << 17, EMI_ENV_ZERO_PDF = 1 << 18,
+       EMI_ENV_MISSED_SPHERE = 1 << 19, EMI_ENV_NEAR = 1 << 20, EMI_ENV_FAR = 1 << 21, EMI_ENVPDF_NON_FINITE = 1 << 22 };
+static _Thread_local uint32_t g_em_info;
 /* Shape::samplePosition: rectangle.cpp:215-221, disk.cpp:252-260, cylinder.cpp:235-250 (sphere: see analytic_sample_direct) */
 static void analytic_sample_position(const analytic_t *sh, float sx, float sy, v3 *p, v3 *n) {
     switch (sh->a.type) {
@@ -478,6 +488,7 @@ static void analytic_sample_direct(const analytic_t *sh, v3 ref, float sx, float
         float refDist2 = dot(refToCenter, refToCenter), invRefDist = 1.0f / sqrtf(refDist2);
         float sinAlpha = radius * invRefDist;
         if (sinAlpha < 1 - EPSILON) {
+            g_em_info |= EMI_SPHERE_CONE;
             float cosAlpha = sqrtf(maxf(1.0f - sinAlpha * sinAlpha, 0.0f));
             v3 fn = scale(refToCenter, invRefDist), fs, ft; coordinate_system(fn, &fs, &ft);        /* Frame(n), include/mitsuba/core/frame.h:53-55 */
             v3 c = uniform_cone(cosAlpha, sx, sy);
@@ -495,6 +506,7 @@ static void analytic_sample_direct(const analytic_t *sh, v3 ref, float sx, float
             *p = add(sh->center, scale(*n, radius));
             *dOut = d;
         } else {
+            g_em_info |= EMI_SPHERE_WHOLE;
             v3 dl = uniform_sphere(sx, sy);
             *p = add(sh->center, scale(dl, radius)); *n = dl;
             v3 d = sub(*p, ref);
@@ -519,7 +531,8 @@ static float analytic_pdf_direct(const analytic_t *sh, v3 ref, v3 d, v3 n, float
     if (sh->a.type == SH_SPHERE) {
         v3 refToCenter = sub(sh->center, ref);
         float invRefDist = 1.0f / length3(refToCenter), sinAlpha = sh->a.radius * invRefDist;
-        if (sinAlpha < 1 - EPSILON) { float cosAlpha = sqrtf(maxf(1 - sinAlpha * sinAlpha, 0.0f)); return (0.5f * INV_PI) / (1 - cosAlpha); }
+        if (sinAlpha < 1 - EPSILON) { g_em_info |= EMI_SPHERE_CONE; float cosAlpha = sqrtf(maxf(1 - sinAlpha * sinAlpha, 0.0f)); return (0.5f * INV_PI) / (1 - cosAlpha); }
+        g_em_info |= EMI_SPHERE_WHOLE;
     }
     if (sh->a.type == SH_SPHERE) return sh->inv_area * dist * dist / fabsf(dot(d, n));   /* sphere.cpp:370-372 (association as written there) */
     return sh->inv_area * (dist * dist) / fabsf(dot(d, n));
@@ -1594,7 +1607,7 @@ static void env_sample_direction(const orc_scene *s, float sx, float sy, v3 *d, 
 /* envmap.cpp:611-638 internalPdfDirection */
 static float env_pdf_direction(const orc_scene *s, v3 d) {
     float uvx = atan2f(d.x, -d.z) * INV_TWOPI, uvy = acosf(minf(1.0f, maxf(-1.0f, d.y))) * INV_PI;
-    if (!isfinite(uvx) || !isfinite(uvy)) return 0.0f;
+    if (!isfinite(uvx) || !isfinite(uvy)) { g_em_info |= EMI_ENVPDF_NON_FINITE; return 0.0f; }
     float u = uvx * (float) s->env_w - 0.5f, v = uvy * (float) s->env_h - 0.5f;
     v3 v1, v2; int yPos; env_bilinear_pair(s, u, v, &v1, &v2, &yPos);
     float sinTheta = sqrtf(maxf(1 - d.y * d.y, 0.0f));
@@ -1647,41 +1660,43 @@ static v3 sample_emitter_direct(const orc_scene *s, v3 ref, v3 refN, float sx, f
         if (em->type == 2) {
             /* ConstantBackgroundEmitter::sampleDirect (constant.cpp:175-217) */
             v3 d; float pdf, nearT, farT;
+            g_em_info |= EMI_CONSTANT;
             if (!is_zero(refN)) {
+                g_em_info |= EMI_CONSTANT_NORMAL;
                 v3 l = cos_hemisphere(sx, sy); pdf = INV_PI * l.z;
                 v3 fs, ft; coordinate_system(refN, &fs, &ft);
                 d = add(add(scale(fs, l.x), scale(ft, l.y)), scale(refN, l.z));
-            } else { d = uniform_sphere(sx, sy); pdf = INV_FOURPI; }
-            if (!bsphere_intersect(s->env_bs_center, s->env_bs_radius, ref, d, &nearT, &farT)) return V(0, 0, 0);
-            if (!(nearT < 0 && farT > 0)) return V(0, 0, 0);
+            } else { g_em_info |= EMI_CONSTANT_NO_NORMAL; d = uniform_sphere(sx, sy); pdf = INV_FOURPI; }
+            if (!bsphere_intersect(s->env_bs_center, s->env_bs_radius, ref, d, &nearT, &farT)) { g_em_info |= EMI_ENV_MISSED_SPHERE; return V(0, 0, 0); }
+            if (!(nearT < 0 && farT > 0)) { g_em_info |= !(nearT < 0) ? EMI_ENV_NEAR : EMI_ENV_FAR; return V(0, 0, 0); }
             dr->p = add(ref, scale(d, farT)); dr->n = normalize(sub(s->env_bs_center, dr->p)); dr->d = d; dr->dist = farT; dr->pdf = pdf;
-            if (!is_zero(refN) && dot(d, refN) <= 0) value = V(0, 0, 0);       /* NB pdf stays non-zero: the shadow ray is still traced */
+            if (!is_zero(refN) && dot(d, refN) <= 0) { g_em_info |= EMI_CONSTANT_ZERO_VALUE; value = V(0, 0, 0); }       /* NB pdf stays non-zero: the shadow ray is still traced */
             else { float r = 1.0f / pdf; value = V(em->radiance[0] * r, em->radiance[1] * r, em->radiance[2] * r); }
         } else if (em->type == 3 || em->type == 4) {
             /* PointEmitter::sampleDirect (point.cpp:133-149), SpotEmitter::sampleDirect (spot.cpp:187-203) + falloffCurve (:108-128) */
-            dr->delta = 1;
+            dr->delta = 1; g_em_info |= em->type == 4 ? EMI_SPOT : EMI_POINT;
             dr->p = V(em->to_world[3], em->to_world[7], em->to_world[11]);
             dr->d = sub(dr->p, ref); dr->dist = length3(dr->d);
             float invDist = 1.0f / dr->dist; dr->d = scale(dr->d, invDist); dr->n = V(0, 0, 0); dr->pdf = 1.0f;
             v3 I = V(em->radiance[0], em->radiance[1], em->radiance[2]);
             if (em->type == 4) {
                 v3 local = mat3(&s->spot_to_local[ei * 9], neg(dr->d)); float cosTheta = local.z, f;
-                if (cosTheta <= s->spot_cos_cutoff[ei]) f = 0.0f;
-                else if (cosTheta >= s->spot_cos_beam[ei]) f = 1.0f;
-                else f = (s->spot_cutoff[ei] - acosf(cosTheta)) * s->spot_inv_transition[ei];
+                if (cosTheta <= s->spot_cos_cutoff[ei]) { g_em_info |= EMI_SPOT_OUTSIDE; f = 0.0f; }
+                else if (cosTheta >= s->spot_cos_beam[ei]) { g_em_info |= EMI_SPOT_BEAM; f = 1.0f; }
+                else { g_em_info |= EMI_SPOT_TRANSITION; f = (s->spot_cutoff[ei] - acosf(cosTheta)) * s->spot_inv_transition[ei]; }
                 I = scale(I, f);
             }
             value = scale(I, invDist * invDist);
         } else if (em->type == 7) {
             /* CollimatedBeamEmitter::sampleDirect (collimated.cpp:129-133): direct sampling always fails for a response function on a 0-D space */
-            dr->pdf = 0.0f; return V(0, 0, 0);
+            g_em_info |= EMI_COLLIMATED; dr->pdf = 0.0f; return V(0, 0, 0);
         } else {
             /* DirectionalEmitter::sampleDirect (directional.cpp:159-180) */
-            dr->delta = 1;
+            dr->delta = 1; g_em_info |= EMI_DIRECTIONAL;
             v3 d = V(em->to_world[2], em->to_world[6], em->to_world[10]);
             v3 diskCenter = sub(s->dir_bs_center, scale(d, s->dir_bs_radius));
             float distance = dot(sub(ref, diskCenter), d);
-            if (distance < 0) return V(0, 0, 0);
+            if (distance < 0) { g_em_info |= EMI_DIRECTIONAL_BEHIND; return V(0, 0, 0); }
             dr->p = sub(ref, scale(d, distance)); dr->d = neg(d); dr->n = d; dr->dist = distance; dr->pdf = 1.0f;
             value = V(em->radiance[0], em->radiance[1], em->radiance[2]);
         }
@@ -1699,11 +1714,16 @@ static v3 sample_emitter_direct(const orc_scene *s, v3 ref, v3 refN, float sx, f
     if (em->type == 1) {
         /* EnvironmentMap::sampleDirect (src/emitters/envmap.cpp:520-547) */
         v3 value, dl; float pdf, nearT, farT;
+        g_em_info |= EMI_ENVMAP;
         env_sample_direction(s, sx, sy, &dl, &value, &pdf);
         v3 dw = mat3(s->env_to_world, dl);
-        if (is_zero(value) || pdf == 0 || !bsphere_intersect(s->env_bs_center, s->env_bs_radius, ref, dw, &nearT, &farT) || nearT >= 0 || farT <= 0) {
-            dr->pdf = 0.0f; return V(0, 0, 0);
-        }
+        uint32_t why = 0;                                  /* (the reference's one condition, its terms in their order) */
+        if (is_zero(value)) why = EMI_ENV_ZERO_VALUE;
+        else if (pdf == 0) why = EMI_ENV_ZERO_PDF;
+        else if (!bsphere_intersect(s->env_bs_center, s->env_bs_radius, ref, dw, &nearT, &farT)) why = EMI_ENV_MISSED_SPHERE;
+        else if (nearT >= 0) why = EMI_ENV_NEAR;
+        else if (farT <= 0) why = EMI_ENV_FAR;
+        if (why) { g_em_info |= why; dr->pdf = 0.0f; return V(0, 0, 0); }
         dr->pdf = pdf; dr->p = add(ref, scale(dw, farT)); dr->n = normalize(sub(s->env_bs_center, dr->p)); dr->dist = farT; dr->d = dw;
         { float r = 1.0f / pdf; value = scale(value, r); }
         if (test_visibility == 1) {
@@ -1715,6 +1735,7 @@ static v3 sample_emitter_direct(const orc_scene *s, v3 ref, v3 refN, float sx, f
         return value;
     }
     dr->ref = ref;
+    g_em_info |= (uint32_t) em->shape >= s->d.n_shapes ? EMI_AREA_ANALYTIC : EMI_AREA_MESH;
     if ((uint32_t) em->shape >= s->d.n_shapes) {       /* area light on an analytic shape: Shape::sampleDirect / Sphere::sampleDirect, no sample reuse */
         analytic_sample_direct(&s->analytic[(uint32_t) em->shape - s->d.n_shapes], ref, sx, sy, &dr->p, &dr->n, &dr->d, &dr->dist, &dr->pdf);
     } else {
@@ -1779,6 +1800,41 @@ void orc_sample_emitter_direct(const orc_scene *s, const float *rp, const float 
     v3 val = sample_emitter_direct(s, V(rp[0], rp[1], rp[2]), refN, u, v, &dr, 1, NULL);
     o[0] = val.x; o[1] = val.y; o[2] = val.z; o[3] = dr.p.x; o[4] = dr.p.y; o[5] = dr.p.z; o[6] = dr.d.x; o[7] = dr.d.y; o[8] = dr.d.z;
     o[9] = dr.dist; o[10] = dr.pdf; o[11] = is_zero(val) ? 0.0f : pdf_emitter_direct(s, &dr, refN);
+}
+/* Scene::sampleEmitterDirect over arrays, without the visibility test (the device's shadow queue makes it): out17 per case = value rgb, p, d, dist, pdf, n, emitter index,
+ * !isOnSurface, em_pdf (raw only); raw = Scene::sampleAttenuatedEmitterDirect's form (the value not yet divided by the selection probability); branches: EMI_* per case */
+void orc_emitter_sample_units(const orc_scene *s, const float *ref, const float *refN, const float *uv, uint64_t n, int raw, float *out, uint32_t *branches) {
+    for (uint64_t i = 0; i < n; ++i) {
+        direct_t dr; memset(&dr, 0, sizeof(dr)); g_em_info = 0; float *o = out + i * 17;
+        v3 val = sample_emitter_direct(s, V(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]), V(refN[3 * i], refN[3 * i + 1], refN[3 * i + 2]), uv[2 * i], uv[2 * i + 1], &dr, raw ? 2 : 0, NULL);
+        o[0] = val.x; o[1] = val.y; o[2] = val.z; o[3] = dr.p.x; o[4] = dr.p.y; o[5] = dr.p.z; o[6] = dr.d.x; o[7] = dr.d.y; o[8] = dr.d.z; o[9] = dr.dist; o[10] = dr.pdf;
+        o[11] = dr.n.x; o[12] = dr.n.y; o[13] = dr.n.z; o[14] = (float) dr.emitter; o[15] = dr.delta ? 1.0f : 0.0f; o[16] = raw ? dr.em_pdf : 0.0f;
+        if (branches) branches[i] = g_em_info;
+    }
+}
+/* what a BSDF-sampled ray that finds emitter `emitter` evaluates, over arrays: out8 per case = area light: emitter_eval(n, -d) rgb, pdf_emitter_direct (facing = dot(d, refN) >= 0
+ * as the caller knew it); envmap: env_eval rgb, env_pdf_direction of the local direction; constant: env_eval rgb; the rest 0.  Returns 0, or -1 for an index out of range or a
+ * point / spot / directional / collimated emitter (no ray finds one) */
+int orc_emitter_eval_units(const orc_scene *s, uint32_t emitter, const float *ref, const float *d, const float *nrm, const float *dist, const float *facing, uint64_t n, float *out, uint32_t *branches) {
+    if (emitter >= s->d.n_emitters || s->emitters[emitter].type > 2) return -1;
+    const uint32_t type = s->emitters[emitter].type;
+    for (uint64_t i = 0; i < n; ++i) {
+        float *o = out + i * 8; for (int k = 0; k < 8; ++k) o[k] = 0.0f;
+        const v3 dv = V(d[3 * i], d[3 * i + 1], d[3 * i + 2]); g_em_info = 0;
+        if (type == 0) {
+            direct_t dr; memset(&dr, 0, sizeof(dr));
+            dr.ref = V(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]); dr.d = dv; dr.n = V(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]); dr.dist = dist[i]; dr.emitter = (int32_t) emitter;
+            g_em_info |= (uint32_t) s->emitters[emitter].shape >= s->d.n_shapes ? EMI_AREA_ANALYTIC : EMI_AREA_MESH;
+            v3 e = emitter_eval(s, (int32_t) emitter, dr.n, neg(dv));
+            o[0] = e.x; o[1] = e.y; o[2] = e.z; o[3] = pdf_emitter_direct(s, &dr, facing[i] != 0 ? dv : neg(dv));      /* dot(d, d) >= 0, dot(d, -d) < 0 for every d != 0 */
+        } else {
+            v3 e = env_eval(s, dv); o[0] = e.x; o[1] = e.y; o[2] = e.z;
+            g_em_info |= type == 1 ? EMI_ENVMAP : EMI_CONSTANT;
+            if (type == 1) o[3] = env_pdf_direction(s, mat3(s->env_to_local, dv));
+        }
+        if (branches) branches[i] = g_em_info;
+    }
+    return 0;
 }
 
 /* ---- bitmap textures: TMIPMap (include/mitsuba/render/mipmap.h): evalTexel :504-560, evalBox :562-566, evalBilinear :572-596, eval :625-705,
@@ -2377,6 +2433,9 @@ static v3 path_li(const orc_scene *s, v3 o, v3 d, float mint, float maxt, sample
 static inline float mi_fastexp(float v) { return (float) exp((double) v); }
 static inline float mi_fastlog(float v) { return (float) log((double) v); }
 typedef struct { float t; v3 p; v3 transmittance; float pdf_success, pdf_failure; } mrec_t;
+/* what medium_sample_distance did since the bits were last cleared (orc_medium_units): set where the branches are taken */
+enum { MEDI_CHOSEN = 1, MEDI_NOT_CHOSEN = 2, MEDI_CHANNEL_0 = 4, MEDI_CHANNEL_1 = 8, MEDI_CHANNEL_2 = 16, MEDI_SUCCESS = 32, MEDI_P_EQUALS_O = 64, MEDI_BEYOND = 128, MEDI_CUT = 256 };
+static _Thread_local uint32_t g_med_info;
 static inline void medium_sigma_t(const orc_medium *m, float *st) { for (int i = 0; i < 3; ++i) st[i] = m->sigma_a[i] + m->sigma_s[i]; }     /* medium.cpp:36 */
 /* HomogeneousMedium::evalTransmittance (homogeneous.cpp:266-273) over [mint, maxt] of a ray */
 static v3 medium_transmittance(const orc_medium *m, float mint, float maxt) {
@@ -2389,15 +2448,15 @@ static int medium_sample_distance(const orc_medium *m, v3 o, v3 d, float mint, f
     float st[3]; medium_sigma_t(m, st);
     float rnd = next1D(sp), sampled, density = m->sampling_density;
     if (rnd < m->medium_sampling_weight) {
-        rnd /= m->medium_sampling_weight;
-        if (m->strategy == 0) { int ch = (int) (next1D(sp) * 3); if (ch > 2) ch = 2; density = st[ch]; }
+        rnd /= m->medium_sampling_weight; g_med_info |= MEDI_CHOSEN;
+        if (m->strategy == 0) { int ch = (int) (next1D(sp) * 3); if (ch > 2) ch = 2; density = st[ch]; g_med_info |= MEDI_CHANNEL_0 << ch; }
         sampled = -mi_fastlog(1 - rnd) / density;
-    } else sampled = INFINITY;
+    } else { g_med_info |= MEDI_NOT_CHOSEN; sampled = INFINITY; }
     const float distSurf = maxt - mint; int success = 1;
     if (sampled < distSurf) {
         r->t = sampled + mint; r->p = add(o, scale(d, r->t));
-        if (r->p.x == o.x && r->p.y == o.y && r->p.z == o.z) success = 0;
-    } else { sampled = distSurf; success = 0; }
+        if (r->p.x == o.x && r->p.y == o.y && r->p.z == o.z) { g_med_info |= MEDI_P_EQUALS_O; success = 0; } else g_med_info |= MEDI_SUCCESS;
+    } else { g_med_info |= MEDI_BEYOND; sampled = distSurf; success = 0; }
     if (m->strategy == 0) {
         r->pdf_failure = 0; r->pdf_success = 0;
         for (int i = 0; i < 3; ++i) { float tmp = mi_fastexp(-st[i] * sampled); r->pdf_failure += tmp; r->pdf_success += st[i] * tmp; }
@@ -2406,7 +2465,7 @@ static int medium_sample_distance(const orc_medium *m, v3 o, v3 d, float mint, f
     r->transmittance = V(mi_fastexp(st[0] * (-sampled)), mi_fastexp(st[1] * (-sampled)), mi_fastexp(st[2] * (-sampled)));
     r->pdf_success = r->pdf_success * m->medium_sampling_weight;
     r->pdf_failure = m->medium_sampling_weight * r->pdf_failure + (1 - m->medium_sampling_weight);
-    if (maxf(maxf(r->transmittance.x, r->transmittance.y), r->transmittance.z) < 1e-20f) r->transmittance = V(0, 0, 0);
+    if (maxf(maxf(r->transmittance.x, r->transmittance.y), r->transmittance.z) < 1e-20f) { g_med_info |= MEDI_CUT; r->transmittance = V(0, 0, 0); }
     return success;
 }
 /* IsotropicPhaseFunction::eval (isotropic.cpp:74-76), HGPhaseFunction::eval (hg.cpp:108-111); wi = -ray.d, wo = the sampled direction */
@@ -2427,6 +2486,32 @@ static v3 phase_sample(const orc_medium *m, v3 wi, sampler_t *sp) {
     v3 n = neg(wi), fs, ft; coordinate_system(n, &fs, &ft);           /* Frame(-pRec.wi).toWorld */
     v3 l = V(sinTheta * cosPhi, sinTheta * sinPhi, cosTheta);
     return add(add(scale(fs, l.x), scale(ft, l.y)), scale(n, l.z));
+}
+/* the four routines above over arrays of n cases; in10 per case = mode 0 (evalTransmittance): -, -, -, -, -, -, mint, maxt; mode 1 (sampleDistance): o xyz, d xyz, mint, maxt, and
+ * the two values its sampler hands out; mode 2 (PhaseFunction::sample, then eval of its own result): wi xyz, the 2-D sample; mode 3 (eval): wi xyz, wo xyz.  out12 = mode 0:
+ * transmittance rgb; mode 1: success, t, p xyz, transmittance rgb, pdfSuccess, pdfFailure, values drawn (t and p start out zero); mode 2: wo xyz, eval; mode 3: eval; the rest 0.
+ * branches (may be NULL): MEDI_* per case of mode 1.  -1: medium or mode out of range */
+int orc_medium_units(const orc_scene *s, uint32_t medium, int mode, const float *in, uint64_t n, float *out, uint32_t *branches) {
+    if (medium >= s->d.n_media || mode < 0 || mode > 3) return -1;
+    const orc_medium *m = &s->media[medium];
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *p = in + i * 10; float *o = out + i * 12; for (int k = 0; k < 12; ++k) o[k] = 0.0f;
+        g_med_info = 0;
+        if (mode == 0) { v3 t = medium_transmittance(m, p[6], p[7]); o[0] = t.x; o[1] = t.y; o[2] = t.z; }
+        else if (mode == 1) {
+            sampler_t sp; memset(&sp, 0, sizeof(sp)); sp.kind = 2; sp.replay = p + 8;
+            mrec_t r; memset(&r, 0, sizeof(r));
+            int ok = medium_sample_distance(m, V(p[0], p[1], p[2]), V(p[3], p[4], p[5]), p[6], p[7], &sp, &r);
+            o[0] = ok ? 1.0f : 0.0f; o[1] = r.t; o[2] = r.p.x; o[3] = r.p.y; o[4] = r.p.z; o[5] = r.transmittance.x; o[6] = r.transmittance.y; o[7] = r.transmittance.z;
+            o[8] = r.pdf_success; o[9] = r.pdf_failure; o[10] = (float) sp.call;
+        } else if (mode == 2) {
+            sampler_t sp; memset(&sp, 0, sizeof(sp)); sp.kind = 2; sp.replay = p + 3;
+            v3 wi = V(p[0], p[1], p[2]), wo = phase_sample(m, wi, &sp);
+            o[0] = wo.x; o[1] = wo.y; o[2] = wo.z; o[3] = phase_eval(m, wi, wo);
+        } else o[0] = phase_eval(m, V(p[0], p[1], p[2]), V(p[3], p[4], p[5]));
+        if (branches) branches[i] = g_med_info;
+    }
+    return 0;
 }
 static inline int shape_interior(const orc_scene *s, uint32_t shape) { return s->d.shape_media ? s->d.shape_media[shape * 2] : -1; }
 static inline int shape_exterior(const orc_scene *s, uint32_t shape) { return s->d.shape_media ? s->d.shape_media[shape * 2 + 1] : -1; }

@@ -114,3 +114,121 @@ def texture_properties(lookup, sc, keep=None):
 def test_texture_properties_oracle(mi, oracle):
     sc, orc, per = U.texture_reference(oracle, mi.scenes)
     texture_properties(lambda t, uv, pa: orc.texture_units(t, uv, pa), sc)
+
+
+# ------------------------------------------------------------------------------------------------ emitters
+LIGHT_ALL = U.LIGHT_SCENES + U.UNIT_LIGHT_SCENES
+SPOT_ZONES = ["spot_outside", "spot_outside", "spot_transition", "spot_transition", "spot_beam", "spot_beam"]      # one ulp below, on, one ulp above: the cut-off cosine (<=), then the beam cosine (>=)
+
+
+def scene_branches(sc, name):
+    """the branches of orc_emitter_sample_units a scene has, from its emitter list"""
+    kinds = {e["type"] for e in sc.emitters}; want = set()
+    if any(e["type"] == 0 and e["shape"] < len(sc.shapes) for e in sc.emitters): want.add("area_mesh")
+    analytic = [sc.analytic[e["shape"] - len(sc.shapes)] for e in sc.emitters if e["type"] == 0 and e["shape"] >= len(sc.shapes)]
+    if analytic: want.add("area_analytic")
+    if any(a["type"] == 2 for a in analytic): want |= {"sphere_cone", "sphere_whole"}
+    if 1 in kinds: want |= {"envmap", "env_missed_sphere", "env_near", "env_far"}
+    # a sample of zero value: the tent warp reaches one texel beyond the chosen one, which is black only in the unit maps (the row with a single texel)
+    if name in U.UNIT_LIGHT_SCENES: want.add("env_zero_value")
+    if 2 in kinds: want |= {"constant", "constant_normal", "constant_no_normal", "constant_zero_value", "env_missed_sphere", "env_near", "env_far"}
+    if 3 in kinds: want.add("point")
+    if 4 in kinds: want |= {"spot", "spot_outside", "spot_beam", "spot_transition"}
+    if 5 in kinds: want |= {"directional", "directional_behind"}
+    if 7 in kinds: want.add("collimated")
+    return want
+
+
+@pytest.mark.parametrize("name", LIGHT_ALL)
+def test_emitter_census(mi, oracle, golden_scenes, name):
+    """conditions on the INPUTS of the emitter comparisons, measured on the oracle alone: every branch the scene has is taken by at least 1 % of the sampling cases, at
+    least 0.2 of them carry a value, no case makes env_pdf_direction form a non-finite texel coordinate, and the points aimed at a spot light's cones hit the stored
+    cosines exactly (the zones flip between the neighbours the comparisons `<=` and `>=` say).  env_zero_pdf is exempt: a sample has zero density only where its value
+    is zero, and that term comes first."""
+    r = U.light_reference(oracle, golden_scenes, mi.scenes, name); sc = r["sc"]; s = r["sample"]; B = oracle.Oracle.EMITTER_BRANCHES; br = s["branches"]
+    share = {k: float(((br & v) != 0).mean()) for k, v in B.items()}; want = scene_branches(sc, name)
+    value = float((s["out"][:, :3] != 0).any(1).mean())
+    print(f"[emitter-census] {name}: value {value:.3f}; " + ", ".join(f"{k} {share[k]:.4f}" for k in B if share[k] > 0))
+    assert {k for k in B if share[k] > 0} - {"env_zero_value", "env_zero_pdf"} <= want, (name, share)
+    for k in sorted(want): assert share[k] >= 0.01, (name, k, share[k])
+    assert value >= 0.2, (name, value)
+    assert share["envpdf_non_finite"] == 0 and np.isfinite(s["inp"]["ref"]).all() and np.isfinite(s["inp"]["uv"]).all()
+    assert (s["inp"]["uv"] >= 0).all() and (s["inp"]["uv"] <= np.float32(U.ONE_MINUS)).all() and (s["inp"]["ref_n"][::5] == 0).all()
+    for special in (0.0, U.ONE_MINUS, U.TWO_M32):
+        for col in (0, 1): assert (s["inp"]["uv"][:, col] == np.float32(special)).mean() >= 0.03, (name, special, col)      # one in sixteen each (u = 0 gives some up in the unit scenes)
+    if "spot" in want:
+        t = s["inp"]["spot_target"]; spot = (br & B["spot"]) != 0
+        for j, zone in enumerate(SPOT_ZONES):
+            mine = spot & (t == j); assert mine.sum() >= 8 and ((br[mine] & B[zone]) != 0).all(), (name, j, zone, int(mine.sum()))
+    # the raw form: the same record, the value not yet divided by the selection probability
+    lit = s["out"][:, 10] != 0; raw = s["raw"]
+    assert (bits(raw[:, 3:16]) == bits(s["out"][:, 3:16]))[lit].all() and (raw[lit, 16] > 0).all() and (bits(raw[lit, :3] * (np.float32(1) / raw[lit, 16:17])) == bits(s["out"][lit, :3])).all()
+    for e, ev in r["eval"].items():
+        vs = float((ev["out"][:, :3] != 0).any(1).mean()); ps = float((ev["out"][:, 3] != 0).mean())
+        print(f"[emitter-census] {name} eval emitter {e} ({U.EMITTER_KIND_NAMES[sc.emitters[e]['type']]}): value {vs:.3f} density {ps:.3f}")
+        assert ((ev["branches"] & B["envpdf_non_finite"]) == 0).all() and all(np.isfinite(ev["inp"][k]).all() for k in ("ref", "d", "n", "dist"))
+        assert vs >= 0.2 and (ps >= 0.2 or sc.emitters[e]["type"] == 2), (name, e, vs, ps)
+        if sc.emitters[e]["type"] == 0 and e in [i for i, em in enumerate(sc.emitters) if em["shape"] >= len(sc.shapes) and sc.analytic[em["shape"] - len(sc.shapes)]["type"] == 2]:
+            for k in ("sphere_cone", "sphere_whole"): assert ((ev["branches"] & B[k]) != 0).mean() >= 0.01, (name, e, k)
+
+
+def test_emitter_units_equal_pinned_export(mi, oracle, golden_scenes):
+    """orc_emitter_sample_units is orc_sample_emitter_direct -- the export test_oracle_golden pins to the compiled reference -- bit for bit wherever that one's
+    visibility test lets the sample through"""
+    L = oracle.lib(); o12 = np.zeros(12, np.float32); seen = 0
+    for name in U.LIGHT_SCENES:
+        r = U.light_reference(oracle, golden_scenes, mi.scenes, name); inp = r["sample"]["inp"]; out = r["sample"]["out"]; orc = oracle.Oracle(r["sc"])
+        for i in range(0, U.N_LIGHT, 16):
+            L.orc_sample_emitter_direct(orc.h, inp["ref"][i].ctypes.data, inp["ref_n"][i].ctypes.data, float(inp["uv"][i, 0]), float(inp["uv"][i, 1]), o12.ctypes.data)
+            if not o12[:3].any(): continue
+            assert (bits(o12[:11]) == bits(out[i, :11])).all(), (name, i, o12, out[i]); seen += 1
+    assert seen > 200
+
+
+def test_light_unit_scenes(mi):
+    """the unit scenes are what the comparisons need: a zero-area triangle in the middle (8 x 4: at the head) of a light mesh of three and of one of five triangles, the selection table
+    0, 0.5, 0.75, 1, maps without a black row, one row with a single texel, row guide tables with more buckets than bins for the odd sizes"""
+    for (w, h), name in zip(U.ENV_SIZES, U.UNIT_LIGHT_SCENES):
+        sc = U.light_scene(mi.scenes, w, h); assert sc.name == name and U.emitter_cdf(sc).tolist() == [0.0, 0.5, 0.75, 1.0]
+        for (e, ts), count, middle in zip(U._mesh_lights(sc), (3, 5), (0, 0) if (w, h) == U.ENV_SIZES[1] else (1, 2)):
+            area = np.linalg.norm(np.cross(ts[:, 1] - ts[:, 0], ts[:, 2] - ts[:, 0]), axis=1); assert len(ts) == count and area[middle] == 0 and (np.delete(area, middle) > 0).all()
+        rgb = sc.envmap["rgb"]; assert rgb.shape == (h, w, 3) and (rgb.sum((1, 2)) > 0).all() and ((rgb[U.SINGLE_TEXEL_ROW] != 0).any(1).sum() == 1)
+        kr, kc = U.guide_buckets(w, h); assert kr >= h and (kr > h or h & (h - 1) == 0)
+    assert U.guide_buckets(5, 3) == (4, 2) and U.guide_buckets(64, 32) == (32, 16) and U.guide_buckets(1024, 512) == (512, 256)
+
+
+# ------------------------------------------------------------------------------------------------ participating media
+MEDIUM_ALL = U.MEDIUM_SCENES + ["medium_units"]
+
+
+def medium_branches(med):
+    """the branches of medium_sample_distance a record can take.  A weight of 1 always chooses the medium, and then no distance it can draw leaves less than 1e-20 of
+    the thinnest channel (-log(2^-24) = 16.6 mean free paths at most); a channel with sigma_t = 0 keeps its transmittance at 1; the single strategy on such a channel
+    draws an infinite distance every time"""
+    st = np.asarray(med["sigma_a"], np.float32) + np.asarray(med["sigma_s"], np.float32); w = med["medium_sampling_weight"]; want = {"chosen", "beyond"}
+    if w < 1: want.add("not_chosen")
+    if med["strategy"] == 0: want |= {"channel_0", "channel_1", "channel_2"}
+    if not (med["strategy"] == 1 and med["sampling_density"] == 0): want |= {"success", "p_equals_o"}
+    if w < 1 and st.min() > 0: want.add("cut")
+    return want
+
+
+@pytest.mark.parametrize("name", MEDIUM_ALL)
+def test_medium_census(mi, oracle, golden_scenes, name):
+    """conditions on the INPUTS of the medium comparisons, measured on the oracle alone: every branch of medium_sample_distance a record can take is taken by at least
+    1 % of its cases; the values drawn are what the strategy says; the transmittance cases reach 0, 1 and what lies between"""
+    r = U.medium_reference(oracle, golden_scenes, mi.scenes, name); B = oracle.Oracle.MEDIUM_BRANCHES; assert r["records"]
+    for m, per in r["records"].items():
+        med = r["sc"].media[m]; br = per["distance"]["branches"]; share = {k: float(((br & v) != 0).mean()) for k, v in B.items()}; want = medium_branches(med)
+        print(f"[medium-census] {name} record {m} (strategy {med['strategy']}, weight {med['medium_sampling_weight']:.3g}, g {med['g']:.3g}): " + ", ".join(f"{k} {v:.3f}" for k, v in share.items()))
+        assert {k for k in B if share[k] > 0} <= want | {"cut"}, (name, m, share)
+        for k in sorted(want): assert share[k] >= 0.01, (name, m, k, share[k])
+        out = per["distance"]["out"]; chosen = (br & B["chosen"]) != 0
+        assert (out[:, 10] == np.where(chosen & (med["strategy"] == 0), 2.0, 1.0)).all() and (out[:, 0] == ((br & B["success"]) != 0)).all()
+        t = per["transmittance"]["out"][:, :3]; assert (t == 0).any() and (t == 1).any() and ((t > 0.01) & (t < 0.99)).any() and not np.isnan(t).any()
+        assert np.isfinite(per["phase_sample"]["out"][:, :4]).all() and np.isfinite(per["phase_eval"]["out"][:, 0]).all()
+        assert (np.abs(np.linalg.norm(per["phase_sample"]["out"][:, :3].astype(np.float64), axis=1) - 1) < 1e-2).all()      # (a sanity check only: at |g| = 0.999 the map's cosTheta cancels and may pass 1 by some 1e-4, in the reference too)
+    if name == "medium_units":
+        media = r["sc"].media; assert sorted({round(md["g"], 7) for md in media if md["phase"] == 1}) == sorted(round(float(np.float32(g)), 7) for g in U.HG_G)
+        assert {md["strategy"] for md in media} == {0, 1, 2} and {md["medium_sampling_weight"] for md in media} >= {1.0, 0.5, 2.0 ** -10, U.FLT_MIN}
+        assert any(min(a + b for a, b in zip(md["sigma_a"], md["sigma_s"])) == 0 for md in media)

@@ -1,4 +1,5 @@
-"""Inputs of the unit-level comparisons of the BSDF and texture routines (tests/test_unit_inputs.py on the CPU, tests/test_gpu_units.py on the device): one generator,
+"""Inputs of the unit-level comparisons of the BSDF, texture and emitter routines (tests/test_unit_inputs.py on the CPU, tests/test_gpu_units.py and
+tests/test_gpu_light_units.py on the device): one generator,
 fixed seeds, so that both sides and both tests see the same numbers.  Directions and sample values are aimed at what camera-driven paths almost never produce:
 grazing and exactly normal incidence, sample values 0 and 1 - 2^-24, directions below a one-sided surface, texture coordinates on texel edges and wrap seams,
 degenerate and non-finite footprints."""
@@ -216,3 +217,360 @@ def texture_reference(oracle, S):
             per[t] = dict(uv=uv, pa=pa, ref=ref, info=info, plain=orc.texture_units(t, uv), keep=info[:, 2] <= MAX_EWA_TEXELS)
         _TEX_REF["ref"] = (sc, orc, per)
     return _TEX_REF["ref"]
+
+
+# ------------------------------------------------------------------------------------------------ emitters
+# Inputs of the comparisons of Scene::sampleEmitterDirect and of what a BSDF-sampled ray that finds an emitter evaluates (mi_debug_emitter_sample / _eval against
+# orc_emitter_sample_units / orc_emitter_eval_units): reference points on the lights' planes, at their vertices, inside and far from a sphere light, on a spot light's
+# cones, behind a directional light's disk and outside the environment's bounding sphere; sample values on the entries of the tables the searches walk.
+LIGHT_SCENES = ["cornell_small", "cbox_lights", "cbox_collimated", "open_constant", "shape_lights", "atrium_small", "fog_sky", "sky_view", "veach_small"]
+N_LIGHT = 4096
+ENV_SIZES = [(5, 3), (8, 4), (64, 32)]            # width, height of the unit scene's environment maps: the odd ones give guide tables with more buckets than bins
+UNIT_LIGHT_SCENES = [f"light_units_{w}x{h}" for w, h in ENV_SIZES]
+MI_EPSILON = 1e-4
+TWO_M32 = 2.0 ** -32
+EMITTER_KIND_NAMES = {0: "area", 1: "envmap", 2: "constant", 3: "point", 4: "spot", 5: "directional", 7: "collimated"}
+SINGLE_TEXEL_ROW = 1                              # the row of the unit scene's maps that holds one non-black texel
+
+
+def light_envmap(w, h):
+    """dim rows (0.01 .. 0.05) with one lit texel each at the seam columns 0 and w - 1 and in the pole rows 0 and h - 1; row SINGLE_TEXEL_ROW holds a single
+    non-black texel (column w // 2): its column table is all empty bins but one.  No row is entirely black: its table would be 0 x infinity on every side, which the
+    reference does not define."""
+    rng = np.random.default_rng([w, h, 577]); rgb = rng.uniform(0.01, 0.05, (h, w, 3))
+    rgb[0, 0] = (40.0, 30.0, 20.0); rgb[h - 1, w - 1] = (10.0, 30.0, 50.0)
+    if h > 3: rgb[2, w - 1] = (25.0, 25.0, 5.0); rgb[h - 2, 0] = (5.0, 20.0, 20.0)
+    rgb[SINGLE_TEXEL_ROW] = 0.0; rgb[SINGLE_TEXEL_ROW, w // 2] = (3.0, 2.0, 1.0)
+    return np.ascontiguousarray(rgb, f32)
+
+
+def light_scene(S, w, h):
+    """The unit scene: a floor, a light mesh of three triangles and one of five, each with a zero-area triangle (empty bins on both routes of the triangle search),
+    under a w x h environment map.  The zero-area triangle sits in the middle of each mesh, under the 8 x 4 map at its head: a search arrives at an empty bin only
+    where the table starts with one (v = 0), and DiscreteDistribution::sample then steps on to the first bin that is not empty -- unlike the environment map's
+    sampleReuse, which has no such step (emitter_sample_inputs).  Emitter weights 2, 1, 1: the selection table is 0, 0.5, 0.75, 1, so that the reused sample of the environment
+    map is 2 u without a rounding error.  The 5 x 3 map sits in the world frame (world directions are its local ones), the others are rotated."""
+    verts, tris, shapes = [], [], []
+    def mesh(points, faces, bsdf, emitter):
+        fv, ft = len(verts), len(tris); verts.extend(points); tris.extend([tuple(fv + i for i in f) for f in faces])
+        shapes.append(dict(first_tri=ft, tri_count=len(faces), first_vert=fv, vert_count=len(points), bsdf=bsdf, emitter=emitter, face_normals=1, group=0, interior=-1, exterior=-1))
+    mesh([(4, 0, -4), (-4, 0, -4), (-4, 0, 4), (4, 0, 4)], [(0, 1, 2), (0, 2, 3)], 0, -1)
+    # (1, 2, 0), (0, 2, 1), (0.5, 2, 0.5) lie on one line: the cross product of the sides is exactly zero
+    head = (w, h) == ENV_SIZES[1]; order = (lambda f, k: [f[k]] + f[:k] + f[k + 1:]) if head else (lambda f, k: f)
+    mesh([(0, 2, 0), (1, 2, 0), (0, 2, 1), (0.5, 2, 0.5), (1, 2, 1)], order([(0, 1, 2), (1, 2, 3), (1, 4, 2)], 1), 1, 1)
+    mesh([(2, 2.5, 0), (3, 2.5, 0), (2, 2.5, 1), (2.5, 2.5, 0.5), (3, 2.5, 1), (4, 2.5, 0), (4, 2.5, 1)], order([(0, 1, 2), (1, 4, 2), (1, 2, 3), (1, 5, 4), (5, 6, 4)], 2), 1, 2)
+    bsdfs = [S.make_bsdf(reflectance=(0.5, 0.5, 0.5)), S.make_bsdf(reflectance=(0.0, 0.0, 0.0))]
+    emitters = [dict(type=S.EMITTER_ENVMAP, shape=-1, radiance=(0.0, 0.0, 0.0), weight=2.0), dict(type=S.EMITTER_AREA, shape=1, radiance=(9.0, 7.0, 5.0), weight=1.0),
+                dict(type=S.EMITTER_AREA, shape=2, radiance=(2.0, 6.0, 3.0), weight=1.0)]
+    to_world = np.eye(4, dtype=f32) if (w, h) == ENV_SIZES[0] else (S.rotate((0, 1, 0), 25.0) @ S.rotate((1, 0, 0), 8.0)).astype(f32)
+    env = dict(rgb=light_envmap(w, h), to_world=to_world, scale=0.8, filtered=False)
+    cam = S.look_at((0.5, 1.0, -5.0), (0.5, 1.0, 0.0), (0, 1, 0))
+    return S.finish_scene(verts, tris, shapes, bsdfs, emitters, cam, 50.0, 0.05, 100.0, 32, 32, 1, S.SAMPLER_SOBOL, 4, 3, envmap=env, name=f"light_units_{w}x{h}")
+
+
+def emitter_cdf(sc):
+    """the emitter-selection table as both sides build it (float32 running sum, times the reciprocal of the total, last entry 1)"""
+    c = [f32(0)]
+    for e in sc.emitters: c.append(f32(c[-1] + f32(e["weight"])))
+    norm = f32(1) / c[-1]; c = [f32(x * norm) for x in c]; c[0] = f32(0); c[-1] = f32(1)
+    return np.asarray(c, f32)
+
+
+def guide_buckets(w, h):
+    """bucket counts of the guide tables of a w x h environment map (rows, columns): csrc/scene_build.cpp"""
+    p2 = lambda v: 1 << max(0, int(v - 1).bit_length())
+    return min(p2(h), 4096), min(max(p2(w) // 4, 1), 1024)
+
+
+def _mesh_lights(sc):
+    """(emitter index, triangles [t, 3, 3]) of every area light on a mesh"""
+    return [(e, sc.pos[sc.idx[sc.shapes[em["shape"]]["first_tri"]:sc.shapes[em["shape"]]["first_tri"] + sc.shapes[em["shape"]]["tri_count"]]].astype(np.float64))
+            for e, em in enumerate(sc.emitters) if em["type"] == 0 and em["shape"] < len(sc.shapes)]
+
+
+def _analytic_lights(sc):
+    return [(e, sc.analytic[em["shape"] - len(sc.shapes)]) for e, em in enumerate(sc.emitters) if em["type"] == 0 and em["shape"] >= len(sc.shapes)]
+
+
+def scene_box(sc):
+    """the box both sides derive the directional light's disk and the environment's bounding sphere from: the vertices and the boxes of the analytic shapes (a
+    sphere's exactly, the others' by their corner points -- no scene here has one of those next to a directional or environment emitter)"""
+    lo, hi = sc.pos.min(0).astype(np.float64), sc.pos.max(0).astype(np.float64)
+    for a in sc.get("analytic") or []:
+        m = np.asarray(a["to_world"], np.float64).reshape(4, 4)
+        if a["type"] == 2: pts = [m[:3, 3] - a["radius"], m[:3, 3] + a["radius"]]
+        else:
+            r = a["radius"] if a["type"] == 3 else 1.0; z = [0.0, a["length"]] if a["type"] == 3 else [0.0]
+            pts = [(m @ np.array([x, y, zz, 1.0]))[:3] for x in (-r, r) for y in (-r, r) for zz in z]
+        lo = np.minimum(lo, np.min(pts, 0)); hi = np.maximum(hi, np.max(pts, 0))
+    return lo, hi
+
+
+def _unit(rng, n):
+    v = rng.normal(size=(n, 3)); return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def spot_tables(em):
+    """cos(cutoff), cos(beam) and the rotation part of the inverse transform of a spot light as both sides store them (float32; cosf through the double routine)"""
+    import math
+    rad = f32(np.pi) / f32(180.0); cutoff = f32(em["cutoff"]) * rad; beam = f32(em["beam"]) * rad
+    m = np.asarray(em["to_world"], f32).reshape(4, 4); a = [m[0, 0], m[0, 1], m[0, 2], m[1, 0], m[1, 1], m[1, 2], m[2, 0], m[2, 1], m[2, 2]]
+    det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]); i = f32(1) / det
+    row2 = [(a[3] * a[7] - a[4] * a[6]) * i, (a[1] * a[6] - a[0] * a[7]) * i, (a[0] * a[4] - a[1] * a[3]) * i]
+    return f32(math.cos(float(cutoff))), f32(math.cos(float(beam))), np.asarray(row2, f32)
+
+
+def spot_cos_theta(em, ref):
+    """Frame::cosTheta of the direction from a spot light to `ref` [n, 3] in the light's frame, in the operation order of SpotEmitter::sampleDirect (float32)"""
+    _, _, r2 = spot_tables(em); m = np.asarray(em["to_world"], f32).reshape(4, 4); ref = np.asarray(ref, f32)
+    dx, dy, dz = (m[0, 3] - ref[:, 0]), (m[1, 3] - ref[:, 1]), (m[2, 3] - ref[:, 2])
+    inv = f32(1) / np.sqrt(dx * dx + dy * dy + dz * dz); dx, dy, dz = dx * inv, dy * inv, dz * inv
+    return r2[0] * -dx + r2[1] * -dy + r2[2] * -dz
+
+
+def _spot_points(em, rng, scale):
+    """reference points whose cosTheta is EXACTLY the stored cut-off cosine, the stored beam cosine, or one ulp either side of one of them: candidates around each
+    cone, kept where spot_cos_theta hits the target; in the order (below, on, above) x (cut-off, beam), repeated.  test_unit_inputs checks through the oracle's zones
+    that the targets were hit."""
+    cc, cb, _ = spot_tables(em); m = np.asarray(em["to_world"], np.float64).reshape(4, 4); per = []
+    targets = [t for c in (cc, cb) for t in (np.nextafter(c, f32(-1)), c, np.nextafter(c, f32(2)))]
+    k = 20000; theta0 = np.arccos(np.asarray([float(c) for c in (cc, cb)]))
+    for j, t in enumerate(targets):
+        th = theta0[j // 3] + rng.uniform(-4e-7, 4e-7, k); ph = rng.uniform(0, 2 * np.pi, k); dist = rng.uniform(0.2, 1.0, k) * scale
+        local = np.stack([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)], 1)
+        ref = (m[:3, 3] + (local @ m[:3, :3].T) * dist[:, None]).astype(f32)
+        hit = ref[spot_cos_theta(em, ref) == t]
+        assert len(hit) >= 8, (j, len(hit))
+        per.append(hit[:64])
+    n = min(len(p) for p in per)
+    return np.stack([p[:n] for p in per], 1).reshape(-1, 3)            # rows 6 i .. 6 i + 5: the six targets
+
+
+def light_points(sc, rng):
+    """the special reference points of a scene, one array [k, 3] per kind"""
+    lo, hi = scene_box(sc); size = float(np.linalg.norm(hi - lo)); out = {}
+    tris = [t for _, ts in _mesh_lights(sc) for t in ts if np.linalg.norm(np.cross(t[1] - t[0], t[2] - t[0])) > 0]
+    if tris:
+        T = np.asarray(tris); k = 256; t = T[rng.integers(0, len(T), k)]; ab = rng.uniform(-1.0, 2.0, (k, 2))
+        out["light_plane"] = t[:, 0] + (t[:, 1] - t[:, 0]) * ab[:, :1] + (t[:, 2] - t[:, 0]) * ab[:, 1:]
+        out["light_vertex"] = np.asarray([t for _, ts in _mesh_lights(sc) for t in ts]).reshape(-1, 3)
+    for e, a in _analytic_lights(sc):
+        m = np.asarray(a["to_world"], np.float64).reshape(4, 4)
+        if a["type"] in (0, 1):
+            xy = rng.uniform(-2.0, 2.0, (128, 2)); out[f"light_plane_{e}"] = (np.concatenate([xy, np.zeros((128, 1)), np.ones((128, 1))], 1) @ m.T)[:, :3]
+        if a["type"] == 2:
+            c, r = m[:3, 3], a["radius"]; u = _unit(rng, 96)
+            band = r / (1.0 - MI_EPSILON * np.repeat([0.5, 0.9, 1.0, 1.1, 2.0, 10.0], 16))      # sinAlpha = radius / distance around 1 - epsilon, from both sides
+            out[f"sphere_{e}"] = np.concatenate([np.tile(c, (8, 1)), c + u[:16] * r, c + u * band[:, None], c + u[:16] * r * 0.5, c + u[:32] * r * 1e4])
+    for em in sc.emitters:
+        m = np.asarray(em.get("to_world", np.eye(4)), np.float64).reshape(4, 4)
+        if em["type"] in (3, 4): out.setdefault("light_position", []).append(m[:3, 3])
+        if em["type"] == 4: out["spot_cones"] = _spot_points(em, rng, 0.5 * size)
+        if em["type"] == 5:
+            d = m[:3, 2]; c = 0.5 * (lo + hi); r = 0.5 * size * 1.1; centre = c - d * r; t = np.cross(d, _unit(rng, 96)); s = rng.uniform(0.0, 2.0, (96, 1)) * r
+            out["directional_disk"] = np.concatenate([centre + t[:48] * s[:48], centre + t[48:] * s[48:] - d * rng.uniform(0.0, 1.0, (48, 1)) * r])
+        if em["type"] in (1, 2):
+            cam = np.asarray(sc.cam_to_world, np.float64).reshape(4, 4)[:3, 3]; l2, h2 = np.minimum(lo, cam), np.maximum(hi, cam)
+            c = 0.5 * (l2 + h2); r = max(MI_EPSILON, 0.5 * float(np.linalg.norm(h2 - l2)) * 1.5); u = _unit(rng, 192)
+            # on the sphere, and outside it by a share of 1e-4 .. 0.2 of the radius: close enough for a sampled direction to meet the sphere ahead or behind about as often as it misses
+            out["environment_sphere"] = np.concatenate([c + u[:32] * r, c + u[32:] * r * (1.0 + 10.0 ** rng.uniform(-4.0, -0.7, (160, 1)))])
+    if "light_position" in out: out["light_position"] = np.tile(np.asarray(out["light_position"]), (16, 1))
+    return {k: np.asarray(v, np.float64) for k, v in out.items()}
+
+
+def _env_row_cdf(rgb):
+    lum = rgb.astype(np.float64) @ np.array([0.212671, 0.715160, 0.072169]); h = len(lum)
+    c = np.concatenate([[0.0], np.cumsum(lum.sum(1) * np.sin((np.arange(h) + 0.5) * np.pi / h))]); return c / c[-1]
+
+
+def sample_edges(sc):
+    """sample values on the entries of the tables the searches walk, each with its float32 neighbours: for u the emitter table's entries and k / n, and -- mapped back
+    through the sample reuse of the environment emitter's bin -- the bucket borders b / K of the column guide tables; for v the borders of the row guide table and the
+    entries of every light mesh's triangle table"""
+    def around(x):
+        x = np.asarray(x, f32).reshape(-1); a = np.concatenate([np.nextafter(x, f32(-1)), x, np.nextafter(x, f32(2))]); return a[(a > 0) & (a < 1)]      # 0 has its own share; 1 is no sample value
+    c = emitter_cdf(sc); n = len(sc.emitters); u = [c, np.arange(n + 1, dtype=f32) / f32(n)]; v = []
+    if sc.envmap is not None:
+        h, w = sc.envmap["rgb"].shape[:2]; kr, kc = guide_buckets(w, h); e = [i for i, em in enumerate(sc.emitters) if em["type"] == 1][0]
+        u.append(c[e] + (c[e + 1] - c[e]) * (np.arange(kc + 1, dtype=f32) / f32(kc))); v.append(np.arange(kr + 1, dtype=f32) / f32(kr)); v.append(_env_row_cdf(sc.envmap["rgb"]))
+    for _, ts in _mesh_lights(sc):
+        area = 0.5 * np.linalg.norm(np.cross(ts[:, 1] - ts[:, 0], ts[:, 2] - ts[:, 0]), axis=1); v.append(np.cumsum(area) / area.sum()); v.append(np.arange(len(ts) + 1) / len(ts))
+    return around(np.concatenate(u)), (around(np.concatenate(v)) if v else np.zeros(0, f32))
+
+
+def emitter_sample_inputs(name, sc):
+    """ref [n, 3], ref_n [n, 3], uv [n, 2], `kinds`: which special kind of reference point a case holds ("" = uniform in the box), and `spot_target`: for a point of
+    _spot_points which of its six targets it hits (else -1)"""
+    rng = np.random.default_rng([zlib.crc32(name.encode()), 1618]); n = N_LIGHT
+    lo, hi = scene_box(sc); ref = rng.uniform(lo, hi, (n, 3)); kinds = np.array([""] * n, dtype=object); target = np.full(n, -1)
+    special = light_points(sc, rng); m = n // 2; names = sorted(special)
+    if "environment_sphere" in names: names += ["environment_sphere"] * 2             # (three turns: of its points only those the emitter search gives to the environment count, and of those a sampled direction must still meet the sphere)
+    # the second half: the special kinds in turn
+    for j in range(m):
+        k = names[j % len(names)]; p = special[k]
+        if k == "spot_cones": i = (j // len(names)) % len(p); row = p[i]; target[n - m + j] = i % 6      # in order: all six targets come up equally often
+        else: row = p[rng.integers(0, len(p))]
+        ref[n - m + j] = row; kinds[n - m + j] = k
+    nrm = _unit(rng, n); nrm[::5] = 0.0                                             # every fifth one a two-sided surface
+    ue, ve = sample_edges(sc); uv = np.minimum(rng.uniform(size=(n, 2)).astype(f32), f32(ONE_MINUS))
+    for col, edges in ((0, ue), (1, ve)):
+        r = rng.integers(0, 16, n); uv[r == 0, col] = 0.0; uv[r == 1, col] = ONE_MINUS; uv[r == 2, col] = TWO_M32
+        if len(edges): pick = r == 3; uv[pick, col] = edges[rng.integers(0, len(edges), int(pick.sum()))]
+    # u = 0 is given only to tables whose first bin is not empty.  An empty first bin turns the reused sample into 0 / 0 and then -- through the tent warp and
+    # floorf -- into a float-to-int conversion of NaN, which C leaves undefined.  That is the environment map's sampleReuse; of its tables only the column table of
+    # the unit maps' SINGLE_TEXEL_ROW starts with empty bins: a case whose v selects that row (or lies within 1e-6 of its interval) takes u = 2^-32 in place of 0.
+    # Both searches then still cross the empty bins.  (The emitter and triangle tables are DiscreteDistribution::sample's, which steps over empty bins before the
+    # sample is reused: v = 0 on the 8 x 4 scene's triangle tables, which start with an empty bin, is defined and stays.)
+    if name in UNIT_LIGHT_SCENES:
+        rc = _env_row_cdf(sc.envmap["rgb"]); r = SINGLE_TEXEL_ROW
+        hit = (uv[:, 0] == 0) & (uv[:, 1] >= rc[r] - 1e-6) & (uv[:, 1] <= rc[r + 1] + 1e-6); uv[hit, 0] = TWO_M32
+    return dict(ref=np.ascontiguousarray(ref, f32), ref_n=np.ascontiguousarray(nrm, f32), uv=np.ascontiguousarray(uv), kinds=kinds, spot_target=target)
+
+
+EVAL_DIRECTIONS = [(0, 1, 0), (0, -1, 0), (0.0, 0.3, 0.9539392), (-0.0, 0.3, 0.9539392), (0.0, -0.6, 0.8), (1, 0, 0), (-1, 0, 0), (0, 0, 1), (0, 0, -1),
+                   (0, 0.6, 0.8), (0.6, 0, 0.8), (0.6, 0.8, 0), (0, 0.6, -0.8), (-0.6, 0.8, 0)]      # the poles, the seam (x = +-0, z > 0), the axes, a zero component
+
+
+def evaluable(sc):
+    return [e for e, em in enumerate(sc.emitters) if em["type"] in (0, 1, 2)]
+
+
+def emitter_eval_inputs(name, sc, e, sample_inp, sampled):
+    """the inputs of what a BSDF-sampled ray that finds emitter e evaluates: ref [n, 3], d [n, 3], n [n, 3], dist [n], facing [n].  Directions: uniform, with a quarter
+    out of EVAL_DIRECTIONS (for an environment map in its own frame and in the world's) and on the borders and centres of its texels; emitter normals: uniform, with a
+    quarter at |d . n| of 0, 1e-7, 1e-4; every fourth case is the oracle's own sample for emitter_sample_inputs' case where that chose emitter e (`sampled`)."""
+    ev = evaluable(sc); n = N_LIGHT // len(ev); rng = np.random.default_rng([zlib.crc32(name.encode()), e, 3141]); em = sc.emitters[e]
+    lo, hi = scene_box(sc); size = float(np.linalg.norm(hi - lo)); ref = rng.uniform(lo, hi, (n, 3)); d = _unit(rng, n)
+    pts = light_points(sc, rng).get(f"sphere_{e}")                                    # a sphere light: half of the reference points at its centre, on it, in its band, far away
+    if pts is not None: j = np.arange(n // 2, n); ref[j] = pts[rng.integers(0, len(pts), len(j))]
+    edge = rng.uniform(size=n) < 0.25; ed = np.asarray(EVAL_DIRECTIONS, np.float64)[rng.integers(0, len(EVAL_DIRECTIONS), n)]
+    if em["type"] == 1:
+        h, w = sc.envmap["rgb"].shape[:2]; m = np.asarray(sc.envmap["to_world"], np.float64).reshape(4, 4)[:3, :3]
+        # directions through the borders and the centres of texels: (col + 0 or 0.5) / w, (row + 0 or 0.5) / h
+        tex = rng.uniform(size=n) < 0.25; ph = 2 * np.pi * rng.integers(0, 2 * w + 1, n) / (2 * w); th = np.pi * rng.integers(0, 2 * h + 1, n) / (2 * h)
+        tdir = np.stack([np.sin(ph) * np.sin(th), np.cos(th), -np.cos(ph) * np.sin(th)], 1)
+        ed = np.where(tex[:, None] & ~edge[:, None], tdir, ed); edge |= tex
+        local = rng.uniform(size=n) < 0.5; ed = np.where(local[:, None], ed @ m.T, ed)
+    d = np.where(edge[:, None], ed, d).astype(f32)
+    t = np.cross(d.astype(np.float64), _unit(rng, n)); t /= np.maximum(np.linalg.norm(t, axis=1, keepdims=True), 1e-30)
+    c = np.where(rng.uniform(size=n) < 0.25, np.asarray([0.0, 1e-7, 1e-4])[rng.integers(0, 3, n)], rng.uniform(0.0, 1.0, n)) * np.where(rng.uniform(size=n) < 0.75, -1.0, 1.0)
+    nrm = (t * np.sqrt(1 - c * c)[:, None] + d * c[:, None]).astype(f32)
+    dist = (rng.uniform(0.01, 1.0, n) * size).astype(f32); facing = (rng.uniform(size=n) < 0.75).astype(f32)
+    ref = ref.astype(f32)
+    mine = np.flatnonzero((sampled[:, 14] == e) & (sampled[:, 10] != 0) & np.isfinite(sampled[:, 3:14]).all(1))
+    take = np.arange(0, n, 4)[:len(mine)]
+    if len(take):
+        src = mine[:len(take)]; ref[take] = sample_inp["ref"][src]; d[take] = sampled[src, 6:9]; nrm[take] = sampled[src, 11:14]; dist[take] = sampled[src, 9]; facing[take] = 1.0
+    return dict(ref=ref, d=np.ascontiguousarray(d, f32), n=nrm, dist=dist, facing=facing)
+
+
+_LIGHT_REF = {}
+
+
+def light_scenes(golden_scenes, S):
+    """name -> scene: the golden scenes of LIGHT_SCENES and the three unit scenes"""
+    if "scenes" not in _LIGHT_REF:
+        _LIGHT_REF["scenes"] = {**{k: golden_scenes[k] for k in LIGHT_SCENES}, **{f"light_units_{w}x{h}": light_scene(S, w, h) for w, h in ENV_SIZES}}
+    return _LIGHT_REF["scenes"]
+
+
+def light_reference(oracle, golden_scenes, S, name):
+    """the inputs of scene `name` and the oracle's answers, computed once: dict(sc, sample = dict(inp, out [n, 17], branches, raw [n, 17]), eval = {emitter:
+    dict(inp, out [n, 8], branches)})"""
+    if name not in _LIGHT_REF:
+        sc = light_scenes(golden_scenes, S)[name]; orc = oracle.Oracle(sc); inp = emitter_sample_inputs(name, sc)
+        out, br = orc.emitter_sample_units(inp["ref"], inp["ref_n"], inp["uv"]); raw, _ = orc.emitter_sample_units(inp["ref"], inp["ref_n"], inp["uv"], raw=True)
+        ev = {}
+        for e in evaluable(sc):
+            ei = emitter_eval_inputs(name, sc, e, inp, out); eo, eb = orc.emitter_eval_units(e, ei["ref"], ei["d"], ei["n"], ei["dist"], ei["facing"])
+            ev[e] = dict(inp=ei, out=eo, branches=eb)
+        _LIGHT_REF[name] = dict(sc=sc, sample=dict(inp=inp, out=out, branches=br, raw=raw), eval=ev)
+    return _LIGHT_REF[name]
+
+
+# ------------------------------------------------------------------------------------------------ participating media
+# Inputs of the comparisons of the medium routines (mi_debug_medium against orc_medium_units): the records of the fog scenes and those of a table of its own.
+MEDIUM_SCENES = ["fog_box", "fog_mis", "fog_sky"]
+N_MEDIUM = 2048
+FLT_MIN = float(np.finfo(f32).tiny)
+HG_G = [0.0, 5e-5, 1.5e-4, 0.4, -0.4, 0.9, -0.9, 0.999, -0.999]      # 5e-5 and 1.5e-4: either side of the |g| < epsilon switch of the Henyey-Greenstein map
+AXES = np.array([(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)], np.float64)
+
+
+def medium_scene(S):
+    """the unit light scene under a medium table of its own (no shape refers to it: the routines are called on the records): the manual strategy, a channel with
+    sigma_t = 0 under each strategy, medium_sampling_weight of 1, 0.5, 2^-10 and the smallest normal float (neither make_medium nor the commit refuses a weight), and a
+    Henyey-Greenstein record per entry of HG_G"""
+    sc = light_scene(S, *ENV_SIZES[1]); sa, ss = (0.05, 0.1, 0.2), (0.9, 0.8, 0.7)
+    media = [S.make_medium(sa, ss, strategy=S.MEDIUM_MANUAL, sampling_density=0.7),
+             S.make_medium((0.0, 0.1, 0.2), (0.0, 0.5, 0.3)), S.make_medium((0.0, 0.1, 0.2), (0.0, 0.5, 0.3), strategy=S.MEDIUM_SINGLE), S.make_medium((0.2, 0.0, 0.1), (0.3, 0.0, 0.5), strategy=S.MEDIUM_SINGLE, channel=0),
+             S.make_medium((0.0, 0.1, 0.2), (0.0, 0.5, 0.3), strategy=S.MEDIUM_MANUAL, sampling_density=0.4)]
+    media += [S.make_medium(sa, ss, medium_sampling_weight=w) for w in (1.0, 0.5, 2.0 ** -10, FLT_MIN)]
+    media += [S.make_medium((0.2, 0.05, 0.2), (0.5, 1.0, 0.5), strategy=S.MEDIUM_SINGLE, medium_sampling_weight=w) for w in (1.0, 2.0 ** -10)]
+    media += [S.make_medium(sa, ss, phase=S.PHASE_HG, g=g) for g in HG_G]
+    sc.media = media; sc.sensor_medium = -1; sc.integrator = S.INTEGRATOR_VOLPATH_SIMPLE; sc.name = "medium_units"
+    sc.shape_media = np.full((len(sc.shapes) + len(sc.analytic), 2), -1, np.int32)
+    return sc
+
+
+def _directions_with_axes(rng, n):
+    d = _unit(rng, n); ax = rng.uniform(size=n) < 0.25; d[ax] = AXES[rng.integers(0, 6, int(ax.sum()))]; return d
+
+
+def _with_edges(rng, x, edges):
+    """one in sixteen of x replaced by each entry of `edges`"""
+    r = rng.integers(0, 16, len(x)); x = x.copy()
+    for j, e in enumerate(edges[:15]): x[r == j] = e
+    return x
+
+
+def medium_inputs(name, record, med):
+    """per mode the inputs [n, 10] of mi_debug_medium / orc_medium_units for one medium record"""
+    rng = np.random.default_rng([zlib.crc32(name.encode()), record, 1414]); n = N_MEDIUM; w = f32(med["medium_sampling_weight"]); out = {}
+    # transmittance over [mint, maxt]: lengths 1e-6 .. 300 (the longest leave nothing of any channel), mint = maxt, maxt = infinity
+    t = np.zeros((n, 10)); t[:, 6] = rng.uniform(0.0, 2.0, n); t[:, 7] = t[:, 6] + 10.0 ** rng.uniform(-6.0, 2.5, n)
+    r = rng.integers(0, 16, n); t[r == 0, 7] = t[r == 0, 6]; t[r == 1, 7] = np.inf
+    out["transmittance"] = t.astype(f32)
+    # distance sampling
+    a = np.zeros((n, 10)); a[:, 0:3] = rng.uniform(-2.0, 2.0, (n, 3)); a[:, 3:6] = _directions_with_axes(rng, n)
+    a[:, 6] = np.where(rng.uniform(size=n) < 0.5, 0.0, rng.uniform(0.0, 1.0, n)); a[:, 7] = a[:, 6] + 10.0 ** rng.uniform(-3.0, 2.0, n)
+    r = rng.integers(0, 16, n); a[r == 0, 7] = a[r == 0, 6]; a[r == 1, 7] = np.inf
+    # a quarter: segments that leave less than 1e-20 of every channel (50 .. 500 mean free paths of the thinnest one; with a channel of sigma_t = 0 nothing does)
+    st = np.asarray(med["sigma_a"], np.float64) + np.asarray(med["sigma_s"], np.float64); thin = st.min() if st.min() > 0 else 1.0
+    far = (r >= 2) & (r <= 5); a[far, 7] = a[far, 6] + rng.uniform(50.0, 500.0, int(far.sum())) / thin
+    # the first value: uniform, half of them scaled into [0, weight) so that a small weight still chooses the medium; 0, the weight itself and one ulp below it,
+    # 1 - 2^-24, 2^-32, and -- with an origin of magnitude 1e4 and mint = 0 -- weight * 2^-32 and weight * 2^-20: distances so short that o + t d == o
+    u = rng.uniform(size=n); u = np.where(rng.uniform(size=n) < 0.5, u * float(w), u)
+    u = _with_edges(rng, np.minimum(u.astype(f32), f32(ONE_MINUS)), [0.0, w, np.nextafter(w, f32(0)), ONE_MINUS, TWO_M32, f32(w * f32(TWO_M32)), f32(w * f32(2.0 ** -20))])
+    short = (u == f32(w * f32(TWO_M32))) | (u == f32(w * f32(2.0 ** -20))); a[short, 0:3] = _unit(rng, int(short.sum())) * 1e4; a[short, 6] = 0.0; a[short, 7] = 1e3
+    third, two = f32(1.0 / 3.0), f32(2.0 / 3.0)
+    v = _with_edges(rng, np.minimum(rng.uniform(size=n).astype(f32), f32(ONE_MINUS)), [0.0, ONE_MINUS, np.nextafter(third, f32(0)), third, np.nextafter(third, f32(1)), np.nextafter(two, f32(0)), two, np.nextafter(two, f32(1))])
+    a[:, 8] = np.minimum(u, f32(ONE_MINUS)); a[:, 9] = v
+    out["distance"] = a.astype(f32)
+    # phase function: wi uniform, a quarter along the axes; the 2-D sample with its edge values
+    p = np.zeros((n, 10)); p[:, 0:3] = _directions_with_axes(rng, n)
+    for col in (3, 4): p[:, col] = _with_edges(rng, np.minimum(rng.uniform(size=n).astype(f32), f32(ONE_MINUS)), [0.0, ONE_MINUS, TWO_M32, 0.5])
+    out["phase_sample"] = p.astype(f32)
+    e = np.zeros((n, 10)); e[:, 0:3] = _directions_with_axes(rng, n); e[:, 3:6] = _directions_with_axes(rng, n)
+    r = rng.integers(0, 16, n); e[r == 0, 3:6] = e[r == 0, 0:3]; e[r == 1, 3:6] = -e[r == 1, 0:3]      # the two peaks of the lobe
+    out["phase_eval"] = e.astype(f32)
+    return out
+
+
+def medium_scenes(golden_scenes, S):
+    if "media" not in _LIGHT_REF: _LIGHT_REF["media"] = {**{k: golden_scenes[k] for k in MEDIUM_SCENES}, "medium_units": medium_scene(S)}
+    return _LIGHT_REF["media"]
+
+
+def medium_reference(oracle, golden_scenes, S, name):
+    """per medium record of scene `name`: {mode: dict(inp, out [n, 12], branches)}; every fourth phase_eval case takes the oracle's own sample of the phase_sample
+    case of the same row"""
+    key = "media:" + name
+    if key not in _LIGHT_REF:
+        sc = medium_scenes(golden_scenes, S)[name]; orc = oracle.Oracle(sc); per = {}
+        for m, med in enumerate(sc.media):
+            inp = medium_inputs(name, m, med); sampled, _ = orc.medium_units(m, "phase_sample", inp["phase_sample"])
+            inp["phase_eval"][::4, 0:3] = inp["phase_sample"][::4, 0:3]; inp["phase_eval"][::4, 3:6] = sampled[::4, 0:3]
+            per[m] = {mode: dict(zip(("out", "branches"), orc.medium_units(m, mode, a)), inp=a) for mode, a in inp.items()}
+        _LIGHT_REF[key] = dict(sc=sc, records=per)
+    return _LIGHT_REF[key]
