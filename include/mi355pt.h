@@ -395,6 +395,62 @@ int mi_denoise_image(uint32_t device, uint32_t width, uint32_t height, const flo
  * request beyond MI355PT_POOL_LIMIT or the free device memory is MI_ERR_DEVICE naming it.  A render that never calls this launches, allocates and records nothing extra. */
 int mi_render_denoise(mi_render *r, const mi_denoise_params *p, float *host_out /* H x W x 3 */, float *resolved_sigma_position);
 int mi_render_denoise_device(mi_render *r, const mi_denoise_params *p, void *device_out, float *resolved_sigma_position);
+
+/* -- denoiser, temporal stage: the accumulated colour of the previous frame is reprojected into the current one and blended with it in front of the filter levels
+ *    (csrc/temporal.h, csrc/kernels_temporal.hip).  float32, one rounding per operation, in the order written: the result equals a sequential model bit for bit
+ *    (tests/temporal_model.py).
+ *    A history (mi_history) belongs to one device and one image size w x h.  It holds, per pixel, the accumulated colour a (3 floats, still demodulated), a count n
+ *    (float; 0 = no history here), a normal Nh and a position Ph; the projection Mh of the frame that wrote it (12 floats); whether that frame was demodulated; and
+ *    the number of frames accumulated since creation or reset.
+ *    A projection M is rows X, Y, W of the world -> pixel map of the film: for a world point q, X = ((M[0] q.x + M[1] q.y) + M[2] q.z) + M[3], Y likewise from
+ *    M[4..7], Wc likewise from M[8..11]; the centre of pixel (i, j) of the rendered window is at (X / Wc, Y / Wc) = (i + 0.5, j + 0.5).
+ *    Inputs of one frame: C, N, P and optionally A as mi_denoise_image takes them; optionally Pprev (H x W x 3), the world position each pixel's surface point had in
+ *    the previous frame (NULL: Pprev = P, static geometry); the frame's M; mi_denoise_params; mi_temporal_params.
+ *      1. demodulation: rule 3 of mi_denoise_image, unchanged, gives c0 and D.
+ *      2. tp, the temporal position tolerance: sigma_position > 0 gives that value; sigma_position < 0 gives |sigma_position| x the diagonal of the box of the finite
+ *         pixels of the current P, exactly as rule 2 of mi_denoise_image resolves it; no finite pixel or a diagonal of 0: tp = 0.
+ *      3. pixel p is "alone" when any component of c0(p), N(p), P(p) or Pprev(p) is non-finite, or when the history holds no frame: a(p) = c0(p), n(p) = 0 if
+ *         non-finite, 1 otherwise.  Every other pixel:
+ *         1. q = Pprev(p); X, Y, Wc from the history's Mh; !(Wc > 0): no history.
+ *         2. fx = X / Wc - 0.5f, fy = Y / Wc - 0.5f; !(fx > -1 && fx < w && fy > -1 && fy < h): no history.
+ *         3. x0 = floorf(fx), y0 = floorf(fy), tx = fx - x0, ty = fy - y0.
+ *         4. taps (x0 + i, y0 + j), j outer, i inner over 0..1, weight b = (i ? tx : 1 - tx) (j ? ty : 1 - ty).  A tap counts when it lies inside the image, b > 0,
+ *            the history count there is > 0, d2(q - Ph(tap)) <= tp tp, and (N(p).x Nh.x + N(p).y Nh.y) + N(p).z Nh.z >= min_normal_dot (a NaN fails each
+ *            comparison).  Counted taps add sw += b, sn += b n(tap), s.k += b a(tap).k.
+ *         5. sw > 0: hist = s / sw, nh = sn / sw, n' = min(nh + 1, max_history), alpha = 1 / n', a(p).k = hist.k + (c0(p).k - hist.k) alpha, n(p) = n'.
+ *            Otherwise no history: a(p) = c0(p), n(p) = 1.
+ *      4. the new history is (a, n, N, P) of every pixel with Mh := M; the stage reads the old history while it writes the new one (two buffer sets that ping-pong).
+ *      5. filter: rule 4 of mi_denoise_image with c_0 := a, and rule 5 gives the output; iterations = 0 gives a x D (a without demodulation).
+ *    The first frame of a history equals mi_denoise_image bit for bit (iterations >= 1); a moved surface whose displacement exceeds tp drops its history.
+ *    Refused with MI_ERR_INVALID naming the cause: the checks of mi_denoise_image; max_history < 1 or non-finite; a zero or non-finite temporal sigma_position;
+ *    min_normal_dot outside [-1, 1]; an image size or device other than the history's; a demodulate value that differs from the history's last frame (reset first);
+ *    NULL M. */
+typedef struct mi_history mi_history;
+typedef struct { float max_history, sigma_position, min_normal_dot; uint32_t pad; } mi_temporal_params;
+/* Two sets of history records (40 B per pixel each: float4 (a.r, a.g, a.b, n), float4 (N, P.x), float2 (P.y, P.z)) in one device allocation; a request beyond
+ * MI355PT_POOL_LIMIT or the free device memory is MI_ERR_DEVICE naming it.  reset gives back the state after create (no frame; nothing is written to the device). */
+int mi_history_create(uint32_t device, uint32_t width, uint32_t height, mi_history **out);
+void mi_history_destroy(mi_history *h);
+int mi_history_reset(mi_history *h);
+int mi_history_frames(mi_history *h, uint32_t *frames);
+/* the current records: color = H x W x 3, the accumulated colour, still demodulated; count = H x W.  Either may be NULL.  Without a frame: MI_ERR_INVALID */
+int mi_history_read(mi_history *h, float *color, float *count);
+/* one temporal frame on host arrays (albedo NULL when demodulate is 0, prev_position NULL for static geometry); the two resolved widths may be NULL */
+int mi_denoise_image_temporal(mi_history *h, const float *color, const float *normal, const float *position, const float *albedo, const float *prev_position,
+                              const float *world_to_pixel12, const mi_denoise_params *p, const mi_temporal_params *t, float *out,
+                              float *resolved_sigma_position, float *resolved_temporal_position);
+/* One temporal frame on a render's own films: radiance and guides as mi_render_denoise takes them, with the same field rules and refusals; Pprev = P; M = the scene's
+ * current projection (mi_scene_world_to_pixel).  The history must be on the render's device and of its film size.  The films are read, never written. */
+int mi_render_denoise_temporal(mi_render *r, mi_history *h, const mi_denoise_params *p, const mi_temporal_params *t, float *host_out /* H x W x 3 */,
+                               float *resolved_sigma_position, float *resolved_temporal_position);
+int mi_render_denoise_temporal_device(mi_render *r, mi_history *h, const mi_denoise_params *p, const mi_temporal_params *t, void *device_out,
+                                      float *resolved_sigma_position, float *resolved_temporal_position);
+/* The projection of a committed scene: rows 0, 1 and 3 of diag(width, height, 1, 1) x inverse(sample_to_camera) x inverse(to_world), computed in double from the camera
+ * as it stands after the last mi_scene_update_camera and rounded to float once.  The sample space spans the rendered crop window; a thin lens projects through the
+ * lens centre.  A singular camera matrix: MI_ERR_INVALID. */
+int mi_scene_world_to_pixel(mi_scene *s, float *out12);
+/* A process that never calls the functions of this section allocates and launches nothing extra. */
+
 /* Debug / parity: what a shading stage recomputes for the sensor rays of individual (px, py, sampleIndex) triples from the path state in the queues, batched as
  * mi_render_samples (generate only): out8 = the path's aperture sample ((0.5, 0.5) without a lens), then the rx / ry directions scaled by 1 / sqrt(spp).  A parity hook, not a
  * product call.  Its kernel looks Sobol values up in the render's GLOBAL nibble tables from st0.y / st0.z, as k_env_primary does; the shade kernels call the same functions on

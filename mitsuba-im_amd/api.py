@@ -80,6 +80,10 @@ class MiDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("demodulate", C.c_uint32), ("pad", C.c_uint32 * 3)]
 
 
+class MiTemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_float), ("sigma_position", C.c_float), ("min_normal_dot", C.c_float), ("pad", C.c_uint32)]
+
+
 # field kinds in the order of the reference's EField (src/integrators/misc/field.cpp:57-67) = MI_FIELD_* of include/mi355pt.h
 FIELD_NAMES = ("position", "relPosition", "distance", "geoNormal", "shNormal", "uv", "albedo", "shapeIndex", "primIndex")
 SCALAR_FIELDS = ("distance", "shapeIndex", "primIndex")      # the three values of these are equal
@@ -119,7 +123,7 @@ EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_s
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_lens", "mi_scene_set_film",
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_adaptive", "mi_render_run_adaptive", "mi_render_read_sample_counts", "mi_render_adaptive_stats",
-           "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_denoise_image", "mi_render_denoise", "mi_render_denoise_device", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
+           "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_denoise_image", "mi_render_denoise", "mi_render_denoise_device", "mi_history_create", "mi_history_destroy", "mi_history_reset", "mi_history_frames", "mi_history_read", "mi_denoise_image_temporal", "mi_render_denoise_temporal", "mi_render_denoise_temporal_device", "mi_scene_world_to_pixel", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
            "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_emitter_sample", "mi_debug_emitter_eval", "mi_debug_medium", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_create_direct", "mi_host_create_ao", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
                 "mi_host_set_camera", "mi_host_set_lens", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
@@ -192,6 +196,15 @@ class Lib:
         L.mi_denoise_image.argtypes = [u32, u32, u32, vp, vp, vp, vp, C.POINTER(MiDenoiseParams), vp, C.POINTER(f32)]
         L.mi_render_denoise.argtypes = [vp, C.POINTER(MiDenoiseParams), vp, C.POINTER(f32)]
         L.mi_render_denoise_device.argtypes = [vp, C.POINTER(MiDenoiseParams), vp, C.POINTER(f32)]
+        L.mi_history_create.argtypes = [u32, u32, u32, C.POINTER(vp)]
+        L.mi_history_destroy.argtypes = [vp]; L.mi_history_destroy.restype = None
+        L.mi_history_reset.argtypes = [vp]
+        L.mi_history_frames.argtypes = [vp, C.POINTER(u32)]
+        L.mi_history_read.argtypes = [vp, vp, vp]
+        L.mi_denoise_image_temporal.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(MiDenoiseParams), C.POINTER(MiTemporalParams), vp, C.POINTER(f32), C.POINTER(f32)]
+        L.mi_render_denoise_temporal.argtypes = [vp, vp, C.POINTER(MiDenoiseParams), C.POINTER(MiTemporalParams), vp, C.POINTER(f32), C.POINTER(f32)]
+        L.mi_render_denoise_temporal_device.argtypes = [vp, vp, C.POINTER(MiDenoiseParams), C.POINTER(MiTemporalParams), vp, C.POINTER(f32), C.POINTER(f32)]
+        L.mi_scene_world_to_pixel.argtypes = [vp, vp]
         L.mi_render_set_profiling.argtypes = [vp, i32]
         L.mi_render_debug_sensor_differentials.argtypes = [vp, vp, u64, vp]
         L.mi_debug_intersect.argtypes = [vp, vp, u64, i32, vp]
@@ -287,6 +300,63 @@ def denoise_image(color, normal, position, albedo=None, iterations=5, sigma_colo
     out = np.zeros_like(c); res = C.c_float(0.0)
     L.check(L.L.mi_denoise_image(int(device), c.shape[1], c.shape[0], _p(c), _p(n), _p(p), _p(a), C.byref(prm), _p(out), C.byref(res)))
     return out, float(res.value)
+
+
+# starting values of the temporal stage (nobody has tuned them)
+TEMPORAL_DEFAULTS = dict(max_history=32.0, temporal_sigma_position=-0.01, min_normal_dot=0.9)
+
+
+class History:
+    """mi_history handle: the accumulated colour, count and guides of the previous frame for one device and one image size (two record sets of 40 B per pixel on
+    the device).  One history serves all frames of a sequence; reset() gives back the state after creation."""
+
+    def __init__(self, width, height, device=0):
+        L = lib(); self.L = L; self.width = int(width); self.height = int(height); self.device = int(device); self.h = None
+        h = C.c_void_p(); L.check(L.L.mi_history_create(self.device, self.width, self.height, C.byref(h))); self.h = h
+
+    def reset(self):
+        self.L.check(self.L.L.mi_history_reset(self.h))
+
+    @property
+    def frames(self):
+        """frames accumulated since creation or reset"""
+        n = C.c_uint32(); self.L.check(self.L.L.mi_history_frames(self.h, C.byref(n))); return n.value
+
+    def read(self):
+        """-> (accumulated colour H x W x 3, still demodulated; count H x W).  Without a frame: MiError code 1."""
+        col = np.zeros((self.height, self.width, 3), np.float32); cnt = np.zeros((self.height, self.width), np.float32)
+        self.L.check(self.L.L.mi_history_read(self.h, _p(col), _p(cnt))); return col, cnt
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.L.mi_history_destroy(self.h); self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def denoise_image_temporal(history, color, normal, position, albedo=None, prev_position=None, world_to_pixel=None, iterations=5, sigma_color=4.0, sigma_normal=0.3,
+                           sigma_position=-0.05, max_history=32.0, temporal_sigma_position=-0.01, min_normal_dot=0.9):
+    """One temporal frame (mi_denoise_image_temporal, include/mi355pt.h) on H x W x 3 float32 arrays: the history's accumulated colour is reprojected through the
+    projection of the frame that wrote it, blended with this frame's (demodulated) colour, and the a-trous levels run on the result.  prev_position: the world
+    position each pixel's surface point had in the previous frame (None: static geometry); world_to_pixel: this frame's 3 x 4 projection (Scene.world_to_pixel()).
+    -> (out, resolved spatial position width, resolved temporal tolerance)."""
+    L = history.L; c = np.ascontiguousarray(color, np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("denoise_image_temporal: colour must be H x W x 3")
+    if c.shape[:2] != (history.height, history.width):
+        raise MiError(1, f"denoise_image_temporal: the history has the image size {history.width} x {history.height}, the frame {c.shape[1]} x {c.shape[0]}")
+    n = np.ascontiguousarray(normal, np.float32); p = np.ascontiguousarray(position, np.float32)
+    a = None if albedo is None else np.ascontiguousarray(albedo, np.float32); q = None if prev_position is None else np.ascontiguousarray(prev_position, np.float32)
+    for name, g in (("normal", n), ("position", p), ("albedo", a), ("prev_position", q)):
+        if g is not None and g.shape != c.shape:
+            raise ValueError(f"denoise_image_temporal: {name} has shape {g.shape}, the colour {c.shape}")
+    m = None if world_to_pixel is None else np.ascontiguousarray(world_to_pixel, np.float32).reshape(12)
+    prm = MiDenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position), 0 if a is None else 1)
+    tpr = MiTemporalParams(float(max_history), float(temporal_sigma_position), float(min_normal_dot), 0)
+    out = np.zeros_like(c); res = C.c_float(0.0); tres = C.c_float(0.0)
+    L.check(L.L.mi_denoise_image_temporal(history.h, _p(c), _p(n), _p(p), _p(a), _p(q), _p(m), C.byref(prm), C.byref(tpr), _p(out), C.byref(res), C.byref(tres)))
+    return out, float(res.value), float(tres.value)
 
 
 def pack_materials(bsdfs):
@@ -456,6 +526,11 @@ class Scene:
         out = np.zeros((n.value // rec, rec // 4), np.uint32)
         self.L.check(self.L.L.mi_debug_read_geometry(self.h, code, _p(out), n.value)); return out
 
+    def world_to_pixel(self):
+        """The 3 x 4 projection of the camera as it stands (mi_scene_world_to_pixel): rows X, Y, W of world -> pixel; pixel (i, j)'s centre is at (X / W, Y / W) =
+        (i + 0.5, j + 0.5).  A thin lens projects through the lens centre."""
+        out = np.zeros((3, 4), np.float32); self.L.check(self.L.L.mi_scene_world_to_pixel(self.h, _p(out))); return out
+
     def revision(self):
         """(revision, tree_builds): in-place edits applied so far / host-side tree builds (1 for the life of a committed scene)."""
         rev, builds = C.c_uint64(), C.c_uint64()
@@ -581,7 +656,7 @@ class Render:
                            1 if shading_samples is None else int(shading_samples), -1.0 if ray_length is None else float(ray_length))
         self.params = p
         h = C.c_void_p(); L.check(L.L.mi_render_create(scene.h, C.byref(p), C.byref(h))); self.h = h
-        self.field_names = []; self.last_denoise_sigma_position = None
+        self.field_names = []; self.last_denoise_sigma_position = None; self.last_temporal_sigma_position = None
         if fields is None: fields = sc.get("fields")          # the scene description's own list (scene files with a `multichannel` integrator); [] = none
         if fields: self.set_fields(fields)
         ad = sc.get("adaptive")                               # the scene description's own parameters (scene files with an `adaptive` integrator); None = uniform sampling
@@ -643,6 +718,22 @@ class Render:
             sc = self.scene.sc; out = np.zeros((sc.height, sc.width, 3), np.float32)
             self.L.check(self.L.L.mi_render_denoise(self.h, C.byref(prm), _p(out), C.byref(res)))
         self.last_denoise_sigma_position = float(res.value); return out
+
+    def denoise_temporal(self, history, iterations=5, sigma_color=4.0, sigma_normal=0.3, sigma_position=-0.05, demodulate=None, max_history=32.0,
+                         temporal_sigma_position=-0.01, min_normal_dot=0.9, device_ptr=None):
+        """One temporal frame on this render's own films (mi_render_denoise_temporal): radiance and guides as denoise() takes them, the previous position of every
+        pixel = its position (static geometry: a surface that moved further than the tolerance drops its history), the projection = the scene's camera as it stands.
+        `history` (api.History) must be on this render's device and of its film size.  -> H x W x 3, or None with device_ptr.  The resolved widths are left in
+        last_denoise_sigma_position and last_temporal_sigma_position."""
+        if demodulate is None: demodulate = "albedo" in self.field_names
+        prm = MiDenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position), int(bool(demodulate)))
+        tpr = MiTemporalParams(float(max_history), float(temporal_sigma_position), float(min_normal_dot), 0); res = C.c_float(0.0); tres = C.c_float(0.0)
+        if device_ptr is not None:
+            self.L.check(self.L.L.mi_render_denoise_temporal_device(self.h, history.h, C.byref(prm), C.byref(tpr), C.c_void_p(device_ptr), C.byref(res), C.byref(tres))); out = None
+        else:
+            sc = self.scene.sc; out = np.zeros((sc.height, sc.width, 3), np.float32)
+            self.L.check(self.L.L.mi_render_denoise_temporal(self.h, history.h, C.byref(prm), C.byref(tpr), _p(out), C.byref(res), C.byref(tres)))
+        self.last_denoise_sigma_position = float(res.value); self.last_temporal_sigma_position = float(tres.value); return out
 
     def field_samples(self, pairs):
         """The fields of individual (px, py, sampleIndex) triples -> [n, F, 3]."""

@@ -19,6 +19,7 @@
 #include "ao_const.h"
 #include "adaptive.h"
 #include "denoise.h"
+#include "temporal.h"
 
 extern "C" {
 void mi_launch_generate(const DScene &, const RenderConst &, const Queues &, const BatchDesc &, uint32_t, hipStream_t);
@@ -80,6 +81,8 @@ void mi_launch_dn_prepare_render(const DenoiseBufs &, const DenoiseFilmSrc &, in
 void mi_launch_dn_prepare_image(const DenoiseBufs &, const float *, const float *, const float *, const float *, int, int, int, hipStream_t);
 void mi_launch_dn_bounds(const DenoiseBufs &, size_t, float, hipStream_t);
 void mi_launch_dn_level(const DenoiseBufs &, int, const DenoiseLevel &, bool, float *, hipStream_t);
+void mi_launch_tp_accumulate(const DenoiseBufs &, const TemporalSet &, const TemporalSet &, const TemporalFrame &, hipStream_t);
+void mi_launch_tp_output(const DenoiseBufs &, float *, size_t, int, hipStream_t);
 }
 
 // Shading stage dispatch.  Dynamic LDS: Sobol nibble tables + (small scenes) the scene tables + (scenes with non-diffuse BSDFs) the per-wave path-order list.
@@ -1690,6 +1693,19 @@ static int dnFilter(const DenoiseBufs &b, uint32_t width, uint32_t height, const
     if (resolved) *resolved = sigma;
     return MI_OK;
 }
+// where the render form finds radiance and guides: the film planes and the first shNormal / position / albedo entry of the field list; a missing one is refused by name
+static int dnRenderSource(const std::string &fn, const mi_render *r, const mi_denoise_params *p, DenoiseFilmSrc *f) {
+    const mi::SceneHost &h = r->scene->h;
+    int fN = -1, fP = -1, fA = -1;      // the first entry of each kind
+    for (int i = (int) r->nFields - 1; i >= 0; --i) { if (r->fields[i].field == MI_FIELD_SH_NORMAL) fN = i; if (r->fields[i].field == MI_FIELD_POSITION) fP = i; if (r->fields[i].field == MI_FIELD_ALBEDO) fA = i; }
+    const char *why = r->adaptFilm ? "; a film that holds an adaptive run has no field film" : "";
+    if (fN < 0) return fail(MI_ERR_INVALID, fn + ": the render has no shNormal field (mi_render_set_fields" + why + ")");
+    if (fP < 0) return fail(MI_ERR_INVALID, fn + ": the render has no position field (mi_render_set_fields" + why + ")");
+    if (p->demodulate && fA < 0) return fail(MI_ERR_INVALID, fn + ": demodulate without albedo: the render has no albedo field (mi_render_set_fields)");
+    f->film = r->film; f->spill = r->spill; f->ffilm = r->fieldFilm; f->fspill = r->fieldSpill; f->W = (int) h.width + 2 * h.border; f->H = (int) h.height + 2 * h.border; f->border = h.border;
+    f->nv = 3 * (int) r->nFields; f->fN = fN; f->fP = fP; f->fA = fA;
+    return MI_OK;
+}
 extern "C" {
 int mi_denoise_image(uint32_t device, uint32_t width, uint32_t height, const float *color, const float *normal, const float *position, const float *albedo,
                      const mi_denoise_params *p, float *out, float *resolved_sigma_position) {
@@ -1720,12 +1736,7 @@ int mi_render_denoise_device(mi_render *r, const mi_denoise_params *p, void *dev
     { int rc = dnCheckParams(fn, p); if (rc) return rc; }
     const mi::SceneHost &h = r->scene->h;
     { int rc = dnCheckSize(fn, h.width, h.height); if (rc) return rc; }
-    int fN = -1, fP = -1, fA = -1;      // the first entry of each kind
-    for (int i = (int) r->nFields - 1; i >= 0; --i) { if (r->fields[i].field == MI_FIELD_SH_NORMAL) fN = i; if (r->fields[i].field == MI_FIELD_POSITION) fP = i; if (r->fields[i].field == MI_FIELD_ALBEDO) fA = i; }
-    const char *why = r->adaptFilm ? "; a film that holds an adaptive run has no field film" : "";
-    if (fN < 0) return fail(MI_ERR_INVALID, fn + ": the render has no shNormal field (mi_render_set_fields" + why + ")");
-    if (fP < 0) return fail(MI_ERR_INVALID, fn + ": the render has no position field (mi_render_set_fields" + why + ")");
-    if (p->demodulate && fA < 0) return fail(MI_ERR_INVALID, fn + ": demodulate without albedo: the render has no albedo field (mi_render_set_fields)");
+    DenoiseFilmSrc f{}; { int rc = dnRenderSource(fn, r, p, &f); if (rc) return rc; }
     HIPCHK(hipSetDevice(h.device));
     const int W = (int) h.width + 2 * h.border, H = (int) h.height + 2 * h.border;
     if (p->iterations == 0) {      // the radiance as layout 2 develops it
@@ -1736,8 +1747,6 @@ int mi_render_denoise_device(mi_render *r, const mi_denoise_params *p, void *dev
     }
     const size_t n = (size_t) h.width * h.height;
     if (!r->dnMem) { int rc = dnAlloc(fn, n, &r->dnMem, &r->dn); if (rc) return rc; }
-    DenoiseFilmSrc f{}; f.film = r->film; f.spill = r->spill; f.ffilm = r->fieldFilm; f.fspill = r->fieldSpill; f.W = W; f.H = H; f.border = h.border;
-    f.nv = 3 * (int) r->nFields; f.fN = fN; f.fP = fP; f.fA = fA;
     const int demod = p->demodulate ? 1 : 0;
     mi_launch_dn_prepare_render(r->dn, f, (int) h.width, (int) h.height, demod, r->stream);
     return dnFilter(r->dn, h.width, h.height, p, demod, (float *) device_out, resolved_sigma_position, r->stream);
@@ -1747,6 +1756,182 @@ int mi_render_denoise(mi_render *r, const mi_denoise_params *p, float *host_out,
     int rc = mi_render_denoise_device(r, p, r->layoutTmp, resolved_sigma_position); if (rc) return rc;      // layoutTmp holds 5 floats per film pixel, border included
     HIPCHK(hipMemcpy(host_out, r->layoutTmp, (size_t) r->scene->h.width * r->scene->h.height * 12, hipMemcpyDeviceToHost));
     return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ denoiser, temporal stage (temporal.h, kernels_temporal.hip)
+}  // extern "C"
+struct mi_history {
+    int device = 0; uint32_t width = 0, height = 0;
+    void *mem = nullptr; TemporalSet set[2]{}; float *tail = nullptr;      // one allocation: two record sets + MI_TP_TAIL_FLOATS
+    int cur = 0;                  // the set the last frame wrote
+    uint32_t frames = 0; int demod = 0; float M[12] = {0};
+};
+static int tpCheckParams(const std::string &fn, const mi_temporal_params *t) {
+    if (!(t->max_history >= 1) || !std::isfinite(t->max_history)) return fail(MI_ERR_INVALID, fn + ": max_history must be >= 1 and finite");
+    if (t->sigma_position == 0 || !std::isfinite(t->sigma_position)) return fail(MI_ERR_INVALID, fn + ": the temporal sigma_position must be non-zero and finite (negative: a fraction of the position box's diagonal)");
+    if (!(t->min_normal_dot >= -1.0f && t->min_normal_dot <= 1.0f)) return fail(MI_ERR_INVALID, fn + ": min_normal_dot must lie in [-1, 1]");
+    return MI_OK;
+}
+static int tpCheckHistory(const std::string &fn, const mi_history *h, int device, uint32_t width, uint32_t height, int demod) {
+    if (h->device != device) return fail(MI_ERR_INVALID, fn + ": the history is on device " + std::to_string(h->device) + ", the frame on device " + std::to_string(device));
+    if (h->width != width || h->height != height)
+        return fail(MI_ERR_INVALID, fn + ": the history has the image size " + std::to_string(h->width) + " x " + std::to_string(h->height) + ", the frame " + std::to_string(width) + " x " + std::to_string(height));
+    if (h->frames && h->demod != demod) return fail(MI_ERR_INVALID, fn + ": demodulate differs from the history's last frame (the accumulated colour would mix the two): call mi_history_reset first");
+    return MI_OK;
+}
+// Over prepared records: the temporal tolerance (on the device), the accumulation, then the spatial bounds and the levels (or, with 0 iterations, the output).
+// Synchronises `st`; the history advances only when all of it succeeded.
+static int tpRun(mi_history *h, const DenoiseBufs &b, const float *M, const float *devPprev, const mi_denoise_params *p, const mi_temporal_params *t, int demod, float *devOut,
+                 float *resolved, float *resolvedTemporal, hipStream_t st) {
+    const size_t n = (size_t) h->width * h->height;
+    const bool automatic = t->sigma_position < 0;
+    if (automatic) mi_launch_dn_bounds(b, n, std::fabs(t->sigma_position), st);
+    TemporalFrame F{}; F.w = (int) h->width; F.h = (int) h->height; F.hasHistory = h->frames ? 1 : 0; memcpy(F.Mh, h->M, 48);
+    F.maxHistory = t->max_history; F.minNormalDot = t->min_normal_dot; F.tp = automatic ? 0.0f : t->sigma_position; F.res = automatic ? b.res : nullptr;
+    F.pprev = devPprev; F.tpOut = h->tail;
+    mi_launch_tp_accumulate(b, h->set[h->cur], h->set[h->cur ^ 1], F, st);
+    if (p->iterations == 0) {
+        mi_launch_tp_output(b, devOut, n, demod, st);
+        HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipGetLastError());
+        if (resolved) *resolved = p->sigma_position > 0 ? p->sigma_position : 0.0f;
+    } else { int rc = dnFilter(b, h->width, h->height, p, demod, devOut, resolved, st); if (rc) return rc; }
+    if (resolvedTemporal) HIPCHK(hipMemcpy(resolvedTemporal, h->tail, 4, hipMemcpyDeviceToHost));
+    h->cur ^= 1; ++h->frames; h->demod = demod; memcpy(h->M, M, 48);
+    return MI_OK;
+}
+// inverse of a row-major 4 x 4 matrix in double (Gauss-Jordan, partial pivoting); false: singular
+static bool invert4(const double *m, double *inv) {
+    double a[4][8];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { a[r][c] = m[r * 4 + c]; a[r][4 + c] = r == c ? 1.0 : 0.0; }
+    for (int c = 0; c < 4; ++c) {
+        int piv = c; for (int r = c + 1; r < 4; ++r) if (std::fabs(a[r][c]) > std::fabs(a[piv][c])) piv = r;
+        if (!(std::fabs(a[piv][c]) > 0) || !std::isfinite(a[piv][c])) return false;
+        if (piv != c) for (int k = 0; k < 8; ++k) std::swap(a[piv][k], a[c][k]);
+        const double d = a[c][c]; for (int k = 0; k < 8; ++k) a[c][k] /= d;
+        for (int r = 0; r < 4; ++r) if (r != c) { const double f = a[r][c]; if (f != 0) for (int k = 0; k < 8; ++k) a[r][k] -= f * a[c][k]; }
+    }
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) inv[r * 4 + c] = a[r][4 + c];
+    return true;
+}
+static int sceneWorldToPixel(const std::string &fn, const mi::SceneHost &h, float *out12) {
+    double s2c[16], c2w[16], is2c[16], ic2w[16];
+    for (int i = 0; i < 16; ++i) { s2c[i] = h.s2c[i]; c2w[i] = h.c2w[i]; }
+    if (!invert4(s2c, is2c) || !invert4(c2w, ic2w)) return fail(MI_ERR_INVALID, fn + ": the camera's sample_to_camera or to_world matrix is singular");
+    const int rows[3] = {0, 1, 3}; const double scale[3] = {(double) h.width, (double) h.height, 1.0};
+    for (int i = 0; i < 3; ++i) for (int c = 0; c < 4; ++c) {
+        double v = 0; for (int k = 0; k < 4; ++k) v += is2c[rows[i] * 4 + k] * ic2w[k * 4 + c];
+        out12[i * 4 + c] = (float) (scale[i] * v);
+    }
+    return MI_OK;
+}
+extern "C" {
+int mi_history_create(uint32_t device, uint32_t width, uint32_t height, mi_history **out) {
+    const std::string fn = "mi_history_create";
+    if (!out) return fail(MI_ERR_INVALID, fn + ": null argument");
+    { int rc = dnCheckSize(fn, width, height); if (rc) return rc; }
+    const size_t n = (size_t) width * height;
+    const uint64_t bytes = (uint64_t) n * MI_TP_BYTES_PER_PIXEL + MI_TP_TAIL_FLOATS * 4u;
+    const char *lim = getenv("MI355PT_POOL_LIMIT");
+    if (lim && atoll(lim) > 0 && bytes > (uint64_t) atoll(lim)) return fail(MI_ERR_DEVICE, fn + ": the history buffers (" + std::to_string(bytes) + " bytes) are larger than MI355PT_POOL_LIMIT");
+    HIPCHK(hipSetDevice((int) device));
+    size_t freeB = 0, totalB = 0; HIPCHK(hipMemGetInfo(&freeB, &totalB));
+    if (bytes > freeB) return fail(MI_ERR_DEVICE, fn + ": the history buffers (" + std::to_string(bytes) + " bytes) are larger than the free device memory");
+    void *mem = nullptr; hipError_t e = hipMalloc(&mem, bytes);
+    if (e != hipSuccess) { (void) hipGetLastError(); return fail(MI_ERR_DEVICE, fn + ": cannot allocate the history buffers: " + hipGetErrorString(e)); }
+    mi_history *h = new mi_history(); h->device = (int) device; h->width = width; h->height = height; h->mem = mem;
+    char *base = (char *) mem;      // float4 arrays first, then the float2 arrays, then the tail
+    h->set[0].c = (float4 *) base; h->set[1].c = (float4 *) (base + n * 16); h->set[0].gA = (float4 *) (base + n * 32); h->set[1].gA = (float4 *) (base + n * 48);
+    h->set[0].gB = (float2 *) (base + n * 64); h->set[1].gB = (float2 *) (base + n * 72); h->tail = (float *) (base + n * 80);
+    *out = h; return MI_OK;
+}
+void mi_history_destroy(mi_history *h) {
+    if (!h) return;
+    if (h->mem) { (void) hipSetDevice(h->device); (void) hipFree(h->mem); }
+    delete h;
+}
+int mi_history_reset(mi_history *h) {
+    if (!h) return fail(MI_ERR_INVALID, "mi_history_reset: null argument");
+    h->cur = 0; h->frames = 0; h->demod = 0; memset(h->M, 0, 48); return MI_OK;      // frames = 0: no record is read before the next frame has rewritten it
+}
+int mi_history_frames(mi_history *h, uint32_t *frames) {
+    if (!h || !frames) return fail(MI_ERR_INVALID, "mi_history_frames: null argument");
+    *frames = h->frames; return MI_OK;
+}
+int mi_history_read(mi_history *h, float *color, float *count) {
+    if (!h) return fail(MI_ERR_INVALID, "mi_history_read: null argument");
+    if (!h->frames) return fail(MI_ERR_INVALID, "mi_history_read: the history holds no frame");
+    const size_t n = (size_t) h->width * h->height; std::vector<float> rec(n * 4);
+    HIPCHK(hipSetDevice(h->device)); HIPCHK(hipMemcpy(rec.data(), h->set[h->cur].c, n * 16, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        if (color) { color[i * 3] = rec[i * 4]; color[i * 3 + 1] = rec[i * 4 + 1]; color[i * 3 + 2] = rec[i * 4 + 2]; }
+        if (count) count[i] = rec[i * 4 + 3];
+    }
+    return MI_OK;
+}
+int mi_denoise_image_temporal(mi_history *h, const float *color, const float *normal, const float *position, const float *albedo, const float *prev_position,
+                              const float *M, const mi_denoise_params *p, const mi_temporal_params *t, float *out, float *resolved_sigma_position,
+                              float *resolved_temporal_position) {
+    const std::string fn = "mi_denoise_image_temporal";
+    if (!h || !color || !normal || !position || !p || !t || !out) return fail(MI_ERR_INVALID, fn + ": null argument (history, color, normal, position, params, temporal params, out)");
+    if (!M) return fail(MI_ERR_INVALID, fn + ": null world_to_pixel (the frame's projection M)");
+    { int rc = dnCheckParams(fn, p); if (rc) return rc; }
+    { int rc = tpCheckParams(fn, t); if (rc) return rc; }
+    if (p->demodulate && !albedo) return fail(MI_ERR_INVALID, fn + ": demodulate without albedo");
+    const int demod = p->demodulate ? 1 : 0, nIn = 3 + demod + (prev_position ? 1 : 0);
+    { int rc = tpCheckHistory(fn, h, h->device, h->width, h->height, demod); if (rc) return rc; }
+    const uint32_t width = h->width, height = h->height; const size_t n = (size_t) width * height;
+    HIPCHK(hipSetDevice(h->device));
+    struct Mem { void *scratch = nullptr, *io = nullptr; ~Mem() { if (scratch) (void) hipFree(scratch); if (io) (void) hipFree(io); } } mem;
+    DenoiseBufs b{};
+    { int rc = dnAlloc(fn, n, &mem.scratch, &b); if (rc) return rc; }
+    {   // the staging arrays of the host form, held to the same limits as the scratch
+        const uint64_t bytes = (uint64_t) n * 12u * (uint64_t) (nIn + 1);
+        const char *lim = getenv("MI355PT_POOL_LIMIT");
+        if (lim && atoll(lim) > 0 && bytes > (uint64_t) atoll(lim)) return fail(MI_ERR_DEVICE, fn + ": the staging arrays (" + std::to_string(bytes) + " bytes) are larger than MI355PT_POOL_LIMIT");
+        size_t freeB = 0, totalB = 0; HIPCHK(hipMemGetInfo(&freeB, &totalB));
+        if (bytes > freeB) return fail(MI_ERR_DEVICE, fn + ": the staging arrays (" + std::to_string(bytes) + " bytes) are larger than the free device memory");
+        hipError_t e = hipMalloc(&mem.io, bytes);
+        if (e != hipSuccess) { (void) hipGetLastError(); mem.io = nullptr; return fail(MI_ERR_DEVICE, fn + ": cannot allocate the staging arrays: " + hipGetErrorString(e)); }
+    }
+    float *d = (float *) mem.io, *dC = d, *dN = d + n * 3, *dP = d + n * 6, *dA = demod ? d + n * 9 : nullptr, *dQ = prev_position ? d + n * 3 * (size_t) (3 + demod) : nullptr,
+          *dOut = d + n * 3 * (size_t) nIn;
+    HIPCHK(hipMemcpy(dC, color, n * 12, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dN, normal, n * 12, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dP, position, n * 12, hipMemcpyHostToDevice));
+    if (demod) HIPCHK(hipMemcpy(dA, albedo, n * 12, hipMemcpyHostToDevice));
+    if (dQ) HIPCHK(hipMemcpy(dQ, prev_position, n * 12, hipMemcpyHostToDevice));
+    mi_launch_dn_prepare_image(b, dC, dN, dP, dA, (int) width, (int) height, demod, nullptr);
+    { int rc = tpRun(h, b, M, dQ, p, t, demod, dOut, resolved_sigma_position, resolved_temporal_position, nullptr); if (rc) return rc; }
+    HIPCHK(hipMemcpy(out, dOut, n * 12, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+int mi_render_denoise_temporal_device(mi_render *r, mi_history *hist, const mi_denoise_params *p, const mi_temporal_params *t, void *device_out, float *resolved_sigma_position,
+                                      float *resolved_temporal_position) {
+    const std::string fn = "mi_render_denoise_temporal";
+    if (!r || !hist || !p || !t || !device_out) return fail(MI_ERR_INVALID, fn + ": null argument");
+    { int rc = dnCheckParams(fn, p); if (rc) return rc; }
+    { int rc = tpCheckParams(fn, t); if (rc) return rc; }
+    const mi::SceneHost &h = r->scene->h;
+    { int rc = dnCheckSize(fn, h.width, h.height); if (rc) return rc; }
+    DenoiseFilmSrc f{}; { int rc = dnRenderSource(fn, r, p, &f); if (rc) return rc; }
+    const int demod = p->demodulate ? 1 : 0;
+    { int rc = tpCheckHistory(fn, hist, h.device, h.width, h.height, demod); if (rc) return rc; }
+    float M[12]; { int rc = sceneWorldToPixel(fn, h, M); if (rc) return rc; }
+    HIPCHK(hipSetDevice(h.device));
+    const size_t n = (size_t) h.width * h.height;
+    if (!r->dnMem) { int rc = dnAlloc(fn, n, &r->dnMem, &r->dn); if (rc) return rc; }
+    mi_launch_dn_prepare_render(r->dn, f, (int) h.width, (int) h.height, demod, r->stream);
+    return tpRun(hist, r->dn, M, nullptr, p, t, demod, (float *) device_out, resolved_sigma_position, resolved_temporal_position, r->stream);
+}
+int mi_render_denoise_temporal(mi_render *r, mi_history *hist, const mi_denoise_params *p, const mi_temporal_params *t, float *host_out, float *resolved_sigma_position,
+                               float *resolved_temporal_position) {
+    if (!r || !hist || !p || !t || !host_out) return fail(MI_ERR_INVALID, "mi_render_denoise_temporal: null argument");
+    int rc = mi_render_denoise_temporal_device(r, hist, p, t, r->layoutTmp, resolved_sigma_position, resolved_temporal_position); if (rc) return rc;
+    HIPCHK(hipMemcpy(host_out, r->layoutTmp, (size_t) r->scene->h.width * r->scene->h.height * 12, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+int mi_scene_world_to_pixel(mi_scene *s, float *out12) {
+    if (!s || !out12) return fail(MI_ERR_INVALID, "mi_scene_world_to_pixel: null argument");
+    if (!s->h.committed) return fail(MI_ERR_INVALID, "mi_scene_world_to_pixel: scene not committed");
+    return sceneWorldToPixel("mi_scene_world_to_pixel", s->h, out12);
 }
 
 // ------------------------------------------------------------------------------------------------ unit-level device entry points

@@ -1,7 +1,7 @@
 """Command-line front end: render a Mitsuba XML scene on the MI355X path tracer (what `mitsuba scene.xml` does for the `path` integrator).
 
     python -m mitsuba-im_amd.render scene.xml [-o out.exr|out.pfm|out.npy|out.png] [-D name=value ...] [--spp N] [--sampler sobol|independent] [--device K] [--ao N [--ao-length L]]
-                                    [--denoise [ITERATIONS] [--denoise-sigma C N P] [--denoise-raw PATH]]
+                                    [--denoise [ITERATIONS] [--denoise-sigma C N P] [--denoise-raw PATH] [--denoise-temporal [MAX_HISTORY]]]
 
 The image written is the developed film (sum / weight, linear RGB, as HDRFilm::develop would hand to its writer); `.exr` (FLOAT channels, ZIP), `.pfm` and `.npy`
 keep the linear values; `.png` / `.jpg` get ldrfilm's default sRGB encoding (imageio.py).  There is no CPU fallback: without the HIP library / a GPU this exits with an error.
@@ -26,6 +26,14 @@ as before.  On a scene whose BSDFs have no albedo field (plastic, roughplastic, 
 so.  `--denoise-sigma C N P` sets the colour, normal and position widths (P < 0: that fraction of the scene's extent); `--denoise-raw PATH` also writes the
 unfiltered radiance (`PATH_000.ext`, ... for frames).  Works with `--orbit`, `--spin` and `--focus-pull`: one filter call per frame on the same render.  Not with
 adaptive sampling, whose film has no field channels.
+
+`--denoise-temporal [MAX_HISTORY]` (with `--denoise`, on `--orbit`, `--spin` and `--focus-pull` sequences of at least two frames) puts the temporal stage in front of
+the filter levels: one history (api.History) serves all frames, every frame's accumulated colour is reprojected into the next through the camera of the edited scene
+and blended with it (api.Render.denoise_temporal; a pixel keeps at most MAX_HISTORY frames, default 32).  The render form takes every surface as static: the
+instances a `--spin` moves lose their history where they move further than the tolerance.  Not with adaptive sampling.  It implies `--sample-offset-per-frame`: frame
+f renders the sample indices [f spp, (f + 1) spp) after its clear, so that frames carry independent noise.  The render is then created for frames x spp samples per
+pixel, of which every frame takes its own slice (a run stays within the render's sample count; the Sobol' sampler's index layout and the scale of the ray
+differentials follow that count).  Without the flag every frame renders the indices [0, spp) and the files are what they were.
 
 `--orbit N [--orbit-axis x|y|z]` renders a turntable: N frames with the camera rotated in steps of 360 / N degrees about the axis through the centre of the scene's
 box.  The scene is committed once; every frame is an in-place camera edit of the committed scene (Scene.update_camera), a clear and a run -- no tree build, no
@@ -150,7 +158,7 @@ def use_adaptive(sc, max_error=0.05, max_sample_factor=None):
     return sc
 
 
-def use_denoise(sc, render, iterations=5, sigmas=None, raw=None):
+def use_denoise(sc, render, iterations=5, sigmas=None, raw=None, temporal=None, device=0):
     """`--denoise`: puts the guides the filter needs behind the scene's own field list (what the scene file asks for stays in front and is reused) and returns what
     `developed` needs: the filter's arguments, the count of the scene's own fields and the path of the unfiltered image."""
     from .api import normalize_fields, MiError, DENOISE_DEFAULTS
@@ -164,7 +172,11 @@ def use_denoise(sc, render, iterations=5, sigmas=None, raw=None):
         if e.code != 3 or "albedo" in names: raise
         print(f"{sc.name}: {e}; --denoise filters without albedo demodulation", file=sys.stderr)
         render.set_fields(guides)
-    return dict(widths=widths, own=len(own), raw=raw)
+    dn = dict(widths=widths, own=len(own), raw=raw)
+    if temporal is not None:      # `--denoise-temporal`: one history for all frames
+        from .api import History
+        dn["history"] = History(sc.width, sc.height, device=device); dn["max_history"] = float(temporal)
+    return dn
 
 
 def developed(render, dn=None):
@@ -174,7 +186,8 @@ def developed(render, dn=None):
     if dn is None:
         return rgb, fields, names, None
     own = dn["own"]
-    return render.denoise(**dn["widths"]), (fields[..., :3 * own] if own else None), names[:own], rgb
+    out = render.denoise_temporal(dn["history"], max_history=dn["max_history"], **dn["widths"]) if dn.get("history") is not None else render.denoise(**dn["widths"])
+    return out, (fields[..., :3 * own] if own else None), names[:own], rgb
 
 
 def write_outputs(sc, render, out, dev=None, dn=None, frame=None):
@@ -213,6 +226,8 @@ def main(argv=None):
     ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS", help="filter the radiance on the device with the edge-avoiding a-trous filter, guided by the shNormal / position / albedo field channels (levels, default 5)")
     ap.add_argument("--denoise-sigma", type=float, nargs=3, default=None, metavar=("C", "N", "P"), help="with --denoise: colour, normal and position widths (P < 0: that fraction of the scene's extent)")
     ap.add_argument("--denoise-raw", default=None, metavar="PATH", help="with --denoise: also write the unfiltered radiance")
+    ap.add_argument("--denoise-temporal", type=float, nargs="?", const=32.0, default=None, metavar="MAX_HISTORY", help="with --denoise on a frame sequence: reproject and accumulate the previous frames in front of the filter (frames kept per pixel at the most, default 32); implies --sample-offset-per-frame")
+    ap.add_argument("--sample-offset-per-frame", action="store_true", help="frame f of a sequence renders the sample indices [f spp, (f + 1) spp): independent noise per frame")
     ap.add_argument("--orbit", type=int, default=0, metavar="N", help="turntable of N frames about the scene box's centre: one commit, one in-place camera edit per frame")
     ap.add_argument("--orbit-axis", choices=["x", "y", "z"], default="y")
     ap.add_argument("--spin", type=int, default=0, metavar="N", help="N frames with every instance turned about its own origin: one commit, one in-place instance edit per frame")
@@ -266,6 +281,21 @@ def main(argv=None):
         if a.denoise is not None and sc.get("adaptive"):
             print("error: --denoise cannot be combined with adaptive sampling (--adaptive, or a scene file with an adaptive integrator): an adaptive film has no field channels", file=sys.stderr)
             return 1
+        n_frames = a.focus_pull or a.orbit or a.spin
+        if a.denoise_temporal is not None:
+            if a.denoise is None:
+                print("error: --denoise-temporal belongs to --denoise", file=sys.stderr)
+                return 1
+            if n_frames < 2:
+                print("error: --denoise-temporal needs a frame sequence (--orbit, --spin or --focus-pull with at least two frames): a single frame has no history", file=sys.stderr)
+                return 1
+            if not a.denoise_temporal >= 1:
+                print("error: --denoise-temporal expects a history length >= 1", file=sys.stderr)
+                return 1
+        offset_frames = a.sample_offset_per_frame or a.denoise_temporal is not None
+        if offset_frames and sc.get("adaptive"):
+            print("error: --denoise-temporal / --sample-offset-per-frame cannot be combined with adaptive sampling (--adaptive, or a scene file with an adaptive integrator): an adaptive run chooses its own sample indices", file=sys.stderr)
+            return 1
         out = a.output or (a.scene.rsplit(".", 1)[0] + ".exr")          # hdrfilm's default fileFormat (src/films/hdrfilm.cpp: openexr)
         if a.spin and not (sc.get("instances") or []):
             print(f"error: {a.scene}: --spin turns the instances of shape groups, and this scene has none", file=sys.stderr)
@@ -280,14 +310,14 @@ def main(argv=None):
                 return 1
         t1 = time.perf_counter()
         scene = Scene(sc, device=a.device)
-        render = Render(scene, device=a.device)
-        dn = use_denoise(sc, render, a.denoise, a.denoise_sigma, a.denoise_raw) if a.denoise is not None else None
+        render = Render(scene, device=a.device, spp=sc.spp * n_frames if offset_frames and n_frames else None)
+        dn = use_denoise(sc, render, a.denoise, a.denoise_sigma, a.denoise_raw, a.denoise_temporal, a.device) if a.denoise is not None else None
         t2 = time.perf_counter()
         frame_no = [0]
 
-        def go():      # one frame into the clear film: the adaptive run of a scene with adaptive parameters (api.Render picked them up), else every pixel's spp samples
+        def go(f=0):      # frame f into the clear film: the adaptive run of a scene with adaptive parameters (api.Render picked them up), else every pixel's spp samples
             if not sc.get("adaptive"):
-                return render.run()
+                return render.run(s0=f * sc.spp, s1=(f + 1) * sc.spp) if offset_frames else render.run()
             render.run_adaptive()
             if a.sample_counts is not None:
                 frames = a.orbit or a.spin or a.focus_pull
@@ -300,7 +330,7 @@ def main(argv=None):
             for f, (dist, c2w) in enumerate(zip(pull, cams)):
                 tf = time.perf_counter()
                 if c2w is not None: scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far)
-                scene.update_lens(sc.aperture_radius, dist); render.clear(); go()
+                scene.update_lens(sc.aperture_radius, dist); render.clear(); go(f)
                 frame_s.append(time.perf_counter() - tf)
                 if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}", dn=dn, frame=f):
                     return 1
@@ -312,7 +342,7 @@ def main(argv=None):
             stem, ext = out.rsplit(".", 1); frame_s = []
             for f, c2w in enumerate(orbit_cameras(sc, a.orbit, a.orbit_axis)):
                 tf = time.perf_counter()
-                scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far); render.clear(); go()
+                scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far); render.clear(); go(f)
                 frame_s.append(time.perf_counter() - tf)
                 if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}", dn=dn, frame=f):
                     return 1
@@ -324,7 +354,7 @@ def main(argv=None):
             stem, ext = out.rsplit(".", 1); frame_s = []
             for f, insts in enumerate(spin_instances(sc, a.spin, a.spin_axis)):
                 tf = time.perf_counter()
-                scene.update_instances(insts); render.clear(); go()
+                scene.update_instances(insts); render.clear(); go(f)
                 frame_s.append(time.perf_counter() - tf)
                 if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}", dn=dn, frame=f):
                     return 1
