@@ -513,6 +513,20 @@ int mi_debug_libm(int fn, const float *x, const float *y, uint64_t n, float *out
  * Records whose evaluation needs a hit record are refused by name with MI_ERR_UNSUPPORTED: mask (its logic is inline in the shade stage), bumpmap, normalmap, a record with
  * a bound texture, and a coating / mixturebsdf / blendbsdf over one of them. */
 int mi_debug_bsdf(mi_scene *s, uint32_t material, int mode, const float *wi3, const float *wo3, const float *uv2, const float *extra1, uint64_t n, float *out);
+/* The surface step between a hit and the BSDF query, one caller-supplied hit per case: picking its.dpdu / its.dpdv, Intersection::computePartials and the filtered lookup,
+ * the perturbed frame of a bumpmap / normalmap, and the unwrap mask -> bumpmap / normalmap -> coating with the textured parameters loaded into the nested records -- the
+ * routines the shade stages call, in their order, through the widest instantiation (texcoords, analytic shapes, instances, tables in global memory).
+ * rays8 = o, mint, d, maxt; hits4 / instance1 = t, u, v, prim and the instance index exactly as mi_debug_intersect_inst returns them (instance1 may be NULL: none; prim < 0:
+ * a miss, whose outputs are all zero); diff6 = the two differential directions rxd, ryd (common origin o) of a camera ray, NULL = a later bounce: level-0 lookups, no partials.
+ * mode 0 (record), out51 = its.uv as the lookups use it (an analytic shape's own parameterisation) 2, dpdu 3, dpdv 3, dudx dvdx dudy dvdy (zero without differentials),
+ *          opacity 3 (zero without a mask), the value loaded into the first textured parameter on the chain 3 (zero: none), masked (0 / 1), bumped (0 / 1), coating record
+ *          (-1: none), leaf record, the leaf's `reflectance` after its texture was applied 3, perturbed frame s 3, t 3, n 3 (zero when not bumped), wi in the frame the query
+ *          uses 3, then the hit as given: t, u, v, prim, instance, and its shading frame n 3, s 3, t 3.
+ * mode 1 (sample), query3 = the 2-D sample and the extra sampler value: out11 as mi_debug_bsdf's mode 0 on the resolved (coating, leaf) with that wi; wo in query-frame
+ *          coordinates; the values are those before the mask's lobe choice, the opacity multiply and the sign rejection of a perturbed frame.
+ * mode 2 (eval + pdf), query3 = a WORLD direction, taken into the query frame by the same routines: out4 as mi_debug_bsdf's mode 1.
+ * A NULL pointer, n == 0, a mode outside 0..2, modes 1 / 2 without query3, or a hit that names a primitive or instance the scene does not have: MI_ERR_INVALID. */
+int mi_debug_surface(mi_scene *s, int mode, const float *rays8, const float *hits4, const int32_t *instance1, const float *diff6, const float *query3, uint64_t n, float *out);
 /* The texture routines one call at a time: record `texture` of mi_scene_set_textures at uv2.  Bitmaps: scale and offset as the shade stage applies them; partials4 = (dudx,
  * dvdx, dudy, dvdy) per lookup selects the filtered lookup of a camera hit (TMIPMap::eval under the record's filter), NULL the level-0 lookup of every later bounce
  * (bilinear, or the nearest texel under the nearest filter).  Procedural textures ignore the partials.  The EWA loops run over the footprint's bounding box: the caller

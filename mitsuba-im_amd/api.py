@@ -124,7 +124,7 @@ EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_s
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_adaptive", "mi_render_run_adaptive", "mi_render_read_sample_counts", "mi_render_adaptive_stats",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_denoise_image", "mi_render_denoise", "mi_render_denoise_device", "mi_history_create", "mi_history_destroy", "mi_history_reset", "mi_history_frames", "mi_history_read", "mi_denoise_image_temporal", "mi_render_denoise_temporal", "mi_render_denoise_temporal_device", "mi_scene_world_to_pixel", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
-           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_emitter_sample", "mi_debug_emitter_eval", "mi_debug_medium", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
+           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_emitter_sample", "mi_debug_emitter_eval", "mi_debug_medium", "mi_debug_surface", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_create_direct", "mi_host_create_ao", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
                 "mi_host_set_camera", "mi_host_set_lens", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
 
@@ -220,6 +220,7 @@ class Lib:
         L.mi_debug_emitter_sample.argtypes = [vp, vp, vp, vp, u64, i32, vp]
         L.mi_debug_emitter_eval.argtypes = [vp, u32, vp, vp, vp, vp, vp, u64, vp]
         L.mi_debug_medium.argtypes = [vp, u32, i32, vp, u64, vp]
+        L.mi_debug_surface.argtypes = [vp, i32, vp, vp, vp, vp, vp, u64, vp]
         L.mi_debug_geometry_bytes.argtypes = [vp, u32, C.POINTER(u64)]
         L.mi_debug_read_geometry.argtypes = [vp, u32, vp, u64]
         L.mi_debug_pool_shape.argtypes = [u64, i32, u32, C.POINTER(MiPoolOverrides), C.POINTER(MiPoolShape)]
@@ -619,6 +620,20 @@ class Scene:
         2-D sample -> wo, the phase function's value for it.  "phase_eval": wi, wo -> value."""
         a = np.ascontiguousarray(inputs, np.float32).reshape(-1, 10); out = np.zeros((len(a), 12), np.float32)
         self.L.check(self.L.L.mi_debug_medium(self.h, int(medium), self.MEDIUM_MODES[mode], _p(a), len(a), _p(out))); return out
+
+    SURFACE_MODES = {"record": 0, "sample": 1, "eval": 2}
+
+    def surface_units(self, mode, rays8, hits4, instance=None, diff6=None, query3=None):
+        """The device's surface step on chosen hits (mi_debug_surface), one case per row: rays8 [n, 8], hits4 [n, 4] and instance [n] as intersect(with_instance=True)
+        returns them, diff6 [n, 6] = the differential directions of a camera ray (None: a later bounce).  "record" -> [n, 51] (uv, tangents, partials, opacity, first
+        textured value, flags, coating and leaf records, leaf reflectance, perturbed frame, wi of the query, the hit and its frame); "sample" with query3 = the 2-D sample
+        and the extra value -> [n, 11]; "eval" with query3 = a world direction -> [n, 4]."""
+        m = self.SURFACE_MODES[mode]; rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8); n = len(rays8); hits4 = np.ascontiguousarray(hits4, np.float32).reshape(-1, 4)
+        ins = None if instance is None else np.ascontiguousarray(instance, np.int32).reshape(-1); d6 = None if diff6 is None else np.ascontiguousarray(diff6, np.float32).reshape(-1, 6)
+        q = None if query3 is None else np.ascontiguousarray(query3, np.float32).reshape(-1, 3)
+        if len(hits4) != n or any(a is not None and len(a) != n for a in (ins, d6, q)): raise ValueError("surface_units: one hit, instance, differential pair and query per ray")
+        out = np.zeros((n, (51, 11, 4)[m]), np.float32)
+        self.L.check(self.L.L.mi_debug_surface(self.h, m, _p(rays8), _p(hits4), _p(ins), _p(d6), _p(q), n, _p(out))); return out
 
     def camera_rays(self, pos2, aperture2=None, differentials=False):
         """Sensor rays (o, mint, d, maxt) at film positions pos2.  aperture2: the aperture sample of every ray of a lens scene (None: (0.5, 0.5), the reference's default

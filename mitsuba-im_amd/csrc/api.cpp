@@ -66,6 +66,7 @@ void mi_launch_debug_texture(const DScene &, uint32_t, const float *, const floa
 void mi_launch_debug_emitter_sample(const DScene &, int, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_emitter_eval(const DScene &, int, int, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_debug_medium(const DScene &, uint32_t, int, const float *, uint64_t, float *, hipStream_t);
+void mi_launch_debug_surface(const DScene &, int, const float *, const float *, const int *, const float *, const float *, uint64_t, float *, hipStream_t);
 void mi_launch_field_film(const DScene &, const FieldArgs &, const Queues &, const BatchDesc &, float *, float *, hipStream_t);
 void mi_launch_field_samples(const DScene &, const FieldArgs &, const Queues &, uint64_t, float *, hipStream_t);
 void mi_launch_field_layout(const float *, const float *, float *, int, int, int, int, int, hipStream_t);
@@ -2112,6 +2113,31 @@ int mi_debug_bsdf(mi_scene *s, uint32_t material, int mode, const float *wi, con
     if (rc) return rc;
     for (uint64_t i = 0; i < n; ++i) memcpy(out + i * per, &raw[i * 12], per * 4);
     return MI_OK;
+}
+// The surface step between a hit and the BSDF query (kernels_units.hip).  The hits are caller-supplied, so every primitive and instance index is checked against the
+// committed tables here, before any device work.
+int mi_debug_surface(mi_scene *s, int mode, const float *rays, const float *hits, const int32_t *inst, const float *diff, const float *query, uint64_t n, float *out) {
+    if (!s || !rays || !hits || !out || !n || mode < 0 || mode > 2 || (mode != 0 && !query)) return fail(MI_ERR_INVALID, "mi_debug_surface: bad argument");
+    if (!s->h.committed) return fail(MI_ERR_INVALID, "mi_debug_surface: the scene must be committed");
+    const DScene &d = s->h.d;
+    for (uint64_t i = 0; i < n; ++i) {
+        const float p = hits[4 * i + 3]; const int32_t in = inst ? inst[i] : -1;
+        if (!(p >= 0)) continue;                                            // a miss
+        if (in < -1 || (in >= 0 && ((uint32_t) in >= d.n_instances || !d.instances)) || !(p < (float) (in >= 0 ? d.n_tris : d.n_tris + d.n_analytic)))
+            return fail(MI_ERR_INVALID, "mi_debug_surface: hit " + std::to_string(i) + " names a primitive or an instance the scene does not have");
+    }
+    HIPCHK(hipSetDevice(s->h.device));
+    const uint64_t words = n * (8 + 4 + 1 + (diff ? 6 : 0) + (query ? 3 : 0)); std::vector<float> in(words);
+    float *pr = in.data(), *ph = pr + 8 * n, *pi = ph + 4 * n, *pd = pi + n, *pq = pd + (diff ? 6 * n : 0);
+    memcpy(pr, rays, n * 32); memcpy(ph, hits, n * 16);
+    for (uint64_t i = 0; i < n; ++i) { const int32_t v = inst ? inst[i] : -1; memcpy(pi + i, &v, 4); }
+    if (diff) memcpy(pd, diff, n * 24);
+    if (query) memcpy(pq, query, n * 12);
+    const int per = mode == 0 ? 51 : mode == 1 ? 11 : 4;
+    return withBuffers(in.data(), words * 4, out, n * per * 4, [&](void *i, void *o) {
+        const float *b = (const float *) i;
+        mi_launch_debug_surface(s->h.d, mode, b, b + 8 * n, (const int *) (b + 12 * n), diff ? b + 13 * n : nullptr, query ? b + 13 * n + (diff ? 6 * n : 0) : nullptr, n, (float *) o, nullptr);
+    });
 }
 int mi_debug_texture(mi_scene *s, uint32_t texture, const float *uv, const float *partials, uint64_t n, float *out) {
     if (!s || !s->h.committed || !uv || !out || !n) return fail(MI_ERR_INVALID, "mi_debug_texture: bad argument");

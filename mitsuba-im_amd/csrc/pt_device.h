@@ -344,6 +344,9 @@ DEV float hypot2f(float a, float b) {                          // src/libcore/ma
     else r = 0.0f;
     return r;
 }
+// math::floorToInt = (int) std::floor(v) (include/mitsuba/core/math.h:100) as the reference's x86-64 binary converts it: a value no int holds (infinity, NaN, |v| >= 2^31)
+// becomes INT_MIN.  The device's own conversion saturates instead, and INT_MAX + 1 is then a MIP level below zero that passes every `level >= n_levels` test
+DEV int floorToInt(float v) { const float f = floorf(v); return (f >= -2147483648.0f && f < 2147483648.0f) ? (int) f : (int) 0x80000000u; }
 DEV float miLog2(float v) { const float invLn2 = 1.4426950408889634f; return (float) log((double) v) * invLn2; }   // math.cpp:103-106 (1 / logf(2))
 DEV v3 mipEval(const DScene &sc, const TextureD &t, float uvx, float uvy, float d0x, float d0y, float d1x, float d1y) {
     if (t.filter == 0u) return mipBox(sc, t, 0, uvx, uvy);
@@ -354,7 +357,7 @@ DEV v3 mipEval(const DScene &sc, const TextureD &t, float uvx, float uvy, float 
     float root = hypot2f(A - C, B), Aprime = 0.5f * (A + C - root), Cprime = 0.5f * (A + C + root),
           majorRadius = Aprime != 0 ? sqrtf(F / Aprime) : 0, minorRadius = Cprime != 0 ? sqrtf(F / Cprime) : 0;
     if (t.filter == 2u || !(minorRadius > 0) || !(majorRadius > 0) || F < 0) {
-        float level = miLog2(maxf(majorRadius, MI_EPSILON)); int ilevel = (int) floorf(level);
+        float level = miLog2(maxf(majorRadius, MI_EPSILON)); int ilevel = floorToInt(level);      // an infinite radius (F / Aprime overflows under a huge, thin footprint): INT_MIN, the level-0 lookup
         if (ilevel < 0) return mipBilinear(sc, t, 0, uvx, uvy);
         float a = level - (float) ilevel;
         return mipBilinear(sc, t, ilevel, uvx, uvy) * (1.0f - a) + mipBilinear(sc, t, ilevel + 1, uvx, uvy) * a;
@@ -627,6 +630,16 @@ DEV void analyticUV(const AnalyticD &sh, float lx, float ly, v3 pRay, float &uvx
         uvx = phi / (2 * MI_PI); uvy = local.z / sh.length;
         dpdu = xfVector(sh.to_world, V(-local.y, local.x, 0) * (2 * MI_PI)); dpdv = xfVector(sh.to_world, V(0, 0, sh.length));
     }
+}
+// its.dpdu / its.dpdv of a hit as computePartials and the bump / normal-map adapters take them: an analytic shape's own parameterisation (which also sets huvx, huvy;
+// a triangle hit leaves them alone), the UV tangents of a triangle whose mesh has texcoords (flags & 16), else its two edge vectors; the member of an instance is
+// taken to world space (instance.cpp:134-139).  (lx, ly) and pRay as analyticUV takes them
+template <bool L>
+DEV void surfaceTangents(const DScene &sc, const Tabs<L> &tb, const Hit &h, uint32_t prim, int inst, float lx, float ly, v3 pRay, float &huvx, float &huvy, v3 &dpdu, v3 &dpdv) {
+    if (inst < 0 && prim >= sc.n_tris) analyticUV(sc.analytic[prim - sc.n_tris], lx, ly, pRay, huvx, huvy, dpdu, dpdv);
+    else if (h.flags & 16u) { const TriUV &tu = sc.triuv[prim]; dpdu = ld3(tu.dpdu); dpdv = ld3(tu.dpdv); }
+    else { typename AS<L>::p4 rec = tb.shade4 + prim * (uint32_t) MI_SHADE_WORDS; f4 r0 = rec[0], r1 = rec[1], r2 = rec[2]; dpdu = V(r1.x - r0.x, r1.y - r0.y, r1.z - r0.z); dpdv = V(r2.x - r0.x, r2.y - r0.y, r2.z - r0.z); }
+    if (inst >= 0) { dpdu = xfVector(sc.instances[inst].to_world, dpdu); dpdv = xfVector(sc.instances[inst].to_world, dpdv); }
 }
 // Shape::fillIntersectionRecord (rectangle.cpp:155-168, disk.cpp:172-200, sphere.cpp:196-245, cylinder.cpp:203-233) + computeShadingFrame
 // + wi (skdtree.h:421-427).  Disk: the reference leaves geoFrame unset; defined as the shading normal.

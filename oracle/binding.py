@@ -108,6 +108,7 @@ def lib():
         L.orc_emitter_sample_units.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_emitter_eval_units.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p, C.c_void_p]
         L.orc_medium_units.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.orc_surface_units.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_filter_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_sfmt_sequence.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
         L.orc_sfmt_floats.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
@@ -304,6 +305,25 @@ class Oracle:
         """orc_medium_units: `mode` out of MEDIUM_MODES, inputs [n, 10] as laid out in pt_oracle.c -> [n, 12] and the branches taken (MEDIUM_BRANCHES; distance only)."""
         a = np.ascontiguousarray(inputs, np.float32).reshape(-1, 10); n = len(a); out = np.zeros((n, 12), np.float32); br = np.zeros(n, np.uint32)
         if lib().orc_medium_units(self.h, int(medium), self.MEDIUM_MODES[mode], _ptr(a), n, _ptr(out), _ptr(br)) != 0: raise ValueError(f"oracle: medium {medium} is out of range")
+        return out, br
+
+    SURFACE_TANGENTS = {"uv_tangents": 1, "edges": 2, "rectangle": 3, "disk": 4, "sphere": 5, "cylinder": 6}      # branches & 7
+    SURFACE_PARTIALS = {"none": 0, "zero_tangents": 1, "prx_or_pry_zero": 2, "solve_failed": 3, "regular": 4}      # (branches >> 13) & 7
+    SURFACE_BRANCHES = {"instanced": 1 << 3, "degenerate_uv": 1 << 4, "texture_only": 1 << 5, "mask": 1 << 6, "mask_bump": 1 << 7, "bump_bitmap": 1 << 8, "bump_procedural": 1 << 9,
+                        "normalmap": 1 << 10, "bump_mixture": 1 << 11, "coat_textured": 1 << 12, "ewa": 1 << 16, "filter_fallback": 1 << 17, "bump_flipped": 1 << 18,
+                        "sign_change": 1 << 19, "miss": 1 << 20, "ewa_long": 1 << 21}
+    SURFACE_MODES = {"record": 0, "sample": 1, "eval": 2}
+    SURFACE_WIDTH = {0: 51, 1: 11, 2: 4}
+
+    def surface_units(self, mode, rays8, diff6=None, query3=None):
+        """orc_surface_units: the surface step (hit fill, partials, material chain, perturbed frame, query) on rays8 [n, 8]; diff6 [n, 6] = the differential directions
+        (None: a later bounce); query3 [n, 3] = the 2-D sample and the extra value ("sample") or a world direction ("eval") -> [n, 51 / 11 / 4] as laid out in pt_oracle.c
+        and the branches taken (SURFACE_TANGENTS, SURFACE_PARTIALS, SURFACE_BRANCHES)."""
+        m = self.SURFACE_MODES[mode]; rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8); n = len(rays8)
+        d6 = None if diff6 is None else np.ascontiguousarray(diff6, np.float32).reshape(-1, 6); q = None if query3 is None else np.ascontiguousarray(query3, np.float32).reshape(-1, 3)
+        assert (d6 is None or len(d6) == n) and (m == 0 or (q is not None and len(q) == n))
+        out = np.zeros((n, self.SURFACE_WIDTH[m]), np.float32); br = np.zeros(n, np.uint32)
+        if lib().orc_surface_units(self.h, _ptr(rays8), _ptr(d6), _ptr(q), n, m, _ptr(out), _ptr(br)) != 0: raise ValueError("oracle: surface_units mode out of range")
         return out, br
 
     def camera_ray(self, sx, sy):

@@ -1913,6 +1913,9 @@ static float hypot2f(float a, float b) {                       /* src/libcore/ma
     else r = 0.0f;
     return r;
 }
+/* math::floorToInt = (int) std::floor(v) (math.h:100) as the reference's x86-64 binary converts it (cvttss2si): infinity, NaN and |v| >= 2^31 become INT_MIN -- written out,
+ * since C leaves that conversion undefined */
+static inline int floor_to_int(float v) { const float f = floorf(v); return (f >= -2147483648.0f && f < 2147483648.0f) ? (int) f : (-2147483647 - 1); }
 static inline float mi_log2(float v) { const float invLn2 = 1.0f / logf(2.0f); return (float) log((double) v) * invLn2; }   /* math.cpp:103-106 */
 static v3 mip_eval(const orc_scene *s, const orc_texture *t, float uvx, float uvy, float d0x, float d0y, float d1x, float d1y) {
     if (t->filter == 0) { g_tex_info.branches |= TEXI_NEAREST; return mip_box(s, t, 0, uvx, uvy); }
@@ -1923,7 +1926,7 @@ static v3 mip_eval(const orc_scene *s, const orc_texture *t, float uvx, float uv
     float root = hypot2f(A - C, B), Aprime = 0.5f * (A + C - root), Cprime = 0.5f * (A + C + root),
           majorRadius = Aprime != 0 ? sqrtf(F / Aprime) : 0, minorRadius = Cprime != 0 ? sqrtf(F / Cprime) : 0;
     if (t->filter == 2 || !(minorRadius > 0) || !(majorRadius > 0) || F < 0) {
-        float level = mi_log2(maxf(majorRadius, EPSILON)); int ilevel = (int) floorf(level);
+        float level = mi_log2(maxf(majorRadius, EPSILON)); int ilevel = floor_to_int(level);
         g_tex_info.branches |= t->filter == 2 ? TEXI_TRILINEAR : TEXI_DEGENERATE; g_tex_info.level = ilevel;
         if (ilevel < 0) { g_tex_info.branches |= TEXI_LEVEL_NEGATIVE; return mip_bilinear(s, t, 0, uvx, uvy); }
         float a = level - (float) ilevel;
@@ -1943,11 +1946,14 @@ static v3 mip_eval(const orc_scene *s, const orc_texture *t, float uvx, float uv
     return add(scale(mip_ewa(s, t, ilevel, uvx, uvy, A, B, C), 1.0f - a), scale(mip_ewa(s, t, ilevel + 1, uvx, uvy, A, B, C), a));
 }
 /* Intersection::computePartials (src/librender/intersection.cpp:5-76) for a hit of the CAMERA ray (rx/ry: its differentials, common origin o) */
+/* what the calling thread's last compute_partials / perturb_frame did (orc_surface_units): 1 zero tangents, 2 prx == 0 || pry == 0, 3 the 2x2 solve failed, 4 regular;
+ * the bump normal was flipped to the geometric side.  Set where the branches are taken */
+static _Thread_local struct { int partials; int bump_flipped; } g_surf_info;
 static int compute_partials(const hit_t *h, v3 o, v3 rxd, v3 ryd, float *dudx, float *dvdx, float *dudy, float *dvdy) {
     *dudx = *dvdx = *dudy = *dvdy = 0.0f;
-    if (is_zero(h->dpdu) && is_zero(h->dpdv)) return 1;
+    if (is_zero(h->dpdu) && is_zero(h->dpdv)) { g_surf_info.partials = 1; return 1; }
     const float pp = dot(h->ng, h->p), pox = dot(h->ng, o), poy = dot(h->ng, o), prx = dot(h->ng, rxd), pry = dot(h->ng, ryd);
-    if (prx == 0 || pry == 0) return 1;
+    if (prx == 0 || pry == 0) { g_surf_info.partials = 2; return 1; }
     const float tx = (pp - pox) / prx, ty = (pp - poy) / pry;
     float absX = fabsf(h->ng.x), absY = fabsf(h->ng.y), absZ = fabsf(h->ng.z); int a0, a1;
     if (absX > absY && absX > absZ) { a0 = 1; a1 = 2; } else if (absY > absZ) { a0 = 0; a1 = 2; } else { a0 = 0; a1 = 1; }
@@ -1955,8 +1961,8 @@ static int compute_partials(const hit_t *h, v3 o, v3 rxd, v3 ryd, float *dudx, f
     v3 px = add(o, scale(rxd, tx)), py = add(o, scale(ryd, ty));
     float Bx0 = comp(px, a0) - comp(h->p, a0), Bx1 = comp(px, a1) - comp(h->p, a1), By0 = comp(py, a0) - comp(h->p, a0), By1 = comp(py, a1) - comp(h->p, a1);
     float det = A00 * A11 - A01 * A10;
-    if (fabsf(det) <= 0x1p-128f) { *dudx = 1; *dvdx = 0; *dudy = 0; *dudy = 1; return 1; }       /* solveLinearSystem2x2 fails (util.cpp:529-541); NB the reference's second fallback assigns dudy twice */
-    float inverse = 1.0f / det;
+    if (fabsf(det) <= 0x1p-128f) { g_surf_info.partials = 3; *dudx = 1; *dvdx = 0; *dudy = 0; *dudy = 1; return 1; }       /* solveLinearSystem2x2 fails (util.cpp:529-541); NB the reference's second fallback assigns dudy twice */
+    float inverse = 1.0f / det; g_surf_info.partials = 4;
     *dudx = (A11 * Bx0 - A01 * Bx1) * inverse; *dvdx = (A00 * Bx1 - A10 * Bx0) * inverse;
     *dudy = (A11 * By0 - A01 * By1) * inverse; *dvdy = (A00 * By1 - A10 * By0) * inverse;
     return 1;
@@ -2039,7 +2045,7 @@ static void perturb_frame(const orc_scene *s, const orc_material *m, const hit_t
         v3 dpdv = add(its->dpdv, scale(its->ns, dDispDv - dot(its->ns, its->dpdv)));
         v3 n = normalize(cross(dpdu, dpdv));
         *ps = normalize(sub(dpdu, scale(n, dot(n, dpdu)))); *pt = cross(n, *ps);
-        if (dot(n, its->ng) < 0) n = scale(n, -1.0f);
+        if (dot(n, its->ng) < 0) { g_surf_info.bump_flipped = 1; n = scale(n, -1.0f); }
         *pn = n;
     } else {                                                              /* NormalMap::getFrame (normalmap.cpp:108-127): Texture::eval(its, false) */
         v3 c = texture_eval(s, tx, its->uvx, its->uvy, NULL);
@@ -2317,6 +2323,98 @@ static v3 sm_sample(const smat_t *sm, v3 wi, float u, float v, v3 *wo, float *pd
     }
     *wo = neg(wi); *eta = 1.0f; *delta = 2; *pdf = 1 - sm->prob;       /* :202-208 */
     return V((1.0f - sm->opacity.x) / *pdf, (1.0f - sm->opacity.y) / *pdf, (1.0f - sm->opacity.z) / *pdf);
+}
+/* ---- the surface step between a hit and the BSDF query, one case at a time (the device's mi_debug_surface): the oracle's own hit fill, compute_partials,
+ * resolve_material and perturb_frame, then -- modes 1 and 2 -- the level below mask and bump / normal map queried in the perturbed frame (ct_*), before the mask's lobe
+ * choice, the opacity multiply and the sign rejection.  rays8 = o, mint, d, maxt; diff6 = the two differential directions rxd, ryd (NULL: a later bounce -- level-0
+ * lookups, no partials); query3 = mode 1: the 2-D sample and the extra sampler value, mode 2: a WORLD direction (mode 0: ignored, may be NULL).
+ * out, in the device's layout: mode 0 (51 floats) = uv 2, dpdu 3, dpdv 3, partials 4, opacity 3, the value loaded into the first textured parameter on the chain 3,
+ * masked, bumped, coating record (-1: none), leaf record, the leaf's reflectance 3, ps 3, pt 3, pn 3 (zero when not bumped), wi in the query frame 3, then the hit itself:
+ * t, u, v, primitive, instance, and its shading frame ns 3, s 3, t 3.  mode 1 (11) = weight rgb, pdf, wo xyz (query frame), eta, delta, null, extra drawn.  mode 2 (4) = value rgb, pdf.  A miss writes zeros.
+ * branches (may be NULL): SURF_* per case.  -1: mode out of range, or modes 1 / 2 without query3 */
+enum { SURF_TANGENT_MASK = 7, SURF_UV_TANGENTS = 1, SURF_EDGES = 2, SURF_RECTANGLE = 3, SURF_DISK = 4, SURF_SPHERE = 5, SURF_CYLINDER = 6,
+       SURF_INSTANCED = 1 << 3, SURF_DEGENERATE_UV = 1 << 4, SURF_TEXTURE_ONLY = 1 << 5, SURF_MASK = 1 << 6, SURF_MASK_BUMP = 1 << 7, SURF_BUMP_BITMAP = 1 << 8,
+       SURF_BUMP_PROCEDURAL = 1 << 9, SURF_NORMALMAP = 1 << 10, SURF_BUMP_MIXTURE = 1 << 11, SURF_COAT_TEXTURED = 1 << 12,
+       SURF_PARTIALS_SHIFT = 13 /* 3 bits: g_surf_info.partials */, SURF_EWA = 1 << 16, SURF_FILTER_FALLBACK = 1 << 17, SURF_BUMP_FLIPPED = 1 << 18, SURF_SIGN_CHANGE = 1 << 19,
+       SURF_MISS = 1 << 20, SURF_EWA_LONG = 1 << 21 /* the EWA loops visited more than 16384 texels */ };
+static inline uint32_t mat_texture(const orc_scene *s, uint32_t m) { return (s->materials[m].m.flags >> 8) & 0xFFFFu; }
+int orc_surface_units(const orc_scene *s, const float *rays8, const float *diff6, const float *query3, uint64_t n, int mode, float *out, uint32_t *branches) {
+    if (mode < 0 || mode > 2 || (mode != 0 && !query3)) return -1;
+    const int per = mode == 0 ? 51 : mode == 1 ? 11 : 4;
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *r = rays8 + i * 8; float *o = out + i * per; for (int k = 0; k < per; ++k) o[k] = 0.0f;
+        const v3 ro = V(r[0], r[1], r[2]), rd = V(r[4], r[5], r[6]);
+        float mint, maxt, t = 0, u = 0, v = 0; uint32_t prim = 0; int32_t inst = -1; uint32_t br = 0;
+        g_tex_info.branches = 0; g_tex_info.level = 0; g_tex_info.texels = 0; g_surf_info.partials = 0; g_surf_info.bump_flipped = 0;
+        if (!clip_interval(s, ro, rd, r[3], r[7], 0, &mint, &maxt) || !traverse(s, ro, rd, mint, maxt, 0, &t, &prim, &inst, &u, &v)) { if (branches) branches[i] = SURF_MISS; continue; }
+        hit_t its; fill_hit(s, ro, rd, t, prim, inst, u, v, &its);
+        if (its.material < 0 || (uint32_t) its.material >= s->d.n_materials) { if (branches) branches[i] = SURF_MISS; continue; }
+        if (prim >= s->d.n_tris) br |= SURF_RECTANGLE + s->analytic[prim - s->d.n_tris].a.type;
+        else if (s->uv && (s->shapes[s->tri_shape[prim]].flags & 2u)) {
+            br |= SURF_UV_TANGENTS;
+            const uint32_t i0 = s->idx[prim * 3], i1 = s->idx[prim * 3 + 1], i2 = s->idx[prim * 3 + 2];       /* the determinant of computeUVTangents (scene creation) */
+            const float du1 = s->uv[i1 * 2] - s->uv[i0 * 2], dv1 = s->uv[i1 * 2 + 1] - s->uv[i0 * 2 + 1], du2 = s->uv[i2 * 2] - s->uv[i0 * 2], dv2 = s->uv[i2 * 2 + 1] - s->uv[i0 * 2 + 1];
+            if (du1 * dv2 - dv1 * du2 == 0) br |= SURF_DEGENERATE_UV;
+        } else br |= SURF_EDGES;
+        if (inst >= 0) br |= SURF_INSTANCED;
+        v3 rxd = V(0, 0, 0), ryd = V(0, 0, 0); const int diffs = diff6 != NULL;
+        if (diffs) { rxd = V(diff6[i * 6], diff6[i * 6 + 1], diff6[i * 6 + 2]); ryd = V(diff6[i * 6 + 3], diff6[i * 6 + 4], diff6[i * 6 + 5]); }
+        float pa[4] = { 0, 0, 0, 0 };
+        if (diffs) compute_partials(&its, ro, rxd, ryd, &pa[0], &pa[1], &pa[2], &pa[3]);
+        const smat_t sm = resolve_material(s, (uint32_t) its.material, &its, diffs, ro, &rxd, &ryd);
+        /* the records of the chain, as the shade stage walks them: mask -> bump / normal map -> coating -> leaf */
+        uint32_t cur = (uint32_t) its.material; int coat = -1, first = -1; const orc_material *mm = &s->materials[cur].m;      /* first: whose parameter was loaded first -- 0 the mask's opacity, 1 the coating record, 2 the leaf */
+#define SURF_VISIT(role) do { if (first < 0 && mat_texture(s, cur)) first = (role); } while (0)
+        if (mm->type == BSDF_MASK) {
+            SURF_VISIT(0); br |= SURF_MASK; cur = mm->distr; mm = &s->materials[cur].m;
+            if (mm->type == BSDF_BUMPMAP || mm->type == BSDF_NORMALMAP) br |= SURF_MASK_BUMP;
+        }
+        if (mm->type == BSDF_BUMPMAP || mm->type == BSDF_NORMALMAP) {
+            if (mm->type == BSDF_NORMALMAP) br |= SURF_NORMALMAP; else br |= s->textures[mat_texture(s, cur) - 1].type == 2 ? SURF_BUMP_BITMAP : SURF_BUMP_PROCEDURAL;
+            cur = mm->distr; mm = &s->materials[cur].m;
+            if (mm->type == BSDF_MIXTURE) br |= SURF_BUMP_MIXTURE;
+        }
+        if (mm->type == BSDF_COATING || mm->type == BSDF_ROUGHCOATING) {
+            SURF_VISIT(1); coat = (int) cur; cur = mm->distr; mm = &s->materials[cur].m;
+            if (mat_texture(s, cur)) br |= SURF_COAT_TEXTURED;
+        }
+        SURF_VISIT(2);
+#undef SURF_VISIT
+        if (first >= 0 && !(br & (SURF_MASK | SURF_BUMP_BITMAP | SURF_BUMP_PROCEDURAL | SURF_NORMALMAP))) br |= SURF_TEXTURE_ONLY;
+        br |= (uint32_t) g_surf_info.partials << SURF_PARTIALS_SHIFT;
+        if ((g_tex_info.branches & (TEXI_EWA_CLAMPED | TEXI_EWA_UNCLAMPED)) && !(g_tex_info.branches & TEXI_EWA_TO_BILINEAR)) br |= SURF_EWA;
+        if (g_tex_info.branches & (TEXI_DEGENERATE | TEXI_EWA_TO_BILINEAR | TEXI_EWA_ZERO_DENOMINATOR)) br |= SURF_FILTER_FALLBACK;
+        if (g_surf_info.bump_flipped) br |= SURF_BUMP_FLIPPED;
+        if (g_tex_info.texels > 16384u) br |= SURF_EWA_LONG;
+        const v3 wiQ = sm.bumped ? frame_to_local(sm.ps, sm.pt, sm.pn, to_world(&its, its.wi)) : its.wi;
+        if (mode == 0) {
+            o[0] = its.uvx; o[1] = its.uvy; o[2] = its.dpdu.x; o[3] = its.dpdu.y; o[4] = its.dpdu.z; o[5] = its.dpdv.x; o[6] = its.dpdv.y; o[7] = its.dpdv.z;
+            o[8] = pa[0]; o[9] = pa[1]; o[10] = pa[2]; o[11] = pa[3];
+            if (sm.masked) { o[12] = sm.opacity.x; o[13] = sm.opacity.y; o[14] = sm.opacity.z; }
+            if (first == 0) { o[15] = sm.opacity.x; o[16] = sm.opacity.y; o[17] = sm.opacity.z; }
+            else if (first > 0) { const float *fv = first == 1 ? sm.coatm.m.reflectance : sm.inner.m.reflectance; o[15] = fv[0]; o[16] = fv[1]; o[17] = fv[2]; }
+            o[18] = (float) sm.masked; o[19] = (float) sm.bumped; o[20] = (float) coat; o[21] = (float) cur;
+            o[22] = sm.inner.m.reflectance[0]; o[23] = sm.inner.m.reflectance[1]; o[24] = sm.inner.m.reflectance[2];
+            if (sm.bumped) { o[25] = sm.ps.x; o[26] = sm.ps.y; o[27] = sm.ps.z; o[28] = sm.pt.x; o[29] = sm.pt.y; o[30] = sm.pt.z; o[31] = sm.pn.x; o[32] = sm.pn.y; o[33] = sm.pn.z; }
+            o[34] = wiQ.x; o[35] = wiQ.y; o[36] = wiQ.z; o[37] = t; o[38] = u; o[39] = v; o[40] = (float) prim; o[41] = (float) inst;
+            o[42] = its.ns.x; o[43] = its.ns.y; o[44] = its.ns.z; o[45] = its.s.x; o[46] = its.s.y; o[47] = its.s.z; o[48] = its.tt.x; o[49] = its.tt.y; o[50] = its.tt.z;
+            if (its.wi.z * wiQ.z <= 0) br |= SURF_SIGN_CHANGE;
+        } else if (mode == 1) {
+            const float *q = query3 + i * 3; v3 wo = V(0, 0, 0); float pdf = 0, eta = 0; int delta = 0;
+            g_extra_unit = q[2]; g_extra_drawn = 0;
+            const v3 w = ct_sample(&sm, wiQ, q[0], q[1], &wo, &pdf, &eta, &delta, NULL);
+            g_extra_unit = 0.5f;
+            o[0] = w.x; o[1] = w.y; o[2] = w.z; o[3] = pdf; o[4] = wo.x; o[5] = wo.y; o[6] = wo.z; o[7] = eta; o[8] = delta != 0 ? 1.0f : 0.0f; o[9] = delta == 2 ? 1.0f : 0.0f; o[10] = (float) g_extra_drawn;
+            if (sm.bumped && !is_zero(w)) { const v3 woL = to_local(&its, frame_to_world(sm.ps, sm.pt, sm.pn, wo)); if (woL.z * wo.z <= 0) br |= SURF_SIGN_CHANGE; }
+        } else {
+            const float *q = query3 + i * 3; const v3 wo = to_local(&its, V(q[0], q[1], q[2]));
+            const v3 woQ = sm.bumped ? frame_to_local(sm.ps, sm.pt, sm.pn, to_world(&its, wo)) : wo;
+            const v3 e = ct_eval(&sm, wiQ, woQ); o[0] = e.x; o[1] = e.y; o[2] = e.z; o[3] = ct_pdf(&sm, wiQ, woQ);
+            if (sm.bumped && wo.z * woQ.z <= 0) br |= SURF_SIGN_CHANGE;
+        }
+        if (branches) branches[i] = br;
+    }
+    return 0;
 }
 static int sm_is_smooth(const smat_t *sm) {
     if (!sm->n_mix) return material_is_smooth(&sm->inner.m);

@@ -189,3 +189,19 @@ def test_fused_walk_ray_sets_without_gpu(mi):
     assert (~counts[(d == 0).any(1)]).all()                              # an axis-parallel ray never qualifies: its zero components keep the inverted box shut
     sl = mi.scenes.sliver_stack(); r = F.sliver_rays(sl)
     assert 4000 <= len(sl.idx) <= 4200 and len(r) == 2400 and np.allclose(np.linalg.norm(r[:, 4:7], axis=1), 1, atol=1e-6)
+
+
+def test_surface_units_entry_refuses_without_gpu(mi):
+    """mi_debug_surface is exported, and its bad-argument paths are decided on the arguments alone, before the commit check and before any device call: a NULL scene,
+    ray, hit or output pointer, n == 0, a mode outside 0..2, modes 1 / 2 without their query values; with good arguments an uncommitted scene is what is refused."""
+    L = mi.lib(); assert "mi_debug_surface" in mi.api.EXPORTS and hasattr(L.L, "mi_debug_surface")
+    h = _uncommitted_scene(mi, mi.scenes.cornell_box(16, 9, 1))
+    rays = np.zeros((1, 8), np.float32); hits = np.full((1, 4), -1.0, np.float32); inst = np.full(1, -1, np.int32); q = np.zeros((1, 3), np.float32); out = np.zeros((1, 51), np.float32)
+    r, t, i, qq, o = (a.ctypes.data for a in (rays, hits, inst, q, out))
+    def call(*a): rc = L.L.mi_debug_surface(*a); return rc, L.L.mi_last_error()
+    for args in ((None, 0, r, t, i, None, None, 1, o), (h, 0, None, t, i, None, None, 1, o), (h, 0, r, None, i, None, None, 1, o), (h, 0, r, t, i, None, None, 1, None), (h, 0, r, t, i, None, None, 0, o),
+                 (h, -1, r, t, i, None, None, 1, o), (h, 3, r, t, i, None, qq, 1, o), (h, 1, r, t, i, None, None, 1, o), (h, 2, r, t, i, None, None, 1, o)):
+        rc, msg = call(*args); assert rc == 1 and b"mi_debug_surface: bad argument" in msg, (args[1], rc, msg)
+    for args in ((h, 0, r, t, i, None, None, 1, o), (h, 0, r, t, None, None, None, 1, o), (h, 1, r, t, i, None, qq, 1, o), (h, 2, r, t, i, None, qq, 1, o)):
+        rc, msg = call(*args); assert rc == 1 and b"mi_debug_surface: the scene must be committed" in msg, (args[1], rc, msg)
+    L.L.mi_scene_destroy(h)

@@ -2,7 +2,8 @@
 tests/test_gpu_light_units.py on the device): one generator,
 fixed seeds, so that both sides and both tests see the same numbers.  Directions and sample values are aimed at what camera-driven paths almost never produce:
 grazing and exactly normal incidence, sample values 0 and 1 - 2^-24, directions below a one-sided surface, texture coordinates on texel edges and wrap seams,
-degenerate and non-finite footprints."""
+degenerate and non-finite footprints.  The surface step between a hit and the BSDF query (tests/test_surface_inputs.py, tests/test_gpu_surface_units.py) gets rays aimed at
+chosen primitives instead: see surface_inputs."""
 import zlib
 import numpy as np
 
@@ -574,3 +575,267 @@ def medium_reference(oracle, golden_scenes, S, name):
             per[m] = {mode: dict(zip(("out", "branches"), orc.medium_units(m, mode, a)), inp=a) for mode, a in inp.items()}
         _LIGHT_REF[key] = dict(sc=sc, records=per)
     return _LIGHT_REF[key]
+
+
+# ------------------------------------------------------------------------------------------------ the surface step
+# Inputs of the comparison of the surface step between a hit and the BSDF query (mi_debug_surface against orc_surface_units): rays AIMED at a chosen primitive and
+# target point -- grazing incidence, triangle edges and vertices, seams, poles and centres of the analytic shapes, target uv on texel edges and wrap seams of the bound
+# bitmap -- with differentials scaled by 1, 1e-3 and 1e3, perpendicular to the surface or non-finite; on the committed textured scenes and two unit scenes.
+SURFACE_SCENES = ["layered_room", "layered_room_procedural", "masked_room", "bitmap_room", "textured_plastics", "textured_plastics_smooth", "textured_shapes"]
+SURFACE_UNIT_SCENES = ["surface_units_instanced", "surface_units_edges"]
+N_SURFACE, N_SURFACE_UNIT = 2048, 4096
+DIFF_SCALES = [1.0, 1e-3, 1e3]
+BUMP_SCALES = [0.0, -1.0, 1e4]
+CONSTANT_NORMALS = [(0.5, 0.5, 1.0), (0.5, 0.5, 0.5), (0.5, 0.5, 0.0)]
+
+
+class _Meshes:
+    def __init__(self): self.verts, self.tris, self.nrm, self.uv, self.shapes = [], [], [], [], []
+
+    def add(self, pts, faces, bsdf, uv=None, normals=None, group=0, emitter=-1):
+        fv, ft = len(self.verts), len(self.tris); self.verts += [tuple(map(float, p)) for p in pts]; self.tris += [tuple(fv + i for i in f) for f in faces]
+        self.uv += [tuple(t) for t in uv] if uv is not None else [(0.0, 0.0)] * len(pts); self.nrm += [tuple(t) for t in normals] if normals is not None else [(0.0, 1.0, 0.0)] * len(pts)
+        self.shapes.append(dict(first_tri=ft, tri_count=len(faces), first_vert=fv, vert_count=len(pts), bsdf=bsdf, emitter=emitter, face_normals=int(normals is None), group=group,
+                                has_uv=int(uv is not None), interior=-1, exterior=-1))
+        return len(self.shapes) - 1
+
+    def quad(self, x0, x1, z0, z1, bsdf, group=0, uv=((0, 0), (0, 1), (1, 1), (1, 0))):
+        """in the plane y = 0, facing +y"""
+        return self.add([(x0, 0, z0), (x0, 0, z1), (x1, 0, z1), (x1, 0, z0)], [(0, 1, 2), (0, 2, 3)], bsdf, uv=uv, group=group)
+
+    def mound(self, x0, x1, z0, z1, height, bsdf, group=0, nu=4, nv=3):
+        pts, uv, nrm, faces = [], [], [], []
+        for j in range(nv + 1):
+            for i in range(nu + 1):
+                u, v = i / nu, j / nv; y = height * np.sin(np.pi * u) * np.sin(np.pi * v)
+                dydx = height * np.pi / (x1 - x0) * np.cos(np.pi * u) * np.sin(np.pi * v); dydz = height * np.pi / (z1 - z0) * np.sin(np.pi * u) * np.cos(np.pi * v)
+                nn = np.array([-dydx, 1.0, -dydz]); nn /= np.linalg.norm(nn)
+                pts.append((x0 + (x1 - x0) * u, y, z0 + (z1 - z0) * v)); uv.append((u, v)); nrm.append(tuple(map(float, nn)))
+        for j in range(nv):
+            for i in range(nu):
+                a = j * (nu + 1) + i; faces += [(a, a + nu + 1, a + 1), (a + 1, a + nu + 1, a + nu + 2)]
+        return self.add(pts, faces, bsdf, uv=uv, normals=nrm, group=group)
+
+    def room(self, lo, hi, bsdf, light_bsdf, emitters, S):
+        """a closed box of plain quads WITHOUT texture coordinates, facing inward, and a small light under its ceiling"""
+        (x0, y0, z0), (x1, y1, z1) = lo, hi
+        for q in ([(x0, y0, z0), (x0, y0, z1), (x1, y0, z1), (x1, y0, z0)], [(x0, y1, z0), (x1, y1, z0), (x1, y1, z1), (x0, y1, z1)], [(x0, y0, z0), (x0, y1, z0), (x0, y1, z1), (x0, y0, z1)],
+                  [(x1, y0, z0), (x1, y0, z1), (x1, y1, z1), (x1, y1, z0)], [(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0)], [(x0, y0, z1), (x0, y1, z1), (x1, y1, z1), (x1, y0, z1)]):
+            self.add(q, [(0, 1, 2), (0, 2, 3)], bsdf)
+        y = y1 - 0.05; si = self.add([(-0.5, y, -0.5), (0.5, y, -0.5), (0.5, y, 0.5), (-0.5, y, 0.5)], [(0, 1, 2), (0, 2, 3)], light_bsdf, emitter=len(emitters))
+        emitters.append(dict(type=S.EMITTER_AREA, shape=si, radiance=(10.0, 10.0, 10.0), weight=1.0))
+
+
+def _constant_bitmap(S, rgb, filter_type):
+    base = np.ascontiguousarray(np.tile(np.asarray(rgb, f32), (4, 4, 1)))
+    return S.make_texture(S.TEXTURE_BITMAP, pyramid=dict(base=base, levels=[(4, 4, base.reshape(-1).copy())], wrapped=True), filter_type=filter_type)
+
+
+def _finish(S, M, bsdfs, emitters, tex, name, **kw):
+    cam = S.look_at((0.0, 3.0, -5.5), (0.0, 0.5, 0.0), (0, 1, 0))
+    return S.finish_scene(M.verts, M.tris, M.shapes, bsdfs, emitters, cam, 50.0, 0.05, 100.0, 32, 32, 1, S.SAMPLER_SOBOL, 4, 3, normals=M.nrm, uvs=M.uv, name=name, textures=tex, **kw)
+
+
+def surface_scene_instanced(S):
+    """A shape group -- three UV-mapped quads and a smooth-shaded UV-mapped mound -- instanced three times (identity, rotation, rotation with non-uniform scale) inside
+    a plain room without texture coordinates.  The members carry a bitmap-textured diffuse (EWA), a bump map over a bitmap-textured diffuse (bilinear), a normal map
+    and a mask over the bump map: the `inst >= 0` branch of the tangent selection with every kind of record that needs tangents."""
+    pyr = S.load_texture_pyramid(); nimg = S.normal_map_image()
+    tex = [S.make_texture(S.TEXTURE_BITMAP, pyramid=pyr, uscale=2.0, vscale=1.5, uoffset=0.1, filter_type=S.MIP_EWA),
+           S.make_texture(S.TEXTURE_BITMAP, pyramid=pyr, uscale=1.5, vscale=2.0, voffset=0.05, filter_type=S.MIP_BILINEAR),
+           S.make_texture(S.TEXTURE_BITMAP, pyramid=dict(base=nimg, levels=S.build_mip_pyramid(nimg, S.WRAP_REPEAT, S.WRAP_REPEAT)), uscale=1.5, vscale=1.0, filter_type=S.MIP_BILINEAR)]
+    B = []
+    def add(**kw): B.append(S.make_bsdf(**kw)); return len(B) - 1
+    d_ewa = add(reflectance=(0.5, 0.5, 0.5)); B[d_ewa]["texture"] = 0
+    d_bil = add(reflectance=(0.5, 0.5, 0.5)); B[d_bil]["texture"] = 1
+    bump = add(kind=S.BSDF_BUMPMAP, nested=d_bil, texture=1, scale=0.25)
+    plain = add(reflectance=(0.6, 0.55, 0.5)); nmap = add(kind=S.BSDF_NORMALMAP, nested=plain, texture=2)
+    mask = add(kind=S.BSDF_MASK, reflectance=(0.55, 0.6, 0.7), nested=bump)
+    wall = add(reflectance=(0.7, 0.7, 0.7)); light = add(reflectance=(0.5, 0.5, 0.5))
+    M = _Meshes(); emitters = []
+    M.room((-6, -2, -6), (6, 6, 6), wall, light, emitters, S)
+    M.quad(-1.6, -0.9, -0.5, 0.5, d_ewa, group=1); M.quad(-0.8, -0.1, -0.5, 0.5, bump, group=1, uv=((0, 0), (0, 0.7), (1.3, 0.9), (1.1, 0.1))); M.quad(0.9, 1.6, -0.5, 0.5, mask, group=1)
+    M.mound(0.0, 0.8, -0.5, 0.5, 0.3, nmap, group=1)
+    inst = [S.make_instance(0, S.translate(0.0, 0.0, 0.0)), S.make_instance(0, S.translate(0.5, 2.0, 2.5) @ S.rotate((1, 0, 0), -55.0)),
+            S.make_instance(0, S.translate(2.5, 2.5, -2.0) @ S.rotate((0, 1, 1), 40.0) @ S.scale(1.3, 0.7, 1.1))]
+    return _finish(S, M, B, emitters, tex, "surface_units_instanced", instances=inst)
+
+
+def surface_scene_edges(S):
+    """Quads in a row, one record each: bump maps of scale 0, -1 and 1e4 over a bitmap-textured diffuse, a bump map whose displacement uses the nearest filter (zero
+    gradient), normal maps that are constant (0.5, 0.5, 1) (the unperturbed normal), (0.5, 0.5, 0.5) (a zero normal) and (0.5, 0.5, 0) (a normal in the tangent plane), a
+    bump-mapped triangle whose three texture coordinates coincide, a coating over a textured diffuse, an axis-aligned textured sphere (its poles: dpdu = 0), inside a
+    plain room without texture coordinates."""
+    pyr = S.load_texture_pyramid()
+    tex = [S.make_texture(S.TEXTURE_BITMAP, pyramid=pyr, uscale=2.0, vscale=1.5, uoffset=0.1, filter_type=S.MIP_EWA),
+           S.make_texture(S.TEXTURE_BITMAP, pyramid=pyr, uscale=1.5, vscale=2.0, voffset=0.05, filter_type=S.MIP_BILINEAR),
+           S.make_texture(S.TEXTURE_BITMAP, pyramid=pyr, uscale=1.5, vscale=2.0, filter_type=S.MIP_NEAREST)] + [_constant_bitmap(S, c, S.MIP_NEAREST) for c in CONSTANT_NORMALS]      # nearest: the texel itself (the bilinear weights of a constant do not always add up to 1)
+    B = []
+    def add(**kw): B.append(S.make_bsdf(**kw)); return len(B) - 1
+    d_ewa = add(reflectance=(0.5, 0.5, 0.5)); B[d_ewa]["texture"] = 0
+    d_bil = add(reflectance=(0.5, 0.5, 0.5)); B[d_bil]["texture"] = 1
+    plain = add(reflectance=(0.6, 0.55, 0.5))
+    recs = [add(kind=S.BSDF_BUMPMAP, nested=d_bil, texture=1, scale=s) for s in BUMP_SCALES] + [add(kind=S.BSDF_BUMPMAP, nested=d_bil, texture=2, scale=0.25)]
+    recs += [add(kind=S.BSDF_NORMALMAP, nested=plain, texture=3 + i) for i in range(3)]
+    degenerate = add(kind=S.BSDF_BUMPMAP, nested=d_bil, texture=1, scale=0.25)
+    coat = add(kind=S.BSDF_COATING, nested=d_ewa, reflectance=(0.1, 0.2, 0.3), scale=0.5, ior=1.5)
+    wall = add(reflectance=(0.7, 0.7, 0.7)); light = add(reflectance=(0.5, 0.5, 0.5))
+    M = _Meshes(); emitters = []
+    M.room((-6, -2, -6), (6, 6, 6), wall, light, emitters, S)
+    for i, r in enumerate(recs + [coat]): M.quad(-4.0 + i, -3.1 + i, -0.5, 0.5, r)
+    M.shapes[-3]["aim_weight"] = 0.5                                                 # the zero normal: every output of its cases is NaN; surface_inputs aims at it half as often
+    M.add([(-4.0, 0, 1.0), (-4.0, 0, 2.0), (-3.0, 0, 2.0)], [(0, 1, 2)], degenerate, uv=[(0.3, 0.3)] * 3)
+    ball = S.make_analytic(S.SHAPE_SPHERE, S.translate(0.0, 1.0, 2.5), d_ewa, radius=0.5)
+    return _finish(S, M, B, emitters, tex, "surface_units_edges", analytic=[ball])
+
+
+def surface_scenes(golden_scenes, S):
+    if "surface" not in _LIGHT_REF:
+        _LIGHT_REF["surface"] = {**{k: golden_scenes[k] for k in SURFACE_SCENES}, "surface_units_instanced": surface_scene_instanced(S), "surface_units_edges": surface_scene_edges(S)}
+    return _LIGHT_REF["surface"]
+
+
+def chain(sc, m):
+    """the records the surface step walks from record m: mask -> bumpmap / normalmap -> coating -> leaf"""
+    out = [m]
+    for kinds in ((9,), (11, 12), (17, 19)):
+        if sc.bsdfs[out[-1]]["type"] in kinds: out.append(int(sc.bsdfs[out[-1]]["distr"]))
+    return out
+
+
+def chain_textures(sc, m):
+    return [sc.textures[sc.bsdfs[r]["texture"]] for r in chain(sc, m) if sc.bsdfs[r].get("texture", -1) >= 0]
+
+
+def surface_no_libm(sc, m, differentials):
+    """no_libm extended over the chain: the leaf calls no math-library routine (a coating's absorption calls exp), and no texture on the chain is looked up through the
+    trilinear or EWA filter (logarithm, atan / sin / cos), which only a hit with differentials does"""
+    c = chain(sc, m)
+    return no_libm(sc, c[-1]) and not any(sc.bsdfs[r]["type"] in (17, 19) for r in c) and not (differentials and any(t["type"] == 2 and t["filter"] >= 2 for t in chain_textures(sc, m)))
+
+
+def _frame(n):
+    a = np.where(np.abs(n[:, :1]) > 0.9, np.array([[0.0, 1.0, 0.0]]), np.array([[1.0, 0.0, 0.0]])); s = np.cross(n, a); s /= np.linalg.norm(s, axis=1, keepdims=True)
+    return s, np.cross(n, s)
+
+
+EDGE_BARYCENTRICS = [(0, 0), (1, 0), (0, 1), (0.5, 0.5), (0.5, 0), (0, 0.5), (0.25, 0), (0, 0.75), (0.125, 0.875)]      # (b1, b2): the vertices and points on the three edges
+
+
+def surface_inputs(name, sc):
+    """rays8 [n, 8], diff6 [n, 6], and what each case was aimed at: `target` (-1 - a: analytic shape a, else the mesh shape), `instance`, `kind` ("" plain, "edge",
+    "texel", "graze"), `diff_kind` ("", "perpendicular", "nonfinite") and the differential scale"""
+    n = N_SURFACE_UNIT if name in SURFACE_UNIT_SCENES else N_SURFACE; rng = np.random.default_rng([zlib.crc32(name.encode()), 4242])
+    pos = sc.pos.astype(np.float64); lo, hi = scene_box(sc); size = float(np.linalg.norm(hi - lo))
+    entries = [(si, -1) for si, sh in enumerate(sc.shapes) if not sh.get("group", 0)]
+    entries += [(si, ii) for ii, ins in enumerate(sc.instances) for si, sh in enumerate(sc.shapes) if sh.get("group", 0) == ins["group"] + 1]
+    entries += [(-1 - a, -1) for a in range(len(sc.analytic))]
+    weight = np.asarray([sc.shapes[e].get("aim_weight", 1.0) if e >= 0 else 1.0 for e, _ in entries]); weight = np.cumsum(weight) / weight.sum()
+    P = np.zeros((n, 3)); N = np.zeros((n, 3)); target = np.zeros(n, np.int64); instance = np.full(n, -1); kind = np.array([""] * n, dtype=object)
+    special = rng.integers(0, 8, n)                                                 # 0: edges, vertices, seams, poles, centres; 1: texel edges of the bound bitmap
+    for i in range(n):
+        e, ii = entries[min(int(np.searchsorted(weight, rng.uniform(), side="right")), len(entries) - 1)]; target[i] = e; instance[i] = ii
+        if e >= 0:
+            sh = sc.shapes[e]; t = sh["first_tri"] + int(rng.integers(0, sh["tri_count"])); i0, i1, i2 = (int(v) for v in sc.idx[t])
+            r1, r2 = rng.uniform(size=2); b1, b2 = np.sqrt(r1) * (1 - r2), np.sqrt(r1) * r2
+            if special[i] == 0: b1, b2 = EDGE_BARYCENTRICS[rng.integers(0, len(EDGE_BARYCENTRICS))]; kind[i] = "edge"
+            bitmaps = [tx for tx in chain_textures(sc, sh["bsdf"]) if tx["type"] == 2]
+            if special[i] == 1 and sh.get("has_uv", 0) and sc.uv is not None and bitmaps:
+                # a target uv whose texture-space u (or v) lies on a level-0 texel edge (an integer multiple of 1 / w: the wrap seam when it is a multiple of w), one float32 ulp either side included
+                tx = bitmaps[0]; w0, h0 = (int(v) for v in sc.texture_levels[tx["first_level"]][:2]); t0, t1, t2 = (sc.uv[j].astype(np.float64) for j in (i0, i1, i2))
+                uv = t0 * (1 - b1 - b2) + t1 * b1 + t2 * b2; ax = int(rng.integers(0, 2)); sz, sca, off = ((w0, tx["uscale"], tx["uoffset"]), (h0, tx["vscale"], tx["voffset"]))[ax]
+                k = np.round((uv[ax] * sca + off) * sz); k = np.round(k / sz) * sz if rng.uniform() < 0.25 else k
+                u32 = f32((k / sz - off) / sca); u32 = [np.nextafter(u32, f32(-1e9)), u32, np.nextafter(u32, f32(1e9))][rng.integers(0, 3)]; uv[ax] = float(u32)
+                A = np.stack([t1 - t0, t2 - t0], 1)
+                if abs(np.linalg.det(A)) > 1e-12:
+                    c1, c2 = np.linalg.solve(A, uv - t0)
+                    if c1 >= 0 and c2 >= 0 and c1 + c2 <= 1: b1, b2 = c1, c2; kind[i] = "texel"
+            p = pos[i0] * (1 - b1 - b2) + pos[i1] * b1 + pos[i2] * b2; fn = np.cross(pos[i1] - pos[i0], pos[i2] - pos[i0])
+            if ii >= 0:
+                m = np.asarray(sc.instances[ii]["to_world"], np.float64).reshape(4, 4); p = m[:3, :3] @ p + m[:3, 3]; fn = np.linalg.inv(m[:3, :3]).T @ fn
+        else:
+            a = sc.analytic[-1 - e]; m = np.asarray(a["to_world"], np.float64).reshape(4, 4); sp = special[i] == 0
+            if sp: kind[i] = "edge"
+            if a["type"] in (0, 1):                                                 # rectangle: its edges and corners; disk: its centre and rim
+                # (next to a rim, not on it: where it is another shape's rim as well, which of the two a ray meets is a tie no side defines)
+                if a["type"] == 0: x, y = rng.uniform(-1, 1, 2) if not sp else np.asarray([(-1, 0.3), (1, -1), (0, 1), (0, 0)][rng.integers(0, 4)], np.float64)
+                else:
+                    r = np.sqrt(rng.uniform()) if not sp else [0.0, 0.999, 0.5][rng.integers(0, 3)]; ph = rng.uniform(0, 2 * np.pi) if not sp else [0.0, np.pi, 0.5 * np.pi][rng.integers(0, 3)]
+                    x, y = r * np.cos(ph), r * np.sin(ph)
+                pl = np.array([x, y, 0.0]); nl = np.array([0.0, 0.0, 1.0])
+            else:                                                                   # sphere: seam and poles; cylinder: seam, next to its rims
+                ph = rng.uniform(0, 2 * np.pi) if not sp or rng.uniform() < 0.3 else 0.0
+                if a["type"] == 2:
+                    th = np.arccos(rng.uniform(-1, 1)) if not sp else [0.0, np.pi, 0.5 * np.pi, 1e-4][rng.integers(0, 4)]
+                    nl = np.array([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)]); pl = nl * a["radius"]
+                else:
+                    z = rng.uniform(0, 1) if not sp else [0.001, 0.999, 0.5][rng.integers(0, 3)]
+                    nl = np.array([np.cos(ph), np.sin(ph), 0.0]); pl = nl * a["radius"] + np.array([0.0, 0.0, z * a["length"]])
+            p = m[:3, :3] @ pl + m[:3, 3]; fn = np.linalg.inv(m[:3, :3]).T @ nl
+        P[i] = p; N[i] = fn / max(np.linalg.norm(fn), 1e-300)
+    # origins on a hemisphere around the target: a quarter with incidence cosines out of EDGE_Z, a quarter of all cases from the back side
+    cz = rng.uniform(0.05, 1.0, n); graze = rng.uniform(size=n) < 0.25; cz = np.where(graze, np.asarray(EDGE_Z)[rng.integers(0, len(EDGE_Z), n)], cz); kind[graze & (kind == "")] = "graze"
+    ph = rng.uniform(0, 2 * np.pi, n); sn = np.sqrt(np.maximum(0.0, 1 - cz * cz)); s, t = _frame(N); side = np.where(rng.uniform(size=n) < 0.75, 1.0, -1.0)
+    w = s * (sn * np.cos(ph))[:, None] + t * (sn * np.sin(ph))[:, None] + N * (cz * side)[:, None]
+    # the poles of an axis-aligned sphere are met exactly only along its axis
+    for i in range(n):
+        if target[i] < 0 and kind[i] == "edge" and sc.analytic[-1 - target[i]]["type"] == 2 and abs(abs(N[i, 2]) - 1.0) < 1e-12:
+            a = sc.analytic[-1 - target[i]]; w[i] = np.round(N[i]); P[i] = np.asarray(a["to_world"], np.float64).reshape(4, 4)[:3, 3] + w[i] * a["radius"]
+    o = (P + w * (rng.uniform(0.03, 0.12, n) * size)[:, None]).astype(f32); d = P - o.astype(np.float64); d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(f32)
+    rays = np.zeros((n, 8), f32); rays[:, 0:3] = o; rays[:, 3] = MI_EPSILON; rays[:, 4:7] = d; rays[:, 7] = np.inf
+    # differentials: the spacing of the scene's own camera pixels around d, scaled as RayDifferential::scaleDifferential does
+    delta = 2.0 * np.tan(np.radians(sc.xfov) / 2) / sc.width; d64 = d.astype(np.float64); ds, dt = _frame(d64)
+    rx = d64 + ds * delta; rx /= np.linalg.norm(rx, axis=1, keepdims=True); ry = d64 + dt * delta; ry /= np.linalg.norm(ry, axis=1, keepdims=True)
+    scale = np.asarray(DIFF_SCALES)[rng.integers(0, len(DIFF_SCALES), n)]
+    rxd = d64 + (rx - d64) * scale[:, None]; ryd = d64 + (ry - d64) * scale[:, None]
+    r = rng.integers(0, 16, n); diff_kind = np.array([""] * n, dtype=object)
+    perp = r == 0; which = rng.uniform(size=n) < 0.5; tang = np.cross(N, d64); diff_kind[perp] = "perpendicular"      # prx == 0: no differential at all, or one in the tangent plane
+    rxd[perp & which] = 0.0; ryd[perp & ~which] = np.where(np.abs(N[perp & ~which]) == 1.0, 0.0, tang[perp & ~which])
+    bad = r == 1; diff_kind[bad] = "nonfinite"; col = rng.integers(0, 3, n); val = np.asarray([np.nan, np.inf, -np.inf])[rng.integers(0, 3, n)]
+    rxd[bad, col[bad]] = val[bad]
+    diff = np.ascontiguousarray(np.concatenate([rxd, ryd], 1), f32)
+    return dict(rays=rays, diff=diff, target=target, instance=instance, kind=kind, diff_kind=diff_kind, scale=scale)
+
+
+_SURF_REF = {}
+
+
+def surface_reference(oracle, golden_scenes, S, name):
+    """the inputs of scene `name` and the oracle's answers, computed once: dict(sc, inp, query (the 2-D samples + extra values), wo_world, and per run -- "record" and
+    "sample" with differentials, "record_plain" and "eval" without -- (out, branches))"""
+    if name not in _SURF_REF:
+        sc = surface_scenes(golden_scenes, S)[name]; orc = oracle.Oracle(sc); inp = surface_inputs(name, sc); n = len(inp["rays"]); b = bsdf_inputs(name, 0)
+        query = np.ascontiguousarray(np.concatenate([b["uv"][:n], b["extra"][:n, None]], 1), f32)
+        runs = {"record": orc.surface_units("record", inp["rays"], inp["diff"]), "record_plain": orc.surface_units("record", inp["rays"]),
+                "sample": orc.surface_units("sample", inp["rays"], inp["diff"], query)}
+        # eval directions: bsdf_inputs' wo in the hit's frame, every fourth case the oracle's own sample (of the run without differentials) where it is non-zero -- in world space
+        rec = runs["record_plain"][0]; sampled = orc.surface_units("sample", inp["rays"], None, query)[0]; wo = eval_wo(dict(wo=b["wo"][:n]), sampled)
+        took = (wo != b["wo"][:n]).any(1) & (rec[:, 19] != 0)                           # a sample of a bumped record lives in the perturbed frame
+        fs = np.where(took[:, None], rec[:, 25:28], rec[:, 45:48]); ft = np.where(took[:, None], rec[:, 28:31], rec[:, 48:51]); fn = np.where(took[:, None], rec[:, 31:34], rec[:, 42:45])
+        with np.errstate(invalid="ignore"): wo_world = np.ascontiguousarray(fs * wo[:, 0:1] + ft * wo[:, 1:2] + fn * wo[:, 2:3], f32)
+        wo_world[~np.isfinite(wo_world).all(1)] = (0.0, 1.0, 0.0)
+        runs["eval"] = orc.surface_units("eval", inp["rays"], None, wo_world)
+        _SURF_REF[name] = dict(sc=sc, inp=inp, query=query, wo_world=wo_world, runs=runs)
+    return _SURF_REF[name]
+
+
+def hit_records(sc, record):
+    """per case of a mode-0 record [n, 51]: the material record at the head of the hit's chain (-1: a miss) -- from the primitive the oracle or the device reports"""
+    prim = record[:, 40].astype(np.int64); nt = len(sc.idx); miss = (record[:, 18:22] == 0).all(1) & (record[:, 37] == 0)
+    shape_bsdf = np.asarray([s["bsdf"] for s in sc.shapes] + [a["bsdf"] for a in sc.analytic], np.int64)
+    shape = np.where(prim < nt, sc.tri_shape[np.minimum(prim, nt - 1)].astype(np.int64), len(sc.shapes) + prim - nt)
+    return np.where(miss, -1, shape_bsdf[shape])
+
+
+def zero_normal_records(sc):
+    """records whose chain holds a normal map that is (0.5, 0.5, 0.5) everywhere: the perturbed normal is normalize(0)"""
+    out = set()
+    for m in range(len(sc.bsdfs)):
+        for r in chain(sc, m):
+            b = sc.bsdfs[r]
+            if b["type"] == 12:
+                t = sc.textures[b["texture"]]
+                if t["type"] == 2:
+                    w, h, off = (int(v) for v in sc.texture_levels[t["first_level"]])
+                    if (sc.texture_texels[off:off + w * h * 3] == f32(0.5)).all(): out.add(m)
+    return out
