@@ -51,9 +51,7 @@ __global__ __launch_bounds__(WG) void k_ao(DScene sc, RenderConst rc, AoConst ac
                 if (AN) { const float4 ro = qat(q.rayO[0], slot); ro3 = V(ro.x, ro.y, ro.z); }
                 const int inst = (AN && q.hitInst) ? qat(q.hitInst, slot) : -1;
                 Hit h;
-                if (AN && inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], ro3, d, hr.x, prim, hr.y, hr.z, h);
-                else if (AN && prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], ro3, d, hr.x, hr.y, hr.z, h);
-                else fillHit<SMALL, AN>(sc, tb, d, hr.x, prim, hr.y, hr.z, h);
+                fillHitAny<SMALL, AN>(sc, tb, inst, ro3, d, hr.x, hr.y, hr.z, prim, h);
                 float sx, sy; directSample2D(sc, rc, m32, q, bd, pid, s0.y, s0.z, ac.n, ac.array, ac.own_dim, ac.pass, sx, sy);
                 const v3 wo = toWorld(h, cosHemisphere(sx, sy));      // its.toWorld(squareToCosineHemisphere(sample)): the shading frame, no flip, no normal test (:115)
                 ++shadowRays;

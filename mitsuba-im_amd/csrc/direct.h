@@ -9,6 +9,7 @@
 // has the reference's order: Le, emitter terms 0 .. N-1, BSDF terms 0 .. M-1 (direct.cpp:167, :241, :305).
 #pragma once
 #include "kernels_common.h"
+#include "surface.h"
 #include "direct_const.h"
 
 // (px, py, sample index) of a path, as k_generate derived them from the path id
@@ -47,23 +48,7 @@ __global__ __launch_bounds__(WG) void k_direct(DScene sc, RenderConst rc, Direct
     const SobolTabLds m32{(lds_u32_ptr) s_nib, rc.nib_count, rc.sobol_scramble};
     const uint32_t nibWords = rc.sampler == 1 ? rc.nib_dims * rc.nib_count * 16u : 4u;
     if (rc.sampler == 1) { for (uint32_t i = tid; i < nibWords; i += WG) s_nib[i] = rc.sobol_nib[i]; }
-    Tabs<SMALL> tb;
-    if (SMALL) {      // scene tables staged in LDS, the layout of k_shade
-        uint32_t *base = s_dyn + ((nibWords + 3u) & ~3u);
-        const uint32_t wShade = sc.n_tris * (4u * MI_SHADE_WORDS), wMat = sc.n_materials * 16u, wEm = sc.n_emitters * 12u, wEc = (sc.n_emitters + 1u + 3u) & ~3u, wAc = sc.area_cdf_len;
-        uint32_t *pS = base, *pM = pS + wShade, *pE = pM + wMat, *pEc = pE + wEm, *pAc = pEc + wEc;
-        const uint32_t *gS = (const uint32_t *) sc.shade, *gM = (const uint32_t *) sc.materials, *gE = (const uint32_t *) sc.emitters, *gEc = (const uint32_t *) sc.emitter_cdf, *gAc = (const uint32_t *) sc.area_cdf;
-        for (uint32_t i = tid; i < wShade; i += WG) pS[i] = gS[i];
-        for (uint32_t i = tid; i < wMat; i += WG) pM[i] = gM[i];
-        for (uint32_t i = tid; i < wEm; i += WG) pE[i] = gE[i];
-        for (uint32_t i = tid; i < sc.n_emitters + 1u; i += WG) pEc[i] = gEc[i];
-        for (uint32_t i = tid; i < wAc; i += WG) pAc[i] = gAc[i];
-        tb.shade4 = (typename AS<SMALL>::p4) pS; tb.materials4 = (typename AS<SMALL>::p4) pM; tb.emitters4 = (typename AS<SMALL>::p4) pE;
-        tb.emitter_cdf = (typename AS<SMALL>::pf) pEc; tb.area_cdf = (typename AS<SMALL>::pf) pAc;
-    } else {
-        tb.shade4 = (typename AS<SMALL>::p4) sc.shade; tb.materials4 = (typename AS<SMALL>::p4) sc.materials; tb.emitters4 = (typename AS<SMALL>::p4) sc.emitters;
-        tb.emitter_cdf = (typename AS<SMALL>::pf) sc.emitter_cdf; tb.area_cdf = (typename AS<SMALL>::pf) sc.area_cdf;
-    }
+    Tabs<SMALL> tb; stageTables<SMALL, WG>(sc, s_dyn + ((nibWords + 3u) & ~3u), tid, tb);      // scene tables staged in LDS, the layout of k_shade
     unsigned long long shadowRays = 0;
     __syncthreads();                                         // tables staged
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -97,39 +82,16 @@ __global__ __launch_bounds__(WG) void k_direct(DScene sc, RenderConst rc, Direct
                 if (AN || TEX) { const float4 ro = qat(q.rayO[0], slot); ro3 = V(ro.x, ro.y, ro.z); }
                 const int inst = (AN && q.hitInst) ? qat(q.hitInst, slot) : -1;
                 Hit h;
-                if (AN && inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], ro3, d, hr.x, prim, hr.y, hr.z, h);
-                else if (AN && prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], ro3, d, hr.x, hr.y, hr.z, h);
-                else fillHit<SMALL, AN>(sc, tb, d, hr.x, prim, hr.y, hr.z, h);
+                fillHitAny<SMALL, AN>(sc, tb, inst, ro3, d, hr.x, hr.y, hr.z, prim, h);
                 if (first && h.emitter >= 0 && !rc.hide_emitters) {              // direct.cpp:166-167
                     const v3 le = emitterEval(tb, h.emitter, h.ns, -d);
                     float4 a = qat(q.acc, pid); a.x += le.x; a.y += le.y; a.z += le.z; qat(q.acc, pid) = a;
                 }
                 if (rc.strict_normals && dot(d, h.ng) * h.wi.z >= 0) break;        // :175-187
                 if (!BS && (dc.n_em == 0u || (h.flags & 4u))) break;                // no emitter sub-samples; bsdf->getType() & BSDF::ESmooth (:217) -- the 2-D sample was requested before the test (:210-214)
-                MaterialD bsdf = loadMaterial(tb, h.material);
-                auto applyTexture = [&](MaterialD &mm) {
-                if (TEX) {                                                       // a textured parameter, as in k_shade: the camera hit takes the filtered lookup (its.getBSDF(ray) -> computePartials)
-                    const uint32_t tex = (mm.flags >> 8) & 0xFFFFu;
-                    if (tex) {
-                        const TextureD &tx = sc.textures[tex - 1]; v3 c;
-                        float huvx = h.uvx, huvy = h.uvy;
-                        const bool onAnalytic = AN && inst < 0 && prim >= sc.n_tris;
-                        if (onAnalytic) { v3 du, dv; analyticUV(sc.analytic[prim - sc.n_tris], hr.y, hr.z, ro3 + d * hr.x, huvx, huvy, du, dv); }
-                        if (tx.type == 2u) {
-                            const float uvx = huvx * tx.uscale + tx.uoffset, uvy = huvy * tx.vscale + tx.voffset;
-                            v3 dpdu, dpdv; float tu_, tv_;
-                            surfaceTangents<SMALL>(sc, tb, h, prim, inst, hr.y, hr.z, ro3 + d * hr.x, tu_, tv_, dpdu, dpdv);
-                            const float2 sp = qat(q.pos, pid); v3 rxd, ryd; sensorDifferentials(sc, rc, m32, s0.y, s0.z, sp.x, sp.y, d, rxd, ryd);
-                            float pa[4]; computePartials(h.p, h.ng, dpdu, dpdv, ro3, rxd, ryd, pa);
-                            c = mipEval(sc, tx, uvx, uvy, pa[0] * tx.uscale, pa[1] * tx.vscale, pa[2] * tx.uscale, pa[3] * tx.vscale);
-                        } else c = textureEval(tx, huvx, huvy);
-                        mm.reflectance[0] = c.x; mm.reflectance[1] = c.y; mm.reflectance[2] = c.z;
-                    }
-                }
-                };
-                applyTexture(bsdf);
-                v3 opac = V(1, 1, 1); bool masked = false;
-                if (RC && bsdf.type == MI_BSDF_T_MASK) { opac = ld3(bsdf.reflectance); masked = true; bsdf = loadMaterial(tb, (int) bsdf.distr); applyTexture(bsdf); }   // mask.cpp: opacity in front of the nested record
+                // the surface step (surface.h): every pass resolves the camera hit again, so the textured parameters always take the filtered lookup (its.getBSDF(ray) -> computePartials)
+                auto diffs = [&](v3 &rxd, v3 &ryd) { const float2 sp = qat(q.pos, pid); sensorDifferentials(sc, rc, m32, s0.y, s0.z, sp.x, sp.y, d, rxd, ryd); };
+                const SurfaceBsdf sf = resolveSurface<SMALL, AN, TEX, RC, false, false, false>(sc, tb, h, prim, inst, hr, ro3, d, true, diffs);
                 const v3 refN = (h.flags & 2u) ? V(0, 0, 0) : h.ns;               // records.inl:160-164
                 if (!BS) {
                     // emitter sub-sample (direct.cpp:220-244); visibility is deferred to the shadow queue
@@ -138,11 +100,11 @@ __global__ __launch_bounds__(WG) void k_direct(DScene sc, RenderConst rc, Direct
                     if (dr.pdf == 0) break;
                     ++shadowRays;                                                // scene.cpp:871-875: a shadow ray is cast whenever pdf != 0
                     const v3 wo = toLocal(h, dr.d);
-                    v3 bsdfVal = ctEval<RC, false>(sc, tb, -1, bsdf, h.wi, wo);
-                    if (RC && masked) bsdfVal = bsdfVal * opac;                  // mask.cpp:124-127
+                    v3 bsdfVal = ctEval<RC, false>(sc, tb, -1, sf.bsdf, h.wi, wo);
+                    if (RC && sf.masked) bsdfVal = bsdfVal * sf.opac;                  // mask.cpp:124-127
                     if (isZero(value) || isZero(bsdfVal) || (rc.strict_normals && !(dot(h.ng, dr.d) * wo.z > 0))) break;
-                    float bp = dr.delta ? 0.0f : ctPdf<RC, false>(sc, tb, -1, bsdf, h.wi, wo);      // emitter->isOnSurface() (:235)
-                    if (RC && masked) bp *= luminance3(opac);                    // mask.cpp:141-146
+                    float bp = dr.delta ? 0.0f : ctPdf<RC, false>(sc, tb, -1, sf.bsdf, h.wi, wo);      // emitter->isOnSurface() (:235)
+                    if (RC && sf.masked) bp *= luminance3(sf.opac);                    // mask.cpp:141-146
                     const float weight = miWeight(dr.pdf * dc.frac_lum, bp * dc.frac_bsdf) * dc.weight_lum;      // :238-239
                     const v3 c = (value * bsdfVal) * weight;                     // :241
                     want = true;
@@ -156,16 +118,13 @@ __global__ __launch_bounds__(WG) void k_direct(DScene sc, RenderConst rc, Direct
                     float sx, sy; directSample2D(sc, rc, m32, q, bd, pid, s0.y, s0.z, dc.n_bs, dc.bs_array, dc.bs_dim, dc.pass, sx, sy);
                     float bPdf = 0, bEta = 1; v3 woL = V(0, 0, 0); bool sampledDelta, sampledNull; v3 bw;
                     bool passThrough = false;                                    // mask.cpp:196-208
-                    if (RC && masked) { const float prob = luminance3(opac); if (sx < prob) sx /= prob; else passThrough = true; }
-                    if (RC && passThrough) {
-                        const float p = 1 - luminance3(opac);
-                        woL = V(-h.wi.x, -h.wi.y, -h.wi.z); bPdf = p; sampledDelta = true; sampledNull = true;
-                        bw = V((1.0f - opac.x) / p, (1.0f - opac.y) / p, (1.0f - opac.z) / p);
-                    } else {
+                    if (RC && sf.masked) passThrough = maskChooseLobe(sf.opac, sx);
+                    if (RC && passThrough) bw = maskPassThrough(h, sf.opac, woL, bPdf, sampledDelta, sampledNull);
+                    else {
                         // bRec.sampler->next1D() inside BSDF::sample (EUsesSampler): the sample's RUNNING dimension, one draw after another over the sub-samples (sobol.cpp:218-228)
                         auto drawExtra = [&]() { if (rc.sampler == 1 && ss.dim >= 5u && ss.dim < dc.array_end) ss.dim = dc.array_end; return next1D(ss, rc.sampler, m32); };
-                        bw = ctSample<RC, false>(sc, tb, -1, bsdf, h.wi, sx, sy, drawExtra, woL, bPdf, bEta, sampledDelta, sampledNull);
-                        if (RC && masked) { const float prob = luminance3(opac); bw = V(bw.x * opac.x / prob, bw.y * opac.y / prob, bw.z * opac.z / prob); bPdf *= prob; }
+                        bw = ctSample<RC, false>(sc, tb, -1, sf.bsdf, h.wi, sx, sy, drawExtra, woL, bPdf, bEta, sampledDelta, sampledNull);
+                        if (RC && sf.masked) { const float prob = luminance3(sf.opac); bw = V(bw.x * sf.opac.x / prob, bw.y * sf.opac.y / prob, bw.z * sf.opac.z / prob); bPdf *= prob; }
                     }
                     if (ss.dim != dim0) qat(q.st0[0], slot) = make_uint4(s0.x, s0.y, s0.z, (s0.w & ~0xFFu) | (ss.dim & 0xFFu));      // the running dimension of the next sub-sample
                     const v3 wo = toWorld(h, woL);

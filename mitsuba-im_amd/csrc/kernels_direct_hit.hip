@@ -6,7 +6,7 @@
 // through fillDirectSamplingRecord (:286-293), skipped under hideEmitters when the sampled component was ENull.  One thread per record, workgroups walk segments.
 template <bool ENV, bool AN>
 __global__ __launch_bounds__(WG) void k_direct_hit(DScene sc, RenderConst rc, DirectConst dc, Queues q) {
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     for (uint32_t seg = blockIdx.x; seg < q.n_seg; seg += gridDim.x) {
         const uint32_t n = q.count[1][seg]; const uint32_t segBase = seg * q.cap;
         for (uint32_t i = threadIdx.x; i < n; i += WG) {
@@ -31,9 +31,7 @@ __global__ __launch_bounds__(WG) void k_direct_hit(DScene sc, RenderConst rc, Di
                 if (AN) { const float4 ro = qat(q.rayO[1], slot); ro3 = V(ro.x, ro.y, ro.z); }
                 const int inst = (AN && q.hitInst) ? qat(q.hitInst, slot) : -1;
                 Hit h;
-                if (AN && inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], ro3, d, hr.x, prim, hr.y, hr.z, h);
-                else if (AN && prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], ro3, d, hr.x, hr.y, hr.z, h);
-                else fillHit<false, AN>(sc, tb, d, hr.x, prim, hr.y, hr.z, h);
+                fillHitAny<false, AN>(sc, tb, inst, ro3, d, hr.x, hr.y, hr.z, prim, h);
                 if (h.emitter < 0) continue;                                   // :279-280
                 value = emitterEval(tb, h.emitter, h.ns, -d);
                 lumPdf = sampledDelta ? 0.0f : pdfEmitterDirect<AN>(sc, tb, h.emitter, ro3, d, h.ns, h.dist, facingRef);

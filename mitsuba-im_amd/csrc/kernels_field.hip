@@ -6,6 +6,7 @@
 // At depth 1 of a batch the queue slot of a path IS its path id (k_generate writes slot = pid), so between the first extend launch and the first shade launch path
 // `pid` is fully described by q.hit[pid], q.rayO[0][pid] / q.rayD[0][pid], q.pos[pid] and (scenes with instances) q.hitInst[pid]: no per-path field buffer exists.
 #include "kernels_common.h"
+#include "surface.h"
 #include "fields.h"
 
 // The unfiltered lookup of Texture2D::eval(uv) (src/librender/texture.cpp:112-121): `field` hands the BSDF an intersection without UV partials, which is the lookup
@@ -62,11 +63,9 @@ DEV void fieldEval(const DScene &sc, const FieldArgs &fa, const Queues &q, uint6
     const float4 ro = q.rayO[0][pid], rd = q.rayD[0][pid];
     const v3 o = V(ro.x, ro.y, ro.z), d = V(rd.x, rd.y, rd.z); const float t = hr.x, u = hr.y, v = hr.z;
     const int inst = (sc.n_instances && q.hitInst) ? q.hitInst[pid] : -1;
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     Hit h; const bool analytic = inst < 0 && prim >= sc.n_tris;
-    if (inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], o, d, t, prim, u, v, h);
-    else if (analytic) fillHitAnalytic(sc.analytic[prim - sc.n_tris], o, d, t, u, v, h);
-    else fillHit<false, true>(sc, tb, d, t, prim, u, v, h);
+    fillHitAny<false, true>(sc, tb, inst, o, d, t, u, v, prim, h);      // (past the instance test, prim >= sc.n_tris is `analytic`)
     if (analytic) { v3 du, dv; analyticUV(sc.analytic[prim - sc.n_tris], u, v, o + d * t, h.uvx, h.uvy, du, dv); }
     v3 rel = V(0, 0, 0), albedo = V(0, 0, 0); float shapeIndex = -1.0f, primIndex = 0.0f;
     if (fa.needs & (1u << MI_FIELD_REL_POSITION)) rel = xfPoint(fa.w2c, h.p);

@@ -1,5 +1,6 @@
 // kernels_trace.hip -- extend (closest hit) and shadow (any hit) stages, unit-level intersection entry point (see kernels_common.h)
 #include "kernels_common.h"
+#include "surface.h"
 #include <algorithm>
 #include "trace.h"
 #include "trace_fused.h"
@@ -121,11 +122,8 @@ __global__ __launch_bounds__(WG) void k_ray_intersect(DScene sc, const float *ra
     }
     mi_intersection rec; memset(&rec, 0, sizeof(rec)); rec.valid = hit ? 1u : 0u; rec.prim = 0xFFFFFFFFu; rec.instance = -1; rec.material = -1; rec.emitter = -1;
     if (hit) {
-        Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
-        Hit h;
-        if (inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], o, d, t, prim, u, v, h);
-        else if (prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], o, d, t, u, v, h);
-        else fillHit<false, true>(sc, tb, d, t, prim, u, v, h);
+        const Tabs<false> tb = globalTabs(sc);
+        Hit h; fillHitAny<false, true>(sc, tb, inst, o, d, t, u, v, prim, h);
         if (inst < 0 && prim >= sc.n_tris) { v3 du, dv; analyticUV(sc.analytic[prim - sc.n_tris], u, v, o + d * t, h.uvx, h.uvy, du, dv); }
         rec.t = t; rec.p[0] = h.p.x; rec.p[1] = h.p.y; rec.p[2] = h.p.z; rec.ng[0] = h.ng.x; rec.ng[1] = h.ng.y; rec.ng[2] = h.ng.z;
         rec.ns[0] = h.ns.x; rec.ns[1] = h.ns.y; rec.ns[2] = h.ns.z; rec.s[0] = h.s.x; rec.s[1] = h.s.y; rec.s[2] = h.s.z; rec.tt[0] = h.t.x; rec.tt[1] = h.t.y; rec.tt[2] = h.t.z;

@@ -4,6 +4,7 @@
 // oracle's orc_bsdf_sample_ex / orc_bsdf_eval / orc_texture_eval; and the surface step between a hit and the BSDF query on caller-supplied hits (mi_debug_surface against
 // orc_surface_units).  Nothing here restates a routine: the kernels call what the shade stage calls.
 #include "kernels_common.h"
+#include "surface.h"
 
 // in9 = wi xyz, wo xyz, u, v, extra.  The record is resolved as the shade stage resolves an untextured hit (shade.h: a coating / roughcoating record becomes `coat`,
 // its nested record `bsdf`; mask, bumpmap, normalmap and textured records are refused on the host), then queried through ctSample / ctEval / ctPdf<true, true, false>:
@@ -12,7 +13,7 @@
 __global__ __launch_bounds__(WG) void k_debug_bsdf(DScene sc, int material, int mode, const float *in, uint64_t n, float *out) {
     const uint64_t i = (uint64_t) blockIdx.x * WG + threadIdx.x;
     if (i >= n) return;
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     const float *p = in + i * 9; float *o = out + i * 12;
     const v3 wi = V(p[0], p[1], p[2]), woIn = V(p[3], p[4], p[5]);
     int coat = -1; MaterialD bsdf = loadMaterial(tb, material);
@@ -53,7 +54,7 @@ template <bool RAW>
 __global__ __launch_bounds__(WG) void k_debug_emitter_sample(DScene sc, const float *in, uint64_t n, float *out) {
     const uint64_t i = (uint64_t) blockIdx.x * WG + threadIdx.x;
     if (i >= n) return;
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     const float *p = in + i * 8; float *o = out + i * 17;
     Direct dr; dr.p = V(0, 0, 0); dr.n = V(0, 0, 0); dr.d = V(0, 0, 0); dr.dist = 0.0f; dr.pdf = 0.0f; dr.em_pdf = 0.0f; dr.emitter = 0; dr.delta = false;
     const v3 value = sampleEmitterDirect<true, true, false, RAW>(sc, tb, V(p[0], p[1], p[2]), V(p[3], p[4], p[5]), p[6], p[7], dr);
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(WG) void k_debug_emitter_sample(DScene sc, const fl
 __global__ __launch_bounds__(WG) void k_debug_emitter_eval(DScene sc, int emitter, int kind, const float *in, uint64_t n, float *out) {
     const uint64_t i = (uint64_t) blockIdx.x * WG + threadIdx.x;
     if (i >= n) return;
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     const float *p = in + i * 11; float *o = out + i * 8;
     const v3 ref = V(p[0], p[1], p[2]), d = V(p[3], p[4], p[5]), nrm = V(p[6], p[7], p[8]);
 #pragma unroll
@@ -112,8 +113,9 @@ __global__ __launch_bounds__(WG) void k_debug_medium(DScene sc, uint32_t medium,
 // The surface step between a hit and the BSDF query, for one caller-supplied hit per thread: rays8 = o, mint, d, maxt; hits4 = t, u, v, prim as mi_debug_intersect_inst
 // returns them (prim < 0: a miss, which writes zeros), insts = its instance indices (NULL: none); diffs6 = the two differential directions rxd, ryd of a camera ray
 // (NULL: a later bounce -- level-0 lookups, no partials); query3 = mode 1: the 2-D sample and the extra sampler value, mode 2: a WORLD direction.  The widest
-// instantiation the stages have: fillHit<false, true>, tables in global memory, ctSample / ctEval / ctPdf<true, true>.  The kernel calls routines and nothing else; its
-// unwrap sequence is that of shade.h:150-189 (texture -> mask -> bump / normal map -> coating, each followed by applyTexture), line by line.
+// instantiation the stages have: fillHit<false, true>, tables in global memory, ctSample / ctEval / ctPdf<true, true>.  The kernel calls routines and nothing else: the
+// unwrap sequence (texture -> mask -> bump / normal map -> coating, each followed by the textured load) is resolveSurface, and the query frame queryWi / queryFrame, of
+// surface.h -- the routines the shade, direct and volumetric stages run, with every gate on.
 // mode 0 (record): out51 = uv as the lookups use it 2, dpdu 3, dpdv 3, partials 4 (zero without differentials), opacity 3 (zero without a mask), the value loaded into the
 //   first textured parameter on the chain 3, masked, bumped, coating record (-1: none), leaf record, the leaf's reflectance after applyTexture 3, ps 3, pt 3, pn 3 (zero when
 //   not bumped), wi in the frame the query uses 3, the hit as given: t, u, v, prim, instance, and its shading frame ns 3, s 3, t 3
@@ -122,79 +124,46 @@ __global__ __launch_bounds__(WG) void k_debug_medium(DScene sc, uint32_t medium,
 __global__ __launch_bounds__(WG) void k_debug_surface(DScene sc, int mode, const float *rays, const float *hits, const int *insts, const float *diffs, const float *query, uint64_t n, float *out) {
     const uint64_t i = (uint64_t) blockIdx.x * WG + threadIdx.x;
     if (i >= n) return;
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     const int per = mode == 0 ? 51 : mode == 1 ? 11 : 4; float *o = out + i * per;
     for (int k = 0; k < per; ++k) o[k] = 0.0f;
     const float *r = rays + i * 8; const v3 ro3 = V(r[0], r[1], r[2]), d = V(r[4], r[5], r[6]);
     const float4 hr = make_float4(hits[4 * i], hits[4 * i + 1], hits[4 * i + 2], hits[4 * i + 3]);
     if (!(hr.w >= 0)) return;
     const uint32_t prim = (uint32_t) hr.w; const int inst = insts ? insts[i] : -1;
-    Hit h;
-    if (inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], ro3, d, hr.x, prim, hr.y, hr.z, h);
-    else if (prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], ro3, d, hr.x, hr.y, hr.z, h);
-    else fillHit<false, true>(sc, tb, d, hr.x, prim, hr.y, hr.z, h);
+    Hit h; fillHitAny<false, true>(sc, tb, inst, ro3, d, hr.x, hr.y, hr.z, prim, h);
     if (h.material < 0 || (uint32_t) h.material >= sc.n_materials) return;
     // the record's own uv, tangents and partials
     float ruvx = h.uvx, ruvy = h.uvy; v3 rdpdu, rdpdv; surfaceTangents<false>(sc, tb, h, prim, inst, hr.y, hr.z, ro3 + d * hr.x, ruvx, ruvy, rdpdu, rdpdv);
     v3 rxd = V(0, 0, 0), ryd = V(0, 0, 0); float rpa[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
     if (diffs) { rxd = V(diffs[6 * i], diffs[6 * i + 1], diffs[6 * i + 2]); ryd = V(diffs[6 * i + 3], diffs[6 * i + 4], diffs[6 * i + 5]); computePartials(h.p, h.ng, rdpdu, rdpdv, ro3, rxd, ryd, rpa); }
-    // ---- shade.h:150-189
-    int curMat = h.material, coat = -1; MaterialD bsdf = loadMaterial(tb, curMat);
-    v3 opac = V(0, 0, 0), firstValue = V(0, 0, 0), bps = V(0, 0, 0), bpt = V(0, 0, 0), bpn = V(0, 0, 0); bool masked = false, bumped = false, haveFirst = false;
-    auto applyTexture = [&](MaterialD &mm) {                                 // shade.h:151-175
-        const uint32_t tex = (mm.type == MI_BSDF_T_BUMPMAP || mm.type == MI_BSDF_T_NORMALMAP) ? 0u : (mm.flags >> 8) & 0xFFFFu;
-        if (tex) {
-            const TextureD &tx = sc.textures[tex - 1]; v3 c;
-            float huvx = h.uvx, huvy = h.uvy;
-            const bool onAnalytic = inst < 0 && prim >= sc.n_tris;
-            if (onAnalytic) { v3 du, dv; analyticUV(sc.analytic[prim - sc.n_tris], hr.y, hr.z, ro3 + d * hr.x, huvx, huvy, du, dv); }
-            if (tx.type == 2u) {
-                const float uvx = huvx * tx.uscale + tx.uoffset, uvy = huvy * tx.vscale + tx.voffset;
-                if (diffs) {                                                 // depth == 1: the camera ray carries differentials
-                    v3 dpdu, dpdv; float tu_, tv_;
-                    surfaceTangents<false>(sc, tb, h, prim, inst, hr.y, hr.z, ro3 + d * hr.x, tu_, tv_, dpdu, dpdv);
-                    float pa[4]; computePartials(h.p, h.ng, dpdu, dpdv, ro3, rxd, ryd, pa);
-                    c = mipEval(sc, tx, uvx, uvy, pa[0] * tx.uscale, pa[1] * tx.vscale, pa[2] * tx.uscale, pa[3] * tx.vscale);
-                } else c = tx.filter != 0u ? mipBilinear(sc, tx, 0, uvx, uvy) : mipBox(sc, tx, 0, uvx, uvy);
-            } else c = textureEval(tx, huvx, huvy);
-            mm.reflectance[0] = c.x; mm.reflectance[1] = c.y; mm.reflectance[2] = c.z;
-            if (!haveFirst) { firstValue = c; haveFirst = true; }
-        }
-    };
-    applyTexture(bsdf);                                                      // :176
-    if (bsdf.type == MI_BSDF_T_MASK) {                                       // :177-179
-        opac = ld3(bsdf.reflectance); masked = true; curMat = (int) bsdf.distr; bsdf = loadMaterial(tb, curMat); applyTexture(bsdf);
-    }
-    if (bsdf.type == MI_BSDF_T_BUMPMAP || bsdf.type == MI_BSDF_T_NORMALMAP) { // :180-188
-        float huvx = h.uvx, huvy = h.uvy; v3 dpdu, dpdv;
-        surfaceTangents<false>(sc, tb, h, prim, inst, hr.y, hr.z, ro3 + d * hr.x, huvx, huvy, dpdu, dpdv);
-        perturbFrame(sc, bsdf, h, huvx, huvy, dpdu, dpdv, bps, bpt, bpn); bumped = true;
-        curMat = (int) bsdf.distr; bsdf = loadMaterial(tb, curMat); applyTexture(bsdf);
-    }
-    if (bsdf.type == MI_BSDF_T_COATING || bsdf.type == MI_BSDF_T_ROUGHCOATING) { coat = curMat; curMat = (int) bsdf.distr; bsdf = loadMaterial(tb, curMat); applyTexture(bsdf); }      // :189
-    // ---- the query frame (shade.h:203-204, :247)
-    const v3 wiQ = bumped ? frameToLocal(bps, bpt, bpn, toWorld(h, h.wi)) : h.wi;
+    // ---- the surface step, every gate on; the differentials are the caller's, the first textured value is kept for the record
+    v3 firstValue = V(0, 0, 0); bool haveFirst = false;
+    const SurfaceBsdf sf = resolveSurface<false, true, true, true, true, true, true>(sc, tb, h, prim, inst, hr, ro3, d, diffs != nullptr, [&](v3 &a, v3 &b) { a = rxd; b = ryd; },
+                                                                                   [&](v3 c) { if (!haveFirst) { firstValue = c; haveFirst = true; } });
+    const v3 wiQ = queryWi<true>(h, sf);
     if (mode == 0) {
+        const v3 opac = sf.masked ? sf.opac : V(0, 0, 0);                    // (the stages' default opacity is 1; the record's is zero without a mask)
         o[0] = ruvx; o[1] = ruvy; o[2] = rdpdu.x; o[3] = rdpdu.y; o[4] = rdpdu.z; o[5] = rdpdv.x; o[6] = rdpdv.y; o[7] = rdpdv.z;
         o[8] = rpa[0]; o[9] = rpa[1]; o[10] = rpa[2]; o[11] = rpa[3];
         o[12] = opac.x; o[13] = opac.y; o[14] = opac.z; o[15] = firstValue.x; o[16] = firstValue.y; o[17] = firstValue.z;
-        o[18] = masked ? 1.0f : 0.0f; o[19] = bumped ? 1.0f : 0.0f; o[20] = (float) coat; o[21] = (float) curMat;
-        o[22] = bsdf.reflectance[0]; o[23] = bsdf.reflectance[1]; o[24] = bsdf.reflectance[2];
-        o[25] = bps.x; o[26] = bps.y; o[27] = bps.z; o[28] = bpt.x; o[29] = bpt.y; o[30] = bpt.z; o[31] = bpn.x; o[32] = bpn.y; o[33] = bpn.z;
+        o[18] = sf.masked ? 1.0f : 0.0f; o[19] = sf.bumped ? 1.0f : 0.0f; o[20] = (float) sf.coat; o[21] = (float) sf.leaf;
+        o[22] = sf.bsdf.reflectance[0]; o[23] = sf.bsdf.reflectance[1]; o[24] = sf.bsdf.reflectance[2];
+        o[25] = sf.ps.x; o[26] = sf.ps.y; o[27] = sf.ps.z; o[28] = sf.pt.x; o[29] = sf.pt.y; o[30] = sf.pt.z; o[31] = sf.pn.x; o[32] = sf.pn.y; o[33] = sf.pn.z;
         o[34] = wiQ.x; o[35] = wiQ.y; o[36] = wiQ.z; o[37] = hr.x; o[38] = hr.y; o[39] = hr.z; o[40] = hr.w; o[41] = (float) inst;
         o[42] = h.ns.x; o[43] = h.ns.y; o[44] = h.ns.z; o[45] = h.s.x; o[46] = h.s.y; o[47] = h.s.z; o[48] = h.t.x; o[49] = h.t.y; o[50] = h.t.z;
     } else if (mode == 1) {
         const float *p = query + 3 * i; const float extraValue = p[2]; bool drawn = false;
         auto drawExtra = [&]() { drawn = true; return extraValue; };
         v3 wo = V(0, 0, 0); float pdf = 0.0f, eta = 0.0f; bool delta = false, nullComp = false;
-        const v3 w = ctSample<true, true>(sc, tb, coat, bsdf, wiQ, p[0], p[1], drawExtra, wo, pdf, eta, delta, nullComp);
+        const v3 w = ctSample<true, true>(sc, tb, sf.coat, sf.bsdf, wiQ, p[0], p[1], drawExtra, wo, pdf, eta, delta, nullComp);
         o[0] = w.x; o[1] = w.y; o[2] = w.z; o[3] = pdf; o[4] = wo.x; o[5] = wo.y; o[6] = wo.z; o[7] = eta;
         o[8] = delta ? 1.0f : 0.0f; o[9] = nullComp ? 1.0f : 0.0f; o[10] = drawn ? 1.0f : 0.0f;
     } else {
         const float *p = query + 3 * i; const v3 wo = toLocal(h, V(p[0], p[1], p[2]));
-        const v3 woQ = bumped ? frameToLocal(bps, bpt, bpn, toWorld(h, wo)) : wo;
-        const v3 e = ctEval<true, true>(sc, tb, coat, bsdf, wiQ, woQ);
-        o[0] = e.x; o[1] = e.y; o[2] = e.z; o[3] = ctPdf<true, true>(sc, tb, coat, bsdf, wiQ, woQ);
+        v3 wiE, woQ; bool rejected; queryFrame<true>(h, sf, wo, wiE, woQ, rejected);      // (the sign rejection is applied by the stages after this query, not here)
+        const v3 e = ctEval<true, true>(sc, tb, sf.coat, sf.bsdf, wiE, woQ);
+        o[0] = e.x; o[1] = e.y; o[2] = e.z; o[3] = ctPdf<true, true>(sc, tb, sf.coat, sf.bsdf, wiE, woQ);
     }
 }
 

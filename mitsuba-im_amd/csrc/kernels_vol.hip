@@ -12,6 +12,7 @@
 // Built for: meshes + analytic shapes (media on scene-level shapes), every plain BSDF incl. `null`, textures, area / point / spot / directional emitters.  Refused at
 // mi_render_create: adapters (mixturebsdf / bumpmap / normalmap) that nest a `null` / `thindielectric`.  A `mask` attenuates the walks by 1 - opacity (surfaceNullEval).
 #include "kernels_common.h"
+#include "surface.h"
 #include "trace.h"
 
 // EnvironmentMap::evalEnvironment for a ray that carries differentials (the sensor ray; envmap.cpp:398-411 -> TMIPMap::eval over the map's pyramid), as k_env_primary
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(WG) void k_shade_vol(DScene sc, RenderConst rc, Que
     const int nb = buf ^ 1;
     const SobolTabLds m32{(lds_u32_ptr) s_nib, rc.nib_count, rc.sobol_scramble};
     if (rc.sampler == 1) { const uint32_t nibWords = rc.nib_dims * rc.nib_count * 16u; for (uint32_t i = tid; i < nibWords; i += WG) s_nib[i] = rc.sobol_nib[i]; }
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     unsigned long long pathLen = 0;
     __syncthreads();
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -78,9 +79,7 @@ __global__ __launch_bounds__(WG) void k_shade_vol(DScene sc, RenderConst rc, Que
                     const uint32_t pmA = sc.prim_media ? sc.prim_media[prim] : 0u;
                     if (pmA) {
                         Hit ha; const int instA = q.hitInst ? q.hitInst[slot] : -1;
-                        if (instA >= 0) fillHitInstanced(sc, tb, sc.instances[instA], o, d, hr.x, prim, hr.y, hr.z, ha);
-                        else if (prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], o, d, hr.x, hr.y, hr.z, ha);
-                        else fillHit<false, true>(sc, tb, d, hr.x, prim, hr.y, hr.z, ha);
+                        fillHitAny<false, true>(sc, tb, instA, o, d, hr.x, hr.y, hr.z, prim, ha);
                         const v3 p2 = o + d * rc.alpha_dist; const int mA = targetMedium(pmA, ha.ng, d);
                         wantAlpha = true;
                         alO = make_float4(ha.p.x, ha.p.y, ha.p.z, __uint_as_float((uint32_t) (mA + 1) | (0x7FFFu << 8) | (1u << 24) | (1u << 29)));
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(WG) void k_shade_vol(DScene sc, RenderConst rc, Que
                 }
                 const int interactions = rc.max_depth - depth - 1;
                 // ---- the interaction: a point in the medium, or the surface at the end of the segment
-                bool nee = false; v3 nref = V(0, 0, 0), nrefN = V(0, 0, 0); Hit h; MaterialD bsdf; uint32_t pm = 0; bool bumped = false, masked = false; v3 bps = V(0, 0, 0), bpt = V(0, 0, 0), bpn = V(0, 0, 0), opac = V(1, 1, 1);
+                bool nee = false; v3 nref = V(0, 0, 0), nrefN = V(0, 0, 0); Hit h; SurfaceBsdf sf; uint32_t pm = 0;
                 if (mediumEvent) {
                     { const float r = 1.0f / mRec.pdfSuccess; T = T * ((ld3(md.sigma_s) * mRec.transmittance) * r); }
                     nee = others; nref = mRec.p;                             // EDirectMediumRadiance
@@ -104,41 +103,12 @@ __global__ __launch_bounds__(WG) void k_shade_vol(DScene sc, RenderConst rc, Que
                         pathLen += (unsigned) depth; break;
                     }
                     const int inst = q.hitInst ? q.hitInst[slot] : -1;
-                    if (inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], o, d, hr.x, prim, hr.y, hr.z, h);
-                    else if (prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], o, d, hr.x, hr.y, hr.z, h);
-                    else fillHit<false, true>(sc, tb, d, hr.x, prim, hr.y, hr.z, h);
+                    fillHitAny<false, true>(sc, tb, inst, o, d, hr.x, hr.y, hr.z, prim, h);
                     if (h.emitter >= 0 && emitted && (!rc.hide_emitters || scattered)) { add = T * emitterEval(tb, h.emitter, h.ns, -d); haveAdd = true; }
                     if (rc.strict_normals && (-dot(h.ng, d)) * h.wi.z < 0) { pathLen += (unsigned) depth; break; }
-                    bsdf = loadMaterial(tb, h.material);
-                    auto applyTexture = [&](MaterialD &mm) {
-                    if (TEX) {                                               // a textured reflectance (shade.h applyTexture); only the sensor ray carries differentials
-                        const uint32_t tex = (WRAP && (mm.type == MI_BSDF_T_BUMPMAP || mm.type == MI_BSDF_T_NORMALMAP)) ? 0u : (mm.flags >> 8) & 0xFFFFu;      // (an adapter's texture is its displacement / normal map)
-                        if (tex) {
-                            const TextureD &tx = sc.textures[tex - 1]; v3 c; float huvx = h.uvx, huvy = h.uvy;
-                            const bool onAnalytic = inst < 0 && prim >= sc.n_tris;
-                            if (onAnalytic) { v3 du, dv; analyticUV(sc.analytic[prim - sc.n_tris], hr.y, hr.z, o + d * hr.x, huvx, huvy, du, dv); }
-                            if (tx.type == 2u) {
-                                const float uvx = huvx * tx.uscale + tx.uoffset, uvy = huvy * tx.vscale + tx.voffset;
-                                if (depth == 1) {
-                                    v3 dpdu, dpdv; float tu_, tv_;
-                                    surfaceTangents<false>(sc, tb, h, prim, inst, hr.y, hr.z, o + d * hr.x, tu_, tv_, dpdu, dpdv);
-                                    const float2 sp = q.pos[pid]; v3 rxd, ryd; sensorDifferentials(sc, rc, m32, ss.a, ss.b, sp.x, sp.y, d, rxd, ryd);
-                                    float pa[4]; computePartials(h.p, h.ng, dpdu, dpdv, o, rxd, ryd, pa);
-                                    c = mipEval(sc, tx, uvx, uvy, pa[0] * tx.uscale, pa[1] * tx.vscale, pa[2] * tx.uscale, pa[3] * tx.vscale);
-                                } else c = tx.filter != 0u ? mipBilinear(sc, tx, 0, uvx, uvy) : mipBox(sc, tx, 0, uvx, uvy);
-                            } else c = textureEval(tx, huvx, huvy);
-                            mm.reflectance[0] = c.x; mm.reflectance[1] = c.y; mm.reflectance[2] = c.z;
-                        }
-                    }
-                    };
-                    applyTexture(bsdf);
-                    if (bsdf.type == MI_BSDF_T_MASK) { opac = ld3(bsdf.reflectance); masked = true; bsdf = loadMaterial(tb, (int) bsdf.distr); applyTexture(bsdf); }      // mask.cpp (shade.h)
-                    if (WRAP && TEX && (bsdf.type == MI_BSDF_T_BUMPMAP || bsdf.type == MI_BSDF_T_NORMALMAP)) {      // bumpmap.cpp / normalmap.cpp: getFrame(its), then the nested record (shade.h)
-                        float huvx = h.uvx, huvy = h.uvy; v3 dpdu, dpdv;
-                        surfaceTangents<false>(sc, tb, h, prim, inst, hr.y, hr.z, o + d * hr.x, huvx, huvy, dpdu, dpdv);
-                        perturbFrame(sc, bsdf, h, huvx, huvy, dpdu, dpdv, bps, bpt, bpn); bumped = true;
-                        bsdf = loadMaterial(tb, (int) bsdf.distr); applyTexture(bsdf);
-                    }
+                    // the surface step (surface.h): material, textured reflectance (only the sensor ray carries differentials), mask, bump / normal map
+                    auto diffs = [&](v3 &rxd, v3 &ryd) { const float2 sp = q.pos[pid]; sensorDifferentials(sc, rc, m32, ss.a, ss.b, sp.x, sp.y, d, rxd, ryd); };
+                    sf = resolveSurface<false, true, TEX, true, WRAP && TEX, false, WRAP>(sc, tb, h, prim, inst, hr, o, d, depth == 1, diffs);
                     pm = sc.prim_media ? sc.prim_media[prim] : 0u;           // (interior + 1) | (exterior + 1) << 16 of the shape that was hit; 0: not a medium transition
                     nee = others && !(h.flags & 4u); nref = h.p;            // EDirectSurfaceRadiance, BSDFs with a smooth component
                     if (!(h.flags & 2u)) nrefN = h.ns;                       // records.inl:160-164
@@ -152,10 +122,9 @@ __global__ __launch_bounds__(WG) void k_shade_vol(DScene sc, RenderConst rc, Que
                         if (mediumEvent) { const float ph = phaseEval(md, -d, dr.d); x = V(ph, ph, ph); }
                         else {
                             const v3 wo = toLocal(h, dr.d);
-                            v3 wiQ = h.wi, woQ = wo; bool rejected = false;
-                            if (WRAP && bumped) { wiQ = frameToLocal(bps, bpt, bpn, toWorld(h, h.wi)); woQ = frameToLocal(bps, bpt, bpn, toWorld(h, wo)); rejected = wo.z * woQ.z <= 0; }      // bumpmap.cpp:165-180
-                            x = (!rejected && (!rc.strict_normals || dot(h.ng, dr.d) * wo.z > 0)) ? mxEval<true, WRAP>(sc, tb, bsdf, wiQ, woQ) : V(0, 0, 0);
-                            if (masked) x = x * opac;                            // mask.cpp:117-118
+                            v3 wiQ, woQ; bool rejected; queryFrame<WRAP>(h, sf, wo, wiQ, woQ, rejected);      // bumpmap.cpp:165-180
+                            x = (!rejected && (!rc.strict_normals || dot(h.ng, dr.d) * wo.z > 0)) ? mxEval<true, WRAP>(sc, tb, sf.bsdf, wiQ, woQ) : V(0, 0, 0);
+                            if (sf.masked) x = x * sf.opac;                      // mask.cpp:117-118
                             if (pm) m2 = targetMedium(pm, h.ng, dr.d);      // scene.cpp:920-921
                             onSurface = 1u << 24;
                         }
@@ -178,20 +147,12 @@ __global__ __launch_bounds__(WG) void k_shade_vol(DScene sc, RenderConst rc, Que
                 float bPdf = 0, bEta = 1; v3 woL = V(0, 0, 0); bool sampledDelta, sampledNull;
                 float sx, sy; next2D(ss, rc.sampler, m32, sx, sy);
                 auto drawExtra = [&]() { return next1D(ss, rc.sampler, m32); };
-                if (bsdf.type == MI_BSDF_T_THINDIELECTRIC) bsdf.flags |= MI_THIN_SIGNED_COS;      // the pdf-less ThinDielectric::sample overload this integrator calls (pt_device.h)
-                v3 bw; bool passThrough = false; float invProb = 1.0f;      // mask.cpp:152-172, the overload WITHOUT a pdf: sample.x *= 1 / prob, result * opacity * (1 / prob)
-                if (masked) { const float prob = luminance3(opac); if (sx < prob) { invProb = 1.0f / prob; sx *= invProb; } else passThrough = true; }
-                if (passThrough) {
-                    const float p = 1 - luminance3(opac);
-                    woL = V(-h.wi.x, -h.wi.y, -h.wi.z); bEta = 1.0f; bPdf = p; sampledDelta = true; sampledNull = true;
-                    bw = V((1.0f - opac.x) / p, (1.0f - opac.y) / p, (1.0f - opac.z) / p);
-                } else
-                if (WRAP && bumped) {                                        // bumpmap.cpp:196-216
-                    const v3 wiQ = frameToLocal(bps, bpt, bpn, toWorld(h, h.wi)); v3 woQ = V(0, 0, 0);
-                    bw = mxSample<true, WRAP>(sc, tb, bsdf, wiQ, sx, sy, drawExtra, woQ, bPdf, bEta, sampledDelta, sampledNull);
-                    if (!isZero(bw)) { woL = toLocal(h, frameToWorld(bps, bpt, bpn, woQ)); if (woL.z * woQ.z <= 0) bw = V(0, 0, 0); }
-                } else bw = mxSample<true, WRAP>(sc, tb, bsdf, h.wi, sx, sy, drawExtra, woL, bPdf, bEta, sampledDelta, sampledNull);
-                if (masked && !passThrough) bw = V(bw.x * opac.x * invProb, bw.y * opac.y * invProb, bw.z * opac.z * invProb);
+                if (sf.bsdf.type == MI_BSDF_T_THINDIELECTRIC) sf.bsdf.flags |= MI_THIN_SIGNED_COS;      // the pdf-less ThinDielectric::sample overload this integrator calls (pt_device.h)
+                v3 bw; bool passThrough = false; float invProb = 1.0f;      // mask.cpp:152-172, the overload WITHOUT a pdf: sample.x *= 1 / prob, result * opacity * (1 / prob) -- not maskChooseLobe's division
+                if (sf.masked) { const float prob = luminance3(sf.opac); if (sx < prob) { invProb = 1.0f / prob; sx *= invProb; } else passThrough = true; }
+                if (passThrough) bw = maskPassThrough(h, sf.opac, woL, bPdf, sampledDelta, sampledNull);
+                else bw = sampleInQueryFrame<WRAP>(h, sf, [&](v3 wi, v3 &wo) __attribute__((always_inline)) { return mxSample<true, WRAP>(sc, tb, sf.bsdf, wi, sx, sy, drawExtra, wo, bPdf, bEta, sampledDelta, sampledNull); }, woL);      // bumpmap.cpp:196-216
+                if (sf.masked && !passThrough) bw = V(bw.x * sf.opac.x * invProb, bw.y * sf.opac.y * invProb, bw.z * sf.opac.z * invProb);
                 if (isZero(bw)) { pathLen += (unsigned) depth; break; }
                 // which radiance types the next iteration gathers (volpath_simple.cpp:236-257)
                 const bool rtOthers = (depth + 1 < rc.max_depth || rc.max_depth < 0) && others; bool rtEmitted = false; bool nullChain = (fl & VOL_NULLCHAIN) != 0;
@@ -233,7 +194,7 @@ template <bool WIDE, bool NX>      // NX: ENull lobes behind a wrapper (mask, mi
 __global__ __launch_bounds__(WG) void k_shadow_vol(DScene sc, Queues q) {
     __shared__ int s_stk[STACK_DEPTH * WG];
     const uint32_t tid = threadIdx.x;
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     unsigned long long rays = 0;
     for (uint32_t seg = blockIdx.x; seg < q.n_seg; seg += gridDim.x) {
     // two passes over the segment's records, a barrier in between: first the alpha walks (written from the back of the area), then the emitter-sampling records -- a

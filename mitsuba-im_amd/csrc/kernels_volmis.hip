@@ -11,6 +11,7 @@
 // State word st0.w: bits 0..7 dimension, 8..15 depth, 16 EEmittedRadiance, 17 the spawning sample was a Dirac delta, 18 the ray looks for an emitter, 19 scattered,
 // 20..27 medium + 1, 28 dot(d, refN) >= 0 at the spawning vertex, 29 skip the Russian roulette (the previous pass was a `null` pass-through); st2 = the sampling density.
 #include "kernels_common.h"
+#include "surface.h"
 #include "trace.h"
 
 // EnvironmentMap::evalEnvironment for a ray that carries differentials (the sensor ray; envmap.cpp:398-411 -> TMIPMap::eval over the map's pyramid), as k_env_primary
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(WG) void k_shade_volmis(DScene sc, RenderConst rc, 
     const int nb = buf ^ 1;
     const SobolTabLds m32{(lds_u32_ptr) s_nib, rc.nib_count, rc.sobol_scramble};
     if (rc.sampler == 1) { const uint32_t nibWords = rc.nib_dims * rc.nib_count * 16u; for (uint32_t i = tid; i < nibWords; i += WG) s_nib[i] = rc.sobol_nib[i]; }
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     unsigned long long pathLen = 0;
     __syncthreads();
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -71,9 +72,7 @@ __global__ __launch_bounds__(WG) void k_shade_volmis(DScene sc, RenderConst rc, 
             Hit h; bool haveHit = false; const int inst = (q.hitInst && prim != 0xFFFFFFFFu) ? q.hitInst[slot] : -1;
             auto fill = [&]() {
                 if (haveHit) return; haveHit = true;
-                if (inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], o, d, hr.x, prim, hr.y, hr.z, h);
-                else if (prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], o, d, hr.x, hr.y, hr.z, h);
-                else fillHit<false, true>(sc, tb, d, hr.x, prim, hr.y, hr.z, h);
+                fillHitAny<false, true>(sc, tb, inst, o, d, hr.x, hr.y, hr.z, prim, h);
             };
             do {
                 // ---- rayIntersectAndLookForEmitter, first intersection (volpath.cpp:370-431) for the ray the previous pass sampled
@@ -127,9 +126,7 @@ __global__ __launch_bounds__(WG) void k_shade_volmis(DScene sc, RenderConst rc, 
                     const uint32_t pmA = sc.prim_media ? sc.prim_media[prim] : 0u;
                     if (pmA) {
                         Hit ha; const int instA = q.hitInst ? q.hitInst[slot] : -1;
-                        if (instA >= 0) fillHitInstanced(sc, tb, sc.instances[instA], o, d, hr.x, prim, hr.y, hr.z, ha);
-                        else if (prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], o, d, hr.x, hr.y, hr.z, ha);
-                        else fillHit<false, true>(sc, tb, d, hr.x, prim, hr.y, hr.z, ha);
+                        fillHitAny<false, true>(sc, tb, instA, o, d, hr.x, hr.y, hr.z, prim, ha);
                         const v3 p2 = o + d * rc.alpha_dist; const int mA = targetMedium(pmA, ha.ng, d);
                         wantAlpha = true;
                         alO = make_float4(ha.p.x, ha.p.y, ha.p.z, __uint_as_float((uint32_t) (mA + 1) | (0x7FFFu << 8) | (1u << 24) | (1u << 29)));
@@ -137,7 +134,7 @@ __global__ __launch_bounds__(WG) void k_shade_volmis(DScene sc, RenderConst rc, 
                     }
                 }
                 const int interactions = rc.max_depth - depth - 1;
-                bool nee = false; v3 nref = V(0, 0, 0), nrefN = V(0, 0, 0); MaterialD bsdf; uint32_t pm = 0; bool bumped = false, masked = false; v3 bps = V(0, 0, 0), bpt = V(0, 0, 0), bpn = V(0, 0, 0), opac = V(1, 1, 1);
+                bool nee = false; v3 nref = V(0, 0, 0), nrefN = V(0, 0, 0); SurfaceBsdf sf; uint32_t pm = 0;
                 if (mediumEvent) {
                     if (depth >= rc.max_depth && rc.max_depth != -1) { pathLen += (unsigned) depth; break; }      // :112-113
                     { const float r = 1.0f / mRec.pdfSuccess; T = T * ((ld3(md.sigma_s) * mRec.transmittance) * r); }
@@ -156,36 +153,9 @@ __global__ __launch_bounds__(WG) void k_shade_volmis(DScene sc, RenderConst rc, 
                     if (h.emitter >= 0 && emitted && (!rc.hide_emitters || scattered)) { const v3 e = T * emitterEval(tb, h.emitter, h.ns, -d); add = haveAdd ? add + e : e; haveAdd = true; }
                     if (depth >= rc.max_depth && rc.max_depth != -1) { pathLen += (unsigned) depth; break; }      // :203-204
                     if ((-dot(h.ng, d)) * h.wi.z < 0 && rc.strict_normals) { pathLen += (unsigned) depth; break; }
-                    bsdf = loadMaterial(tb, h.material);
-                    auto applyTexture = [&](MaterialD &mm) {
-                    if (TEX) {
-                        const uint32_t tex = (WRAP && (mm.type == MI_BSDF_T_BUMPMAP || mm.type == MI_BSDF_T_NORMALMAP)) ? 0u : (mm.flags >> 8) & 0xFFFFu;
-                        if (tex) {
-                            const TextureD &tx = sc.textures[tex - 1]; v3 c; float huvx = h.uvx, huvy = h.uvy;
-                            const bool onAnalytic = inst < 0 && prim >= sc.n_tris;
-                            if (onAnalytic) { v3 du, dv; analyticUV(sc.analytic[prim - sc.n_tris], hr.y, hr.z, o + d * hr.x, huvx, huvy, du, dv); }
-                            if (tx.type == 2u) {
-                                const float uvx = huvx * tx.uscale + tx.uoffset, uvy = huvy * tx.vscale + tx.voffset;
-                                if (depth == 1) {
-                                    v3 dpdu, dpdv; float tu_, tv_;
-                                    surfaceTangents<false>(sc, tb, h, prim, inst, hr.y, hr.z, o + d * hr.x, tu_, tv_, dpdu, dpdv);
-                                    const float2 sp = q.pos[pid]; v3 rxd, ryd; sensorDifferentials(sc, rc, m32, ss.a, ss.b, sp.x, sp.y, d, rxd, ryd);
-                                    float pa[4]; computePartials(h.p, h.ng, dpdu, dpdv, o, rxd, ryd, pa);
-                                    c = mipEval(sc, tx, uvx, uvy, pa[0] * tx.uscale, pa[1] * tx.vscale, pa[2] * tx.uscale, pa[3] * tx.vscale);
-                                } else c = tx.filter != 0u ? mipBilinear(sc, tx, 0, uvx, uvy) : mipBox(sc, tx, 0, uvx, uvy);
-                            } else c = textureEval(tx, huvx, huvy);
-                            mm.reflectance[0] = c.x; mm.reflectance[1] = c.y; mm.reflectance[2] = c.z;
-                        }
-                    }
-                    };
-                    applyTexture(bsdf);
-                    if (bsdf.type == MI_BSDF_T_MASK) { opac = ld3(bsdf.reflectance); masked = true; bsdf = loadMaterial(tb, (int) bsdf.distr); applyTexture(bsdf); }      // mask.cpp (shade.h)
-                    if (WRAP && TEX && (bsdf.type == MI_BSDF_T_BUMPMAP || bsdf.type == MI_BSDF_T_NORMALMAP)) {      // bumpmap.cpp / normalmap.cpp: getFrame(its), then the nested record (shade.h)
-                        float huvx = h.uvx, huvy = h.uvy; v3 dpdu, dpdv;
-                        surfaceTangents<false>(sc, tb, h, prim, inst, hr.y, hr.z, o + d * hr.x, huvx, huvy, dpdu, dpdv);
-                        perturbFrame(sc, bsdf, h, huvx, huvy, dpdu, dpdv, bps, bpt, bpn); bumped = true;
-                        bsdf = loadMaterial(tb, (int) bsdf.distr); applyTexture(bsdf);
-                    }
+                    // the surface step (surface.h): material, textured reflectance (only the sensor ray carries differentials), mask, bump / normal map
+                    auto diffs = [&](v3 &rxd, v3 &ryd) { const float2 sp = q.pos[pid]; sensorDifferentials(sc, rc, m32, ss.a, ss.b, sp.x, sp.y, d, rxd, ryd); };
+                    sf = resolveSurface<false, true, TEX, true, WRAP && TEX, false, WRAP>(sc, tb, h, prim, inst, hr, o, d, depth == 1, diffs);
                     pm = sc.prim_media ? sc.prim_media[prim] : 0u;
                     nee = !(h.flags & 4u); nref = h.p;
                     if (!(h.flags & 2u)) nrefN = h.ns;
@@ -199,13 +169,12 @@ __global__ __launch_bounds__(WG) void k_shade_volmis(DScene sc, RenderConst rc, 
                         if (mediumEvent) { const float ph = phaseEval(md, -d, dr.d); x = V(ph, ph, ph); w = miWeight(dr.pdf, dr.delta ? 0.0f : ph); }      // PhaseFunction::pdf = eval (phase.cpp:21-23)
                         else {
                             const v3 wo = toLocal(h, dr.d);
-                            v3 wiQ = h.wi, woQ = wo; bool rejected = false;
-                            if (WRAP && bumped) { wiQ = frameToLocal(bps, bpt, bpn, toWorld(h, h.wi)); woQ = frameToLocal(bps, bpt, bpn, toWorld(h, wo)); rejected = wo.z * woQ.z <= 0; }      // bumpmap.cpp:165-180
-                            v3 bv = rejected ? V(0, 0, 0) : mxEval<true, WRAP>(sc, tb, bsdf, wiQ, woQ);
-                            if (masked) bv = bv * opac;                           // mask.cpp:117-118
+                            v3 wiQ, woQ; bool rejected; queryFrame<WRAP>(h, sf, wo, wiQ, woQ, rejected);      // bumpmap.cpp:165-180
+                            v3 bv = rejected ? V(0, 0, 0) : mxEval<true, WRAP>(sc, tb, sf.bsdf, wiQ, woQ);
+                            if (sf.masked) bv = bv * sf.opac;                     // mask.cpp:117-118
                             const bool ok = !isZero(bv) && (!rc.strict_normals || dot(h.ng, dr.d) * wo.z > 0);
                             float bp = 0.0f;
-                            if (ok && !dr.delta) { bp = mxPdf<true, WRAP>(sc, tb, bsdf, wiQ, woQ); if (masked) bp *= luminance3(opac); }      // mask.cpp:141-146
+                            if (ok && !dr.delta) { bp = mxPdf<true, WRAP>(sc, tb, sf.bsdf, wiQ, woQ); if (sf.masked) bp *= luminance3(sf.opac); }      // mask.cpp:141-146
                             x = ok ? bv : V(0, 0, 0); w = ok ? miWeight(dr.pdf, bp) : 0.0f;
                             if (pm) m2 = targetMedium(pm, h.ng, dr.d);
                             onSurface = 1u << 24;
@@ -231,18 +200,10 @@ __global__ __launch_bounds__(WG) void k_shade_volmis(DScene sc, RenderConst rc, 
                 float sx, sy; next2D(ss, rc.sampler, m32, sx, sy);
                 auto drawExtra = [&]() { return next1D(ss, rc.sampler, m32); };
                 v3 bw; bool passThrough = false;                            // mask.cpp:174-214 (shade.h)
-                if (masked) { const float prob = luminance3(opac); if (sx < prob) sx /= prob; else passThrough = true; }
-                if (passThrough) {
-                    const float p = 1 - luminance3(opac);
-                    woL = V(-h.wi.x, -h.wi.y, -h.wi.z); bEta = 1.0f; bPdf = p; sampledDelta = true; sampledNull = true;
-                    bw = V((1.0f - opac.x) / p, (1.0f - opac.y) / p, (1.0f - opac.z) / p);
-                } else
-                if (WRAP && bumped) {                                        // bumpmap.cpp:218-240
-                    const v3 wiQ = frameToLocal(bps, bpt, bpn, toWorld(h, h.wi)); v3 woQ = V(0, 0, 0);
-                    bw = mxSample<true, WRAP>(sc, tb, bsdf, wiQ, sx, sy, drawExtra, woQ, bPdf, bEta, sampledDelta, sampledNull);
-                    if (!isZero(bw)) { woL = toLocal(h, frameToWorld(bps, bpt, bpn, woQ)); if (woL.z * woQ.z <= 0) bw = V(0, 0, 0); }
-                } else bw = mxSample<true, WRAP>(sc, tb, bsdf, h.wi, sx, sy, drawExtra, woL, bPdf, bEta, sampledDelta, sampledNull);
-                if (masked && !passThrough) { const float prob = luminance3(opac); bw = V(bw.x * opac.x / prob, bw.y * opac.y / prob, bw.z * opac.z / prob); bPdf *= prob; }
+                if (sf.masked) passThrough = maskChooseLobe(sf.opac, sx);
+                if (passThrough) bw = maskPassThrough(h, sf.opac, woL, bPdf, sampledDelta, sampledNull);
+                else bw = sampleInQueryFrame<WRAP>(h, sf, [&](v3 wi, v3 &wo) __attribute__((always_inline)) { return mxSample<true, WRAP>(sc, tb, sf.bsdf, wi, sx, sy, drawExtra, wo, bPdf, bEta, sampledDelta, sampledNull); }, woL);      // bumpmap.cpp:218-240
+                if (sf.masked && !passThrough) { const float prob = luminance3(sf.opac); bw = V(bw.x * sf.opac.x / prob, bw.y * sf.opac.y / prob, bw.z * sf.opac.z / prob); bPdf *= prob; }
                 if (isZero(bw)) { pathLen += (unsigned) depth; break; }
                 const v3 wo = toWorld(h, woL);
                 if (dot(h.ng, wo) * woL.z <= 0 && rc.strict_normals) { pathLen += (unsigned) depth; break; }
@@ -283,7 +244,7 @@ template <bool WIDE, bool ENV, bool NX>      // NX: as in k_shadow_vol
 __global__ __launch_bounds__(WG) void k_shadow_volmis(DScene sc, Queues q) {
     __shared__ int s_stk[STACK_DEPTH * WG];
     const uint32_t tid = threadIdx.x;
-    Tabs<false> tb; tb.shade4 = (AS<false>::p4) sc.shade; tb.materials4 = (AS<false>::p4) sc.materials; tb.emitters4 = (AS<false>::p4) sc.emitters; tb.emitter_cdf = sc.emitter_cdf; tb.area_cdf = sc.area_cdf;
+    const Tabs<false> tb = globalTabs(sc);
     unsigned long long shadowRays = 0, normalRays = 0;
     for (uint32_t seg = blockIdx.x; seg < q.n_seg; seg += gridDim.x) {
     // two passes, a barrier in between: the records written from the back of the area (emitter searches, alpha walks) first, then the emitter-sampling records
@@ -308,9 +269,7 @@ __global__ __launch_bounds__(WG) void k_shadow_volmis(DScene sc, Queues q) {
                 if (!surface) t = INFINITY;
                 if (medium >= 0) tr = tr * mediumTransmittance(sc.media[medium], 0.0f, t);
                 if (!surface) break;
-                if (inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], o, d, t, prim, u, v, h);
-                else if (prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], o, d, t, u, v, h);
-                else fillHit<false, true>(sc, tb, d, t, prim, u, v, h);
+                fillHitAny<false, true>(sc, tb, inst, o, d, t, u, v, prim, h);
                 const MaterialD hm = loadMaterial(tb, h.material);
                 if (interactions == maxInteractions || !(NX ? surfaceHasNull(tb, hm) : materialHasNull(hm.type)) || h.emitter >= 0) break;
                 if (isZero(tr)) { surface = false; break; }

@@ -2,6 +2,7 @@
 // unit per (RC, ENV) pair so that `make -j` compiles the variants side by side.
 #pragma once
 #include "kernels_common.h"
+#include "surface.h"
 #ifndef MI_SHADE_MIN_WAVES
 #define MI_SHADE_MIN_WAVES 1      // waves per SIMD asked of the compiler (A/B builds; DESIGN.md §3: a register cap only moves the live set into scratch)
 #endif
@@ -23,25 +24,7 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
     if (rc.sampler == 1) {   // stage the Sobol' nibble tables in LDS (nib_dims x nib_count x 16 words)
         for (uint32_t i = tid; i < nibWords; i += WG) s_nib[i] = rc.sobol_nib[i];
     }
-    // Scene tables: shading records, materials, emitters, CDFs.  Small scenes (<= 128 triangles ...) are staged in LDS: the shading
-    // stage chases hit -> triangle record -> material -> emitter CDF -> light triangle, and each hop is an L2 round trip otherwise.
-    Tabs<SMALL> tb;
-    if (SMALL) {
-        uint32_t *base = s_dyn + ((nibWords + 3u) & ~3u);
-        const uint32_t wShade = sc.n_tris * (4u * MI_SHADE_WORDS), wMat = sc.n_materials * 16u, wEm = sc.n_emitters * 12u, wEc = (sc.n_emitters + 1u + 3u) & ~3u, wAc = sc.area_cdf_len;
-        uint32_t *pS = base, *pM = pS + wShade, *pE = pM + wMat, *pEc = pE + wEm, *pAc = pEc + wEc;
-        const uint32_t *gS = (const uint32_t *) sc.shade, *gM = (const uint32_t *) sc.materials, *gE = (const uint32_t *) sc.emitters, *gEc = (const uint32_t *) sc.emitter_cdf, *gAc = (const uint32_t *) sc.area_cdf;
-        for (uint32_t i = tid; i < wShade; i += WG) pS[i] = gS[i];
-        for (uint32_t i = tid; i < wMat; i += WG) pM[i] = gM[i];
-        for (uint32_t i = tid; i < wEm; i += WG) pE[i] = gE[i];
-        for (uint32_t i = tid; i < sc.n_emitters + 1u; i += WG) pEc[i] = gEc[i];
-        for (uint32_t i = tid; i < wAc; i += WG) pAc[i] = gAc[i];
-        tb.shade4 = (typename AS<SMALL>::p4) pS; tb.materials4 = (typename AS<SMALL>::p4) pM; tb.emitters4 = (typename AS<SMALL>::p4) pE;
-        tb.emitter_cdf = (typename AS<SMALL>::pf) pEc; tb.area_cdf = (typename AS<SMALL>::pf) pAc;
-    } else {
-        tb.shade4 = (typename AS<SMALL>::p4) sc.shade; tb.materials4 = (typename AS<SMALL>::p4) sc.materials; tb.emitters4 = (typename AS<SMALL>::p4) sc.emitters;
-        tb.emitter_cdf = (typename AS<SMALL>::pf) sc.emitter_cdf; tb.area_cdf = (typename AS<SMALL>::pf) sc.area_cdf;
-    }
+    Tabs<SMALL> tb; stageTables<SMALL, WG>(sc, s_dyn + ((nibWords + 3u) & ~3u), tid, tb);      // scene tables: small scenes are staged in LDS (surface.h)
     // Material-sorted shading (scenes that mix BSDF classes): the paths of a segment are first ordered by the class of the surface
     // they hit -- diffuse-like from the front, rough conductors from the back of an LDS index list (wave64 ballots, order preserving) --
     // so a wave runs either the cheap diffuse code or the microfacet code, not both.  The queues are then read through that list.
@@ -81,8 +64,7 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
         //   B: BSDF sampling                                                     -> next ray / state
         bool alive = false, wantShadow = false, toSample = false;
         float4 shO, shD, shC;
-        Hit h; MaterialD bsdf; SamplerState ss; v3 T = V(0, 0, 0); float eta = 1.0f; uint32_t pid = 0; int depth = 0; bool unscattered = false; v3 opac = V(1, 1, 1); bool masked = false; bool bumped = false; v3 bps = V(0, 0, 0), bpt = bps, bpn = bps; int coat = -1;   // bumpmap / normalmap: perturbed frame (RC variants)
-          // mask wrapper (mask.cpp): opacity in front of `bsdf` (RC variants)
+        Hit h; SurfaceBsdf sf; SamplerState ss; v3 T = V(0, 0, 0); float eta = 1.0f; uint32_t pid = 0; int depth = 0; bool unscattered = false;   // sf: the resolved surface (surface.h) -- leaf record, mask opacity (RC variants), perturbed frame and coating (WRAP variants)
         if (i < n) {
             const uint32_t slot = segBase + (doSort ? (uint32_t) s_order[i] : i);
             float4 rd = qat(q.rayD[buf], slot), hr = qat(q.hit, slot); uint4 s0 = qat(q.st0[buf], slot); float4 s1 = qat(q.st1[buf], slot);
@@ -130,9 +112,7 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
                 v3 ro3 = V(0, 0, 0);
                 if (AN) { float4 ro = qat(q.rayO[buf], slot); ro3 = V(ro.x, ro.y, ro.z); }      // analytic shapes: hit point = o + t d; sphere lights: reference point of pdfDirect
                 const int inst = (AN && q.hitInst) ? qat(q.hitInst, slot) : -1;
-                if (AN && inst >= 0) fillHitInstanced(sc, tb, sc.instances[inst], ro3, d, hr.x, prim, hr.y, hr.z, h);
-                else if (AN && prim >= sc.n_tris) fillHitAnalytic(sc.analytic[prim - sc.n_tris], ro3, d, hr.x, hr.y, hr.z, h);
-                else fillHit<SMALL, AN>(sc, tb, d, hr.x, prim, hr.y, hr.z, h);
+                fillHitAny<SMALL, AN>(sc, tb, inst, ro3, d, hr.x, hr.y, hr.z, prim, h);
                 if (depth > 1) {
                     if (h.emitter >= 0) {                                    // path.cpp:229-233, 257-264
                         v3 value = emitterEval(tb, h.emitter, h.ns, -d);
@@ -147,40 +127,9 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
                     }
                 }
                 if (!(depth <= rc.max_depth || rc.max_depth < 0)) { pathLen += (unsigned) depth; break; }   // loop guard path.cpp:135
-                int curMat = h.material; bsdf = loadMaterial(tb, curMat);
-                auto applyTexture = [&](MaterialD &mm) {
-                if (TEX) {                                                   // a textured parameter: m_reflectance->eval(bRec.its) (diffuse.cpp:112-121) and its siblings
-                    const uint32_t tex = (mm.type == MI_BSDF_T_BUMPMAP || mm.type == MI_BSDF_T_NORMALMAP) ? 0u : (mm.flags >> 8) & 0xFFFFu;      // (an adapter's texture is its displacement / normal map)
-                    if (tex) {
-                        const TextureD &tx = sc.textures[tex - 1]; v3 c;
-                        float huvx = h.uvx, huvy = h.uvy;
-                        const bool onAnalytic = AN && inst < 0 && prim >= sc.n_tris;         // an analytic shape: its own parameterisation, evaluated on demand
-                        if (onAnalytic) { v3 du, dv; analyticUV(sc.analytic[prim - sc.n_tris], hr.y, hr.z, ro3 + d * hr.x, huvx, huvy, du, dv); }   // (tangents: recomputed below where a filtered lookup needs them)
-                        if (tx.type == 2u) {                                 // BitmapTexture::eval (src/textures/bitmap.cpp:434-502) under Texture2D::eval (texture.cpp:112-121)
-                            const float uvx = huvx * tx.uscale + tx.uoffset, uvy = huvy * tx.vscale + tx.voffset;
-                            if (depth == 1) {                                // its.getBSDF(ray) -> computePartials: only the camera ray carries differentials (records.inl:68-75)
-                                v3 dpdu, dpdv; float tu_, tv_;
-                                surfaceTangents<SMALL>(sc, tb, h, prim, inst, hr.y, hr.z, ro3 + d * hr.x, tu_, tv_, dpdu, dpdv);
-                                const float2 sp = qat(q.pos, pid); v3 rxd, ryd; sensorDifferentials(sc, rc, m32, ss.a, ss.b, sp.x, sp.y, d, rxd, ryd);
-                                float pa[4]; computePartials(h.p, h.ng, dpdu, dpdv, ro3, rxd, ryd, pa);
-                                c = mipEval(sc, tx, uvx, uvy, pa[0] * tx.uscale, pa[1] * tx.vscale, pa[2] * tx.uscale, pa[3] * tx.vscale);
-                            } else c = tx.filter != 0u ? mipBilinear(sc, tx, 0, uvx, uvy) : mipBox(sc, tx, 0, uvx, uvy);
-                        } else c = textureEval(tx, huvx, huvy);
-                        mm.reflectance[0] = c.x; mm.reflectance[1] = c.y; mm.reflectance[2] = c.z;
-                    }
-                }
-                };
-                applyTexture(bsdf);
-                if (RC && bsdf.type == MI_BSDF_T_MASK) {                     // mask.cpp: this record's (textured) `reflectance` is the opacity in front of the nested record `distr`
-                    opac = ld3(bsdf.reflectance); masked = true; curMat = (int) bsdf.distr; bsdf = loadMaterial(tb, curMat); applyTexture(bsdf);
-                }
-                if (WRAP && TEX && (bsdf.type == MI_BSDF_T_BUMPMAP || bsdf.type == MI_BSDF_T_NORMALMAP)) {      // bumpmap.cpp / normalmap.cpp: getFrame(its), then the nested record
-                    float huvx = h.uvx, huvy = h.uvy; v3 dpdu, dpdv;
-                    surfaceTangents<SMALL>(sc, tb, h, prim, inst, hr.y, hr.z, ro3 + d * hr.x, huvx, huvy, dpdu, dpdv);
-                    perturbFrame(sc, bsdf, h, huvx, huvy, dpdu, dpdv, bps, bpt, bpn); bumped = true;
-                    curMat = (int) bsdf.distr; bsdf = loadMaterial(tb, curMat); applyTexture(bsdf);
-                }
-                if (WRAP && (bsdf.type == MI_BSDF_T_COATING || bsdf.type == MI_BSDF_T_ROUGHCOATING)) { coat = curMat; bsdf = loadMaterial(tb, (int) bsdf.distr); applyTexture(bsdf); }      // coating.cpp: the layer around the nested record
+                // the surface step (surface.h): material, textured parameters (filtered on the camera hit, whose differentials come from the film position), mask, bump / normal map, coating
+                auto diffs = [&](v3 &rxd, v3 &ryd) { const float2 sp = qat(q.pos, pid); sensorDifferentials(sc, rc, m32, ss.a, ss.b, sp.x, sp.y, d, rxd, ryd); };
+                sf = resolveSurface<SMALL, AN, TEX, RC, WRAP && TEX, WRAP, true>(sc, tb, h, prim, inst, hr, ro3, d, depth == 1, diffs);
                 if (depth == 1 && h.emitter >= 0 && !rc.hide_emitters) {    // path.cpp:148-150 (EEmittedRadiance only on the camera segment)
                     add = T * emitterEval(tb, h.emitter, h.ns, -d); haveAdd = true;
                 }
@@ -193,15 +142,12 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
                     if (dr.pdf != 0) {
                         ++shadowRays;                                        // scene.cpp:871-875: a shadow ray is cast whenever pdf != 0
                         v3 wo = toLocal(h, dr.d);
-                        v3 wiQ = h.wi, woQ = wo; bool rejected = false;
-                        if (WRAP && bumped) {                                                // bumpmap.cpp:165-180: the query in the perturbed frame
-                            wiQ = frameToLocal(bps, bpt, bpn, toWorld(h, h.wi)); woQ = frameToLocal(bps, bpt, bpn, toWorld(h, wo)); rejected = wo.z * woQ.z <= 0;
-                        }
-                        v3 bsdfVal = rejected ? V(0, 0, 0) : ctEval<RC, WRAP>(sc, tb, coat, bsdf, wiQ, woQ);
-                        if (RC && masked) bsdfVal = bsdfVal * opac;                          // mask.cpp:124-127
+                        v3 wiQ, woQ; bool rejected; queryFrame<WRAP>(h, sf, wo, wiQ, woQ, rejected);      // bumpmap.cpp:165-180: the query in the perturbed frame
+                        v3 bsdfVal = rejected ? V(0, 0, 0) : ctEval<RC, WRAP>(sc, tb, sf.coat, sf.bsdf, wiQ, woQ);
+                        if (RC && sf.masked) bsdfVal = bsdfVal * sf.opac;                    // mask.cpp:124-127
                         if (!isZero(value) && !isZero(bsdfVal) && (!rc.strict_normals || dot(h.ng, dr.d) * wo.z > 0)) {
-                            float bp = (dr.delta || rejected) ? 0.0f : ctPdf<RC, WRAP>(sc, tb, coat, bsdf, wiQ, woQ);     // emitter->isOnSurface() && measure == ESolidAngle (path.cpp:191-192)
-                            if (RC && masked) bp *= luminance3(opac);                          // mask.cpp:141-146
+                            float bp = (dr.delta || rejected) ? 0.0f : ctPdf<RC, WRAP>(sc, tb, sf.coat, sf.bsdf, wiQ, woQ);     // emitter->isOnSurface() && measure == ESolidAngle (path.cpp:191-192)
+                            if (RC && sf.masked) bp *= luminance3(sf.opac);                    // mask.cpp:141-146
                             float weight = miWeight(dr.pdf, bp);
                             v3 c = ((T * value) * bsdfVal) * weight;
                             wantShadow = true;
@@ -227,22 +173,14 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
             // BSDF sampling (path.cpp:207-226)
             float bPdf = 0, bEta = 1; v3 woL = V(0, 0, 0);
             float sx, sy; next2D(ss, rc.sampler, m32, sx, sy);
-            bool sampledDelta, sampledNull; float extra = 0.0f; v3 bw;
+            bool sampledDelta, sampledNull; v3 bw;
             bool passThrough = false;                                                   // mask.cpp:196-208: the nested BSDF with probability luminance(opacity), else straight through
-            if (RC && masked) { const float prob = luminance3(opac); if (sx < prob) sx /= prob; else passThrough = true; }
-            if (RC && passThrough) {
-                const float p = 1 - luminance3(opac);
-                woL = V(-h.wi.x, -h.wi.y, -h.wi.z); bEta = 1.0f; bPdf = p; sampledDelta = true; sampledNull = true;
-                bw = V((1.0f - opac.x) / p, (1.0f - opac.y) / p, (1.0f - opac.z) / p);
-            } else {
+            if (RC && sf.masked) passThrough = maskChooseLobe(sf.opac, sx);
+            if (RC && passThrough) bw = maskPassThrough(h, sf.opac, woL, bPdf, sampledDelta, sampledNull);
+            else {
                 auto drawExtra = [&]() { return next1D(ss, rc.sampler, m32); };        // bRec.sampler->next1D() inside BSDF::sample (EUsesSampler), only if the sampled BSDF asks
-                (void) extra;
-                if (WRAP && bumped) {                                                  // bumpmap.cpp:199-222
-                    const v3 wiQ = frameToLocal(bps, bpt, bpn, toWorld(h, h.wi)); v3 woQ = V(0, 0, 0);
-                    bw = ctSample<RC, WRAP>(sc, tb, coat, bsdf, wiQ, sx, sy, drawExtra, woQ, bPdf, bEta, sampledDelta, sampledNull);
-                    if (!isZero(bw)) { woL = toLocal(h, frameToWorld(bps, bpt, bpn, woQ)); if (woL.z * woQ.z <= 0) bw = V(0, 0, 0); }
-                } else bw = ctSample<RC, WRAP>(sc, tb, coat, bsdf, h.wi, sx, sy, drawExtra, woL, bPdf, bEta, sampledDelta, sampledNull);
-                if (RC && masked) { const float prob = luminance3(opac); bw = V(bw.x * opac.x / prob, bw.y * opac.y / prob, bw.z * opac.z / prob); bPdf *= prob; }
+                bw = sampleInQueryFrame<WRAP>(h, sf, [&](v3 wi, v3 &wo) __attribute__((always_inline)) { return ctSample<RC, WRAP>(sc, tb, sf.coat, sf.bsdf, wi, sx, sy, drawExtra, wo, bPdf, bEta, sampledDelta, sampledNull); }, woL);
+                if (RC && sf.masked) { const float prob = luminance3(sf.opac); bw = V(bw.x * sf.opac.x / prob, bw.y * sf.opac.y / prob, bw.z * sf.opac.z / prob); bPdf *= prob; }
             }
             v3 wo = toWorld(h, woL);
             if (isZero(bw) || (rc.strict_normals && dot(h.ng, wo) * woL.z <= 0)) pathLen += (unsigned) depth;
