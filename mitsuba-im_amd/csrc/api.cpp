@@ -944,8 +944,8 @@ int mi_render_create(mi_scene *s, const mi_render_params *p, mi_render **out) {
     // volumetric integrators: the radiance-type bits and the sensor's medium of a fresh path (kernels_vol.hip; volpath_simple.cpp:103-104: maxDepth = 1 gathers emitted radiance only)
     r->rc.alpha_dist = alphaDistOf(s->h);
     r->rc.integrator = p->integrator;
-    r->rc.state_init = p->integrator == MI_INTEGRATOR_VOLPATH_SIMPLE ? ((1u << 16) | (p->max_depth == 1 ? 0u : (1u << 17)) | (1u << 18) | ((uint32_t) (s->h.d.sensor_medium + 1) << 20))
-                     : p->integrator == MI_INTEGRATOR_VOLPATH ? ((1u << 16) | ((uint32_t) (s->h.d.sensor_medium + 1) << 20)) : 0u;      // volpath: ERadiance, nothing else (kernels_volmis.hip)
+    r->rc.state_init = p->integrator == MI_INTEGRATOR_VOLPATH_SIMPLE ? (VS_EMITTED | (p->max_depth == 1 ? 0u : VS_OTHERS) | VS_NULLCHAIN | ((uint32_t) (s->h.d.sensor_medium + 1) << VS_MEDIUM_SHIFT))
+                     : p->integrator == MI_INTEGRATOR_VOLPATH ? (VS_EMITTED | ((uint32_t) (s->h.d.sensor_medium + 1) << VS_MEDIUM_SHIFT)) : 0u;      // volpath: ERadiance, nothing else (kernels_volmis.hip)
     if (p->sampler == MI_SAMPLER_SOBOL && p->seed) {          // SobolSampler: a nonzero `scramble` goes through sampleTEA (sobol.cpp:96-102; qmc.h:146-156, 4 rounds)
         uint32_t v0 = (uint32_t) p->seed, v1 = (uint32_t) (p->seed >> 32), sum = 0;
         for (int i = 0; i < 4; ++i) {

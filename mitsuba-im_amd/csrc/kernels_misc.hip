@@ -62,11 +62,9 @@ __global__ __launch_bounds__(WG) void k_generate(DScene sc, RenderConst rc, Queu
     }
 }
 
-// Camera rays that leave the scene: EnvironmentMap::evalEnvironment WITH ray differentials (src/emitters/envmap.cpp:384-416) -- texture-space partials
-// of the sensor ray's rx / ry directions, then TMIPMap::eval (EWA, anisotropy <= 10; u repeats, v clamps) over the map's MIP pyramid (input data).
+// Camera rays that leave the scene: EnvironmentMap::evalEnvironment WITH ray differentials (envEvalFiltered, pt_device.h) over the map's MIP pyramid (input data).
 // Runs once per batch between the first extend and the first shade; throughput is 1 at depth 1.
 __global__ __launch_bounds__(WG) void k_env_primary(DScene sc, RenderConst rc, Queues q, int buf) {
-    const TextureD tx = sc.textures[sc.env_texture - 1u];
     for (uint32_t seg = blockIdx.x; seg < q.n_seg; seg += gridDim.x) {
         const uint32_t n = q.count[buf][seg]; const uint64_t segBase = (uint64_t) seg * q.cap;
         for (uint32_t i = threadIdx.x; i < n; i += WG) {
@@ -74,11 +72,7 @@ __global__ __launch_bounds__(WG) void k_env_primary(DScene sc, RenderConst rc, Q
             const float4 rd = q.rayD[buf][segBase + i]; const uint4 s0 = q.st0[buf][segBase + i]; const uint32_t pid = s0.x;
             const v3 d = V(rd.x, rd.y, rd.z); const float2 sp = q.pos[pid];
             v3 rxd, ryd; sensorDifferentials(sc, rc, SobolTab{rc.sobol_nib, rc.nib_count, rc.sobol_scramble}, s0.y, s0.z, sp.x, sp.y, d, rxd, ryd);
-            const v3 v = mat3(sc.env_to_local, d);
-            const float uvx = atan2f(v.x, -v.z) * MI_INV_TWOPI, uvy = acosf(minf(1.0f, maxf(-1.0f, v.y))) * MI_INV_PI;
-            const v3 dvdx = mat3(sc.env_to_local, rxd) - v, dvdy = mat3(sc.env_to_local, ryd) - v;
-            const float t1 = MI_INV_TWOPI / (v.x * v.x + v.z * v.z), t2 = -MI_INV_PI / maxf(sqrtf(maxf(0.0f, 1.0f - v.y * v.y)), MI_EPSILON);
-            const v3 value = mipEval(sc, tx, uvx, uvy, t1 * (dvdx.z * v.x - dvdx.x * v.z), t2 * dvdx.y, t1 * (dvdy.z * v.x - dvdy.x * v.z), t2 * dvdy.y) * sc.env_scale;
+            const v3 value = envEvalFiltered(sc, d, rxd, ryd);
             float4 a = q.acc[pid]; a.x += value.x; a.y += value.y; a.z += value.z; q.acc[pid] = a;
         }
     }

@@ -1739,6 +1739,16 @@ DEV v3 envEval(const DScene &sc, v3 d) {
     float uvx = miAtan2f(v.x, -v.z) * MI_INV_TWOPI, uvy = miAcosf(minf(1.0f, maxf(-1.0f, v.y))) * MI_INV_PI;
     return envBilinear(sc, uvx, uvy) * sc.env_scale;
 }
+// envmap.cpp:384-416 evalEnvironment WITH ray differentials (the sensor ray; rxd / ryd: its rx / ry directions): their texture-space partials, then TMIPMap::eval (EWA,
+// anisotropy <= 10; u repeats, v clamps) over the map's MIP pyramid.  Only for an environment map that has one (sc.env_texture != 0).
+DEV v3 envEvalFiltered(const DScene &sc, v3 d, v3 rxd, v3 ryd) {
+    const TextureD tx = sc.textures[sc.env_texture - 1u];
+    const v3 v = mat3(sc.env_to_local, d);
+    const float uvx = atan2f(v.x, -v.z) * MI_INV_TWOPI, uvy = acosf(minf(1.0f, maxf(-1.0f, v.y))) * MI_INV_PI;
+    const v3 dvdx = mat3(sc.env_to_local, rxd) - v, dvdy = mat3(sc.env_to_local, ryd) - v;
+    const float t1 = MI_INV_TWOPI / (v.x * v.x + v.z * v.z), t2 = -MI_INV_PI / maxf(sqrtf(maxf(0.0f, 1.0f - v.y * v.y)), MI_EPSILON);
+    return mipEval(sc, tx, uvx, uvy, t1 * (dvdx.z * v.x - dvdx.x * v.z), t2 * dvdx.y, t1 * (dvdy.z * v.x - dvdy.x * v.z), t2 * dvdy.y) * sc.env_scale;
+}
 // envmap.cpp:664-669 sampleReuse
 DEV uint32_t envSampleReuse(const float *cdf, uint32_t size, float &sample) {
     uint32_t lo = 0, hi = size + 1;

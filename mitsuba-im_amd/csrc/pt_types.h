@@ -183,3 +183,15 @@ struct RenderConst {
     uint32_t state_init;                  // bits ORed into the state word st0.w of a fresh path (volumetric integrators: radiance-type bits, the sensor's medium)
     uint32_t order_offset_words;          // dynamic-LDS offset of the material-sort index list (0 = no sorting); set per launch
 };
+// The state word st0.w of the volumetric integrators (volume.h unpacks and repacks it, api.cpp composes state_init).  Bits 17 / 18 and 28 / 29 belong to one integrator each.
+#define VS_DIM_MASK 0xFFu              // bits 0..7 sampler dimension
+#define VS_DEPTH_SHIFT 8               // bits 8..15 depth
+#define VS_EMITTED (1u << 16)          // EEmittedRadiance
+#define VS_OTHERS (1u << 17)           // volpath_simple: the bits of ERadianceNoEmission (they change together)
+#define VS_NULLCHAIN (1u << 18)        // volpath_simple: nullChain
+#define VS_DELTA (1u << 17)            // volpath: the spawning sample was a Dirac delta
+#define VS_SEARCH (1u << 18)           // volpath: the ray looks for an emitter
+#define VS_SCATTERED (1u << 19)        // scattered
+#define VS_MEDIUM_SHIFT 20             // bits 20..27 current medium + 1
+#define VS_FACING (1u << 28)           // volpath: dot(d, refN) >= 0 at the spawning vertex
+#define VS_SKIPRR (1u << 29)           // volpath: skip the Russian roulette (the previous pass was a `null` pass-through)
