@@ -41,14 +41,14 @@ __global__ __launch_bounds__(WG) void k_ao(DScene sc, RenderConst rc, AoConst ac
         float4 oA, oB;
         if (i < n) {
             const uint32_t slot = segBase + i;
-            const float4 rd = qat(q.rayD[0], slot), hr = qat(q.hit, slot); const uint4 s0 = qat(q.st0[0], slot);
+            const auto rd = qRayDirection(q, 0, slot); const float4 hr = qat(q.hit, slot); const uint4 s0 = qat(q.st0[0], slot);
             const uint32_t pid = s0.x; const v3 d = V(rd.x, rd.y, rd.z);
             const uint32_t prim = __float_as_uint(hr.w);
             if (prim == 0xFFFFFFFFu) {                       // camera miss: Spectrum(1.0f) whatever the environment is (ao.cpp:91-95); alpha = 0 under EOpacity (records.inl:121-137)
                 if (first) qat(q.acc, pid) = make_float4(1.0f, 1.0f, 1.0f, rc.opacity ? 0.0f : 1.0f);
             } else {
                 v3 ro3 = V(0, 0, 0);
-                if (AN) { const float4 ro = qat(q.rayO[0], slot); ro3 = V(ro.x, ro.y, ro.z); }
+                if (AN) { const auto ro = qRayOrigin(q, 0, slot); ro3 = V(ro.x, ro.y, ro.z); }
                 const int inst = (AN && q.hitInst) ? qat(q.hitInst, slot) : -1;
                 Hit h;
                 fillHitAny<SMALL, AN>(sc, tb, inst, ro3, d, hr.x, hr.y, hr.z, prim, h);
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(WG) void k_ao(DScene sc, RenderConst rc, AoConst ac
         const unsigned long long m = __ballot(want);
         if (want) {
             const uint32_t o = segBase + out + (uint32_t) __popcll(m & lt);
-            qat(q.shO, o) = oA; qat(q.shD, o) = oB; qat(q.shC, o) = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+            qat(q.shO, o) = oA; qat(q.shD, o) = oB; qSetShadowContribution(q, o, 1.0f, 1.0f, 1.0f);
         }
         out += (uint32_t) __popcll(m);
     }

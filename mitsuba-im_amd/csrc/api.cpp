@@ -23,7 +23,7 @@
 
 extern "C" {
 void mi_launch_generate(const DScene &, const RenderConst &, const Queues &, const BatchDesc &, uint32_t, hipStream_t);
-void mi_launch_extend(const DScene &, const Queues &, int, uint32_t, hipStream_t);
+void mi_launch_extend(const DScene &, const Queues &, int, int, uint32_t, hipStream_t);
 void mi_launch_shade_d(const DScene &, const RenderConst &, const Queues &, int, uint32_t, size_t, hipStream_t);
 void mi_launch_shade_d_env(const DScene &, const RenderConst &, const Queues &, int, uint32_t, size_t, hipStream_t);
 void mi_launch_shade_rc(const DScene &, const RenderConst &, const Queues &, int, uint32_t, size_t, hipStream_t);
@@ -33,7 +33,7 @@ void mi_launch_shade_rcw_env(const DScene &, const RenderConst &, const Queues &
 void mi_launch_shadow(const DScene &, const Queues &, uint32_t, hipStream_t);
 bool mi_fused_walk(const DScene &);
 uint32_t mi_fused_grid(void);
-void mi_launch_extend_fused(const DScene &, const Queues &, int, uint32_t *, hipStream_t);
+void mi_launch_extend_fused(const DScene &, const Queues &, int, int, uint32_t *, hipStream_t);
 void mi_launch_shadow_fused(const DScene &, const Queues &, uint32_t *, hipStream_t);
 void mi_launch_shade_vol(const DScene &, const RenderConst &, const Queues &, int, uint32_t, size_t, hipStream_t);
 void mi_launch_shadow_vol(const DScene &, const Queues &, uint32_t, hipStream_t);
@@ -90,12 +90,12 @@ void mi_launch_tp_output(const DenoiseBufs &, float *, size_t, int, hipStream_t)
 // (Round 2 experiment, removed: two launches per bounce -- diffuse hits through the diffuse-only kernel, the rest through the full kernel -- measured SLOWER
 // than one launch of the full kernel over the class-sorted list, 1579 vs 1675 Msamples/s on the Veach scene: a wave of diffuse hits already skips the other
 // BSDFs' code at run time, and the stage runs at two waves per SIMD either way)
-static bool mi_launch_shade(const DScene &scIn, bool ldsTables, const RenderConst &rc, const Queues &q, int buf, uint32_t grid, hipStream_t st, uint32_t *tableBytes = nullptr) {
+static bool mi_launch_shade(const DScene &scIn, bool ldsTables, const RenderConst &rc, const Queues &q, int buf, bool firstBounce, uint32_t grid, hipStream_t st, uint32_t *tableBytes = nullptr) {
     DScene sc = scIn; sc.small_tables = ldsTables ? 1u : 0u;
     size_t lds = rc.sampler == 1 ? (size_t) rc.nib_dims * rc.nib_count * 64 : 16;
     const bool env = sc.env_index >= 0;
     if (sc.small_tables) lds += 16 + 4 * ((size_t) sc.n_tris * (4 * MI_SHADE_WORDS) + sc.n_materials * 16 + sc.n_emitters * 12 + ((sc.n_emitters + 4) & ~3u) + sc.area_cdf_len);
-    RenderConst rcl = rc; rcl.order_offset_words = 0;
+    RenderConst rcl = rc; rcl.order_offset_words = 0; rcl.first_bounce = firstBounce ? 1u : 0u;
     if (tableBytes) *tableBytes = (uint32_t) lds;      // dynamic LDS in front of the order list (mi_render_debug_pool_info)
     if (sc.has_roughconductor && q.cap <= 8192u) {      // path-order list: only where it still fits the 64 KB a launch may request (else unsorted shading)
         const uint32_t off = (uint32_t) ((lds + 15) / 16 * 4); const size_t total = (size_t) off * 4 + (size_t) q.cap * 2 * 4 + 16;
@@ -771,6 +771,14 @@ extern "C" int mi_debug_pool_shape(uint64_t paths, int hasRC, uint32_t integrato
     out->grid_shadow = (uint32_t) std::min<uint64_t>(grid, ov->grid_shadow ? ov->grid_shadow : 4096u);
     return MI_OK;
 }
+// Bytes one slot of a pool takes in the per-slot arrays allocPoolQ allocates (queues.h): what MI355PT_POOL_LIMIT is compared with.
+//   two buffers of ray 24 + state 32 (+ eta 4, + st3 4), the camera rays' interval 8 (both buffers in the volumetric modes), hit 16 (+ instance 4; `direct`: a second hit array),
+//   shadow record 44 (volumetric: two records of 80), accumulator 16, film position 8.  Plain diffuse `path`: 204 B (the four-float records of before: 224).
+static uint64_t mi_pool_slot_bytes(bool vol, bool withEta, bool envConstant, bool instances, bool direct) {
+    const uint64_t perBuf = 12 + 12 + 16 + 12 + 4 + (withEta ? 4 : 0) + (envConstant ? 4 : 0);
+    const uint64_t hit = (16 + (instances ? 4 : 0)) * (direct ? 2 : 1);
+    return 2 * perBuf + (vol ? 16 : 8) + hit + (vol ? 2 * 80 : 44) + 16 + 8;
+}
 // allocates the queues of ONE pool into an empty Q (freePoolQ first); on failure the caller releases whatever was allocated
 static int allocPoolQ(mi_render *r, uint64_t paths, Queues &Q, std::vector<void *> &allocs) {
     // MI355PT_SEGMENTS / MI355PT_GRID_*: 0, a negative value or no number at all count as unset (a segment count of 0 would divide by zero below)
@@ -782,21 +790,26 @@ static int allocPoolQ(mi_render *r, uint64_t paths, Queues &Q, std::vector<void 
     r->grid = grid; Q.cap = g.cap; Q.n_seg = grid;
     r->gridExtend = g.grid_extend; r->gridShade = g.grid_shade; r->gridShadow = g.grid_shadow;
     const uint64_t slots = cap * grid;
+    const bool vol = isVolumetric(r->rc.integrator);
+    const bool withEta = vol || r->scene->h.d.has_roughconductor;      // the RC shade variants and the volumetric stages carry eta (queues.h); `direct` keeps a BSDF value in the throughput record and no eta
     {   // MI355PT_POOL_LIMIT (bytes per pool; tests): behave as if the card had no more room than this -- mi_render_run then falls back to smaller batches
         const char *lim = getenv("MI355PT_POOL_LIMIT");
-        if (lim && atoll(lim) > 0 && slots * 224ull > (uint64_t) atoll(lim)) return fail(MI_ERR_DEVICE, "mi_render_run: path pool larger than MI355PT_POOL_LIMIT");
+        if (lim && atoll(lim) > 0 && slots * mi_pool_slot_bytes(vol, withEta, r->scene->h.d.env_constant != 0, r->scene->h.d.n_instances != 0, r->rc.integrator == MI_INTEGRATOR_DIRECT) > (uint64_t) atoll(lim))
+            return fail(MI_ERR_DEVICE, "mi_render_run: path pool larger than MI355PT_POOL_LIMIT");
     }
     for (int b = 0; b < 2; ++b) {
-        ALLOC(Q.rayO[b], float4, slots); ALLOC(Q.rayD[b], float4, slots);
-        ALLOC(Q.st0[b], uint4, slots); ALLOC(Q.st1[b], float4, slots); ALLOC(Q.st2[b], float, slots);
+        ALLOC(Q.rayO[b], QVec3, slots); ALLOC(Q.rayD[b], QVec3, slots);
+        if (b == 0 || vol) ALLOC(Q.rayT[b], float2, slots); else Q.rayT[b] = nullptr;      // surface integrators: only the camera rays (always buffer 0) have an interval of their own
+        ALLOC(Q.st0[b], uint4, slots); ALLOC(Q.st1[b], QVec3, slots); ALLOC(Q.st2[b], float, slots);
+        if (withEta) ALLOC(Q.eta[b], float, slots); else Q.eta[b] = nullptr;
         if (r->scene->h.d.env_constant) ALLOC(Q.st3[b], float, slots); else Q.st3[b] = nullptr;
         ALLOC(Q.count[b], uint32_t, grid);
     }
     if (r->scene->h.d.n_instances) ALLOC(Q.hitInst, int32_t, slots); else Q.hitInst = nullptr;
-    // shadow records: 48 B; the volumetric integrators add throughput and BSDF / phase value (80 B); volpath leaves up to two records per path and pass (kernels_volmis.hip)
-    const uint64_t shSlots = isVolumetric(r->rc.integrator) ? slots * 2 : slots;
-    ALLOC(Q.hit, float4, slots); ALLOC(Q.shO, float4, shSlots); ALLOC(Q.shD, float4, shSlots); ALLOC(Q.shC, float4, shSlots);
-    if (isVolumetric(r->rc.integrator)) { ALLOC(Q.shT, float4, shSlots); ALLOC(Q.shX, float4, shSlots); } else { Q.shT = nullptr; Q.shX = nullptr; }
+    // shadow records: 44 B; the volumetric integrators keep a wide contribution and add throughput and BSDF / phase value (80 B); volpath leaves up to two records per path and pass (kernels_volmis.hip)
+    const uint64_t shSlots = vol ? slots * 2 : slots;
+    ALLOC(Q.hit, float4, slots); ALLOC(Q.shO, float4, shSlots); ALLOC(Q.shD, float4, shSlots);
+    if (vol) { Q.shC = nullptr; ALLOC(Q.shCw, float4, shSlots); ALLOC(Q.shT, float4, shSlots); ALLOC(Q.shX, float4, shSlots); } else { ALLOC(Q.shC, QVec3, shSlots); Q.shCw = nullptr; Q.shT = nullptr; Q.shX = nullptr; }
     if (r->rc.integrator == MI_INTEGRATOR_DIRECT) {      // the BSDF rays of a pass are extended into a hit array of their own (direct.h)
         const int pi = &Q == &r->q ? 0 : (int) (&Q - r->qx) + 1;
         ALLOC(r->hitB[pi], float4, slots); if (r->scene->h.d.n_instances) ALLOC(r->hitInstB[pi], int32_t, slots); else r->hitInstB[pi] = nullptr;
@@ -1105,7 +1118,7 @@ static int traceBatchDirect(mi_render *r, const BatchDesc &bd, size_t &evUsed, i
     if (fused) HIPCHK(hipMemsetAsync(Q.ticket, 0, MI_TICKETS * sizeof(uint32_t), st));
     mi_launch_generate(sc, r->rc, Q, bd, r->grid, st);
     mark(r, 1, evUsed, st);
-    if (fused) mi_launch_extend_fused(sc, Q, 0, Q.ticket + ticket++, st); else mi_launch_extend(sc, Q, 0, r->gridExtend, st);
+    if (fused) mi_launch_extend_fused(sc, Q, 0, 1, Q.ticket + ticket++, st); else mi_launch_extend(sc, Q, 0, 1, r->gridExtend, st);
     ++r->launchesAll;
     if (r->nFields && !bd.list) {      // field channels of the film samples, as in traceBatch
         mark(r, 0, evUsed, st);
@@ -1122,7 +1135,7 @@ static int traceBatchDirect(mi_render *r, const BatchDesc &bd, size_t &evUsed, i
     for (uint32_t j = 0; j < M; ++j) {
         mark(r, 2, evUsed, st); launchDirectPass(r, Q, bd, 1, j, st);
         mark(r, 1, evUsed, st);
-        if (fused && ticket < MI_TICKETS) mi_launch_extend_fused(sc, QB, 1, Q.ticket + ticket++, st); else mi_launch_extend(sc, QB, 1, r->gridExtend, st);
+        if (fused && ticket < MI_TICKETS) mi_launch_extend_fused(sc, QB, 1, 0, Q.ticket + ticket++, st); else mi_launch_extend(sc, QB, 1, 0, r->gridExtend, st);      // BSDF rays: (Epsilon, inf)
         ++r->launchesAll;
         mark(r, 2, evUsed, st); mi_launch_direct_hit(sc, r->rc, r->dc, QB, r->gridExtend, st);
     }
@@ -1139,7 +1152,7 @@ static int traceBatchAo(mi_render *r, const BatchDesc &bd, size_t &evUsed, int p
     if (fused) HIPCHK(hipMemsetAsync(Q.ticket, 0, MI_TICKETS * sizeof(uint32_t), st));
     mi_launch_generate(scR, r->rc, Q, bd, r->grid, st);
     mark(r, 1, evUsed, st);
-    if (fused) mi_launch_extend_fused(scR, Q, 0, Q.ticket + ticket++, st); else mi_launch_extend(scR, Q, 0, r->gridExtend, st);
+    if (fused) mi_launch_extend_fused(scR, Q, 0, 1, Q.ticket + ticket++, st); else mi_launch_extend(scR, Q, 0, 1, r->gridExtend, st);
     ++r->launchesAll;
     if (r->nFields && !bd.list) {      // field channels of the film samples, as in traceBatch
         mark(r, 0, evUsed, st);
@@ -1176,7 +1189,8 @@ static int traceBatch(mi_render *r, const BatchDesc &bd, const uint32_t *list, s
     int buf = 0; const int maxDepth = r->rc.max_depth > 0 ? r->rc.max_depth : 250;
     for (int depth = 1; depth <= maxDepth; ++depth) {
         mark(r, 1, evUsed, st);
-        if (fused && 2 * depth + 1 < MI_TICKETS) mi_launch_extend_fused(sc, Q, buf, Q.ticket + 2 * depth, st); else mi_launch_extend(sc, Q, buf, r->gridExtend, st);
+        const int ownInterval = (depth == 1 || r->rc.integrator != MI_INTEGRATOR_PATH) ? 1 : 0;      // camera rays carry the near / far clip, the volumetric stages mint = 0 at medium vertices; a surface bounce ray is (Epsilon, inf)
+        if (fused && 2 * depth + 1 < MI_TICKETS) mi_launch_extend_fused(sc, Q, buf, ownInterval, Q.ticket + 2 * depth, st); else mi_launch_extend(sc, Q, buf, ownInterval, r->gridExtend, st);
         ++r->launchesAll;
         if (depth == 1 && r->nFields && !bd.list) {      // field channels of the film samples: q.hit still holds the camera hits, slot = path id (kernels_field.hip)
             mark(r, 0, evUsed, st);
@@ -1191,7 +1205,7 @@ static int traceBatch(mi_render *r, const BatchDesc &bd, const uint32_t *list, s
             if (depth < maxDepth || (depth == 1 && r->rc.opacity)) { mark(r, 3, evUsed, st); (mis ? mi_launch_shadow_volmis : mi_launch_shadow_vol)(sc, Q, r->gridShadow, st); }      // (depth 1 with EOpacity: the alpha walks)
         } else {
         if (depth == 1 && sc.env_texture && !r->rc.hide_emitters) mi_launch_env_primary(sc, r->rc, Q, buf, r->gridExtend, st);   // camera rays that see the sky: filtered lookup (envmap.cpp:398-411)
-        mark(r, 2, evUsed, st); r->lastSorted = mi_launch_shade(sc, r->ldsTables, r->rc, Q, buf, r->gridShade, st, &r->lastTableBytes);
+        mark(r, 2, evUsed, st); r->lastSorted = mi_launch_shade(sc, r->ldsTables, r->rc, Q, buf, depth == 1, r->gridShade, st, &r->lastTableBytes);
         if (depth < maxDepth) { mark(r, 3, evUsed, st); if (fused && 2 * depth + 1 < MI_TICKETS) mi_launch_shadow_fused(sc, Q, Q.ticket + 2 * depth + 1, st); else mi_launch_shadow(sc, Q, r->gridShadow, st); }
         }
         buf ^= 1;
@@ -1636,7 +1650,7 @@ int mi_render_field_samples(mi_render *r, const uint32_t *pairs, uint64_t n, flo
         if (fused) e = hipMemsetAsync(Q.ticket, 0, MI_TICKETS * sizeof(uint32_t), st);
         if (e == hipSuccess) {
             mi_launch_generate(sc, r->rc, Q, bd, r->grid, st);
-            if (fused) mi_launch_extend_fused(sc, Q, 0, Q.ticket + 2, st); else mi_launch_extend(sc, Q, 0, r->gridExtend, st);
+            if (fused) mi_launch_extend_fused(sc, Q, 0, 1, Q.ticket + 2, st); else mi_launch_extend(sc, Q, 0, 1, r->gridExtend, st);
             mi_launch_field_samples(sc, r->fa, Q, n, dOut, st);
             e = hipStreamSynchronize(st); if (e == hipSuccess) e = hipGetLastError();
         }
@@ -1992,27 +2006,36 @@ int mi_debug_intersect_fused(mi_scene *s, const float *rays, uint64_t n, int any
     // slot of ray i: segment by segment, in input order
     std::vector<uint64_t> slotOf(n); { uint64_t i = 0; for (uint32_t sg = 0; sg < nSeg; ++sg) for (uint32_t j = 0; j < segCounts[sg]; ++j) slotOf[i++] = (uint64_t) sg * cap + j; }
     const uint32_t sentinel = 0xFFFFFFFEu;      // no retired ray leaves this in Queues::hit: prim is a triangle index or 0xFFFFFFFF
-    std::vector<float4> hO(slots, make_float4(0, 0, 0, 0)), hD(slots, make_float4(0, 0, 0, 0)), hC(anyHit ? slots : 0, make_float4(1.0f, 0.0f, 0.0f, 0.0f));
+    // the layout of queues.h: shadow records are (o | maxt), (d | path id), contribution rgb; extension rays are origin, direction and the interval in the side array
+    std::vector<float4> hO(anyHit ? slots : 0, make_float4(0, 0, 0, 0)), hD(anyHit ? slots : 0, make_float4(0, 0, 0, 0));
+    std::vector<QVec3> hC(anyHit ? slots : 0, QVec3{1.0f, 0.0f, 0.0f}), hO3(anyHit ? 0 : slots, QVec3{0, 0, 0}), hD3(anyHit ? 0 : slots, QVec3{0, 0, 0});
+    std::vector<float2> hT(anyHit ? 0 : slots, make_float2(0, 0));
     for (uint64_t i = 0; i < n; ++i) {
         const float *r = rays + i * 8; const uint32_t pid = (uint32_t) i; float pidf; memcpy(&pidf, &pid, 4);
-        hO[slotOf[i]] = make_float4(r[0], r[1], r[2], anyHit ? r[7] : r[3]); hD[slotOf[i]] = make_float4(r[4], r[5], r[6], anyHit ? pidf : r[7]);
+        if (anyHit) { hO[slotOf[i]] = make_float4(r[0], r[1], r[2], r[7]); hD[slotOf[i]] = make_float4(r[4], r[5], r[6], pidf); }
+        else { hO3[slotOf[i]] = QVec3{r[0], r[1], r[2]}; hD3[slotOf[i]] = QVec3{r[4], r[5], r[6]}; hT[slotOf[i]] = make_float2(r[3], r[7]); }
     }
     std::vector<void *> bufs; int rc = MI_OK;
     auto alloc = [&](size_t bytes) -> void * { void *p = nullptr; if (rc) return p; hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 16)); if (e != hipSuccess) { rc = fail(MI_ERR_DEVICE, std::string("mi_debug_intersect_fused: ") + hipGetErrorString(e)); return nullptr; } bufs.push_back(p); return p; };
     auto chk = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = fail(MI_ERR_DEVICE, std::string("mi_debug_intersect_fused: ") + hipGetErrorString(e)); };
     Queues q{}; q.cap = cap; q.n_seg = nSeg;
-    float4 *dO = (float4 *) alloc(slots * 16), *dD = (float4 *) alloc(slots * 16);
+    const size_t rayBytes = anyHit ? sizeof(float4) : sizeof(QVec3);
+    void *dO = alloc(slots * rayBytes), *dD = alloc(slots * rayBytes);
     uint32_t *dCount = (uint32_t *) alloc((size_t) nSeg * 4), *dTicket = (uint32_t *) alloc(4); int *dMaxSp = (int *) alloc(4);
     q.counters = (unsigned long long *) alloc(32);
     const size_t spillEntries = (size_t) 3 * sc.bvh_depth + 4;
     q.stkSpill = (int32_t *) alloc(spillEntries * grid * 256u * 4);      // one column per lane of the grid (workgroups of 256)
-    if (anyHit) { q.shO = dO; q.shD = dD; q.shC = (float4 *) alloc(slots * 16); q.acc = (float4 *) alloc(n * 16); q.shCount = dCount; }
-    else { q.rayO[0] = dO; q.rayD[0] = dD; q.count[0] = dCount; q.hit = (float4 *) alloc(slots * 16); }
+    if (anyHit) { q.shO = (float4 *) dO; q.shD = (float4 *) dD; q.shC = (QVec3 *) alloc(slots * sizeof(QVec3)); q.acc = (float4 *) alloc(n * 16); q.shCount = dCount; }
+    else { q.rayO[0] = (QVec3 *) dO; q.rayD[0] = (QVec3 *) dD; q.rayT[0] = (float2 *) alloc(slots * sizeof(float2)); q.count[0] = dCount; q.hit = (float4 *) alloc(slots * 16); }
     if (!rc) {
-        chk(hipMemcpy(dO, hO.data(), slots * 16, hipMemcpyHostToDevice)); chk(hipMemcpy(dD, hD.data(), slots * 16, hipMemcpyHostToDevice));
+        chk(hipMemcpy(dO, anyHit ? (const void *) hO.data() : (const void *) hO3.data(), slots * rayBytes, hipMemcpyHostToDevice));
+        chk(hipMemcpy(dD, anyHit ? (const void *) hD.data() : (const void *) hD3.data(), slots * rayBytes, hipMemcpyHostToDevice));
         chk(hipMemcpy(dCount, segCounts, (size_t) nSeg * 4, hipMemcpyHostToDevice)); chk(hipMemset(dTicket, 0, 4)); chk(hipMemset(dMaxSp, 0, 4)); chk(hipMemset(q.counters, 0, 32));
-        if (anyHit) { chk(hipMemcpy(q.shC, hC.data(), slots * 16, hipMemcpyHostToDevice)); chk(hipMemset(q.acc, 0, n * 16)); }
-        else { std::vector<uint32_t> fill(slots * 4, sentinel); chk(hipMemcpy(q.hit, fill.data(), slots * 16, hipMemcpyHostToDevice)); }
+        if (anyHit) { chk(hipMemcpy(q.shC, hC.data(), slots * sizeof(QVec3), hipMemcpyHostToDevice)); chk(hipMemset(q.acc, 0, n * 16)); }
+        else {
+            chk(hipMemcpy(q.rayT[0], hT.data(), slots * sizeof(float2), hipMemcpyHostToDevice));
+            std::vector<uint32_t> fill(slots * 4, sentinel); chk(hipMemcpy(q.hit, fill.data(), slots * 16, hipMemcpyHostToDevice));
+        }
     }
     std::vector<float4> res(anyHit ? n : slots);
     if (!rc) {

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(WG) void k_direct(DScene sc, RenderConst rc, Direct
         float4 oA, oB, oC; uint4 oS0 = make_uint4(0, 0, 0, 0); float oPdf = 0, oCos = 0;
         if (i < n) {
             const uint32_t slot = segBase + i;
-            const float4 rd = qat(q.rayD[0], slot), hr = qat(q.hit, slot); const uint4 s0 = qat(q.st0[0], slot);
+            const auto rd = qRayDirection(q, 0, slot); const float4 hr = qat(q.hit, slot); const uint4 s0 = qat(q.st0[0], slot);
             const uint32_t pid = s0.x; const v3 d = V(rd.x, rd.y, rd.z);
             const uint32_t prim = __float_as_uint(hr.w);
             do {
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(WG) void k_direct(DScene sc, RenderConst rc, Direct
                     break;
                 }
                 v3 ro3 = V(0, 0, 0);
-                if (AN || TEX) { const float4 ro = qat(q.rayO[0], slot); ro3 = V(ro.x, ro.y, ro.z); }
+                if (AN || TEX) { const auto ro = qRayOrigin(q, 0, slot); ro3 = V(ro.x, ro.y, ro.z); }
                 const int inst = (AN && q.hitInst) ? qat(q.hitInst, slot) : -1;
                 Hit h;
                 fillHitAny<SMALL, AN>(sc, tb, inst, ro3, d, hr.x, hr.y, hr.z, prim, h);
@@ -142,9 +142,9 @@ __global__ __launch_bounds__(WG) void k_direct(DScene sc, RenderConst rc, Direct
         const unsigned long long m = __ballot(want);
         if (want) {
             const uint32_t o = segBase + out + (uint32_t) __popcll(m & lt);
-            if (!BS) { qat(q.shO, o) = oA; qat(q.shD, o) = oB; qat(q.shC, o) = oC; }
-            else {
-                qat(q.rayO[1], o) = oA; qat(q.rayD[1], o) = oB; qat(q.st0[1], o) = oS0; qat(q.st1[1], o) = oC; qat(q.st2[1], o) = oPdf;
+            if (!BS) { qat(q.shO, o) = oA; qat(q.shD, o) = oB; qSetShadowContribution(q, o, oC.x, oC.y, oC.z); }
+            else {      // the BSDF ray's interval is (Epsilon, inf) for every record: the extend launch knows it; no eta (direct.cpp never reads it)
+                qSetRayOrigin(q, 1, o, oA.x, oA.y, oA.z); qSetRayDirection(q, 1, o, oB.x, oB.y, oB.z); qat(q.st0[1], o) = oS0; qSetThroughput(q, 1, o, oC.x, oC.y, oC.z); qat(q.st2[1], o) = oPdf;
                 if (ENV && sc.env_constant) qat(q.st3[1], o) = oCos;
             }
         }

@@ -11,7 +11,7 @@ __global__ __launch_bounds__(WG) void k_direct_hit(DScene sc, RenderConst rc, Di
         const uint32_t n = q.count[1][seg]; const uint32_t segBase = seg * q.cap;
         for (uint32_t i = threadIdx.x; i < n; i += WG) {
             const uint32_t slot = segBase + i;
-            const float4 rd = qat(q.rayD[1], slot), hr = qat(q.hit, slot); const uint4 s0 = qat(q.st0[1], slot); const float4 s1 = qat(q.st1[1], slot);
+            const auto rd = qRayDirection(q, 1, slot), s1 = qThroughput(q, 1, slot); const float4 hr = qat(q.hit, slot); const uint4 s0 = qat(q.st0[1], slot);
             const float bsdfPdf = qat(q.st2[1], slot);
             const uint32_t pid = s0.x; const v3 d = V(rd.x, rd.y, rd.z), bsdfVal = V(s1.x, s1.y, s1.z);
             const bool facingRef = ((s0.w >> 16) & 1u) != 0, sampledDelta = ((s0.w >> 17) & 1u) != 0, sampledNull = ((s0.w >> 18) & 1u) != 0;
@@ -19,7 +19,7 @@ __global__ __launch_bounds__(WG) void k_direct_hit(DScene sc, RenderConst rc, Di
             v3 value; float lumPdf;
             if (prim == 0xFFFFFFFFu) {
                 if (!ENV || (rc.hide_emitters && sampledNull)) continue;      // :288
-                const float4 ro = qat(q.rayO[1], slot); float nearT, farT, pdfSA;
+                const auto ro = qRayOrigin(q, 1, slot); float nearT, farT, pdfSA;
                 if (sc.env_constant) {      // ConstantBackgroundEmitter::pdfDirect (constant.cpp:219-233): the reference normal of the camera hit
                     value = envEval(sc, d);
                     const float c = qat(q.st3[1], slot); pdfSA = c != 2.0f ? MI_INV_PI * maxf(0.0f, c) : MI_INV_FOURPI;
@@ -28,7 +28,7 @@ __global__ __launch_bounds__(WG) void k_direct_hit(DScene sc, RenderConst rc, Di
                 lumPdf = sampledDelta ? 0.0f : pdfSA * (loadEmitter(tb, sc.env_index).weight * sc.emitter_norm);
             } else {
                 v3 ro3 = V(0, 0, 0);
-                if (AN) { const float4 ro = qat(q.rayO[1], slot); ro3 = V(ro.x, ro.y, ro.z); }
+                if (AN) { const auto ro = qRayOrigin(q, 1, slot); ro3 = V(ro.x, ro.y, ro.z); }
                 const int inst = (AN && q.hitInst) ? qat(q.hitInst, slot) : -1;
                 Hit h;
                 fillHitAny<false, AN>(sc, tb, inst, ro3, d, hr.x, hr.y, hr.z, prim, h);

@@ -60,7 +60,7 @@ DEV void fieldEval(const DScene &sc, const FieldArgs &fa, const Queues &q, uint6
         for (int f = 0; f < MI_MAX_FIELDS; ++f) if ((uint32_t) f < fa.n) { out[3 * f] = fa.undefined[f][0]; out[3 * f + 1] = fa.undefined[f][1]; out[3 * f + 2] = fa.undefined[f][2]; }
         return;
     }
-    const float4 ro = q.rayO[0][pid], rd = q.rayD[0][pid];
+    const auto ro = qRayOrigin(q, 0, (uint32_t) pid), rd = qRayDirection(q, 0, (uint32_t) pid);
     const v3 o = V(ro.x, ro.y, ro.z), d = V(rd.x, rd.y, rd.z); const float t = hr.x, u = hr.y, v = hr.z;
     const int inst = (sc.n_instances && q.hitInst) ? q.hitInst[pid] : -1;
     const Tabs<false> tb = globalTabs(sc);

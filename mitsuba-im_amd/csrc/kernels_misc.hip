@@ -8,6 +8,7 @@
 template <bool LENS>
 __global__ __launch_bounds__(WG) void k_generate(DScene sc, RenderConst rc, Queues q, BatchDesc bd) {
     const uint32_t tid = threadIdx.x;
+    const bool storeState = rc.integrator == MI_INTEGRATOR_VOLPATH_SIMPLE || rc.integrator == MI_INTEGRATOR_VOLPATH;      // launch-uniform: the volumetric shade stages load the state at depth 1
     for (uint32_t seg = blockIdx.x; seg < q.n_seg; seg += gridDim.x) {
     const uint64_t segBase = (uint64_t) seg * q.cap;
     uint64_t remaining = bd.n_paths > segBase ? bd.n_paths - segBase : 0;
@@ -48,13 +49,15 @@ __global__ __launch_bounds__(WG) void k_generate(DScene sc, RenderConst rc, Queu
             else next2D(ss, 0, SobolTab{nullptr, 0, 0}, ax, ay);
             lensRay(sc, sx, sy, ax, ay, o, d, mint, maxt);
         } else cameraRay(sc, sx, sy, o, d, mint, maxt);
-        const uint64_t slot = segBase + i;
-        q.rayO[0][slot] = make_float4(o.x, o.y, o.z, mint);
-        q.rayD[0][slot] = make_float4(d.x, d.y, d.z, maxt);
+        const uint32_t slot = (uint32_t) (segBase + i);
+        qSetRayOrigin(q, 0, slot, o.x, o.y, o.z); qSetRayDirection(q, 0, slot, d.x, d.y, d.z);
+        qSetRayInterval(q, 0, slot, mint, maxt);                    // the near and far clip along this ray: the one interval the surface integrators do not know at launch
         // packed: dim | depth << 8 | flags << 16   (flags bit0: facingRef of the previous vertex)
         q.st0[0][slot] = make_uint4((uint32_t) pid, ss.a, ss.b, ss.dim | (1u << 8) | rc.state_init);
-        q.st1[0][slot] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);      // throughput rgb, eta
-        q.st2[0][slot] = 0.0f;                                      // bsdfPdf of the segment that produced this ray
+        if (storeState) {      // throughput (1,1,1), eta 1, bsdfPdf 0 of the segment that produced this ray: constants of the first launch everywhere else (shade.h; direct / ao never read them)
+            qSetThroughput(q, 0, slot, 1.0f, 1.0f, 1.0f); qSetEta(q, 0, slot, 1.0f);
+            q.st2[0][slot] = 0.0f;
+        }
         q.pos[pid] = make_float2(sx, sy);
         q.acc[pid] = make_float4(0, 0, 0, 1.0f);        // Li rgb, alpha (newQuery: alpha = 1, integrator.h:223-229)
     }
@@ -69,7 +72,7 @@ __global__ __launch_bounds__(WG) void k_env_primary(DScene sc, RenderConst rc, Q
         const uint32_t n = q.count[buf][seg]; const uint64_t segBase = (uint64_t) seg * q.cap;
         for (uint32_t i = threadIdx.x; i < n; i += WG) {
             if (__float_as_uint(q.hit[segBase + i].w) != 0xFFFFFFFFu) continue;
-            const float4 rd = q.rayD[buf][segBase + i]; const uint4 s0 = q.st0[buf][segBase + i]; const uint32_t pid = s0.x;
+            const auto rd = qRayDirection(q, buf, (uint32_t) (segBase + i)); const uint4 s0 = q.st0[buf][segBase + i]; const uint32_t pid = s0.x;
             const v3 d = V(rd.x, rd.y, rd.z); const float2 sp = q.pos[pid];
             v3 rxd, ryd; sensorDifferentials(sc, rc, SobolTab{rc.sobol_nib, rc.nib_count, rc.sobol_scramble}, s0.y, s0.z, sp.x, sp.y, d, rxd, ryd);
             const v3 value = envEvalFiltered(sc, d, rxd, ryd);
@@ -198,7 +201,7 @@ __global__ void k_debug_camera_lens(DScene sc, const float *pos, const float *ap
 __global__ void k_debug_sensor_differentials(DScene sc, RenderConst rc, Queues q, uint64_t n, float *out) {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint4 s0 = q.st0[0][i]; const float4 rd = q.rayD[0][i]; const float2 sp = q.pos[s0.x];
+    const uint4 s0 = q.st0[0][i]; const auto rd = qRayDirection(q, 0, (uint32_t) i); const float2 sp = q.pos[s0.x];
     const SobolTab st{rc.sobol_nib, rc.nib_count, rc.sobol_scramble};
     float ax = 0.5f, ay = 0.5f; if (sc.lens_radius != 0.0f) lensSampleOfPath(rc.sampler, st, s0.y, s0.z, ax, ay);
     v3 rxd, ryd; sensorDifferentials(sc, rc, st, s0.y, s0.z, sp.x, sp.y, V(rd.x, rd.y, rd.z), rxd, ryd);

@@ -8,7 +8,7 @@
 // ---------------------------------------------------------------------------------------------- extend
 // Scene::rayIntersect -> ShapeKDTree::rayIntersect (src/librender/skdtree.cpp:112-142): closest hit (t, u, v, prim)
 template <int STACK, int AN, bool WIDE>   // STACK = 0: packet mode; else LDS stack entries per lane (>= the tree's stack need); AN: bit 0 analytic shapes, bit 1 instances; WIDE: 4-wide quantised nodes
-__global__ __launch_bounds__(WG) void k_extend(DScene sc, Queues q, int buf) {
+__global__ __launch_bounds__(WG) void k_extend(DScene sc, Queues q, int buf, int ownInterval) {      // ownInterval (launch-uniform): every ray has its (mint, maxt) in the side array; else all take (Epsilon, inf)
     __shared__ int s_stk[(STACK > 0 ? STACK : 1) * WG];
     __shared__ f4 s_exact[STACK > 0 ? 1 : MI_PACKET_MAX * 3];
     const uint32_t tid = threadIdx.x;
@@ -19,10 +19,12 @@ __global__ __launch_bounds__(WG) void k_extend(DScene sc, Queues q, int buf) {
     const uint64_t segBase = (uint64_t) seg * q.cap;
     rays += n;
     for (uint32_t i = tid; i < n; i += WG) {
-        float4 ro = q.rayO[buf][segBase + i], rd = q.rayD[buf][segBase + i];
+        const uint32_t slot = (uint32_t) (segBase + i);
+        const auto ro = qRayOrigin(q, buf, slot), rd = qRayDirection(q, buf, slot);
+        float2 iv = make_float2(MI_EPSILON, INFINITY); if (ownInterval) iv = qRayInterval(q, buf, slot);
         v3 o = V(ro.x, ro.y, ro.z), d = V(rd.x, rd.y, rd.z);
         float mint, maxt, t = 0, u = 0, v = 0; uint32_t prim = 0xFFFFFFFFu; bool hit = false; int inst = -1;
-        if (clipInterval(sc, o, d, ro.w, rd.w, false, mint, maxt)) {
+        if (clipInterval(sc, o, d, iv.x, iv.y, false, mint, maxt)) {
             if (STACK == 0) hit = packetIntersect<false, AN>(sc, (AS<true>::p4) s_exact, o, d, mint, maxt, t, prim, u, v);
             else hit = traverse<false, AN, WIDE>(sc, o, d, mint, maxt, s_stk + tid, t, prim, u, v, inst);
         }
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(WG) void k_shadow(DScene sc, Queues q) {
             else occluded = traverse<true, AN, WIDE>(sc, o, d, mint, maxt, s_stk + tid, t, prim, u, v, inst);
         }
         if (!occluded) {
-            float4 c = q.shC[segBase + i]; const uint32_t pid = __float_as_uint(sd.w);
+            const auto c = qShadowContribution(q, (uint32_t) (segBase + i)); const uint32_t pid = __float_as_uint(sd.w);
             float4 a = q.acc[pid]; a.x += c.x; a.y += c.y; a.z += c.z; q.acc[pid] = a;
         }
     }
@@ -65,22 +67,22 @@ __global__ __launch_bounds__(WG) void k_shadow(DScene sc, Queues q) {
 
 // ---------------------------------------------------------------------------------------------- fused walk (trace_fused.h): triangle-only trees
 template <bool WIDE>
-__global__ __launch_bounds__(WG) void k_extend_f(DScene sc, Queues q, int buf, uint32_t *ticket, uint32_t thr) {
+__global__ __launch_bounds__(WG) void k_extend_f(DScene sc, Queues q, int buf, int ownInterval, uint32_t *ticket, uint32_t thr) {
     __shared__ int s_lds[FZ_LDS_WORDS];
-    fusedStage<false, WIDE>(sc, q, buf, ticket, thr, s_lds);
+    fusedStage<false, WIDE>(sc, q, buf, ownInterval, ticket, thr, s_lds);
 }
 template <bool WIDE>
 __global__ __launch_bounds__(WG) void k_shadow_f(DScene sc, Queues q, uint32_t *ticket, uint32_t thr) {
     __shared__ int s_lds[FZ_LDS_WORDS];
-    fusedStage<true, WIDE>(sc, q, 0, ticket, thr, s_lds);
+    fusedStage<true, WIDE>(sc, q, 0, 0, ticket, thr, s_lds);
 }
 
 // The same walk for mi_debug_intersect_fused (tests/test_gpu_fused_walk.py): the caller lays the rays into segments, picks the refill threshold, the grid and the LDS
 // stack size (LS = 4 drives shallow trees through the spill path), and reads back the deepest stack any ray needed.
 template <bool ANY, bool WIDE, int LS>
-__global__ __launch_bounds__(WG) void k_debug_fused(DScene sc, Queues q, uint32_t *ticket, uint32_t thr, int *maxSp) {
+__global__ __launch_bounds__(WG) void k_debug_fused(DScene sc, Queues q, int ownInterval, uint32_t *ticket, uint32_t thr, int *maxSp) {
     __shared__ int s_lds[(LS + 10) * WG];
-    fusedStage<ANY, WIDE, LS, true>(sc, q, 0, ticket, thr, s_lds, maxSp);
+    fusedStage<ANY, WIDE, LS, true>(sc, q, 0, ownInterval, ticket, thr, s_lds, maxSp);
 }
 
 // ---------------------------------------------------------------------------------------------- unit-level entry point (parity tests)
@@ -148,9 +150,9 @@ static const bool kForceStack24 = getenv("MI355PT_STACK24") != nullptr;      // 
     if (sc.packet_n) hipLaunchKernelGGL((KERNEL<0, (AN) & 1, false>), dim3(grid), dim3(WG), 0, st, __VA_ARGS__); \
     else if (sc.bvh_wide) MI_BY_STACK_W(KERNEL, AN, true, __VA_ARGS__); \
     else MI_BY_STACK_W(KERNEL, AN, false, __VA_ARGS__); } while (0)
-void mi_launch_extend(const DScene &sc, const Queues &q, int buf, uint32_t grid, hipStream_t st) {
+void mi_launch_extend(const DScene &sc, const Queues &q, int buf, int ownInterval, uint32_t grid, hipStream_t st) {
     const int mode = (sc.n_analytic ? 1 : 0) | (sc.n_instances ? 2 : 0);
-    if (mode == 3) MI_BY_STACK(k_extend, 3, sc, q, buf); else if (mode == 2) MI_BY_STACK(k_extend, 2, sc, q, buf); else if (mode == 1) MI_BY_STACK(k_extend, 1, sc, q, buf); else MI_BY_STACK(k_extend, 0, sc, q, buf);
+    if (mode == 3) MI_BY_STACK(k_extend, 3, sc, q, buf, ownInterval); else if (mode == 2) MI_BY_STACK(k_extend, 2, sc, q, buf, ownInterval); else if (mode == 1) MI_BY_STACK(k_extend, 1, sc, q, buf, ownInterval); else MI_BY_STACK(k_extend, 0, sc, q, buf, ownInterval);
 }
 void mi_launch_shadow(const DScene &sc, const Queues &q, uint32_t grid, hipStream_t st) {
     const int mode = (sc.n_analytic ? 1 : 0) | (sc.n_instances ? 2 : 0);
@@ -166,9 +168,9 @@ static const uint32_t kFusedGrid = [] { const char *e = getenv("MI355PT_FUSED_GR
 // wide (4-way) trees only: on the small binary trees the while-while kernels win (Veach-MIS 1080p: 1931 vs 1454 Msamples/s), MI355PT_FUSED=2 forces it there too
 bool mi_fused_walk(const DScene &sc) { return kFused && (sc.bvh_wide || kFused == 2) && !sc.packet_n && !sc.n_analytic && !sc.n_instances && sc.geo_bytes < 0xFFFFFF00ull; }
 uint32_t mi_fused_grid(void) { return kFusedGrid; }
-void mi_launch_extend_fused(const DScene &sc, const Queues &q, int buf, uint32_t *ticket, hipStream_t st) {
+void mi_launch_extend_fused(const DScene &sc, const Queues &q, int buf, int ownInterval, uint32_t *ticket, hipStream_t st) {
     const uint32_t g = kFusedGrid;
-    if (sc.bvh_wide) hipLaunchKernelGGL((k_extend_f<true>), dim3(g), dim3(WG), 0, st, sc, q, buf, ticket, kFusedThr); else hipLaunchKernelGGL((k_extend_f<false>), dim3(g), dim3(WG), 0, st, sc, q, buf, ticket, kFusedThr);
+    if (sc.bvh_wide) hipLaunchKernelGGL((k_extend_f<true>), dim3(g), dim3(WG), 0, st, sc, q, buf, ownInterval, ticket, kFusedThr); else hipLaunchKernelGGL((k_extend_f<false>), dim3(g), dim3(WG), 0, st, sc, q, buf, ownInterval, ticket, kFusedThr);
 }
 void mi_launch_shadow_fused(const DScene &sc, const Queues &q, uint32_t *ticket, hipStream_t st) {
     const uint32_t g = kFusedGrid;
@@ -176,9 +178,10 @@ void mi_launch_shadow_fused(const DScene &sc, const Queues &q, uint32_t *ticket,
 }
 // ldsStack: 4 or FZ_LDS_STACK (mi_debug_intersect_fused checks it)
 void mi_launch_debug_fused(const DScene &sc, const Queues &q, int anyHit, uint32_t ldsStack, uint32_t *ticket, uint32_t thr, uint32_t grid, int *maxSp, hipStream_t st) {
+    const int ownInterval = anyHit ? 0 : 1;      // the caller's extension rays bring their own (mint, maxt)
 #define MI_DBG_FUSED(ANY, WIDE) do { \
-    if (ldsStack == 4u) hipLaunchKernelGGL((k_debug_fused<ANY, WIDE, 4>), dim3(grid), dim3(WG), 0, st, sc, q, ticket, thr, maxSp); \
-    else hipLaunchKernelGGL((k_debug_fused<ANY, WIDE, FZ_LDS_STACK>), dim3(grid), dim3(WG), 0, st, sc, q, ticket, thr, maxSp); } while (0)
+    if (ldsStack == 4u) hipLaunchKernelGGL((k_debug_fused<ANY, WIDE, 4>), dim3(grid), dim3(WG), 0, st, sc, q, ownInterval, ticket, thr, maxSp); \
+    else hipLaunchKernelGGL((k_debug_fused<ANY, WIDE, FZ_LDS_STACK>), dim3(grid), dim3(WG), 0, st, sc, q, ownInterval, ticket, thr, maxSp); } while (0)
     if (anyHit) { if (sc.bvh_wide) MI_DBG_FUSED(true, true); else MI_DBG_FUSED(true, false); }
     else { if (sc.bvh_wide) MI_DBG_FUSED(false, true); else MI_DBG_FUSED(false, false); }
 #undef MI_DBG_FUSED

@@ -25,8 +25,8 @@ __global__ __launch_bounds__(WG) void k_shade_vol(DScene sc, RenderConst rc, Que
         ShadowRec sh, al; float4 nrO, nrD, nS1; uint4 nS0;
         if (i < n) {
             const uint64_t slot = out.segBase + i;
-            const float4 ro = q.rayO[buf][slot], rd = q.rayD[buf][slot], hr = q.hit[slot]; const uint4 s0 = q.st0[buf][slot];
-            SamplerState ss; uint32_t pid; int depth, medium; v3 T; float eta; unpackPathState(s0, q.st1[buf][slot], pid, ss, depth, medium, T, eta);
+            float4 ro, rd; loadRayWithInterval(q, buf, slot, ro, rd); const float4 hr = q.hit[slot]; const uint4 s0 = q.st0[buf][slot];
+            SamplerState ss; uint32_t pid; int depth, medium; v3 T; float eta; unpackPathState(s0, loadThroughputEta(q, buf, slot), pid, ss, depth, medium, T, eta);
             uint32_t fl = s0.w & (VS_EMITTED | VS_OTHERS | VS_NULLCHAIN | VS_SCATTERED);
             const v3 o = V(ro.x, ro.y, ro.z), d = V(rd.x, rd.y, rd.z);
             const uint32_t prim = __float_as_uint(hr.w); const float tHit = prim == 0xFFFFFFFFu ? INFINITY : hr.x;
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(WG) void k_shade_vol(DScene sc, RenderConst rc, Que
         const uint64_t wE = out.backRecord(q, wantAlpha), wS = out.frontRecord(wantShadow), wA = out.survivor(alive);
         if (wantAlpha) { q.shO[wE] = al.o; q.shD[wE] = al.d; }
         if (wantShadow) storeShadowRecord(q, wS, sh);
-        if (alive) { q.rayO[nb][wA] = nrO; q.rayD[nb][wA] = nrD; q.st0[nb][wA] = nS0; q.st1[nb][wA] = nS1; q.st2[nb][wA] = 0.0f; }
+        if (alive) { storeRayWithInterval(q, nb, wA, nrO, nrD); q.st0[nb][wA] = nS0; storeThroughputEta(q, nb, wA, nS1); q.st2[nb][wA] = 0.0f; }
     });
     waveAddCounter(&q.counters[2], pathLen, lane);
 }

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(WG) void k_shade_volmis(DScene sc, RenderConst rc, 
         ShadowRec sh, se, al; float4 nrO, nrD, nS1; uint4 nS0; float nS2 = 0, nS3 = 2.0f;
         if (i < n) {
             const uint64_t slot = out.segBase + i;
-            const float4 ro = q.rayO[buf][slot], rd = q.rayD[buf][slot], hr = q.hit[slot]; const uint4 s0 = q.st0[buf][slot]; const float4 s1 = q.st1[buf][slot]; const float prevPdf = q.st2[buf][slot]; const float prevCos = (ENV && sc.env_constant) ? q.st3[buf][slot] : 2.0f;
+            float4 ro, rd; loadRayWithInterval(q, buf, slot, ro, rd); const float4 hr = q.hit[slot]; const uint4 s0 = q.st0[buf][slot]; const float4 s1 = loadThroughputEta(q, buf, slot); const float prevPdf = q.st2[buf][slot]; const float prevCos = (ENV && sc.env_constant) ? q.st3[buf][slot] : 2.0f;
             SamplerState ss; uint32_t pid; int depth, medium; v3 T; float eta; unpackPathState(s0, s1, pid, ss, depth, medium, T, eta);
             uint32_t fl = s0.w;
             const v3 o = V(ro.x, ro.y, ro.z), d = V(rd.x, rd.y, rd.z);
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(WG) void k_shade_volmis(DScene sc, RenderConst rc, 
         if (wantSearch) storeShadowRecord(q, wE, se);
         else if (wantAlpha) { q.shO[wE] = al.o; q.shD[wE] = al.d; }
         if (wantShadow) storeShadowRecord(q, wS, sh);
-        if (alive) { q.rayO[nb][wA] = nrO; q.rayD[nb][wA] = nrD; q.st0[nb][wA] = nS0; q.st1[nb][wA] = nS1; q.st2[nb][wA] = nS2; if (ENV && sc.env_constant) q.st3[nb][wA] = nS3; }
+        if (alive) { storeRayWithInterval(q, nb, wA, nrO, nrD); q.st0[nb][wA] = nS0; storeThroughputEta(q, nb, wA, nS1); q.st2[nb][wA] = nS2; if (ENV && sc.env_constant) q.st3[nb][wA] = nS3; }
     });
     waveAddCounter(&q.counters[2], pathLen, lane);
 }
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(WG) void k_shadow_volmis(DScene sc, Queues q) {
                 // ---- kind 1: rayIntersectAndLookForEmitter behind the first index-matched boundary (volpath.cpp:381-419); interactions = 1 so far
                 int medium = recordMedium(bits); const int maxInteractions = recordMaxInteractions(bits);
                 v3 o = V(so.x, so.y, so.z); const v3 d = V(sd.x, sd.y, sd.z);
-                const float4 c = q.shC[w]; v3 tr = V(c.x, c.y, c.z); int interactions = 1; bool surface = false; Hit h; float t = INFINITY;
+                const float4 c = qShadowContributionWide(q, w); v3 tr = V(c.x, c.y, c.z); int interactions = 1; bool surface = false; Hit h; float t = INFINITY;
                 while (true) {
                     float mint, maxt, u = 0, v = 0; uint32_t prim = 0xFFFFFFFFu; int inst = -1; t = INFINITY; surface = false;
                     ++normalRays;                                                    // Scene::rayIntersect(ray, its): a "normal" ray (skdtree.cpp:118)

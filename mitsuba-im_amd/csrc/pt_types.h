@@ -182,6 +182,7 @@ struct RenderConst {
     float alpha_dist;                     // volumetric integrators, EOpacity: twice the radius of the scene's bounding sphere (records.inl:128-134)
     uint32_t state_init;                  // bits ORed into the state word st0.w of a fresh path (volumetric integrators: radiance-type bits, the sensor's medium)
     uint32_t order_offset_words;          // dynamic-LDS offset of the material-sort index list (0 = no sorting); set per launch
+    uint32_t first_bounce;                // k_shade: this launch sees the fresh paths of k_generate (throughput 1, eta 1, bsdfPdf 0 are not in the queues); set per launch
 };
 // The state word st0.w of the volumetric integrators (volume.h unpacks and repacks it, api.cpp composes state_init).  Bits 17 / 18 and 28 / 29 belong to one integrator each.
 #define VS_DIM_MASK 0xFFu              // bits 0..7 sampler dimension

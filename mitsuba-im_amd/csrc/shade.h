@@ -63,17 +63,20 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
         //   A: tail of the previous bounce, emitted radiance, emitter sampling  -> shadow queue
         //   B: BSDF sampling                                                     -> next ray / state
         bool alive = false, wantShadow = false, toSample = false;
-        float4 shO, shD, shC;
+        float4 shO, shD; v3 shC = V(0, 0, 0);
         Hit h; SurfaceBsdf sf; SamplerState ss; v3 T = V(0, 0, 0); float eta = 1.0f; uint32_t pid = 0; int depth = 0; bool unscattered = false;   // sf: the resolved surface (surface.h) -- leaf record, mask opacity (RC variants), perturbed frame and coating (WRAP variants)
         if (i < n) {
             const uint32_t slot = segBase + (doSort ? (uint32_t) s_order[i] : i);
-            float4 rd = qat(q.rayD[buf], slot), hr = qat(q.hit, slot); uint4 s0 = qat(q.st0[buf], slot); float4 s1 = qat(q.st1[buf], slot);
-            float prevPdf = qat(q.st2[buf], slot);
+            const auto rd = qRayDirection(q, buf, slot); float4 hr = qat(q.hit, slot); uint4 s0 = qat(q.st0[buf], slot);
+            // the first launch of a batch (rc.first_bounce, launch-uniform) sees fresh paths only: throughput (1,1,1), eta 1, bsdfPdf 0 -- k_generate stores none of them.
+            // eta leaves 1 only through a BSDF of the RC variants (every sampler of the others sets it to 1, pt_device.h bsdfSample): they alone have the array
+            float prevPdf = 0.0f; T = V(1, 1, 1);
+            if (!rc.first_bounce) { const auto s1 = qThroughput(q, buf, slot); T = V(s1.x, s1.y, s1.z); prevPdf = qat(q.st2[buf], slot); if (RC) eta = qEta(q, buf, slot); }
             pid = s0.x; ss.a = s0.y; ss.b = s0.z; ss.dim = s0.w & 0xFFu;
             depth = (int) ((s0.w >> 8) & 0xFFu); const bool facingRef = ((s0.w >> 16) & 1u) != 0;
             const bool prevDelta = RC && ((s0.w >> 17) & 1u) != 0;      // the BSDF sample that spawned this ray was a delta component -> lumPdf = 0 (path.cpp:259-260)
             unscattered = RC && ((s0.w >> 18) & 1u) != 0;    // every component sampled so far was ENull (thin dielectric panes): `scattered` is still false (path.cpp:213)
-            v3 d = V(rd.x, rd.y, rd.z); T = V(s1.x, s1.y, s1.z); eta = s1.w;
+            v3 d = V(rd.x, rd.y, rd.z);
             const uint32_t prim = __float_as_uint(hr.w);
             v3 add = V(0, 0, 0); bool haveAdd = false;
             do {
@@ -90,7 +93,7 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
                             // BSDF ray left the scene: env->evalEnvironment + fillDirectSamplingRecord (envmap.cpp:362-378), MIS term path.cpp:257-264
                             // (the ray origin is only needed for the bounding-sphere test: it is requested first and consumed after the environment lookup, whose
                             // atan2f / acosf and texel fetches then cover its round trip to HBM)
-                            const float4 ro = qat(q.rayO[buf], slot); float nearT, farT;
+                            const auto ro = qRayOrigin(q, buf, slot); float nearT, farT;
                             if (!(rc.hide_emitters && unscattered)) {   // path.cpp:238-239: hideEmitters && !scattered
                                 v3 value; float pdfSA;
                                 if (sc.env_constant) {      // ConstantBackgroundEmitter::pdfDirect (constant.cpp:219-233): needs the reference normal of the previous vertex
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
                     break;
                 }
                 v3 ro3 = V(0, 0, 0);
-                if (AN) { float4 ro = qat(q.rayO[buf], slot); ro3 = V(ro.x, ro.y, ro.z); }      // analytic shapes: hit point = o + t d; sphere lights: reference point of pdfDirect
+                if (AN) { const auto ro = qRayOrigin(q, buf, slot); ro3 = V(ro.x, ro.y, ro.z); }      // analytic shapes: hit point = o + t d; sphere lights: reference point of pdfDirect
                 const int inst = (AN && q.hitInst) ? qat(q.hitInst, slot) : -1;
                 fillHitAny<SMALL, AN>(sc, tb, inst, ro3, d, hr.x, hr.y, hr.z, prim, h);
                 if (depth > 1) {
@@ -153,7 +156,7 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
                             wantShadow = true;
                             shO = make_float4(h.p.x, h.p.y, h.p.z, dr.dist * (1 - MI_SHADOW_EPSILON));
                             shD = make_float4(dr.d.x, dr.d.y, dr.d.z, __uint_as_float(pid));
-                            shC = make_float4(c.x, c.y, c.z, 0.0f);
+                            shC = c;
                         }
                     }
                 }
@@ -165,10 +168,10 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
         const unsigned long long mS = __ballot(wantShadow);
         if (wantShadow) {
             const uint32_t o = segBase + outS + (uint32_t) __popcll(mS & lt);
-            qat(q.shO, o) = shO; qat(q.shD, o) = shD; qat(q.shC, o) = shC;
+            qat(q.shO, o) = shO; qat(q.shD, o) = shD; qSetShadowContribution(q, o, shC.x, shC.y, shC.z);
         }
         outS += (uint32_t) __popcll(mS);
-        float4 nrO, nrD, nS1; uint4 nS0; float nS2 = 0, nS3 = 0;
+        v3 nrO = V(0, 0, 0), nrD = V(0, 0, 0); uint4 nS0; float nS2 = 0, nS3 = 0;      // (the bounce ray's interval is (Epsilon, inf) for every survivor: the next extend launch knows it)
         if (toSample) {
             // BSDF sampling (path.cpp:207-226)
             float bPdf = 0, bEta = 1; v3 woL = V(0, 0, 0);
@@ -187,20 +190,20 @@ __global__ __launch_bounds__(WG, MI_SHADE_MIN_WAVES) void k_shade(DScene sc, Ren
             else {
                 T = T * bw; eta *= bEta;
                 alive = true;
-                nrO = make_float4(h.p.x, h.p.y, h.p.z, MI_EPSILON);
-                nrD = make_float4(wo.x, wo.y, wo.z, INFINITY);
+                nrO = h.p; nrD = wo;
                 v3 refN = (h.flags & 2u) ? V(0, 0, 0) : h.ns;           // records.inl:160-164
                 const float cosRef = dot(wo, refN);
                 uint32_t fl = cosRef >= 0 ? 1u : 0u;
                 nS3 = (h.flags & 2u) ? 2.0f : cosRef;
                 nS0 = make_uint4(pid, ss.a, ss.b, (ss.dim & 0xFFu) | ((uint32_t) (depth + 1) << 8) | (fl << 16) | ((RC && sampledDelta) ? (1u << 17) : 0u) | ((RC && sampledNull && (depth == 1 || unscattered)) ? (1u << 18) : 0u));
-                nS1 = make_float4(T.x, T.y, T.z, eta); nS2 = bPdf;
+                nS2 = bPdf;
             }
         }
         const unsigned long long mA = __ballot(alive);
         if (alive) {
             const uint32_t o = segBase + outA + (uint32_t) __popcll(mA & lt);
-            qat(q.rayO[nb], o) = nrO; qat(q.rayD[nb], o) = nrD; qat(q.st0[nb], o) = nS0; qat(q.st1[nb], o) = nS1; qat(q.st2[nb], o) = nS2;
+            qSetRayOrigin(q, nb, o, nrO.x, nrO.y, nrO.z); qSetRayDirection(q, nb, o, nrD.x, nrD.y, nrD.z); qat(q.st0[nb], o) = nS0; qSetThroughput(q, nb, o, T.x, T.y, T.z); qat(q.st2[nb], o) = nS2;
+            if (RC) qSetEta(q, nb, o, eta);
             if (ENV && sc.env_constant) qat(q.st3[nb], o) = nS3;
         }
         outA += (uint32_t) __popcll(mA);

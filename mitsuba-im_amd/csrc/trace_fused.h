@@ -36,7 +36,7 @@ DEV float fastInv(float d) { const float a = fabsf(d) < 1e-30f ? copysignf(1e-30
 // LS: stack entries per lane kept in LDS (s_lds holds (LS + 10) * WG words); production runs LS = FZ_LDS_STACK.  DBG (mi_debug_intersect_fused only): every retired
 // ray adds the deepest stack it saw to *dbgMaxSp with one atomicMax.
 template <bool ANY, bool WIDE, int LS = FZ_LDS_STACK, bool DBG = false>
-DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *ticket, const uint32_t thr, int *s_lds, int *dbgMaxSp = nullptr) {
+DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, const int ownInterval, uint32_t *ticket, const uint32_t thr, int *s_lds, int *dbgMaxSp = nullptr) {      // ownInterval (!ANY, launch-uniform): the rays' (mint, maxt) are in the side array, else (Epsilon, inf)
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const unsigned long long lt = (1ull << lane) - 1ull;
     int *stk = s_lds + tid;
@@ -45,7 +45,6 @@ DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *
     const char *geo = reinterpret_cast<const char *>(sc.nodes);
     const uint32_t triOff = (uint32_t) (reinterpret_cast<const char *>(sc.tris) - geo);      // mi_fused_walk: nodes + leaf records are one allocation smaller than 4 GB
     const uint32_t *segCount = ANY ? q.shCount : q.count[buf];
-    const float4 *rO = ANY ? q.shO : q.rayO[buf], *rD = ANY ? q.shD : q.rayD[buf];
     // per-lane ray (o and d live in LDS for the triangle test, 1 / d and -o / d in registers for the box tests)
     v3 inv = V(0, 0, 0), oi = V(0, 0, 0);
     float mint = 0, best = 0, bu = 0, bv = 0; uint32_t bprim = 0xFFFFFFFFu, pid = 0; uint64_t slot = 0;
@@ -68,18 +67,21 @@ DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *
                 const uint32_t rank = (uint32_t) __popcll(idle & lt);
                 if (((idle >> lane) & 1ull) && rank < take) {
                     slot = (uint64_t) seg * q.cap + nxt + rank;
-                    const float4 ro = rO[slot], rd = rD[slot];
-                    const v3 o = V(ro.x, ro.y, ro.z), d = V(rd.x, rd.y, rd.z);
+                    v3 o, d; float t0 = MI_EPSILON, t1 = INFINITY;
+                    if (ANY) { const float4 ro = q.shO[slot], rd = q.shD[slot]; o = V(ro.x, ro.y, ro.z); d = V(rd.x, rd.y, rd.z); t1 = ro.w; pid = __float_as_uint(rd.w); }
+                    else {
+                        const auto ro = qRayOrigin(q, buf, (uint32_t) slot), rd = qRayDirection(q, buf, (uint32_t) slot); o = V(ro.x, ro.y, ro.z); d = V(rd.x, rd.y, rd.z);
+                        if (ownInterval) { const float2 iv = qRayInterval(q, buf, (uint32_t) slot); t0 = iv.x; t1 = iv.y; }
+                    }
                     float maxt;
-                    const bool inside = ANY ? clipInterval(sc, o, d, MI_EPSILON, ro.w, true, mint, maxt) : clipInterval(sc, o, d, ro.w, rd.w, false, mint, maxt);
-                    if (ANY) pid = __float_as_uint(rd.w);
+                    const bool inside = clipInterval(sc, o, d, t0, t1, ANY, mint, maxt);
                     if (inside) {
                         inv = V(fastInv(d.x), fastInv(d.y), fastInv(d.z)); oi = V(-o.x * inv.x, -o.y * inv.y, -o.z * inv.z);      // 1-ulp reciprocals: the box tests are conservative culling only (2e-6 slack)
                         rayL[0] = o.x; rayL[WG] = o.y; rayL[2 * WG] = o.z; rayL[3 * WG] = o.x; rayL[4 * WG] = o.y;
                         rayL[5 * WG] = d.x; rayL[6 * WG] = d.y; rayL[7 * WG] = d.z; rayL[8 * WG] = d.x; rayL[9 * WG] = d.y;
                         best = maxt; bprim = 0xFFFFFFFFu; bu = 0; bv = 0; cur = 0; sp = 0; if (DBG) spMax = 0;
                     } else if (ANY) {                // the segment misses the scene box: unoccluded
-                        const float4 c = q.shC[slot]; float4 a = q.acc[pid]; a.x += c.x; a.y += c.y; a.z += c.z; q.acc[pid] = a;
+                        const auto c = qShadowContribution(q, (uint32_t) slot); float4 a = q.acc[pid]; a.x += c.x; a.y += c.y; a.z += c.z; q.acc[pid] = a;
                     } else q.hit[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
                 }
                 nxt += take;
@@ -166,7 +168,7 @@ DEV void fusedStage(const DScene &sc, const Queues &q, const int buf, uint32_t *
             cur = FZ_IDLE;
             if (DBG) atomicMax(dbgMaxSp, spMax);
             if (ANY) {
-                if (bprim == 0xFFFFFFFFu) { const float4 c = q.shC[slot]; float4 a = q.acc[pid]; a.x += c.x; a.y += c.y; a.z += c.z; q.acc[pid] = a; }
+                if (bprim == 0xFFFFFFFFu) { const auto c = qShadowContribution(q, (uint32_t) slot); float4 a = q.acc[pid]; a.x += c.x; a.y += c.y; a.z += c.z; q.acc[pid] = a; }
             } else q.hit[slot] = make_float4(best, bu, bv, __uint_as_float(bprim));      // a miss keeps t = the far end of the clipped interval, like traverse()
         }
     }

@@ -42,6 +42,17 @@ DEV SobolTabLds stageSobolTables(const RenderConst &rc, uint32_t *s_nib, uint32_
     if (rc.sampler == 1) { const uint32_t nibWords = rc.nib_dims * rc.nib_count * 16u; for (uint32_t i = tid; i < nibWords; i += WG) s_nib[i] = rc.sobol_nib[i]; }
     return SobolTabLds{(lds_u32_ptr) s_nib, rc.nib_count, rc.sobol_scramble};
 }
+// The volumetric stages hold a ray as (o | mint), (d | maxt) and the second state word as (throughput | eta) in registers; in the queues these are the 12-byte
+// records plus the interval and eta arrays (queues.h) -- both are per path here: a medium vertex starts its ray at mint = 0, a surface vertex at Epsilon
+DEV void loadRayWithInterval(const Queues &q, int buf, uint64_t slot, float4 &ro, float4 &rd) {
+    const auto o = qRayOrigin(q, buf, (uint32_t) slot), d = qRayDirection(q, buf, (uint32_t) slot); const float2 iv = qRayInterval(q, buf, (uint32_t) slot);
+    ro = make_float4(o.x, o.y, o.z, iv.x); rd = make_float4(d.x, d.y, d.z, iv.y);
+}
+DEV void storeRayWithInterval(const Queues &q, int buf, uint64_t slot, float4 ro, float4 rd) {
+    qSetRayOrigin(q, buf, (uint32_t) slot, ro.x, ro.y, ro.z); qSetRayDirection(q, buf, (uint32_t) slot, rd.x, rd.y, rd.z); qSetRayInterval(q, buf, (uint32_t) slot, ro.w, rd.w);
+}
+DEV float4 loadThroughputEta(const Queues &q, int buf, uint64_t slot) { const auto t = qThroughput(q, buf, (uint32_t) slot); return make_float4(t.x, t.y, t.z, qEta(q, buf, (uint32_t) slot)); }
+DEV void storeThroughputEta(const Queues &q, int buf, uint64_t slot, float4 s1) { qSetThroughput(q, buf, (uint32_t) slot, s1.x, s1.y, s1.z); qSetEta(q, buf, (uint32_t) slot, s1.w); }
 DEV void unpackPathState(uint4 s0, float4 s1, uint32_t &pid, SamplerState &ss, int &depth, int &medium, v3 &T, float &eta) {
     pid = s0.x; ss.a = s0.y; ss.b = s0.z; ss.dim = s0.w & VS_DIM_MASK;
     depth = (int) ((s0.w >> VS_DEPTH_SHIFT) & 0xFFu); medium = (int) ((s0.w >> VS_MEDIUM_SHIFT) & 0xFFu) - 1;
@@ -91,7 +102,7 @@ DEV ShadowRec emitterSampleRecord(v3 nref, int m2, int interactions, bool onSurf
     r.t = make_float4(T.x, T.y, T.z, 0.0f); r.x = make_float4(x.x, x.y, x.z, w);
     return r;
 }
-DEV void storeShadowRecord(const Queues &q, uint64_t w, const ShadowRec &r) { q.shO[w] = r.o; q.shD[w] = r.d; q.shC[w] = r.c; q.shT[w] = r.t; q.shX[w] = r.x; }
+DEV void storeShadowRecord(const Queues &q, uint64_t w, const ShadowRec &r) { q.shO[w] = r.o; q.shD[w] = r.d; qSetShadowContributionWide(q, w, r.c); q.shT[w] = r.t; q.shX[w] = r.x; }
 
 // The shadow queue holds two records per path slot: a pass leaves at most one emitter-sampling record per path, written from the FRONT of the segment's area, and at most
 // one alpha walk (or, volpath, one emitter search) written from the BACK; the shadow stage runs the back records first.
@@ -175,7 +186,7 @@ template <bool WEIGHTED>
 DEV void addTransmittedSample(const Queues &q, uint64_t w, uint32_t bits, uint32_t pid, v3 tr, bool blocked) {
     if (bits & SR_ALPHA) { setAlpha(q, pid, alphaOfTransmittance(blocked ? V(0, 0, 0) : tr)); return; }
     if (blocked) return;
-    const float4 c = q.shC[w], tt = q.shT[w], xx = q.shX[w];
+    const float4 c = qShadowContributionWide(q, w), tt = q.shT[w], xx = q.shX[w];
     const float r = 1.0f / c.w;
     const v3 value = V(c.x, c.y, c.z) * (tr * r);                       // value *= evalTransmittance(...) / emPdf
     if (isZero(value) || (WEIGHTED && xx.w == 0.0f)) return;
