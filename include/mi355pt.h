@@ -360,7 +360,7 @@ typedef struct { uint32_t field; float undefined[3]; } mi_field;
  * MI_ERR_INVALID; an unknown kind or an albedo the scene's BSDFs do not support: MI_ERR_UNSUPPORTED.  Without fields a render launches, allocates and records nothing extra. */
 int mi_render_set_fields(mi_render *r, const mi_field *fields, uint32_t n);
 /* Field film read-back.  layout 0: raw sums (H+2b) x (W+2b) x (3F+1), the three values of every field in list order, then the film's own weight; layout 2: developed
- * H x W x 3F = sum / weight.  Without fields: MI_ERR_INVALID.  mi_render_clear zeroes the field film, mi_render_run_rows fills its rows, mi_render_merge_film adds it
+ * H x W x 3F = sum x invWeight with invWeight = weight == 0 ? 0 : 1 / weight, two float roundings (src/libcore/bitmap.cpp:1621-1625).  Without fields: MI_ERR_INVALID.  mi_render_clear zeroes the field film, mi_render_run_rows fills its rows, mi_render_merge_film adds it
  * too when both handles hold the same field list (and fails with MI_ERR_INVALID when they do not). */
 int mi_render_field_film_size(mi_render *r, int layout, uint32_t *height, uint32_t *width, uint32_t *channels, uint32_t *border);
 int mi_render_read_fields(mi_render *r, int layout, float *host_out);
@@ -456,6 +456,19 @@ int mi_scene_world_to_pixel(mi_scene *s, float *out12);
  * product call.  Its kernel looks Sobol values up in the render's GLOBAL nibble tables from st0.y / st0.z, as k_env_primary does; the shade kernels call the same functions on
  * their LDS copy of the tables -- that path is checked through renders (tests/test_gpu_thinlens.py), not here. */
 int mi_render_debug_sensor_differentials(mi_render *r, const uint32_t *pairs, uint64_t n, float *out8);
+/* Debug / parity, film units: caller-supplied samples through the film kernels a render launches -- no kernel of its own.  Sample (plane s, tile pixel pl) sits at index
+ * s x n_pix + pl, as the kernels index the queues; n_pix = the pixels of the tile's rows y0, y0 + row_stride, ... as mi_render_run_rows counts them; pos2 = the film
+ * position (sx, sy), val4 = Li rgb, alpha.  Pool 0 is sized as a run sizes it, the arrays are copied into its position / accumulator queues, the batch descriptions come
+ * from the code mi_render_run_rows uses, the launch goes to the render's stream and is waited for.  batch_planes = 0: one launch; k: consecutive launches of at most k planes.
+ *   which = 0  k_film (mi_render_run_rows' film stage)
+ *   which = 1  k_adapt_accumulate over the active list of the tile, with the set-up of mi_render_run_adaptive (buffers, zeroing, arguments from mi_render_set_adaptive and
+ *              its GIVEN average_luminance > 0); needs a clear film, no fields, row_stride = 1 and n_planes = max_sample_factor x spp (every pixel stops by the last plane).
+ *              No compaction between launches: every launch sees the full list, finished pixels return at once.  Afterwards the film and mi_render_read_sample_counts
+ *              read as after an adaptive run
+ *   which = 2  k_field_film with every hit record of the batch set to a miss: each sample puts the fields' `undefined` triples (val4 is not read); needs fields
+ * MI_ERR_INVALID, by name: a null argument, a tile outside the film, n_planes = 0, a render running on the scene, a missing precondition of `which`, a position that is
+ * not finite or beyond 2^20 in magnitude (the kernels' clamps make any finite position safe; the bound keeps the int conversions of a CPU model defined). */
+int mi_render_debug_film_put(mi_render *r, int which, mi_tile tile, uint32_t row_stride, uint32_t n_planes, uint32_t batch_planes, const float *pos2, const float *val4);
 int mi_render_set_profiling(mi_render *r, int enabled);   /* per-stage HIP-event timing: events are recorded between the stage launches of the first stream, nothing is serialised (off by default) */
 
 /* bool Scene::rayIntersect(const Ray &ray, Intersection &its) for a batch of rays (include/mitsuba/render/scene.h:187-243): rays8 = (o.xyz, mint, d.xyz, maxt) per

@@ -124,7 +124,7 @@ EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_s
            "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_adaptive", "mi_render_run_adaptive", "mi_render_read_sample_counts", "mi_render_adaptive_stats",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_denoise_image", "mi_render_denoise", "mi_render_denoise_device", "mi_history_create", "mi_history_destroy", "mi_history_reset", "mi_history_frames", "mi_history_read", "mi_denoise_image_temporal", "mi_render_denoise_temporal", "mi_render_denoise_temporal_device", "mi_scene_world_to_pixel", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
-           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_emitter_sample", "mi_debug_emitter_eval", "mi_debug_medium", "mi_debug_surface", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
+           "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_render_debug_film_put", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_emitter_sample", "mi_debug_emitter_eval", "mi_debug_medium", "mi_debug_surface", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
 HOST_EXPORTS = ["mi_host_last_error", "mi_host_create", "mi_host_create_devices", "mi_host_create_ex", "mi_host_create_direct", "mi_host_create_ao", "mi_host_destroy", "mi_host_preprocess", "mi_host_render", "mi_host_cancel", "mi_host_statistics",
                 "mi_host_set_camera", "mi_host_set_lens", "mi_host_set_materials", "mi_host_set_emitters", "mi_host_set_envmap_transform", "mi_host_set_vertices", "mi_host_set_instances", "mi_host_set_geometry"]
 
@@ -207,6 +207,7 @@ class Lib:
         L.mi_scene_world_to_pixel.argtypes = [vp, vp]
         L.mi_render_set_profiling.argtypes = [vp, i32]
         L.mi_render_debug_sensor_differentials.argtypes = [vp, vp, u64, vp]
+        L.mi_render_debug_film_put.argtypes = [vp, i32, MiTile, u32, u32, u32, vp, vp]
         L.mi_debug_intersect.argtypes = [vp, vp, u64, i32, vp]
         L.mi_debug_intersect_inst.argtypes = [vp, vp, u64, i32, vp, vp]
         L.mi_debug_intersect_fused.argtypes = [vp, vp, u64, i32, vp, u32, u32, u32, u32, vp, C.POINTER(MiFusedDebugInfo)]
@@ -796,6 +797,17 @@ class Render:
         """What the shading stages recompute for the sensor rays of (px, py, sampleIndex) triples from the path state -> [n, 8]: aperture sample, scaled rx / ry directions."""
         a = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 3); out = np.zeros((len(a), 8), np.float32)
         self.L.check(self.L.L.mi_render_debug_sensor_differentials(self.h, _p(a), len(a), _p(out))); return out
+
+    def film_put_units(self, which, pos2, val4, n_planes, tile=None, row_stride=1, batch_planes=0):
+        """Film units (mi_render_debug_film_put): caller-supplied samples through k_film (which = 0), k_adapt_accumulate (1) or k_field_film with every camera ray a miss
+        (2).  pos2 [n_planes, n_pix, 2] film positions, val4 [n_planes, n_pix, 4] Li rgb + alpha, n_pix = the pixels of the tile's rows as run() counts them, pixel-minor;
+        batch_planes = 0: one launch, k: launches of at most k planes."""
+        sc = self.scene.sc; t = MiTile(0, 0, sc.width, sc.height) if tile is None else MiTile(*tile)
+        rs = int(row_stride); n_pix = (t.x1 - t.x0) * ((t.y1 - t.y0 + rs - 1) // rs) if rs > 0 else 0          # (a stride of 0 is the library's to refuse: it reads nothing)
+        pos2 = np.ascontiguousarray(pos2, np.float32); val4 = np.ascontiguousarray(val4, np.float32)
+        if rs > 0 and (pos2.size != n_planes * n_pix * 2 or val4.size != n_planes * n_pix * 4):
+            raise ValueError(f"film_put_units: {n_planes} planes of {n_pix} pixels need pos2 [{n_planes}, {n_pix}, 2] and val4 [{n_planes}, {n_pix}, 4]")
+        self.L.check(self.L.L.mi_render_debug_film_put(self.h, int(which), t, int(row_stride), int(n_planes), int(batch_planes), _p(pos2), _p(val4)))
 
     def merge_film(self, other):
         """self += other (raw film sums, field planes included, ray counters): both renders idle, same film, same field list."""

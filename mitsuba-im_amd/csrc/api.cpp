@@ -1225,6 +1225,17 @@ static int traceBatch(mi_render *r, const BatchDesc &bd, const uint32_t *list, s
 
 int mi_render_run(mi_render *r, mi_tile tile, uint32_t s0, uint32_t s1) { return mi_render_run_rows(r, tile, 1, s0, s1); }
 
+// The pixels of a tile's rows y0, y0 + stride, ... below y1, and the description of one batch of sample planes over them: path pid = plane x n_pix + tile pixel.
+// mi_render_run_rows and the film-unit entry (mi_render_debug_film_put) describe their batches through these two.
+static uint32_t tilePixels(mi_tile tile, uint32_t rowStride) {
+    const uint32_t nrows = (tile.y1 - tile.y0 + rowStride - 1) / rowStride;
+    return (tile.x1 - tile.x0) * nrows;
+}
+static BatchDesc tileBatch(mi_tile tile, uint32_t rowStride, uint32_t npix, uint32_t sampleBegin, uint32_t nPlanes) {
+    BatchDesc bd{}; bd.tile = tile; bd.n_pix = npix; bd.n_planes = nPlanes; bd.sample_begin = sampleBegin; bd.n_paths = (uint64_t) npix * nPlanes; bd.list = nullptr; bd.row_stride = rowStride;
+    return bd;
+}
+
 int mi_render_run_rows(mi_render *r, mi_tile tile, uint32_t rowStride, uint32_t s0, uint32_t s1) {
     if (!r) return fail(MI_ERR_INVALID, "mi_render_run: null");
     if (rowStride == 0) return fail(MI_ERR_INVALID, "mi_render_run_rows: row stride must be >= 1");
@@ -1235,8 +1246,7 @@ int mi_render_run_rows(mi_render *r, mi_tile tile, uint32_t rowStride, uint32_t 
     if (r->p.sampler == MI_SAMPLER_INDEPENDENT && s1 > (1u << 24)) return fail(MI_ERR_INVALID, "mi_render_run: independent stream supports < 2^24 samples per pixel");
     RunGuard running; { const int rc = beginRun(r, running, true, "mi_render_run"); if (rc) return rc; }
     HIPCHK(hipSetDevice(h.device));
-    const uint32_t nrows = (tile.y1 - tile.y0 + rowStride - 1) / rowStride;          // rows y0, y0 + stride, ... below y1
-    const uint32_t npix = (tile.x1 - tile.x0) * nrows;
+    const uint32_t npix = tilePixels(tile, rowStride);
     uint32_t planes = r->p.planes_per_batch;
     if (!planes) { static const uint64_t target = [] { const char *v = getenv("MI355PT_BATCH_PATHS"); return v && atoll(v) > 0 ? (uint64_t) atoll(v) : (uint64_t) (64u << 20); }(); planes = (uint32_t) std::max<uint64_t>(1, target / npix); }   // ~64 M paths in flight per pool (measured: 16 M 2873, 32 M 3025, 64 M 3055, 128 M 2993 Msamples/s on C2; C4 483 / 501 / 509 / 511)
     if (planes > s1 - s0) planes = std::max<uint32_t>(1, s1 - s0);
@@ -1265,7 +1275,7 @@ int mi_render_run_rows(mi_render *r, mi_tile tile, uint32_t rowStride, uint32_t 
     for (uint32_t s = s0; s < s1; s += planes, ++batch) {
         if (r->cancel.exchange(0)) { HIPCHK(hipDeviceSynchronize()); return fail(MI_CANCELLED, "render cancelled"); }      // consumed where it is observed
         const int pool = batch % nPools; hipStream_t st = r->poolStream(pool);
-        BatchDesc bd{}; bd.tile = tile; bd.n_pix = npix; bd.n_planes = std::min(planes, s1 - s); bd.sample_begin = s; bd.n_paths = (uint64_t) npix * bd.n_planes; bd.list = nullptr; bd.row_stride = rowStride;
+        const BatchDesc bd = tileBatch(tile, rowStride, npix, s, std::min(planes, s1 - s));
         int rc = traceBatch(r, bd, nullptr, evUsed, pool); if (rc) return rc;
         // film accumulation stays in batch order (own-pixel sums are plain read-modify-writes): wait for the previous batch's film kernel
         if (nPools > 1 && lastFilmPool >= 0) HIPCHK(hipStreamWaitEvent(st, r->filmDone[lastFilmPool], 0));
@@ -1450,6 +1460,46 @@ int mi_render_adaptive_stats(mi_render *r, mi_adaptive_stats *out) {
     if (!r || !out) return fail(MI_ERR_INVALID, "mi_render_adaptive_stats: null argument");
     *out = r->as; return MI_OK;
 }
+}  // extern "C"
+// The set-up of an adaptive film, shared by mi_render_run_adaptive and the film-unit entry (mi_render_debug_film_put), in two steps.
+// adaptAlloc: the footprint, state and count buffers, allocated at the first adaptive run and freed with the render.
+static int adaptAlloc(mi_render *r, const std::string &who) {
+    if (r->ad.fp) return MI_OK;
+    const mi::SceneHost &h = r->scene->h; const uint32_t nPixFilm = h.width * h.height;
+    const int hb = (int) std::floor(h.filterRadiusEff + 0.5f), side = 2 * hb + 1;
+    const uint64_t fpBytes = (uint64_t) nPixFilm * side * side * 5u * 4u, bytes = fpBytes + (uint64_t) nPixFilm * (8u + 4u + 4u + 4u + 4u) + MI_ADAPT_RANGES * 4u + 4u;
+    const char *lim = getenv("MI355PT_POOL_LIMIT");
+    if (lim && atoll(lim) > 0 && bytes > (uint64_t) atoll(lim)) return fail(MI_ERR_DEVICE, who + ": the footprint, state and count buffers (" + std::to_string(bytes) + " bytes) are larger than MI355PT_POOL_LIMIT");
+    size_t freeB = 0, totalB = 0; HIPCHK(hipMemGetInfo(&freeB, &totalB));
+    if (bytes > freeB) return fail(MI_ERR_DEVICE, who + ": the footprint, state and count buffers (" + std::to_string(bytes) + " bytes) are larger than the free device memory");
+    hipError_t e = hipMalloc((void **) &r->ad.fp, fpBytes);
+    if (e == hipSuccess) e = hipMalloc((void **) &r->ad.ms, (size_t) nPixFilm * 8);
+    if (e == hipSuccess) e = hipMalloc((void **) &r->ad.n, (size_t) nPixFilm * 4);
+    if (e == hipSuccess) e = hipMalloc((void **) &r->ad.counts, (size_t) nPixFilm * 4);
+    if (e == hipSuccess) e = hipMalloc((void **) &r->adActive[0], (size_t) nPixFilm * 4);
+    if (e == hipSuccess) e = hipMalloc((void **) &r->adActive[1], (size_t) nPixFilm * 4);
+    if (e == hipSuccess) e = hipMalloc((void **) &r->adWave, MI_ADAPT_RANGES * 4);
+    if (e == hipSuccess) e = hipMalloc((void **) &r->adNNext, 4);
+    if (e == hipSuccess) e = hipHostMalloc((void **) &r->adHostN, 4, hipHostMallocDefault);
+    if (e != hipSuccess) { (void) hipGetLastError(); releaseAdaptive(r); return fail(MI_ERR_DEVICE, who + ": cannot allocate the footprint, state and count buffers: " + hipGetErrorString(e)); }
+    r->adPix = nPixFilm;
+    return MI_OK;
+}
+static uint32_t adaptCap(const mi_render *r) { return r->ap.max_sample_factor > 0 ? (uint32_t) r->ap.max_sample_factor * r->p.spp : kAdaptLastIndex - 1u; }
+// adaptBegin: the kernels' arguments from the adaptive parameters and the average luminance, zeroed footprints / state / counts, the round-0 active list = the tile's
+// pixels row by row; from here on the film is an adaptive one.
+static int adaptBegin(mi_render *r, mi_tile tile, uint32_t npix, float avgLum) {
+    const mi::SceneHost &h = r->scene->h; const uint32_t nPixFilm = h.width * h.height;
+    const int hb = (int) std::floor(h.filterRadiusEff + 0.5f), side = 2 * hb + 1;
+    r->ad.n_pix = nPixFilm; r->ad.hb = hb; r->ad.spp = r->p.spp; r->ad.cap = adaptCap(r); r->ad.max_error = r->ap.max_error; r->ad.quantile = r->adQuantile; r->ad.lum_floor = avgLum * 0.01f;
+    r->as = mi_adaptive_stats{}; r->as.average_luminance = avgLum; r->as.quantile = r->adQuantile;
+    r->adaptFilm = true;      // from here on the film is an adaptive one, whether the run completes or not
+    HIPCHK(hipMemsetAsync(r->ad.fp, 0, (size_t) nPixFilm * side * side * 5u * 4u, r->stream)); HIPCHK(hipMemsetAsync(r->ad.ms, 0, (size_t) nPixFilm * 8, r->stream));
+    HIPCHK(hipMemsetAsync(r->ad.n, 0, (size_t) nPixFilm * 4, r->stream)); HIPCHK(hipMemsetAsync(r->ad.counts, 0, (size_t) nPixFilm * 4, r->stream));
+    mi_launch_adapt_tile(r->adActive[0], tile, h.width, npix, r->stream);
+    return MI_OK;
+}
+extern "C" {
 int mi_render_run_adaptive(mi_render *r, mi_tile tile) {
     if (!r) return fail(MI_ERR_INVALID, "mi_render_run_adaptive: null render");
     if (!r->adaptOn) return fail(MI_ERR_INVALID, "mi_render_run_adaptive: no adaptive parameters are set (mi_render_set_adaptive)");
@@ -1459,28 +1509,9 @@ int mi_render_run_adaptive(mi_render *r, mi_tile tile) {
     if (r->nFields) return fail(MI_ERR_UNSUPPORTED, "mi_render_run_adaptive: field channels are set on this render (mi_render_set_fields)");
     HIPCHK(hipSetDevice(h.device));
     const uint32_t spp = r->p.spp, R = r->ap.round_samples ? r->ap.round_samples : spp;
-    const uint32_t cap = r->ap.max_sample_factor > 0 ? (uint32_t) r->ap.max_sample_factor * spp : kAdaptLastIndex - 1u;
-    const uint32_t nPixFilm = h.width * h.height, npix = (tile.x1 - tile.x0) * (tile.y1 - tile.y0);
-    const int hb = (int) std::floor(h.filterRadiusEff + 0.5f), side = 2 * hb + 1;
-    // footprint, state and count buffers: allocated at the first adaptive run, freed with the render
-    if (!r->ad.fp) {
-        const uint64_t fpBytes = (uint64_t) nPixFilm * side * side * 5u * 4u, bytes = fpBytes + (uint64_t) nPixFilm * (8u + 4u + 4u + 4u + 4u) + MI_ADAPT_RANGES * 4u + 4u;
-        const char *lim = getenv("MI355PT_POOL_LIMIT");
-        if (lim && atoll(lim) > 0 && bytes > (uint64_t) atoll(lim)) return fail(MI_ERR_DEVICE, "mi_render_run_adaptive: the footprint, state and count buffers (" + std::to_string(bytes) + " bytes) are larger than MI355PT_POOL_LIMIT");
-        size_t freeB = 0, totalB = 0; HIPCHK(hipMemGetInfo(&freeB, &totalB));
-        if (bytes > freeB) return fail(MI_ERR_DEVICE, "mi_render_run_adaptive: the footprint, state and count buffers (" + std::to_string(bytes) + " bytes) are larger than the free device memory");
-        hipError_t e = hipMalloc((void **) &r->ad.fp, fpBytes);
-        if (e == hipSuccess) e = hipMalloc((void **) &r->ad.ms, (size_t) nPixFilm * 8);
-        if (e == hipSuccess) e = hipMalloc((void **) &r->ad.n, (size_t) nPixFilm * 4);
-        if (e == hipSuccess) e = hipMalloc((void **) &r->ad.counts, (size_t) nPixFilm * 4);
-        if (e == hipSuccess) e = hipMalloc((void **) &r->adActive[0], (size_t) nPixFilm * 4);
-        if (e == hipSuccess) e = hipMalloc((void **) &r->adActive[1], (size_t) nPixFilm * 4);
-        if (e == hipSuccess) e = hipMalloc((void **) &r->adWave, MI_ADAPT_RANGES * 4);
-        if (e == hipSuccess) e = hipMalloc((void **) &r->adNNext, 4);
-        if (e == hipSuccess) e = hipHostMalloc((void **) &r->adHostN, 4, hipHostMallocDefault);
-        if (e != hipSuccess) { (void) hipGetLastError(); releaseAdaptive(r); return fail(MI_ERR_DEVICE, std::string("mi_render_run_adaptive: cannot allocate the footprint, state and count buffers: ") + hipGetErrorString(e)); }
-        r->adPix = nPixFilm;
-    }
+    const uint32_t cap = adaptCap(r);
+    const uint32_t nPixFilm = h.width * h.height, npix = tilePixels(tile, 1);
+    { const int rc = adaptAlloc(r, "mi_render_run_adaptive"); if (rc) return rc; }
     // average luminance: given, or the estimate over N = min(10000, W x H) pixels at the stream's last sample index, through the route of mi_render_samples (taken again
     // at every run: the scene may have been edited); summed in double in index order
     float avgLum = r->ap.average_luminance;
@@ -1514,12 +1545,7 @@ int mi_render_run_adaptive(mi_render *r, mi_tile tile) {
         for (int i = 0; i < nPools; ++i) HIPCHK(hipMalloc((void **) &r->adList[i], need * 12));
         r->adListPaths = need;
     }
-    r->ad.n_pix = nPixFilm; r->ad.hb = hb; r->ad.spp = spp; r->ad.cap = cap; r->ad.max_error = r->ap.max_error; r->ad.quantile = r->adQuantile; r->ad.lum_floor = avgLum * 0.01f;
-    r->as = mi_adaptive_stats{}; r->as.average_luminance = avgLum; r->as.quantile = r->adQuantile;
-    r->adaptFilm = true;      // from here on the film is an adaptive one, whether the run completes or not
-    HIPCHK(hipMemsetAsync(r->ad.fp, 0, (size_t) nPixFilm * side * side * 5u * 4u, r->stream)); HIPCHK(hipMemsetAsync(r->ad.ms, 0, (size_t) nPixFilm * 8, r->stream));
-    HIPCHK(hipMemsetAsync(r->ad.n, 0, (size_t) nPixFilm * 4, r->stream)); HIPCHK(hipMemsetAsync(r->ad.counts, 0, (size_t) nPixFilm * 4, r->stream));
-    mi_launch_adapt_tile(r->adActive[0], tile, h.width, npix, r->stream);
+    { const int rc = adaptBegin(r, tile, npix, avgLum); if (rc) return rc; }
     size_t evUsed = 0; r->launchesAll = 0;
     HIPCHK(hipEventRecord(r->evBegin, r->stream));
     if (nPools > 1) HIPCHK(hipEventRecord(r->joinEv[0], r->stream));
@@ -1566,6 +1592,59 @@ int mi_render_run_adaptive(mi_render *r, mi_tile tile) {
     for (uint32_t y = tile.y0; y < tile.y1; ++y) for (uint32_t x = tile.x0; x < tile.x1; ++x) {
         const uint32_t c = counts[(size_t) y * h.width + x];
         r->as.samples_used += c; r->as.min_count = std::min(r->as.min_count, c); r->as.max_count = std::max(r->as.max_count, c); if (c == cap) ++r->as.pixels_at_cap;
+    }
+    return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ film units (include/mi355pt.h)
+// Caller-supplied samples through the film kernels a render launches: pool 0 sized as a run sizes it, the samples copied into its q.pos / q.acc, the batches described by
+// tileBatch as mi_render_run_rows describes them, the product's launchers on the render's stream.  No kernel of its own.
+int mi_render_debug_film_put(mi_render *r, int which, mi_tile tile, uint32_t rowStride, uint32_t nPlanes, uint32_t batchPlanes, const float *pos2, const float *val4) {
+    const std::string fn = "mi_render_debug_film_put";
+    if (!r || !pos2 || !val4) return fail(MI_ERR_INVALID, fn + ": null argument");
+    if (which < 0 || which > 2) return fail(MI_ERR_INVALID, fn + ": which must be 0 (k_film), 1 (k_adapt_accumulate) or 2 (k_field_film)");
+    if (rowStride == 0) return fail(MI_ERR_INVALID, fn + ": row stride must be >= 1");
+    if (nPlanes == 0) return fail(MI_ERR_INVALID, fn + ": n_planes must be >= 1");
+    const mi::SceneHost &h = r->scene->h;
+    if (tile.x1 <= tile.x0 || tile.y1 <= tile.y0 || tile.x1 > h.width || tile.y1 > h.height) return fail(MI_ERR_INVALID, fn + ": tile outside the film");
+    if (r->scene->busy.load() != 0) return fail(MI_ERR_INVALID, fn + ": a render is running on this scene (or the scene is being updated)");
+    if (which == 0 && r->adaptFilm) return fail(MI_ERR_INVALID, fn + ": the film holds an adaptive run (weights of one sample per pixel); call mi_render_clear first");
+    if (which == 1) {
+        if (!r->adaptOn) return fail(MI_ERR_INVALID, fn + ": which = 1 needs adaptive parameters (mi_render_set_adaptive)");
+        if (!(r->ap.average_luminance > 0)) return fail(MI_ERR_INVALID, fn + ": which = 1 needs a given average_luminance > 0 (there is no scene to estimate it from)");
+        if (filmHoldsSamples(r)) return fail(MI_ERR_INVALID, fn + ": which = 1 needs a clear film (one adaptive film per mi_render_clear)");
+        if (r->nFields) return fail(MI_ERR_INVALID, fn + ": which = 1 needs a render without field channels (mi_render_set_fields)");
+        if (rowStride != 1) return fail(MI_ERR_INVALID, fn + ": which = 1 needs row_stride = 1 (the active list is the tile, row by row)");
+        if (adaptCap(r) != nPlanes) return fail(MI_ERR_INVALID, fn + ": which = 1 needs n_planes = max_sample_factor x spp, so that every pixel has stopped by the last plane");
+    }
+    if (which == 2) {
+        if (!r->nFields) return fail(MI_ERR_INVALID, fn + ": which = 2 needs fields (mi_render_set_fields)");
+        if (r->adaptFilm) return fail(MI_ERR_INVALID, fn + ": the film holds an adaptive run; call mi_render_clear first");
+    }
+    const uint32_t npix = tilePixels(tile, rowStride);
+    const uint64_t total = (uint64_t) npix * nPlanes;
+    // the kernels' clamps make any finite position safe; the bound keeps the conversions to int defined in a CPU model too
+    for (uint64_t i = 0; i < total * 2; ++i) if (!(std::fabs(pos2[i]) <= 1048576.0f)) return fail(MI_ERR_INVALID, fn + ": a film position is not finite or lies beyond 2^20");
+    const uint32_t planes = batchPlanes ? std::min(batchPlanes, nPlanes) : nPlanes;
+    const uint64_t need = (uint64_t) npix * planes;
+    if (need > 0xFFFFFF00ull) return fail(MI_ERR_INVALID, fn + ": batch larger than 2^32 paths");
+    HIPCHK(hipSetDevice(h.device));
+    if (which == 1) { const int rc = adaptAlloc(r, fn); if (rc) return rc; }
+    RunGuard running; { const int rc = beginRun(r, running, true, fn.c_str()); if (rc) return rc; }
+    if (need > r->poolPaths) { const int rc = allocPool(r, need); if (rc) return rc; }
+    Queues &Q = r->q; hipStream_t st = r->stream;
+    if (which == 1) { const int rc = adaptBegin(r, tile, npix, r->ap.average_luminance); if (rc) return rc; }
+    for (uint32_t s = 0; s < nPlanes; s += planes) {
+        const BatchDesc bd = tileBatch(tile, rowStride, npix, s, std::min(planes, nPlanes - s));
+        const uint64_t first = (uint64_t) s * npix;
+        HIPCHK(hipMemcpy(Q.pos, pos2 + first * 2, bd.n_paths * sizeof(float2), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(Q.acc, val4 + first * 4, bd.n_paths * sizeof(float4), hipMemcpyHostToDevice));
+        if (which == 2) HIPCHK(hipMemsetAsync(Q.hit, 0xFF, bd.n_paths * sizeof(float4), st));      // every camera ray leaves the scene (hit.w = 0xFFFFFFFF): the fields' `undefined` values
+        if (which == 0) mi_launch_film(h.d, Q, bd, r->film, r->spill, st);
+        else if (which == 1) mi_launch_adapt_accumulate(h.d, Q, r->ad, r->adActive[0], npix, bd.n_planes, r->film, r->spill, st);      // the full list every time: a finished pixel returns at once
+        else mi_launch_field_film(r->sc, r->fa, Q, bd, r->fieldFilm, r->fieldSpill, st);
+        HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipGetLastError());
+        r->samplesTotal += bd.n_paths;
     }
     return MI_OK;
 }

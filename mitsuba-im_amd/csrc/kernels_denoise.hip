@@ -5,7 +5,7 @@
 #include "denoise.h"
 
 // ---------------------------------------------------------------------------------------------- prepare
-// RENDER: radiance = film layout 2 (k_film_layout: sum x (weight != 0 ? 1 / weight : 0)), guides = field layout 2 (k_field_layout: weight != 0 ? sum / weight : 0),
+// RENDER: radiance = film layout 2 (k_film_layout: sum x (weight != 0 ? 1 / weight : 0)), guides = field layout 2 (k_field_layout: the same expression on the field film's own weight),
 // read from the planes in place.  Image form: interleaved H x W x 3 arrays.  Demodulation: D = A > 1e-3f ? A : 1e-3f (a NaN albedo gives 1e-3f), c0 = C / D.
 template <bool RENDER>
 __global__ __launch_bounds__(WG) void k_dn_prepare(DenoiseBufs b, DenoiseFilmSrc f, const float *C, const float *N, const float *P, const float *A, int w, int h, int demod) {
@@ -16,14 +16,14 @@ __global__ __launch_bounds__(WG) void k_dn_prepare(DenoiseBufs b, DenoiseFilmSrc
         const int x = (int) (i % w), y = (int) (i / w);
         const size_t plane = (size_t) f.W * f.H, src = (size_t) (y + f.border) * f.W + (x + f.border);
         const float wgt = f.film[4 * plane + src] + f.spill[4 * plane + src], inv = wgt != 0 ? 1.0f / wgt : 0.0f;
-        const float fw = f.ffilm[f.nv * plane + src] + f.fspill[f.nv * plane + src];
+        const float fw = f.ffilm[f.nv * plane + src] + f.fspill[f.nv * plane + src], finv = fw != 0 ? 1.0f / fw : 0.0f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             c[k] = (f.film[k * plane + src] + f.spill[k * plane + src]) * inv;
             const size_t kn = (size_t) (3 * f.fN + k) * plane + src, kp = (size_t) (3 * f.fP + k) * plane + src;
-            n[k] = fw != 0 ? (f.ffilm[kn] + f.fspill[kn]) / fw : 0.0f;
-            p[k] = fw != 0 ? (f.ffilm[kp] + f.fspill[kp]) / fw : 0.0f;
-            if (demod) { const size_t ka = (size_t) (3 * f.fA + k) * plane + src; a[k] = fw != 0 ? (f.ffilm[ka] + f.fspill[ka]) / fw : 0.0f; }
+            n[k] = (f.ffilm[kn] + f.fspill[kn]) * finv;
+            p[k] = (f.ffilm[kp] + f.fspill[kp]) * finv;
+            if (demod) { const size_t ka = (size_t) (3 * f.fA + k) * plane + src; a[k] = (f.ffilm[ka] + f.fspill[ka]) * finv; }
         }
     } else {
 #pragma unroll

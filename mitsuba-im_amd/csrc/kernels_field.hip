@@ -153,7 +153,8 @@ __global__ __launch_bounds__(WG) void k_field_samples(DScene sc, FieldArgs fa, Q
 }
 
 // dst[i] += src[i] over the field planes is k_film_add's job (kernels_misc.hip); read-back: SoA planes -> interleaved.  layout 0: raw sums incl. border, nch = 3 F + 1
-// channels (weight last); layout 2: developed, 3 F channels = sum / weight, crop window only
+// channels (weight last); layout 2: developed, 3 F channels = sum x (weight != 0 ? 1 / weight : 0) as k_film_layout and the reference's multichannel develop
+// (src/libcore/bitmap.cpp:1621-1625) compute it, crop window only
 __global__ void k_field_layout(const float *film, const float *spill, float *out, int W, int H, int border, int nch, int layout) {
     const size_t plane = (size_t) W * H;
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -162,8 +163,8 @@ __global__ void k_field_layout(const float *film, const float *spill, float *out
         const int w = W - 2 * border, h = H - 2 * border, nv = nch - 1;
         if (i < (size_t) w * h) {
             const int x = (int) (i % w), y = (int) (i / w); const size_t src = (size_t) (y + border) * W + (x + border);
-            const float wgt = film[nv * plane + src] + spill[nv * plane + src];
-            for (int k = 0; k < nv; ++k) out[i * nv + k] = wgt != 0 ? (film[k * plane + src] + spill[k * plane + src]) / wgt : 0.0f;
+            const float wgt = film[nv * plane + src] + spill[nv * plane + src], inv = wgt != 0 ? 1.0f / wgt : 0.0f;
+            for (int k = 0; k < nv; ++k) out[i * nv + k] = (film[k * plane + src] + spill[k * plane + src]) * inv;
         }
     }
 }

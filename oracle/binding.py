@@ -110,6 +110,8 @@ def lib():
         L.orc_medium_units.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.orc_surface_units.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_filter_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_film_put_units.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]
+        L.orc_film_put_units.restype = None
         L.orc_sfmt_sequence.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
         L.orc_sfmt_floats.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
         _LIB = L
@@ -243,6 +245,14 @@ class Oracle:
         film = np.zeros((sc.height + 2 * b, sc.width + 2 * b, 5), np.float32); counters = np.zeros(3, np.uint64)
         lib().orc_render_image(self.h, s0, s1, y0, y1, threads, _ptr(film), _ptr(counters))
         return film, counters
+
+    def film_put_units(self, pos2, vals, reject=True):
+        """orc_film_put_units: samples i = 0 .. n - 1 (pos2 [n, 2], vals [n, nch]) put one after the other into a zeroed float32 film -> (H + 2b) x (W + 2b) x (nch + 1),
+        weight last.  reject: ImageBlock::put's check on the values (nch = 4: the radiance film); False: the multichannel rule, no check."""
+        pos2 = np.ascontiguousarray(pos2, np.float32).reshape(-1, 2); vals = np.ascontiguousarray(vals, np.float32).reshape(len(pos2), -1)
+        sc = self.sc; b = self.border; nch = vals.shape[1]; assert 1 <= nch <= 31
+        film = np.zeros((sc.height + 2 * b, sc.width + 2 * b, nch + 1), np.float32)
+        lib().orc_film_put_units(self.h, _ptr(pos2), _ptr(vals), len(pos2), int(bool(reject)), nch, _ptr(film)); return film
 
     # unit entry points on arrays (one C call per row)
     def bsdf_sample_units(self, material, wi, uv, extra=None):

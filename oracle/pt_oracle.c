@@ -2954,9 +2954,9 @@ float orc_filter_eval_discretized(const orc_scene *s, float x) {
 void orc_filter_table(const orc_scene *s, float *o, float *radius, int *border) { memcpy(o, s->filter_values, sizeof(s->filter_values)); *radius = s->filter_radius; *border = s->border; }
 int orc_film_border(const orc_scene *s) { return s->border; }
 /* include/mitsuba/render/imageblock.h:161-221 ImageBlock::put for a film-sized block at offset 0, 5 channels (RGB, alpha, weight) */
-static void film_put(const orc_scene *s, float *film, float sxp, float syp, v3 value, float alpha) {
-    float vals[5] = {value.x, value.y, value.z, alpha, 1.0f};
-    for (int i = 0; i < 5; ++i) if (!isfinite(vals[i]) || vals[i] < 0) return;
+/* the same put for nch channels (the values, then the weight 1): film_put is nch = 5 with the check, a multichannel block is 3 F + 1 without it (multichannel.cpp:41-44) */
+static void film_put_n(const orc_scene *s, float *film, float sxp, float syp, const float *vals, int nch, int reject) {
+    if (reject) for (int i = 0; i < nch; ++i) if (!isfinite(vals[i]) || vals[i] < 0) return;
     const int W = (int) s->d.width + 2 * s->border, H = (int) s->d.height + 2 * s->border;
     const float r = s->filter_radius;
     float posx = sxp - 0.5f - (float) (0 - s->border), posy = syp - 0.5f - (float) (0 - s->border);
@@ -2969,9 +2969,25 @@ static void film_put(const orc_scene *s, float *film, float sxp, float syp, v3 v
         float wy = orc_filter_eval_discretized(s, (float) y - posy);
         for (int x = minx; x <= maxx; ++x) {
             float w = orc_filter_eval_discretized(s, (float) x - posx) * wy;
-            float *dst = film + ((size_t) y * W + x) * 5;
-            for (int k = 0; k < 5; ++k) dst[k] += w * vals[k];
+            float *dst = film + ((size_t) y * W + x) * (size_t) nch;
+            for (int k = 0; k < nch; ++k) dst[k] += w * vals[k];
         }
+    }
+}
+static void film_put(const orc_scene *s, float *film, float sxp, float syp, v3 value, float alpha) {
+    const float vals[5] = {value.x, value.y, value.z, alpha, 1.0f};
+    film_put_n(s, film, sxp, syp, vals, 5, 1);
+}
+/* Film units: n caller-supplied samples put one after the other, in index order, into a caller-zeroed film of (H + 2 b) x (W + 2 b) x (nch + 1) floats -- nch values per
+   sample (val[i * nch ..]), then the weight.  reject != 0: ImageBlock::put's check on the values (film_put: nch = 4, Li rgb and alpha); 0: the multichannel rule, no check.
+   nch <= 31. */
+void orc_film_put_units(const orc_scene *s, const float *pos2, const float *val, uint64_t n, int reject, int nch, float *film) {
+    float vals[32];
+    if (nch < 1 || nch > 31) return;
+    for (uint64_t i = 0; i < n; ++i) {
+        for (int k = 0; k < nch; ++k) vals[k] = val[i * (uint64_t) nch + k];
+        vals[nch] = 1.0f;
+        film_put_n(s, film, pos2[i * 2], pos2[i * 2 + 1], vals, nch + 1, reject);
     }
 }
 typedef struct { const orc_scene *s; uint32_t s0, s1, y0, y1; float *film; uint64_t counters[3]; int tid, nthreads; pthread_mutex_t *mtx; } job_t;

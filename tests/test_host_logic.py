@@ -205,3 +205,14 @@ def test_surface_units_entry_refuses_without_gpu(mi):
     for args in ((h, 0, r, t, i, None, None, 1, o), (h, 0, r, t, None, None, None, 1, o), (h, 1, r, t, i, None, qq, 1, o), (h, 2, r, t, i, None, qq, 1, o)):
         rc, msg = call(*args); assert rc == 1 and b"mi_debug_surface: the scene must be committed" in msg, (args[1], rc, msg)
     L.L.mi_scene_destroy(h)
+
+
+def test_film_units_entry_refuses_without_gpu(mi):
+    """mi_render_debug_film_put is exported and bound; its null-argument refusal is decided before any device call (a render handle cannot exist without a device: the
+    other refusals -- tile, planes, positions, the preconditions of `which` -- are in tests/test_gpu_film_units.py test_refusals)"""
+    L = mi.lib(); assert "mi_render_debug_film_put" in mi.api.EXPORTS and hasattr(L.L, "mi_render_debug_film_put")
+    pos = np.zeros((1, 1, 2), np.float32); val = np.zeros((1, 1, 4), np.float32); t = mi.api.MiTile(0, 0, 1, 1)
+    for which in (0, 1, 2, 7):
+        rc = L.L.mi_render_debug_film_put(None, which, t, 1, 1, 0, pos.ctypes.data, val.ctypes.data)
+        assert rc == 1 and b"mi_render_debug_film_put: null argument" in L.L.mi_last_error()
+    assert hasattr(mi.Render, "film_put_units")
