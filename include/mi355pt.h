@@ -280,7 +280,7 @@ int mi_scene_update_instances(mi_scene *s, const mi_instance *instances, uint32_
  * whose `group` differs from the committed one (the message names it).  Every message starts with "mi_scene_update_geometry: ".  All checks come before any change: a
  * refused call leaves the scene, its revision and its device tables untouched, and so does a failed allocation of the edit's own device tables (MI_ERR_DEVICE, "the
  * scene is unchanged").  Any other MI_ERR_DEVICE leaves host and device out of step: commit again.  May be mixed freely with mi_scene_update_vertices / _instances,
- * which stay as they are (the former keeps refusing scenes with shape groups or instances).  Counts, indices, an instance's group, media on group members and analytic
+ * which are that call under their own names and refusals (the former keeps refusing scenes with shape groups or instances).  Counts, indices, an instance's group, media on group members and analytic
  * group members are out of reach of an update.  The trees keep the committed topology: after large deformations traversal slows down, a fresh commit is the remedy. */
 int mi_scene_update_geometry(mi_scene *s, const float *pos, const float *nrm, uint32_t n_verts, const mi_instance *instances, uint32_t n_instances);
 /* revision: in-place edits applied so far; tree_builds: host-side builds (tree, triangle records) this scene has gone through -- an update never moves it.  Either may be NULL */

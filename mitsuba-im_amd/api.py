@@ -447,7 +447,8 @@ class Scene:
         L.check(L.L.mi_scene_commit(h, device))
 
     def clone(self, device=0):
-        """mi_scene_clone: a replica on `device` (a scene of its own: the host-side build is reused, every table uploaded again)."""
+        """mi_scene_clone: a replica on `device` (a scene of its own: the host-side build is reused, every table uploaded again).  The replica shares this
+        object's description `sc`: give it a copy (`twin.sc = copy of sc`) before an update_* call on it, which records the new values there."""
         out = Scene.__new__(Scene); out.L = self.L; out.sc = self.sc; out.h = None
         h = C.c_void_p(); self.L.check(self.L.L.mi_scene_clone(self.h, device, C.byref(h))); out.h = h
         return out

@@ -311,8 +311,7 @@ template <typename T> static int up(void **dst, const std::vector<T> &v) {
     return 0;
 }
 void SceneHost::release() {
-    void **ps[] = {&dRefitOrderAll, &dGroupBox, &dPos, &dLeafSlot, &dLeafBox, &dNodeBox, &dRefitOrder, &dInstXf, &dLeafSlotInst, &dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
-    for (void **p : ps) if (*p) { (void) hipFree(*p); *p = nullptr; }
+    eachDevicePointer([](void *&p) { if (p) { (void) hipFree(p); p = nullptr; } });
 }
 int SceneHost::upload(int dev) {
     release(); device = dev;
@@ -473,8 +472,7 @@ int mi_scene_clone(mi_scene *s, uint32_t device, mi_scene **out) {
     mi_scene *c = new mi_scene();
     c->h = s->h;                                    // inputs + host-derived data
     {   // the copy must not own the source's device allocations
-        void **ps[] = {&c->h.dRefitOrderAll, &c->h.dGroupBox, &c->h.dPos, &c->h.dLeafSlot, &c->h.dLeafBox, &c->h.dNodeBox, &c->h.dRefitOrder, &c->h.dInstXf, &c->h.dLeafSlotInst, &c->h.dMaterialFlags, &c->h.dMedia, &c->h.dPrimMedia, &c->h.dPacketGroups, &c->h.dPacketExact, &c->h.dTexLevels, &c->h.dTexTexels, &c->h.dMipLut, &c->h.dTriUV, &c->h.dTextures, &c->h.dMaterialTables, &c->h.dInstances, &c->h.dEmitterX, &c->h.dAnalytic, &c->h.dNodes, &c->h.dTris, &c->h.dShade, &c->h.dI2, &c->h.dNrm, &c->h.dMaterials, &c->h.dEmitters, &c->h.dEmitterCdf, &c->h.dAreaCdf, &c->h.dFilter, &c->h.dSobolM32, &c->h.dSobolVdc, &c->h.dSobolVdcInv, &c->h.dEnvRGB, &c->h.dEnvCols, &c->h.dEnvRows, &c->h.dEnvWeights, &c->h.dEnvGuideRows, &c->h.dEnvGuideCols};
-        for (void **p : ps) *p = nullptr;
+        c->h.eachDevicePointer([](void *&p) { p = nullptr; });
         c->h.committed = false;
     }
     if (c->h.upload((int) device)) { std::string msg = std::string("mi_scene_clone: upload failed: ") + hipGetErrorString(hipGetLastError()); delete c; return fail(MI_ERR_DEVICE, msg); }
@@ -493,9 +491,9 @@ struct UpdateGuard {
 template <typename T> static hipError_t push(void *dst, const std::vector<T> &v) { return v.empty() || !dst ? hipSuccess : hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice); }
 extern "C" {
 #define UPDATE_ENTER(name) \
-    if (!s) return fail(MI_ERR_INVALID, name ": null scene"); \
-    if (!s->h.committed) return fail(MI_ERR_INVALID, name ": scene not committed (an update edits a committed scene in place)"); \
-    UpdateGuard updating; if (!updating.enter(s)) return fail(MI_ERR_INVALID, name ": a render is running on this scene (cancel it and wait for the run to return)")
+    if (!s) return fail(MI_ERR_INVALID, std::string(name) + ": null scene"); \
+    if (!s->h.committed) return fail(MI_ERR_INVALID, std::string(name) + ": scene not committed (an update edits a committed scene in place)"); \
+    UpdateGuard updating; if (!updating.enter(s)) return fail(MI_ERR_INVALID, std::string(name) + ": a render is running on this scene (cancel it and wait for the run to return)")
 
 int mi_scene_update_camera(mi_scene *s, const float *s2c, const float *c2w, float nearClip, float farClip) {
     if (!s || !s2c || !c2w) return fail(MI_ERR_INVALID, "mi_scene_update_camera: null argument");
@@ -540,155 +538,91 @@ int mi_scene_update_envmap_transform(mi_scene *s, const float *toWorld, float sc
     std::string msg; const int rc = s->h.updateEnvmapTransform(toWorld, scale, msg); if (rc) return fail(rc, msg);
     return MI_OK;
 }
-// Vertex edit.  Host: the checks, pos / nrm and the small tables (SceneHost::updateVertices).  Device: the new vertex arrays go up, k_tri_records rewrites every
-// per-triangle record, k_refit refits the existing tree level by level on one stream, the small tables go back into their allocations (the packet groups into a new
-// one when their count grew).  Synchronous like the other updates.
-int mi_scene_update_vertices(mi_scene *s, const float *pos, const float *nrm, uint32_t nVerts) {
-    if (!s || !pos) return fail(MI_ERR_INVALID, "mi_scene_update_vertices: null argument");
-    UPDATE_ENTER("mi_scene_update_vertices");
-    mi::SceneHost &h = s->h; const size_t cdfLen = h.areaCdf.size(), nGroups = h.packetGroups.size();
-    std::string msg; const int rc = h.checkVertices(pos, nrm, nVerts, msg); if (rc) return fail(rc, msg);
-    if (!h.geoPrepared) h.prepareGeometryEdit();      // derived from the committed tables alone: the scene itself is not changed yet
-    if (h.shade.size() != h.d.n_tris || h.nodes.size() != h.d.n_nodes || h.leafSlotOfPrim.size() != h.d.n_tris || h.leafBoxes.size() != h.tris.size() * 6 || h.nodeBoxes.size() != h.nodes.size() * 6 || h.refitOrder.size() > h.nodes.size())
-        return fail(MI_ERR_DEVICE, "mi_scene_update_vertices: host tables and device tables disagree in size");
-    HIPCHK(hipSetDevice(h.device));
-    if (!h.dPos || !h.dNodeBox || !h.dLeafSlot || !h.dLeafBox || !h.dRefitOrder) {      // first edit: the tables a commit does not need -- all five or none, and before the scene changes
-        void **five[] = {&h.dPos, &h.dNodeBox, &h.dLeafSlot, &h.dLeafBox, &h.dRefitOrder};
-        for (void **p : five) if (*p) { (void) hipFree(*p); *p = nullptr; }
-        bool bad = hipMalloc(&h.dPos, std::max<size_t>(h.pos.size() * 4, 16)) != hipSuccess || hipMalloc(&h.dNodeBox, std::max<size_t>(h.nodeBoxes.size() * 4, 16)) != hipSuccess;
-        bad = bad || mi::up(&h.dLeafSlot, h.leafSlotOfPrim) || mi::up(&h.dLeafBox, h.leafBoxes) || mi::up(&h.dRefitOrder, h.refitOrder);
-        if (bad) {
-            const std::string why = hipGetErrorString(hipGetLastError());
-            for (void **p : five) if (*p) { (void) hipFree(*p); *p = nullptr; }
-            return fail(MI_ERR_DEVICE, "mi_scene_update_vertices: allocation failed, the scene is unchanged: " + why);
-        }
-    }
-    // from here on the scene changes; a device error below leaves host and device tables out of step (see the header)
-    h.applyVertices(pos, nrm, nVerts);
-    if (h.emittersD.size() != h.d.n_emitters || h.areaCdf.size() != cdfLen) return fail(MI_ERR_DEVICE, "mi_scene_update_vertices: host tables and device tables disagree in size");
-    HIPCHK(push(h.dPos, h.pos)); HIPCHK(push(h.dNrm, h.nrm));
-    mi::GeoEditTables g{}; g.pos = (const float *) h.dPos; g.nrm = h.nrm.empty() ? nullptr : (const float *) h.dNrm; g.shade = (TriShade *) h.dShade; g.triuv = h.triuv.empty() ? nullptr : (TriUV *) h.dTriUV;
-    g.tris = const_cast<TriAccelD *>(h.d.tris); g.packetExact = (TriAccelD *) h.dPacketExact; g.leafSlot = (const uint32_t *) h.dLeafSlot; g.leafBox = (float *) h.dLeafBox;
-    g.nodes = (BvhNode *) h.dNodes; g.nodeBox = (float *) h.dNodeBox; g.nTris = h.d.n_tris; g.nPacketExact = (uint32_t) std::min<size_t>(h.packetExact.size(), h.d.n_tris); g.wide = h.wideBvh ? 1u : 0u;
-    mi_launch_tri_records(g, nullptr);
-    for (size_t l = 0; l + 1 < h.refitLevelStart.size(); ++l)      // bottom-up: level l reads the boxes levels < l wrote; stream order is the only synchronisation
-        mi_launch_refit_level(g, (const uint32_t *) h.dRefitOrder, h.refitLevelStart[l], h.refitLevelStart[l + 1] - h.refitLevelStart[l], h.d.n_nodes, nullptr);
-    HIPCHK(hipGetLastError());
-    if (h.packetGroups.size() > nGroups) {      // pairs dissolved: the pass-1 table grew
-        void *grown = nullptr; if (mi::up(&grown, h.packetGroups)) return fail(MI_ERR_DEVICE, "mi_scene_update_vertices: allocation failed");
-        HIPCHK(hipStreamSynchronize(nullptr)); (void) hipFree(h.dPacketGroups); h.dPacketGroups = grown; h.d.packet_groups = (const PacketGroupD *) grown;
-    } else HIPCHK(push(h.dPacketGroups, h.packetGroups));
-    HIPCHK(push(h.dEmitters, h.emittersD)); HIPCHK(push(h.dAreaCdf, h.areaCdf));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    return MI_OK;
-}
-// Instance edit.  Host: the checks, `instances`, the scene box and what depends on it (SceneHost::updateInstances).  Device: the new transform pairs go up,
-// k_instance_records rewrites the two matrices of every InstanceD and the padded box of its leaf record, k_refit refits the scene-level tree level by level on one
-// stream (the group trees are not reachable from node 0 and stay), the small tables go back into their allocations.  Synchronous like the other updates.
-int mi_scene_update_instances(mi_scene *s, const mi_instance *instances, uint32_t n) {
-    if (!s || !instances) return fail(MI_ERR_INVALID, "mi_scene_update_instances: null argument");
-    UPDATE_ENTER("mi_scene_update_instances");
-    mi::SceneHost &h = s->h;
-    std::string msg; const int rc = h.checkInstances(instances, n, msg); if (rc) return fail(rc, msg);
-    if (!h.geoPrepared) h.prepareGeometryEdit();      // derived from the committed tables alone: the scene itself is not changed yet
-    if (h.instancesD.size() != h.d.n_instances || n != h.d.n_instances || h.nodes.size() != h.d.n_nodes || h.leafSlotOfInstance.size() != n || h.leafBoxes.size() != h.tris.size() * 6 || h.nodeBoxes.size() != h.nodes.size() * 6 || h.refitOrder.size() > h.nodes.size())
-        return fail(MI_ERR_DEVICE, "mi_scene_update_instances: host tables and device tables disagree in size");
-    for (uint32_t slot : h.leafSlotOfInstance) if (slot >= h.tris.size()) return fail(MI_ERR_DEVICE, "mi_scene_update_instances: host tables and device tables disagree in size");
-    HIPCHK(hipSetDevice(h.device));
-    if (!h.dInstXf || !h.dLeafSlotInst || !h.dLeafBox || !h.dNodeBox || !h.dRefitOrder) {      // first edit: the tables a commit does not need -- all five or none, and before the scene changes
-        void **five[] = {&h.dInstXf, &h.dLeafSlotInst, &h.dLeafBox, &h.dNodeBox, &h.dRefitOrder};
-        for (void **p : five) if (*p) { (void) hipFree(*p); *p = nullptr; }
-        bool bad = hipMalloc(&h.dInstXf, std::max<size_t>((size_t) n * 96, 16)) != hipSuccess || hipMalloc(&h.dNodeBox, std::max<size_t>(h.nodeBoxes.size() * 4, 16)) != hipSuccess;
-        bad = bad || mi::up(&h.dLeafSlotInst, h.leafSlotOfInstance) || mi::up(&h.dLeafBox, h.leafBoxes) || mi::up(&h.dRefitOrder, h.refitOrder);
-        if (bad) {
-            const std::string why = hipGetErrorString(hipGetLastError());
-            for (void **p : five) if (*p) { (void) hipFree(*p); *p = nullptr; }
-            return fail(MI_ERR_DEVICE, "mi_scene_update_instances: allocation failed, the scene is unchanged: " + why);
-        }
-    }
-    // from here on the scene changes; a device error below leaves host and device tables out of step (see the header)
-    h.applyInstances(instances, n);
-    if (h.emittersD.size() != h.d.n_emitters) return fail(MI_ERR_DEVICE, "mi_scene_update_instances: host tables and device tables disagree in size");
-    std::vector<float> xf((size_t) n * 24);
-    for (uint32_t i = 0; i < n; ++i) { memcpy(&xf[(size_t) i * 24], instances[i].to_world, 48); memcpy(&xf[(size_t) i * 24 + 12], instances[i].to_object, 48); }
-    HIPCHK(push(h.dInstXf, xf));
-    mi::InstEditTables it{}; it.xf = (const float *) h.dInstXf; it.inst = (InstanceD *) h.dInstances; it.leafSlot = (const uint32_t *) h.dLeafSlotInst; it.leafBox = (float *) h.dLeafBox; it.n = n;
-    mi::GeoEditTables g{}; g.leafBox = (float *) h.dLeafBox; g.nodes = (BvhNode *) h.dNodes; g.nodeBox = (float *) h.dNodeBox; g.wide = h.wideBvh ? 1u : 0u;
-    mi_launch_instance_records(it, nullptr);
-    for (size_t l = 0; l + 1 < h.refitLevelStart.size(); ++l)      // bottom-up over the scene-level tree: level l reads the boxes levels < l wrote; stream order is the only synchronisation
-        mi_launch_refit_level(g, (const uint32_t *) h.dRefitOrder, h.refitLevelStart[l], h.refitLevelStart[l + 1] - h.refitLevelStart[l], h.d.n_nodes, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(push(h.dEmitters, h.emittersD)); HIPCHK(push(h.dEmitterX, h.emitterX));      // as the vertex edit pushes them; the scene record travels with the next run
-    HIPCHK(hipStreamSynchronize(nullptr));
-    return MI_OK;
-}
-// Geometry edit: one frame of an animation -- vertices (shape-group members included) and / or instance transforms.  Host: the checks, pos / nrm / instances, the group
-// boxes, the scene box and what depends on it (SceneHost::applyGeometry).  Device, one chain on the null stream: the inputs go up (vertex arrays, group boxes, transform
-// pairs), k_tri_records rewrites every per-triangle record and leaf box, k_instance_records takes the group boxes into InstanceD::glo / ghi and rewrites matrices and
+// Geometry edit: one frame of an animation -- vertices (shape-group members included) and / or instance transforms; mi_scene_update_vertices and _instances are this
+// chain under their own names and refusals.  Host: the checks, pos / nrm / instances, the group boxes, the scene box and what depends on it (SceneHost::applyGeometry).
+// Device, one chain on the null stream: the inputs go up (vertex arrays and group boxes when vertices are given, transform pairs on a scene with instances),
+// k_tri_records rewrites every per-triangle record and leaf box, k_instance_records takes the group boxes into InstanceD::glo / ghi and rewrites matrices and
 // instance leaf boxes, k_refit refits level by level -- every tree when vertices moved (nodes of equal height of all trees share a launch), the scene level alone
-// otherwise -- and the small tables go back into their allocations.  Synchronous like the other updates.
-int mi_scene_update_geometry(mi_scene *s, const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *instances, uint32_t nInstances) {
-    if (!s) return fail(MI_ERR_INVALID, "mi_scene_update_geometry: null scene");
-    if (!pos && !instances) return fail(MI_ERR_INVALID, "mi_scene_update_geometry: null argument: neither vertices nor instances given");
-    UPDATE_ENTER("mi_scene_update_geometry");
+// otherwise (the group trees are not reachable from node 0 and stay) -- and the small tables that follow the vertices go back into their allocations (the packet
+// groups into a new one when their count grew).  Synchronous like the other updates.
+static int updateGeometryOnDevice(mi::GeoEntry entry, mi_scene *s, const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *instances, uint32_t nInstances) {
+    const std::string name = mi::geoEntryName(entry); const bool moved = pos != nullptr;      // vertices given
+    UPDATE_ENTER(name);
     mi::SceneHost &h = s->h; const size_t cdfLen = h.areaCdf.size(), nGroups = h.packetGroups.size();
-    std::string msg; const int rc = h.checkGeometry(pos, nrm, nVerts, instances, nInstances, msg); if (rc) return fail(rc, msg);
+    std::string msg; const int rc = h.checkGeometry(entry, pos, nrm, nVerts, instances, nInstances, msg); if (rc) return fail(rc, msg);
     if (!h.geoPrepared) h.prepareGeometryEdit();      // derived from the committed topology alone: the scene itself is not changed yet
     const uint32_t ni = (uint32_t) h.instances.size(), ng = (uint32_t) (h.groupBoxes.size() / 6);
     if (h.shade.size() != h.d.n_tris || h.nodes.size() != h.d.n_nodes || h.leafSlotOfPrim.size() != h.d.n_tris || h.instancesD.size() != h.d.n_instances || ni != h.d.n_instances || h.leafSlotOfInstance.size() != ni ||
         h.leafBoxes.size() != h.tris.size() * 6 || h.nodeBoxes.size() != h.nodes.size() * 6 || h.refitOrder.size() > h.nodes.size() || h.refitOrderAll.size() > h.nodes.size())
-        return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
-    for (uint32_t slot : h.leafSlotOfInstance) if (slot >= h.tris.size()) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
-    for (uint32_t slot : h.leafSlotOfPrim) if (slot >= h.tris.size()) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
-    for (const InstanceD &in : h.instancesD) if (in.group >= ng) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
+        return fail(MI_ERR_DEVICE, name + ": host tables and device tables disagree in size");
+    for (uint32_t slot : h.leafSlotOfInstance) if (slot >= h.tris.size()) return fail(MI_ERR_DEVICE, name + ": host tables and device tables disagree in size");
+    if (moved) for (const InstanceD &in : h.instancesD) if (in.group >= ng) return fail(MI_ERR_DEVICE, name + ": host tables and device tables disagree in size");      // the group boxes are indexed by it
+    // one slot per triangle (a megabyte on a large mesh, cold in every call): checked when the table goes up.  The kernel reads the device copy, made once below from a
+    // table that only prepareGeometryEdit() writes
+    if (moved && !h.dLeafSlot) for (uint32_t slot : h.leafSlotOfPrim) if (slot >= h.tris.size()) return fail(MI_ERR_DEVICE, name + ": host tables and device tables disagree in size");
     HIPCHK(hipSetDevice(h.device));
-    {   // The tables a commit does not need.  Only what is MISSING is allocated: after an earlier mi_scene_update_vertices / _instances the device's leaf boxes are current
-        // while their host mirror is stale until refreshHostGeometry() -- they must not be uploaded again.  A leaf-box table that does not exist yet means that no edit
-        // has run since the commit, so the mirror prepareGeometryEdit() filled is current.  Every table of the two older calls is allocated here as well, so that their
-        // own first-edit blocks (which free and re-upload the leaf boxes) find nothing missing afterwards.  dNodeBox stays uninitialised: a node's box is written by the
-        // refit of its level before any higher level reads it.
+    {   // The tables a commit does not need: each is allocated by the first edit that uses it, before the scene changes, and only when it is MISSING.  All but one are
+        // staging space or copies of what prepareGeometryEdit() derived from the topology.  The one rule: the device's leaf boxes are newer than the mirror (stale from
+        // the first edit until refreshHostGeometry()); never upload them twice.  A leaf-box table that does not exist yet means that no edit has run on this handle, so
+        // the mirror is current.  dNodeBox stays uninitialised: a node's box is written by the refit of its level before any higher level reads it.
         std::vector<void **> mine; bool bad = false;
-        auto raw = [&](void **p, size_t bytes) { if (*p || bad) return; if (hipMalloc(p, std::max<size_t>(bytes, 16)) != hipSuccess) { *p = nullptr; bad = true; } else mine.push_back(p); };
-        auto filled = [&](void **p, const std::vector<uint32_t> &v) { if (*p || bad) return; if (mi::up(p, v)) bad = true; if (*p) mine.push_back(p); };
-        raw(&h.dPos, h.pos.size() * 4); raw(&h.dNodeBox, h.nodeBoxes.size() * 4); raw(&h.dInstXf, (size_t) ni * 96); raw(&h.dGroupBox, (size_t) ng * 24);
-        filled(&h.dLeafSlot, h.leafSlotOfPrim); filled(&h.dLeafSlotInst, h.leafSlotOfInstance); filled(&h.dRefitOrder, h.refitOrder); filled(&h.dRefitOrderAll, h.refitOrderAll);
-        if (!h.dLeafBox && !bad) { if (mi::up(&h.dLeafBox, h.leafBoxes)) bad = true; if (h.dLeafBox) mine.push_back(&h.dLeafBox); }
+        auto raw = [&](bool used, void **p, size_t bytes) { if (!used || *p || bad) return; if (hipMalloc(p, std::max<size_t>(bytes, 16)) != hipSuccess) { *p = nullptr; bad = true; } else mine.push_back(p); };
+        auto filled = [&](bool used, void **p, const auto &v) { if (!used || *p || bad) return; if (mi::up(p, v)) bad = true; if (*p) mine.push_back(p); };
+        raw(moved, &h.dPos, h.pos.size() * 4); raw(true, &h.dNodeBox, h.nodeBoxes.size() * 4); raw(ni, &h.dInstXf, (size_t) ni * 96); raw(moved && ni, &h.dGroupBox, (size_t) ng * 24);
+        filled(moved, &h.dLeafSlot, h.leafSlotOfPrim); filled(ni, &h.dLeafSlotInst, h.leafSlotOfInstance);
+        filled(true, &h.dLeafBox, h.leafBoxes);      // slot tables, leaf boxes, refit order: the order in which the two older calls allocated them
+        filled(!moved, &h.dRefitOrder, h.refitOrder); filled(moved, &h.dRefitOrderAll, h.refitOrderAll);
         if (bad) {
             const std::string why = hipGetErrorString(hipGetLastError());
             for (void **p : mine) { (void) hipFree(*p); *p = nullptr; }
-            return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: allocation failed, the scene is unchanged: " + why);
+            return fail(MI_ERR_DEVICE, name + ": allocation failed, the scene is unchanged: " + why);
         }
     }
     // from here on the scene changes; a device error below leaves host and device tables out of step (see the header)
     h.applyGeometry(pos, nrm, nVerts, instances, nInstances);
-    if (h.emittersD.size() != h.d.n_emitters || h.areaCdf.size() != cdfLen || h.groupBoxes.size() != (size_t) ng * 6) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: host tables and device tables disagree in size");
-    if (pos) { HIPCHK(push(h.dPos, h.pos)); HIPCHK(push(h.dNrm, h.nrm)); }
-    mi::GeoEditTables g{}; g.pos = (const float *) h.dPos; g.nrm = h.nrm.empty() ? nullptr : (const float *) h.dNrm; g.shade = (TriShade *) h.dShade; g.triuv = h.triuv.empty() ? nullptr : (TriUV *) h.dTriUV;
-    g.tris = const_cast<TriAccelD *>(h.d.tris); g.packetExact = (TriAccelD *) h.dPacketExact; g.leafSlot = (const uint32_t *) h.dLeafSlot; g.leafBox = (float *) h.dLeafBox;
-    g.nodes = (BvhNode *) h.dNodes; g.nodeBox = (float *) h.dNodeBox; g.nTris = h.d.n_tris; g.nPacketExact = (uint32_t) std::min<size_t>(h.packetExact.size(), h.d.n_tris); g.wide = h.wideBvh ? 1u : 0u;
-    if (pos) mi_launch_tri_records(g, nullptr);
-    if (ni) {
-        std::vector<float> xf((size_t) ni * 24);      // the new transforms, or the committed ones again: the instance box also follows the group box
-        for (uint32_t i = 0; i < ni; ++i) { memcpy(&xf[(size_t) i * 24], h.instances[i].to_world, 48); memcpy(&xf[(size_t) i * 24 + 12], h.instances[i].to_object, 48); }
-        HIPCHK(push(h.dInstXf, xf)); HIPCHK(push(h.dGroupBox, h.groupBoxes));
-        mi::InstEditTables it{}; it.xf = (const float *) h.dInstXf; it.inst = (InstanceD *) h.dInstances; it.leafSlot = (const uint32_t *) h.dLeafSlotInst; it.leafBox = (float *) h.dLeafBox; it.n = ni;
-        it.groupBox = (const float *) h.dGroupBox; it.nGroups = ng;
-        mi_launch_instance_records(it, nullptr);
+    if (h.emittersD.size() != h.d.n_emitters || h.areaCdf.size() != cdfLen || h.groupBoxes.size() != (size_t) ng * 6) return fail(MI_ERR_DEVICE, name + ": host tables and device tables disagree in size");
+    const mi::GeoEditTables g = h.geoEditTables(true);
+    if (pos) {
+        HIPCHK(push(h.dPos, h.pos));
+        HIPCHK(push(h.dNrm, h.nrm));
+        mi_launch_tri_records(g, nullptr);
+    }
+    if (ni) {      // the new transforms, or the committed ones again: the instance box also follows the group box
+        const std::vector<float> xf = h.instanceTransformPairs();
+        HIPCHK(push(h.dInstXf, xf));
+        if (pos) HIPCHK(push(h.dGroupBox, h.groupBoxes));      // without new vertices the records' glo / ghi are current
+        mi_launch_instance_records(h.instEditTables(true, (const float *) h.dInstXf, moved), nullptr);
     }
     {   // bottom-up: level l reads the boxes levels < l wrote; stream order is the only synchronisation.  Vertices moved: every tree; instances only: the scene level
         const std::vector<uint32_t> &start = pos ? h.refitLevelStartAll : h.refitLevelStart; const uint32_t *order = (const uint32_t *) (pos ? h.dRefitOrderAll : h.dRefitOrder);
         for (size_t l = 0; l + 1 < start.size(); ++l) mi_launch_refit_level(g, order, start[l], start[l + 1] - start[l], h.d.n_nodes, nullptr);
     }
     HIPCHK(hipGetLastError());
-    if (!ni && pos) {      // the packet tables of a scene without instances, as mi_scene_update_vertices sends them
+    if (pos && !ni) {      // the packet tables: a scene with instances never runs in packet mode
         if (h.packetGroups.size() > nGroups) {      // pairs dissolved: the pass-1 table grew
-            void *grown = nullptr; if (mi::up(&grown, h.packetGroups)) return fail(MI_ERR_DEVICE, "mi_scene_update_geometry: allocation failed");
+            void *grown = nullptr; if (mi::up(&grown, h.packetGroups)) return fail(MI_ERR_DEVICE, name + ": allocation failed");
             HIPCHK(hipStreamSynchronize(nullptr)); (void) hipFree(h.dPacketGroups); h.dPacketGroups = grown; h.d.packet_groups = (const PacketGroupD *) grown;
         } else HIPCHK(push(h.dPacketGroups, h.packetGroups));
     }
-    HIPCHK(push(h.dEmitters, h.emittersD)); HIPCHK(push(h.dAreaCdf, h.areaCdf)); HIPCHK(push(h.dEmitterX, h.emitterX));
+    if (pos) {      // what buildEmitterTables() derives from the vertices; emitterCdf and emitterX follow the emitter records alone and are current on the device
+        HIPCHK(push(h.dEmitters, h.emittersD));
+        HIPCHK(push(h.dAreaCdf, h.areaCdf));
+    }
     HIPCHK(hipStreamSynchronize(nullptr));
     return MI_OK;
+}
+int mi_scene_update_vertices(mi_scene *s, const float *pos, const float *nrm, uint32_t nVerts) {
+    if (!s || !pos) return fail(MI_ERR_INVALID, "mi_scene_update_vertices: null argument");
+    return updateGeometryOnDevice(mi::GeoEntry::Vertices, s, pos, nrm, nVerts, nullptr, 0);
+}
+int mi_scene_update_instances(mi_scene *s, const mi_instance *instances, uint32_t n) {
+    if (!s || !instances) return fail(MI_ERR_INVALID, "mi_scene_update_instances: null argument");
+    return updateGeometryOnDevice(mi::GeoEntry::Instances, s, nullptr, nullptr, 0, instances, n);
+}
+int mi_scene_update_geometry(mi_scene *s, const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *instances, uint32_t nInstances) {
+    if (!s) return fail(MI_ERR_INVALID, "mi_scene_update_geometry: null scene");
+    if (!pos && !instances) return fail(MI_ERR_INVALID, "mi_scene_update_geometry: null argument: neither vertices nor instances given");
+    return updateGeometryOnDevice(mi::GeoEntry::Geometry, s, pos, nrm, nVerts, instances, nInstances);
 }
 int mi_scene_revision(mi_scene *s, uint64_t *revision, uint64_t *treeBuilds) {
     if (!s) return fail(MI_ERR_INVALID, "mi_scene_revision: null scene");

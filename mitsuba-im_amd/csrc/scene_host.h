@@ -7,6 +7,10 @@
 
 namespace mi {
 
+struct GeoEditTables; struct InstEditTables;      // geometry_records.h
+enum class GeoEntry { Vertices, Instances, Geometry };      // which of mi_scene_update_vertices / _instances / _geometry an edit came in through
+inline const char *geoEntryName(GeoEntry e) { return e == GeoEntry::Vertices ? "mi_scene_update_vertices" : e == GeoEntry::Instances ? "mi_scene_update_instances" : "mi_scene_update_geometry"; }
+
 struct SceneHost {
     // inputs (mi_scene_set_*)
     std::vector<float> pos, nrm, uv; std::vector<uint32_t> idx; std::vector<mi_shape> shapes;
@@ -66,25 +70,23 @@ struct SceneHost {
     int updateMaterials(const mi_material *m, uint32_t n, std::string &msg, bool *flagsChanged);
     int updateEmitters(const mi_emitter *e, uint32_t n, std::string &msg);
     int updateEnvmapTransform(const float *toWorld16, float scale, std::string &msg);
-    // Vertex edit: new positions (and normals) for the committed vertex array.  Replaces pos / nrm and the small tables at once; the per-triangle mirrors (tris, shade,
-    // triuv, packetExact) and `nodes` become STALE -- the device recomputes its copies (kernels_geometry.hip) and refreshHostGeometry() brings the mirrors up to date
-    // with the same arithmetic (geometry_records.h) before anything reads them.  Keeping them current eagerly would put the per-triangle host loop back into every edit.
-    int updateVertices(const float *pos, const float *nrm, uint32_t nVerts, std::string &msg);      // = checkVertices, then applyVertices
-    int checkVertices(const float *pos, const float *nrm, uint32_t nVerts, std::string &msg) const;   // every refusal; changes nothing
-    void applyVertices(const float *pos, const float *nrm, uint32_t nVerts);                            // checked arguments only
-    // Instance edit: new to_world / to_object for every committed instance (the groups stay).  Replaces `instances`, the scene box and what depends on it at once;
-    // instancesD and `nodes` become STALE -- the device rewrites its copies (k_instance_records, k_refit) and refreshHostGeometry() repeats the two steps on the mirrors.
-    int updateInstances(const mi_instance *in, uint32_t n, std::string &msg);      // = checkInstances, then applyInstances
-    int checkInstances(const mi_instance *in, uint32_t n, std::string &msg) const;   // every refusal; changes nothing
-    void applyInstances(const mi_instance *in, uint32_t n);                            // checked arguments only
-    // Geometry edit (mi_scene_update_geometry): one frame of an animation -- new positions (and normals) for the whole vertex array, shape-group members included, and / or
-    // new transforms for every instance.  Replaces pos / nrm / instances, the group boxes, the scene box and the small tables at once; the per-triangle mirrors, instancesD
-    // (glo / ghi included) and `nodes` -- scene level AND group trees -- become STALE until refreshHostGeometry() repeats the device's steps.
-    int updateGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *in, uint32_t nInstances, std::string &msg);      // = checkGeometry, then applyGeometry
-    int checkGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *in, uint32_t nInstances, std::string &msg) const;   // every refusal; changes nothing
-    void applyGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *in, uint32_t nInstances);                            // checked arguments only; a null part stays
-    int checkVerticesAs(const std::string &who, bool groupsAllowed, const float *pos, const float *nrm, uint32_t nVerts, std::string &msg) const;      // the rules of checkVertices under another caller's name
-    int checkInstancesAs(const std::string &who, const mi_instance *in, uint32_t n, std::string &msg) const;
+    // Geometry edits: one frame of an animation -- new positions (and normals) for the whole vertex array, shape-group members included, and / or new to_world /
+    // to_object for every committed instance (the groups stay).  Replaces pos / nrm / instances, the group boxes, the scene box and the small tables at once; the
+    // per-triangle mirrors (tris, shade, triuv, packetExact), instancesD (glo / ghi included) and `nodes` -- scene level AND group trees -- become STALE: the device
+    // recomputes its copies (kernels_geometry.hip) and refreshHostGeometry() repeats its steps on the mirrors with the same arithmetic (geometry_records.h) before
+    // anything reads them.  Keeping them current eagerly would put the per-triangle host loop back into every edit.
+    // One check and one apply serve the three entry points; `entry` names the caller in every message and turns on the two refusals only mi_scene_update_vertices makes
+    // (a scene with instances, a shape that is a group member).
+    int updateVertices(const float *pos, const float *nrm, uint32_t nVerts, std::string &msg);      // = checkGeometry as GeoEntry::Vertices, then applyGeometry
+    int updateInstances(const mi_instance *in, uint32_t n, std::string &msg);                        // ... as GeoEntry::Instances ...
+    int updateGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *in, uint32_t nInstances, std::string &msg);      // ... as GeoEntry::Geometry ...
+    int checkGeometry(GeoEntry entry, const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *in, uint32_t nInstances, std::string &msg) const;   // every refusal; changes nothing
+    void applyGeometry(const float *pos, const float *nrm, uint32_t nVerts, const mi_instance *in, uint32_t nInstances);      // checked arguments only; a null part stays, and so does what is derived from it alone
+    // The argument records of the three edit steps (geometry_records.h) over the device tables or over the host mirrors: the device chain (api.cpp) and
+    // refreshHostGeometry() run the same steps on the same layout.  xf = the packed transform pairs where the step reads them.
+    GeoEditTables geoEditTables(bool onDevice);
+    InstEditTables instEditTables(bool onDevice, const float *xf, bool withGroupBoxes);
+    std::vector<float> instanceTransformPairs() const;      // 24 floats per instance: rows 0..2 of to_world, then of to_object
     void buildGroupBoxes();             // groupBoxes: per shape group the union of its member shapes' vertices in shape order, enlarged like a kd-tree root (commitHost() and the geometry edit)
     std::vector<float> groupBoxes;      // 6 floats (lo, hi) per shape group
     std::vector<int> groupRoot;         // root node of every group's tree in `nodes`
@@ -95,9 +97,14 @@ struct SceneHost {
     std::vector<uint32_t> refitOrderAll, refitLevelStartAll;   // the same over the scene-level tree and every group tree: nodes of equal height share a level, no tree reads another tree's nodes
     std::vector<float> leafBoxes, nodeBoxes;   // padded box (lo, hi) per leaf record; exact union of the child boxes per node (a group tree's: valid after its first refit only)
     bool geoPrepared = false, geoStale = false, instStale = false;
-    void *dPos = nullptr, *dLeafSlot = nullptr, *dLeafBox = nullptr, *dNodeBox = nullptr, *dRefitOrder = nullptr;   // device side of a vertex edit, allocated at the first one
-    void *dRefitOrderAll = nullptr, *dGroupBox = nullptr;   // device side of a geometry edit (with all of the above), allocated at the first one: refitOrderAll, the group boxes of the current edit
-    void *dInstXf = nullptr, *dLeafSlotInst = nullptr;   // device side of an instance edit (with dLeafBox, dNodeBox, dRefitOrder), allocated at the first one: the 24-float transform pairs, leafSlotOfInstance
+    // device side of the geometry edits, each table allocated by the first edit that needs it (api.cpp): the vertex array, leafSlotOfPrim, the leaf and node boxes,
+    // refitOrder, refitOrderAll, the group boxes of the current edit, the 24-float transform pairs, leafSlotOfInstance
+    void *dPos = nullptr, *dLeafSlot = nullptr, *dLeafBox = nullptr, *dNodeBox = nullptr, *dRefitOrder = nullptr, *dRefitOrderAll = nullptr, *dGroupBox = nullptr, *dInstXf = nullptr, *dLeafSlotInst = nullptr;
+    // Every device allocation the scene owns, listed here and nowhere else: release() frees and clears each, mi_scene_clone clears those of the copy it is about to upload.
+    template <typename F> void eachDevicePointer(F f) {
+        void **ps[] = {&dRefitOrderAll, &dGroupBox, &dPos, &dLeafSlot, &dLeafBox, &dNodeBox, &dRefitOrder, &dInstXf, &dLeafSlotInst, &dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
+        for (void **p : ps) f(*p);
+    }
     ~SceneHost() { release(); }
 };
 

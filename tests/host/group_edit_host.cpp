@@ -254,6 +254,13 @@ static void interleavings(const char *kind) {
             CHECK(h.updateGeometry(VA.pos.data(), VA.nrm.data(), nv, nullptr, 0, msg) == MI_OK, "vertices back"); h.refreshHostGeometry();
             SceneHost never; fillFrom(never, 0, 0); CHECK(sameTables(h, never), "back through both calls: the committed tables"); }
     }
+    {   // a copy taken mid-sequence, as mi_scene_clone takes it (after refreshHostGeometry()): its first edit finds the edit state prepared; the source keeps its tables
+        SceneHost h; fillFrom(h, 0, 0);
+        CHECK(h.updateGeometry(VB.pos.data(), VB.nrm.data(), nv, nullptr, 0, msg) == MI_OK && h.updateInstances(IB.data(), ni, msg) == MI_OK, "two edits before the copy"); h.refreshHostGeometry();
+        SceneHost twin(h); CHECK(twin.geoPrepared && !twin.geoStale && !twin.instStale && twin.revision == 2, "the copy carries the edit state");
+        CHECK(twin.updateGeometry(VA.pos.data(), VA.nrm.data(), nv, IA.data(), ni, msg) == MI_OK && twin.revision == 3 && h.revision == 2, "the copy's edit advances its own revision"); twin.refreshHostGeometry();
+        SceneHost never; fillFrom(never, 0, 0); CHECK(sameTables(twin, never), "the edited copy holds the committed tables"); enclosed(twin, "edited copy");
+        CHECK(sameTables(h, one), "the source of the copy keeps its tables"); }
     // a scene without instances and without groups: updateGeometry(vertices) is updateVertices, packet tables included, and the two mix
     {   SceneHost a, b; fillFrom(a, 0, 0, false); fillFrom(b, 0, 0, false);
         CHECK(a.updateVertices(VB.pos.data(), VB.nrm.data(), nv, msg) == MI_OK && b.updateGeometry(VB.pos.data(), VB.nrm.data(), nv, nullptr, 0, msg) == MI_OK, "both calls on a scene without instances");

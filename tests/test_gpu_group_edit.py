@@ -221,6 +221,37 @@ def test_sequence_on_one_handle(mi, oracle):
     edit_and_compare(mi, oracle, B, A, "after the recommit", 0.25, inst=True, how=None, gs=gs, r=mi.Render(gs), builds=2)
 
 
+def test_geometry_call_first_then_the_older_call(mi, oracle):
+    """a fresh handle's first edit is update_geometry(pos, nrm), its second update_instances, with no read of the scene in between: the older call finds the tables of
+    the first edit (the device's leaf boxes, newer than their host mirror, among them) and adds its own; tables, intersections and samples equal a fresh scene's"""
+    S = mi.scenes; A = garden(S); other = garden(S, seed=1).instances; V = deformed(A); pairs = triples(A)
+    gs = mi.Scene(clone(A)); r = mi.Render(gs)
+    gs.update_geometry(V.pos, V.nrm); gs.update_instances(other)
+    assert gs.revision() == (2, 1)
+    D = described(V, instances=other); fresh_scene = mi.Scene(clone(D)); got = r.samples(pairs); fresh = mi.Render(fresh_scene).samples(pairs)
+    assert (bits(got) == bits(fresh)).all(), int((bits(got) != bits(fresh)).any(1).sum())
+    same_intersections(gs, fresh_scene, D, "geometry call, then the older call"); compare_tables(gs, fresh_scene)
+    assert gs.revision() == (2, 1)
+
+
+def test_edit_a_clone_taken_mid_sequence(mi, oracle):
+    """two edits on gs (vertices, then instances), a clone() of it, and update_geometry back to A on the clone: the clone's first edit finds the edit state prepared and
+    no device edit table; its tables and samples equal a fresh scene of A, its revision advances by one, and gs renders what it rendered before"""
+    S = mi.scenes; A = garden(S); other = garden(S, seed=1).instances; V = deformed(A); pairs = triples(A)
+    gs = mi.Scene(clone(A)); r = mi.Render(gs)
+    gs.update_geometry(V.pos, V.nrm); gs.update_instances(other); kept = r.samples(pairs)
+    twin = gs.clone(); twin.sc = clone(gs.sc); rev0 = twin.revision()      # a description of its own: Scene.clone() shares the source's
+    twin.update_geometry(A.pos, A.nrm, A.instances)
+    assert twin.revision() == (rev0[0] + 1, rev0[1]) and gs.revision() == (2, 1)
+    fresh_scene = mi.Scene(clone(A)); got = mi.Render(twin).samples(pairs); fresh = mi.Render(fresh_scene).samples(pairs)
+    assert (bits(got) == bits(fresh)).all(), int((bits(got) != bits(fresh)).any(1).sum())
+    same_intersections(twin, fresh_scene, A, "edited clone"); compare_tables(twin, fresh_scene)
+    assert (bits(got) != bits(kept)).any(1).mean() > 0.25      # as "after the recommit" above: the same two descriptions
+    D = described(V, instances=other); fresh_d = mi.Scene(clone(D))
+    assert (bits(r.samples(pairs)) == bits(kept)).all() and (bits(kept) == bits(mi.Render(fresh_d).samples(pairs))).all()
+    compare_tables(gs, fresh_d)
+
+
 # ---------------------------------------------------------------------------------------------- 7. a scene without instances
 def test_scene_without_instances(mi, oracle):
     """cornell_box (32 triangles, the packet path): update_geometry(pos) leaves the device tables and the samples update_vertices(pos) leaves on a second handle;
