@@ -283,6 +283,13 @@ int mi_scene_update_instances(mi_scene *s, const mi_instance *instances, uint32_
  * which are that call under their own names and refusals (the former keeps refusing scenes with shape groups or instances).  Counts, indices, an instance's group, media on group members and analytic
  * group members are out of reach of an update.  The trees keep the committed topology: after large deformations traversal slows down, a fresh commit is the remedy. */
 int mi_scene_update_geometry(mi_scene *s, const float *pos, const float *nrm, uint32_t n_verts, const mi_instance *instances, uint32_t n_instances);
+/* Frame mark: snapshots what a geometry or camera edit can change -- the vertex positions (shape-group members included), every instance's to_world, the 12 floats of
+ * mi_scene_world_to_pixel and the camera origin -- as the "previous" state of the prevPosition / motion fields (below).  Previous = the state at the LAST mark, however
+ * many edits followed it; a scene that was never marked, or was committed again since, has previous = current.  The device tables (vertex array, 48 B per instance) are
+ * allocated by the first mark and freed with the scene; the host keeps the snapshot too, so that a replica (mi_scene_clone) carries it.  A mark renders nothing
+ * differently and moves neither `revision` nor `tree_builds`.  Returns when the device has finished.  MI_ERR_INVALID: null scene, scene not committed, a run in flight,
+ * a singular camera matrix; a failed allocation (MI_ERR_DEVICE) leaves the earlier mark in place. */
+int mi_scene_mark_frame(mi_scene *s);
 /* revision: in-place edits applied so far; tree_builds: host-side builds (tree, triangle records) this scene has gone through -- an update never moves it.  Either may be NULL */
 int mi_scene_revision(mi_scene *s, uint64_t *revision, uint64_t *tree_builds);
 
@@ -345,6 +352,21 @@ int mi_render_adaptive_stats(mi_render *r, mi_adaptive_stats *out);
  *      shapeIndex      index of the hit shape: meshes in mi_scene_set_triangles order, then the analytic shapes; -1 for a hit through an instance (its.shape is then the group
  *                      member, which is not in the scene's shape list: field.cpp:158-167, skdtree.h:416)
  *      primIndex       triangle index within its mesh, also for instanced meshes (skdtree.h:418); 0 for analytic shapes (the reference leaves its.primIndex unset there)
+ *    Two kinds beyond field.cpp's nine follow the scene through its in-place edits; "previous" is the scene's state at the last mi_scene_mark_frame (never marked, or
+ *    committed again since: previous = current).  binary32, one rounding per operation, in the order written (tests/motion_model.py restates it):
+ *      prevPosition    P + (Bprev - Bcur), P = the `position` value.  With b = (1 - u - v, u, v) of the hit and bary(c0, c1, c2) = (c0 b.x + c1 b.y) + c2 b.z per component:
+ *                      a triangle outside a group: Bcur = bary of the corners in its shading record (the expression that gave P), Bprev = bary of the three marked vertices
+ *                      with the triangle's indices; a member of a shape group hit through instance k: Bcur = T(bary of the current object-space corners), Bprev =
+ *                      Tprev(bary of the marked object-space corners), T / Tprev = rows 0..2 of instance k's current / marked to_world applied as
+ *                      ((m0 x + m1 y) + m2 z) + m3 per row; an analytic shape cannot move in place: P.  What did not move since the mark -- the static part of a partly
+ *                      deformed mesh included -- therefore has prevPosition == position bit for bit
+ *      motion          the reference's `motion` integrator in its configuration "d" (src/integrators/misc/motion.cpp:176-201, 258-269) with the marked frame as the target:
+ *                      (Xprev - Xcur, Yprev - Ycur, dprev - dcur).  For q = prevPosition and the projection M marked by mi_scene_mark_frame (the 12 floats of
+ *                      mi_scene_world_to_pixel): Wc = ((M[8] q.x + M[9] q.y) + M[10] q.z) + M[11], Xprev = (the same sum of M[0..3]) / Wc, Yprev likewise from M[4..7];
+ *                      Xcur, Ycur from P and the current projection; d = sqrtf((e.x e.x + e.y e.y) + e.z e.z) with e = q - the marked camera origin (the translation column
+ *                      of the camera's to_world), and with e = P - the current origin.  !(Wc > 0) on either side: the field's `undefined` value
+ *    The host mirror, the drop-in plugin, multi-device renders and adaptive renders do not follow the marked state; the reference's specular configurations ("rd", "ttd", ...)
+ *    are not built.
  *    No finite / non-negative check is applied to field values (multichannel.cpp:41-44). */
 #define MI_FIELD_POSITION 0
 #define MI_FIELD_REL_POSITION 1
@@ -355,6 +377,8 @@ int mi_render_adaptive_stats(mi_render *r, mi_adaptive_stats *out);
 #define MI_FIELD_ALBEDO 6
 #define MI_FIELD_SHAPE_INDEX 7
 #define MI_FIELD_PRIM_INDEX 8
+#define MI_FIELD_PREV_POSITION 9
+#define MI_FIELD_MOTION 10
 typedef struct { uint32_t field; float undefined[3]; } mi_field;
 /* n <= 8 fields; n = 0 removes them and frees the field film.  Allowed only while the film is clear (no samples since mi_render_create / mi_render_clear), else
  * MI_ERR_INVALID; an unknown kind or an albedo the scene's BSDFs do not support: MI_ERR_UNSUPPORTED.  Without fields a render launches, allocates and records nothing extra. */
@@ -439,8 +463,9 @@ int mi_history_read(mi_history *h, float *color, float *count);
 int mi_denoise_image_temporal(mi_history *h, const float *color, const float *normal, const float *position, const float *albedo, const float *prev_position,
                               const float *world_to_pixel12, const mi_denoise_params *p, const mi_temporal_params *t, float *out,
                               float *resolved_sigma_position, float *resolved_temporal_position);
-/* One temporal frame on a render's own films: radiance and guides as mi_render_denoise takes them, with the same field rules and refusals; Pprev = P; M = the scene's
- * current projection (mi_scene_world_to_pixel).  The history must be on the render's device and of its film size.  The films are read, never written. */
+/* One temporal frame on a render's own films: radiance and guides as mi_render_denoise takes them, with the same field rules and refusals; Pprev = the FIRST prevPosition
+ * entry of the render's field list as layout 2 of the field film develops it (the caller marks the scene before each frame's edit, mi_scene_mark_frame), without such a
+ * field Pprev = P; M = the scene's current projection (mi_scene_world_to_pixel).  The history must be on the render's device and of its film size.  The films are read, never written. */
 int mi_render_denoise_temporal(mi_render *r, mi_history *h, const mi_denoise_params *p, const mi_temporal_params *t, float *host_out /* H x W x 3 */,
                                float *resolved_sigma_position, float *resolved_temporal_position);
 int mi_render_denoise_temporal_device(mi_render *r, mi_history *h, const mi_denoise_params *p, const mi_temporal_params *t, void *device_out,
@@ -500,7 +525,8 @@ int mi_debug_intersect_fused(mi_scene *s, const float *rays8, uint64_t n, int an
 /* One device table of a committed scene as it is now, read back whole: what = MI_GEOMETRY_NODES (64-B tree nodes), _LEAF_RECORDS (48-B Wald records in leaf order,
  * word 10 = primitive index), _TRI_SHADE (128-B shading records, triangle order), _TRI_UV (48 B, only scenes with texture coordinates), _PACKET_EXACT (48-B Wald records,
  * triangle order), _PACKET_GROUPS (48-B pass-1 records), _INSTANCES (128-B instance records in instance order: to_world 3 x 4, to_object 3 x 4, group box lo, root node,
- * group box hi, group; size 0 on a scene without instances), _SCENE_BOX (24 B: aabb_lo, then aabb_hi of the scene record the kernels receive).  The caller gives the size in bytes (mi_debug_geometry_bytes); a wrong size is MI_ERR_INVALID. */
+ * group box hi, group; size 0 on a scene without instances), _SCENE_BOX (24 B: aabb_lo, then aabb_hi of the scene record the kernels receive), _PREV_VERTICES (12 B per vertex of mi_scene_set_triangles: the
+ * positions at the last mi_scene_mark_frame), _PREV_INSTANCES (48 B per instance: rows 0..2 of its to_world at the last mark); the last two have size 0 on a scene that was never marked.  The caller gives the size in bytes (mi_debug_geometry_bytes); a wrong size is MI_ERR_INVALID. */
 #define MI_GEOMETRY_NODES 0
 #define MI_GEOMETRY_LEAF_RECORDS 1
 #define MI_GEOMETRY_TRI_SHADE 2
@@ -509,6 +535,8 @@ int mi_debug_intersect_fused(mi_scene *s, const float *rays8, uint64_t n, int an
 #define MI_GEOMETRY_PACKET_GROUPS 5
 #define MI_GEOMETRY_INSTANCES 6
 #define MI_GEOMETRY_SCENE_BOX 7
+#define MI_GEOMETRY_PREV_VERTICES 8
+#define MI_GEOMETRY_PREV_INSTANCES 9
 int mi_debug_geometry_bytes(mi_scene *s, uint32_t what, uint64_t *bytes);
 int mi_debug_read_geometry(mi_scene *s, uint32_t what, void *out, uint64_t bytes);
 int mi_debug_sobol(mi_scene *s, const uint32_t *px_py_k, uint64_t n, uint32_t ndims, uint64_t *out_index, float *out_values);

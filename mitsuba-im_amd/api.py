@@ -84,8 +84,10 @@ class MiTemporalParams(C.Structure):
     _fields_ = [("max_history", C.c_float), ("sigma_position", C.c_float), ("min_normal_dot", C.c_float), ("pad", C.c_uint32)]
 
 
-# field kinds in the order of the reference's EField (src/integrators/misc/field.cpp:57-67) = MI_FIELD_* of include/mi355pt.h
-FIELD_NAMES = ("position", "relPosition", "distance", "geoNormal", "shNormal", "uv", "albedo", "shapeIndex", "primIndex")
+# field kinds in the order of the reference's EField (src/integrators/misc/field.cpp:57-67), then the two that follow the scene's frame mark (Scene.mark_frame)
+# = MI_FIELD_* of include/mi355pt.h
+FIELD_NAMES = ("position", "relPosition", "distance", "geoNormal", "shNormal", "uv", "albedo", "shapeIndex", "primIndex", "prevPosition", "motion")
+MOTION_FIELDS = ("prevPosition", "motion")      # need the marked state: refused where it is not followed (adaptive renders, the host mirror and its `devices` renders)
 SCALAR_FIELDS = ("distance", "shapeIndex", "primIndex")      # the three values of these are equal
 
 
@@ -121,7 +123,7 @@ class MiFusedDebugInfo(C.Structure):
 
 EXPORTS = ["mi_last_error", "mi_set_sobol_tables", "mi_load_sobol_tables", "mi_scene_create", "mi_scene_destroy", "mi_scene_set_triangles",
            "mi_scene_set_analytic", "mi_scene_set_instances", "mi_scene_set_media", "mi_scene_set_materials", "mi_scene_set_material_tables", "mi_scene_set_textures", "mi_scene_set_texture_data", "mi_scene_set_emitters", "mi_scene_set_envmap", "mi_scene_set_envmap_filter", "mi_scene_set_camera", "mi_scene_set_lens", "mi_scene_set_film",
-           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
+           "mi_scene_commit", "mi_scene_ray_intersect", "mi_scene_clone", "mi_scene_update_camera", "mi_scene_update_lens", "mi_scene_update_materials", "mi_scene_update_emitters", "mi_scene_update_envmap_transform", "mi_scene_update_vertices", "mi_scene_update_instances", "mi_scene_update_geometry", "mi_scene_mark_frame", "mi_scene_revision", "mi_render_merge_film", "mi_render_create", "mi_render_destroy", "mi_render_run", "mi_render_run_rows", "mi_render_clear", "mi_render_cancel",
            "mi_render_set_adaptive", "mi_render_run_adaptive", "mi_render_read_sample_counts", "mi_render_adaptive_stats",
            "mi_render_set_fields", "mi_render_field_film_size", "mi_render_read_fields", "mi_render_field_samples", "mi_denoise_image", "mi_render_denoise", "mi_render_denoise_device", "mi_history_create", "mi_history_destroy", "mi_history_reset", "mi_history_frames", "mi_history_read", "mi_denoise_image_temporal", "mi_render_denoise_temporal", "mi_render_denoise_temporal_device", "mi_scene_world_to_pixel", "mi_render_film_size", "mi_render_read_film", "mi_render_read_film_device", "mi_render_samples", "mi_render_stats",
            "mi_render_set_profiling", "mi_render_debug_sensor_differentials", "mi_render_debug_film_put", "mi_debug_intersect", "mi_debug_intersect_inst", "mi_debug_intersect_fused", "mi_debug_sobol", "mi_debug_camera_rays", "mi_debug_camera_rays_lens", "mi_debug_sincosf", "mi_debug_libm", "mi_debug_bsdf", "mi_debug_texture", "mi_debug_emitter_sample", "mi_debug_emitter_eval", "mi_debug_medium", "mi_debug_surface", "mi_debug_geometry_bytes", "mi_debug_read_geometry", "mi_debug_pool_shape", "mi_render_debug_pool_info"]
@@ -172,6 +174,7 @@ class Lib:
         L.mi_scene_update_vertices.argtypes = [vp, vp, vp, u32]
         L.mi_scene_update_instances.argtypes = [vp, vp, u32]
         L.mi_scene_update_geometry.argtypes = [vp, vp, vp, u32, vp, u32]
+        L.mi_scene_mark_frame.argtypes = [vp]
         L.mi_scene_revision.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
         L.mi_render_merge_film.argtypes = [vp, vp]
         L.mi_render_create.argtypes = [vp, C.POINTER(MiRenderParams), C.POINTER(vp)]
@@ -518,12 +521,18 @@ class Scene:
         if pos is not None and nrm is not None: self.sc.nrm = nrm
         if instances is not None: self.sc.instances = instances
 
+    def mark_frame(self):
+        """mi_scene_mark_frame: the scene as it stands -- vertex positions, instance transforms, the projection and the camera origin -- becomes the "previous" state
+        of the prevPosition / motion fields, until the next mark (or commit).  Call it before a frame's edits.  Renders nothing differently; no revision step."""
+        self.L.check(self.L.L.mi_scene_mark_frame(self.h))
+
     GEOMETRY_TABLES = {"nodes": (0, 64), "leaf_records": (1, 48), "tri_shade": (2, 128), "tri_uv": (3, 48), "packet_exact": (4, 48), "packet_groups": (5, 48),
-                       "instances": (6, 128), "scene_box": (7, 24)}
+                       "instances": (6, 128), "scene_box": (7, 24), "prev_vertices": (8, 12), "prev_instances": (9, 48)}
 
     def read_geometry(self, what):
         """One device table as it is now -> uint32 array [records, words]: "nodes", "leaf_records" (word 10 = primitive), "tri_shade", "tri_uv", "packet_exact", "packet_groups", "instances" (word 27 = root node),
-        "scene_box" (one record: aabb_lo, aabb_hi)."""
+        "scene_box" (one record: aabb_lo, aabb_hi), "prev_vertices" / "prev_instances" (the vertex positions / rows 0..2 of every instance's to_world at the last
+        mark_frame(); empty on a scene that was never marked)."""
         code, rec = self.GEOMETRY_TABLES[what]; n = C.c_uint64()
         self.L.check(self.L.L.mi_debug_geometry_bytes(self.h, code, C.byref(n)))
         out = np.zeros((n.value // rec, rec // 4), np.uint32)
@@ -738,8 +747,9 @@ class Render:
 
     def denoise_temporal(self, history, iterations=5, sigma_color=4.0, sigma_normal=0.3, sigma_position=-0.05, demodulate=None, max_history=32.0,
                          temporal_sigma_position=-0.01, min_normal_dot=0.9, device_ptr=None):
-        """One temporal frame on this render's own films (mi_render_denoise_temporal): radiance and guides as denoise() takes them, the previous position of every
-        pixel = its position (static geometry: a surface that moved further than the tolerance drops its history), the projection = the scene's camera as it stands.
+        """One temporal frame on this render's own films (mi_render_denoise_temporal): radiance and guides as denoise() takes them; the previous position of every
+        pixel = the render's first prevPosition field (Scene.mark_frame() before each frame's edits: moved instances and deformed meshes keep their history), without that
+        field = its position (static geometry: a surface that moved further than the tolerance drops its history); the projection = the scene's camera as it stands.
         `history` (api.History) must be on this render's device and of its film size.  -> H x W x 3, or None with device_ptr.  The resolved widths are left in
         last_denoise_sigma_position and last_temporal_sigma_position."""
         if demodulate is None: demodulate = "albedo" in self.field_names
@@ -836,6 +846,9 @@ class HostIntegrator:
         L = scene.L.L; self.L = L; self.scene = scene; sc = scene.sc
         if sc.get("adaptive"):      # never rendered uniformly without saying so
             raise MiError(3, "HostIntegrator: the host mirror does not offer adaptive sampling (the scene description holds `adaptive` parameters); use Render.run_adaptive")
+        for name, _ in normalize_fields(sc.get("fields") or []):      # the replicas of a `devices` render are not marked with the scene: never rendered without saying so
+            if name in MOTION_FIELDS:
+                raise MiError(3, f"HostIntegrator: the host mirror and its `devices` renders do not follow the frame mark (the scene description holds the field `{name}`); use Render")
         L.mi_host_create_ex.restype = C.c_void_p; L.mi_host_last_error.restype = C.c_char_p; L.mi_host_statistics.restype = C.c_char_p
         L.mi_host_create_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int, C.c_double]
         L.mi_host_preprocess.argtypes = [C.c_void_p, C.c_void_p]; L.mi_host_destroy.argtypes = [C.c_void_p]; L.mi_host_statistics.argtypes = [C.c_void_p]

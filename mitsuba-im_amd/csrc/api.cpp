@@ -78,7 +78,7 @@ void mi_launch_adapt_tile(uint32_t *, mi_tile, uint32_t, uint32_t, hipStream_t);
 void mi_launch_adapt_list(const uint32_t *, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
 void mi_launch_adapt_accumulate(const DScene &, const Queues &, const AdaptArgs &, const uint32_t *, uint32_t, uint32_t, float *, float *, hipStream_t);
 void mi_launch_adapt_compact(const uint32_t *, uint32_t, const uint32_t *, uint32_t *, uint32_t *, uint32_t *, hipStream_t);
-void mi_launch_dn_prepare_render(const DenoiseBufs &, const DenoiseFilmSrc &, int, int, int, hipStream_t);
+void mi_launch_dn_prepare_render(const DenoiseBufs &, const DenoiseFilmSrc &, float *, int, int, int, hipStream_t);
 void mi_launch_dn_prepare_image(const DenoiseBufs &, const float *, const float *, const float *, const float *, int, int, int, hipStream_t);
 void mi_launch_dn_bounds(const DenoiseBufs &, size_t, float, hipStream_t);
 void mi_launch_dn_level(const DenoiseBufs &, int, const DenoiseLevel &, bool, float *, hipStream_t);
@@ -148,6 +148,7 @@ struct mi_render {
     // sample per pixel: no other run or merge may add to it).  adActive: the active list of this round and the next; adList[pool]: the triple list of the batch on that pool
     bool adaptOn = false, adaptFilm = false; mi_adaptive_params ap{}; mi_adaptive_stats as{}; AdaptArgs ad{}; float adQuantile = 0;
     uint32_t *adActive[2] = {}, *adWave = nullptr, *adNNext = nullptr, *adHostN = nullptr, *adList[kMaxPools] = {}; uint64_t adListPaths = 0; uint32_t adPix = 0;
+    float *dnPprev = nullptr;   // H x W x 3: the developed prevPosition field, allocated by the first mi_render_denoise_temporal of a render that holds one
     void *dnMem = nullptr; DenoiseBufs dn{};   // denoiser scratch (denoise.h): two colour buffers + the packed guides, allocated at the first mi_render_denoise, freed with the render
     uint64_t sceneRev = 0, filmRev = 0;   // scene revision `sc` was copied from / the samples in the film (and the field film) were traced at
     Queues &pool(int i) { return i ? qx[i - 1] : q; }
@@ -313,6 +314,16 @@ template <typename T> static int up(void **dst, const std::vector<T> &v) {
 void SceneHost::release() {
     eachDevicePointer([](void *&p) { if (p) { (void) hipFree(p); p = nullptr; } });
 }
+int SceneHost::allocMark() {
+    auto raw = [](void **p, size_t bytes) { if (*p) return 0; if (hipMalloc(p, std::max<size_t>(bytes, 16)) != hipSuccess) { *p = nullptr; return 1; } return 0; };
+    return raw(&dPrevPos, pos.size() * 4) | raw(&dPrevInst, instances.size() * 48);
+}
+int SceneHost::uploadMark() {
+    if (allocMark()) return 1;
+    if (!prevPos.empty() && hipMemcpy(dPrevPos, prevPos.data(), prevPos.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return 1;
+    if (!prevInstXf.empty() && hipMemcpy(dPrevInst, prevInstXf.data(), prevInstXf.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return 1;
+    return 0;
+}
 int SceneHost::upload(int dev) {
     release(); device = dev;
     if (hipSetDevice(dev) != hipSuccess) return 1;
@@ -451,6 +462,7 @@ int mi_scene_commit(mi_scene *s, uint32_t device) {
     }
     if (s->h.emitters.empty()) return fail(MI_ERR_UNSUPPORTED, "mi_scene_commit: scene without emitters (the reference would add a sunsky emitter)");
     ensureSobolTables();
+    s->h.marked = false; s->h.prevPos.clear(); s->h.prevInstXf.clear();      // a commit rebuilds the scene: previous = current until the next mi_scene_mark_frame (upload() frees the tables)
     s->h.commitHost();
     if (s->h.bvhDepth > 32) return fail(MI_ERR_UNSUPPORTED, "mi_scene_commit: BVH deeper than the traversal stack (32)");
     if (s->h.wideBvh && s->h.nodes.size() >= (1u << 23)) return fail(MI_ERR_UNSUPPORTED, "mi_scene_commit: more than 2^23 BVH nodes");
@@ -475,7 +487,7 @@ int mi_scene_clone(mi_scene *s, uint32_t device, mi_scene **out) {
         c->h.eachDevicePointer([](void *&p) { p = nullptr; });
         c->h.committed = false;
     }
-    if (c->h.upload((int) device)) { std::string msg = std::string("mi_scene_clone: upload failed: ") + hipGetErrorString(hipGetLastError()); delete c; return fail(MI_ERR_DEVICE, msg); }
+    if (c->h.upload((int) device) || (c->h.marked && c->h.uploadMark())) { std::string msg = std::string("mi_scene_clone: upload failed: ") + hipGetErrorString(hipGetLastError()); delete c; return fail(MI_ERR_DEVICE, msg); }      // the replica carries the frame mark
     *out = c; return MI_OK;
 }
 
@@ -656,6 +668,19 @@ static bool worldToCamera(const mi::SceneHost &h, float *w2c) {
     for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) w2c[i * 4 + j] = (float) inv[i][j]; w2c[i * 4 + 3] = (float) -(inv[i][0] * t[0] + inv[i][1] * t[1] + inv[i][2] * t[2]); }
     return std::fabs(det) > 0;
 }
+// The part of the field arguments that follows the scene through its edits and frame marks (prevPosition / motion): the current and the marked projection and camera
+// origin, the two tables of mi_scene_mark_frame.  A scene that was never marked has no tables and previous = current.  Renders without these kinds are not touched.
+extern "C++" { static int sceneWorldToPixel(const std::string &fn, const mi::SceneHost &h, float *out12); }
+#define MI_FIELD_MOTION_KINDS ((1u << MI_FIELD_PREV_POSITION) | (1u << MI_FIELD_MOTION))
+static int fieldMotionArgs(const std::string &who, const mi::SceneHost &h, FieldArgs &fa) {
+    if (!(fa.needs & MI_FIELD_MOTION_KINDS)) return MI_OK;
+    { int rc = sceneWorldToPixel(who, h, fa.m_cur); if (rc) return rc; }
+    for (int i = 0; i < 3; ++i) fa.o_cur[i] = h.c2w[i * 4 + 3];
+    fa.prev_pos = h.marked && !h.prevPos.empty() ? (const float *) h.dPrevPos : nullptr;
+    fa.prev_inst = h.marked && !h.prevInstXf.empty() ? (const float *) h.dPrevInst : nullptr;
+    memcpy(fa.m_prev, h.marked ? h.prevW2P : fa.m_cur, 48); memcpy(fa.o_prev, h.marked ? h.prevOrigin : fa.o_cur, 12);
+    return MI_OK;
+}
 // A render holds a copy of the scene record.  Every entry point that launches kernels calls this first: when the scene has been edited since (mi_scene_update_*), the
 // copy is taken again -- keeping the per-render packet switch -- together with the two constants that depend on the camera.  Also counts the render as running on the
 // scene, so that an update issued meanwhile is refused; RunGuard's destructor ends that.
@@ -676,6 +701,7 @@ static int beginRun(mi_render *r, RunGuard &g, bool film, const char *who) {
         if (r->nFields) (void) worldToCamera(s->h, r->fa.w2c);
         r->sceneRev = s->h.revision;
     }
+    if (r->nFields) { const int rc = fieldMotionArgs(who, s->h, r->fa); if (rc) return rc; }      // a mark moves no revision: taken again for every run
     if (film) r->filmRev = s->h.revision;
     return MI_OK;
 }
@@ -976,6 +1002,7 @@ void mi_render_destroy(mi_render *r) {
     releaseFields(r);
     releaseAdaptive(r);
     if (r->dnMem) (void) hipFree(r->dnMem);
+    if (r->dnPprev) (void) hipFree(r->dnPprev);
     if (r->dNib) (void) hipFree(r->dNib);
     if (r->pollHost) (void) hipHostFree(r->pollHost);
     if (r->pollEv) (void) hipEventDestroy(r->pollEv);
@@ -1373,6 +1400,7 @@ int mi_render_set_adaptive(mi_render *r, const mi_adaptive_params *p) {
     if (r->p.spp < 8) return fail(MI_ERR_INVALID, "Starting the adaptive integrator with less than 8 samples per pixel does not make much sense -- giving up.");      // :210-212
     if (r->p.integrator == MI_INTEGRATOR_DIRECT || r->p.integrator == MI_INTEGRATOR_AO)
         return fail(MI_ERR_UNSUPPORTED, "mi_render_set_adaptive: adaptive sampling over the direct and ao integrators is not implemented (their adaptive queries renumber the sample arrays, direct.cpp:192, ao.cpp:102); use path, volpath_simple or volpath");
+    if (r->nFields && (r->fa.needs & MI_FIELD_MOTION_KINDS)) return fail(MI_ERR_UNSUPPORTED, "mi_render_set_adaptive: the prevPosition / motion fields are set on this render (mi_render_set_fields); adaptive sampling fills no field film and does not follow the frame mark");
     if (r->nFields) return fail(MI_ERR_UNSUPPORTED, "mi_render_set_adaptive: field channels are set on this render (mi_render_set_fields); adaptive sampling does not fill a field film");
     if (p->max_sample_factor == 0) return fail(MI_ERR_INVALID, "mi_render_set_adaptive: max_sample_factor must not be 0 (negative: no cap, positive: at most max_sample_factor x spp samples per pixel)");
     if (!(p->max_error >= 0)) return fail(MI_ERR_INVALID, "mi_render_set_adaptive: max_error must be >= 0");
@@ -1591,7 +1619,7 @@ int mi_render_set_fields(mi_render *r, const mi_field *fields, uint32_t n) {
     const mi::SceneHost &h = r->scene->h; HIPCHK(hipSetDevice(h.device));
     uint32_t needs = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        if (fields[i].field > MI_FIELD_PRIM_INDEX) return fail(MI_ERR_UNSUPPORTED, "mi_render_set_fields: unknown field kind " + std::to_string(fields[i].field) + " (position, relPosition, distance, geoNormal, shNormal, uv, albedo, shapeIndex, primIndex = 0..8)");
+        if (fields[i].field > MI_FIELD_MOTION) return fail(MI_ERR_UNSUPPORTED, "mi_render_set_fields: unknown field kind " + std::to_string(fields[i].field) + " (position, relPosition, distance, geoNormal, shNormal, uv, albedo, shapeIndex, primIndex, prevPosition, motion = 0..10)");
         needs |= 1u << fields[i].field;
     }
     if (needs & (1u << MI_FIELD_ALBEDO)) {
@@ -1607,6 +1635,8 @@ int mi_render_set_fields(mi_render *r, const mi_field *fields, uint32_t n) {
     FieldArgs fa{}; fa.n = n; fa.needs = needs; fa.n_meshes = (uint32_t) h.shapes.size();
     for (uint32_t i = 0; i < n; ++i) { fa.kind[i] = fields[i].field; memcpy(fa.undefined[i], fields[i].undefined, 12); }
     if (!worldToCamera(h, fa.w2c) && (needs & (1u << MI_FIELD_REL_POSITION))) return fail(MI_ERR_INVALID, "mi_render_set_fields: relPosition needs an invertible camera transform");
+    if ((needs & MI_FIELD_MOTION_KINDS) && r->adaptOn) return fail(MI_ERR_UNSUPPORTED, "mi_render_set_fields: prevPosition / motion on an adaptive render (mi_render_set_adaptive): adaptive sampling fills no field film and does not follow the frame mark");
+    { const int rc = fieldMotionArgs("mi_render_set_fields", h, fa); if (rc) return rc; }
     struct Undo { mi_render *r; ~Undo() { if (r) releaseFields(r); } } undo{r};
     if (needs & (1u << MI_FIELD_SHAPE_INDEX)) {
         std::vector<int32_t> ts(std::max<size_t>(h.idx.size() / 3, 1), -1);
@@ -1724,14 +1754,14 @@ static int dnFilter(const DenoiseBufs &b, uint32_t width, uint32_t height, const
 // where the render form finds radiance and guides: the film planes and the first shNormal / position / albedo entry of the field list; a missing one is refused by name
 static int dnRenderSource(const std::string &fn, const mi_render *r, const mi_denoise_params *p, DenoiseFilmSrc *f) {
     const mi::SceneHost &h = r->scene->h;
-    int fN = -1, fP = -1, fA = -1;      // the first entry of each kind
-    for (int i = (int) r->nFields - 1; i >= 0; --i) { if (r->fields[i].field == MI_FIELD_SH_NORMAL) fN = i; if (r->fields[i].field == MI_FIELD_POSITION) fP = i; if (r->fields[i].field == MI_FIELD_ALBEDO) fA = i; }
+    int fN = -1, fP = -1, fA = -1, fQ = -1;      // the first entry of each kind
+    for (int i = (int) r->nFields - 1; i >= 0; --i) { if (r->fields[i].field == MI_FIELD_PREV_POSITION) fQ = i; if (r->fields[i].field == MI_FIELD_SH_NORMAL) fN = i; if (r->fields[i].field == MI_FIELD_POSITION) fP = i; if (r->fields[i].field == MI_FIELD_ALBEDO) fA = i; }
     const char *why = r->adaptFilm ? "; a film that holds an adaptive run has no field film" : "";
     if (fN < 0) return fail(MI_ERR_INVALID, fn + ": the render has no shNormal field (mi_render_set_fields" + why + ")");
     if (fP < 0) return fail(MI_ERR_INVALID, fn + ": the render has no position field (mi_render_set_fields" + why + ")");
     if (p->demodulate && fA < 0) return fail(MI_ERR_INVALID, fn + ": demodulate without albedo: the render has no albedo field (mi_render_set_fields)");
     f->film = r->film; f->spill = r->spill; f->ffilm = r->fieldFilm; f->fspill = r->fieldSpill; f->W = (int) h.width + 2 * h.border; f->H = (int) h.height + 2 * h.border; f->border = h.border;
-    f->nv = 3 * (int) r->nFields; f->fN = fN; f->fP = fP; f->fA = fA;
+    f->nv = 3 * (int) r->nFields; f->fN = fN; f->fP = fP; f->fA = fA; f->fQ = fQ;
     return MI_OK;
 }
 extern "C" {
@@ -1776,7 +1806,7 @@ int mi_render_denoise_device(mi_render *r, const mi_denoise_params *p, void *dev
     const size_t n = (size_t) h.width * h.height;
     if (!r->dnMem) { int rc = dnAlloc(fn, n, &r->dnMem, &r->dn); if (rc) return rc; }
     const int demod = p->demodulate ? 1 : 0;
-    mi_launch_dn_prepare_render(r->dn, f, (int) h.width, (int) h.height, demod, r->stream);
+    mi_launch_dn_prepare_render(r->dn, f, nullptr, (int) h.width, (int) h.height, demod, r->stream);
     return dnFilter(r->dn, h.width, h.height, p, demod, (float *) device_out, resolved_sigma_position, r->stream);
 }
 int mi_render_denoise(mi_render *r, const mi_denoise_params *p, float *host_out, float *resolved_sigma_position) {
@@ -1946,8 +1976,13 @@ int mi_render_denoise_temporal_device(mi_render *r, mi_history *hist, const mi_d
     HIPCHK(hipSetDevice(h.device));
     const size_t n = (size_t) h.width * h.height;
     if (!r->dnMem) { int rc = dnAlloc(fn, n, &r->dnMem, &r->dn); if (rc) return rc; }
-    mi_launch_dn_prepare_render(r->dn, f, (int) h.width, (int) h.height, demod, r->stream);
-    return tpRun(hist, r->dn, M, nullptr, p, t, demod, (float *) device_out, resolved_sigma_position, resolved_temporal_position, r->stream);
+    float *pprev = nullptr;      // with a prevPosition field: that field, developed, is Pprev; without one Pprev = P
+    if (f.fQ >= 0) {
+        if (!r->dnPprev && hipMalloc((void **) &r->dnPprev, n * 12) != hipSuccess) { (void) hipGetLastError(); r->dnPprev = nullptr; return fail(MI_ERR_DEVICE, fn + ": cannot allocate the previous-position buffer (" + std::to_string(n * 12) + " bytes)"); }
+        pprev = r->dnPprev;
+    }
+    mi_launch_dn_prepare_render(r->dn, f, pprev, (int) h.width, (int) h.height, demod, r->stream);
+    return tpRun(hist, r->dn, M, pprev, p, t, demod, (float *) device_out, resolved_sigma_position, resolved_temporal_position, r->stream);
 }
 int mi_render_denoise_temporal(mi_render *r, mi_history *hist, const mi_denoise_params *p, const mi_temporal_params *t, float *host_out, float *resolved_sigma_position,
                                float *resolved_temporal_position) {
@@ -1960,6 +1995,25 @@ int mi_scene_world_to_pixel(mi_scene *s, float *out12) {
     if (!s || !out12) return fail(MI_ERR_INVALID, "mi_scene_world_to_pixel: null argument");
     if (!s->h.committed) return fail(MI_ERR_INVALID, "mi_scene_world_to_pixel: scene not committed");
     return sceneWorldToPixel("mi_scene_world_to_pixel", s->h, out12);
+}
+// Frame mark: the "previous" state of the prevPosition / motion fields.  The host takes the snapshot (a replica uploads it from there); the device's copy of the
+// vertices comes from the device's own vertex array where a vertex edit has made one -- it holds h.pos, pushed by every such edit -- and from the host otherwise.
+// Both tables are allocated before anything changes: a failed allocation leaves the earlier mark as it was.
+int mi_scene_mark_frame(mi_scene *s) {
+    UPDATE_ENTER("mi_scene_mark_frame");
+    mi::SceneHost &h = s->h;
+    float M[12]; { int rc = sceneWorldToPixel("mi_scene_mark_frame", h, M); if (rc) return rc; }
+    HIPCHK(hipSetDevice(h.device));
+    if (h.allocMark()) { (void) hipGetLastError(); return fail(MI_ERR_DEVICE, "mi_scene_mark_frame: cannot allocate the tables of the previous frame; the earlier mark stays"); }
+    h.prevPos = h.pos; h.prevInstXf.resize(h.instances.size() * 12);
+    for (size_t i = 0; i < h.instances.size(); ++i) memcpy(&h.prevInstXf[i * 12], h.instances[i].to_world, 48);
+    memcpy(h.prevW2P, M, 48); for (int i = 0; i < 3; ++i) h.prevOrigin[i] = h.c2w[i * 4 + 3];
+    h.marked = true;
+    if (h.dPos && !h.prevPos.empty()) HIPCHK(hipMemcpy(h.dPrevPos, h.dPos, h.prevPos.size() * 4, hipMemcpyDeviceToDevice));
+    else HIPCHK(push(h.dPrevPos, h.prevPos));
+    HIPCHK(push(h.dPrevInst, h.prevInstXf));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    return MI_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ unit-level device entry points
@@ -2065,7 +2119,7 @@ int mi_debug_intersect_fused(mi_scene *s, const float *rays, uint64_t n, int any
     return rc;
 }
 // One device table of the scene as it is now: 0 nodes, 1 leaf records, 2 TriShade, 3 TriUV, 4 packet-exact records, 5 packet groups, 6 instance records; 7 = the box
-// of the scene record (held on the host: every run passes the record by value).  mi_debug_geometry_bytes gives the size.
+// of the scene record (held on the host: every run passes the record by value); 8, 9 = the vertices and instance transforms of the last frame mark.  mi_debug_geometry_bytes gives the size.
 static int geometryTable(mi_scene *s, uint32_t what, const void **ptr, uint64_t *bytes, const char *who) {
     if (!s) return fail(MI_ERR_INVALID, std::string(who) + ": null scene");
     if (!s->h.committed) return fail(MI_ERR_INVALID, std::string(who) + ": scene not committed");
@@ -2079,6 +2133,8 @@ static int geometryTable(mi_scene *s, uint32_t what, const void **ptr, uint64_t 
     case 5: *ptr = h.dPacketGroups; *bytes = (uint64_t) h.packetGroups.size() * sizeof(PacketGroupD); break;
     case MI_GEOMETRY_INSTANCES: *ptr = h.dInstances; *bytes = (uint64_t) h.instancesD.size() * sizeof(InstanceD); break;
     case MI_GEOMETRY_SCENE_BOX: *ptr = nullptr; *bytes = 24; break;
+    case MI_GEOMETRY_PREV_VERTICES: *ptr = h.dPrevPos; *bytes = h.marked ? (uint64_t) h.prevPos.size() * 4 : 0; break;          // the two tables of mi_scene_mark_frame
+    case MI_GEOMETRY_PREV_INSTANCES: *ptr = h.dPrevInst; *bytes = h.marked ? (uint64_t) h.prevInstXf.size() * 4 : 0; break;
     default: return fail(MI_ERR_INVALID, std::string(who) + ": unknown table " + std::to_string(what));
     }
     return MI_OK;

@@ -33,5 +33,6 @@ struct DenoiseFilmSrc {
     const float *film, *spill, *ffilm, *fspill;
     int W, H, border, nv;
     int fN, fP, fA;     // field list indices of shNormal, position, albedo (fA < 0: none)
+    int fQ;             // ... of prevPosition (< 0: none): the temporal stage's Pprev, developed into a buffer of its own when prepare is given one
 };
 struct DenoiseLevel { int w, h, step; float kc, kn, kp; const float *res; int demod; };   // res != null: kp = res[1]

@@ -8,7 +8,7 @@
 // RENDER: radiance = film layout 2 (k_film_layout: sum x (weight != 0 ? 1 / weight : 0)), guides = field layout 2 (k_field_layout: the same expression on the field film's own weight),
 // read from the planes in place.  Image form: interleaved H x W x 3 arrays.  Demodulation: D = A > 1e-3f ? A : 1e-3f (a NaN albedo gives 1e-3f), c0 = C / D.
 template <bool RENDER>
-__global__ __launch_bounds__(WG) void k_dn_prepare(DenoiseBufs b, DenoiseFilmSrc f, const float *C, const float *N, const float *P, const float *A, int w, int h, int demod) {
+__global__ __launch_bounds__(WG) void k_dn_prepare(DenoiseBufs b, DenoiseFilmSrc f, const float *C, const float *N, const float *P, const float *A, float *pprev, int w, int h, int demod) {
     const size_t i = (size_t) blockIdx.x * WG + threadIdx.x;
     if (i >= (size_t) w * h) return;
     float c[3], n[3], p[3], a[3] = {0.0f, 0.0f, 0.0f};
@@ -24,6 +24,7 @@ __global__ __launch_bounds__(WG) void k_dn_prepare(DenoiseBufs b, DenoiseFilmSrc
             n[k] = (f.ffilm[kn] + f.fspill[kn]) * finv;
             p[k] = (f.ffilm[kp] + f.fspill[kp]) * finv;
             if (demod) { const size_t ka = (size_t) (3 * f.fA + k) * plane + src; a[k] = (f.ffilm[ka] + f.fspill[ka]) * finv; }
+            if (pprev) { const size_t kq = (size_t) (3 * f.fQ + k) * plane + src; pprev[i * 3 + k] = (f.ffilm[kq] + f.fspill[kq]) * finv; }      // the temporal stage's Pprev: the prevPosition field, developed like the guides
         }
     } else {
 #pragma unroll
@@ -145,13 +146,14 @@ __global__ __launch_bounds__(MI_DN_TILE_W * MI_DN_TILE_H) void k_dn_level(const 
 }
 
 extern "C" {
-void mi_launch_dn_prepare_render(const DenoiseBufs &b, const DenoiseFilmSrc &f, int w, int h, int demod, hipStream_t st) {
+// pprev (H x W x 3, may be null): receives field f.fQ of the field film, developed
+void mi_launch_dn_prepare_render(const DenoiseBufs &b, const DenoiseFilmSrc &f, float *pprev, int w, int h, int demod, hipStream_t st) {
     const size_t n = (size_t) w * h;
-    hipLaunchKernelGGL(k_dn_prepare<true>, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, b, f, nullptr, nullptr, nullptr, nullptr, w, h, demod);
+    hipLaunchKernelGGL(k_dn_prepare<true>, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, b, f, nullptr, nullptr, nullptr, nullptr, pprev, w, h, demod);
 }
 void mi_launch_dn_prepare_image(const DenoiseBufs &b, const float *C, const float *N, const float *P, const float *A, int w, int h, int demod, hipStream_t st) {
     const size_t n = (size_t) w * h;
-    hipLaunchKernelGGL(k_dn_prepare<false>, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, b, DenoiseFilmSrc{}, C, N, P, A, w, h, demod);
+    hipLaunchKernelGGL(k_dn_prepare<false>, dim3((unsigned) ((n + WG - 1) / WG)), dim3(WG), 0, st, b, DenoiseFilmSrc{}, C, N, P, A, nullptr, w, h, demod);
 }
 // leaves res[0] = the resolved width (0: position term off) and res[1] = kp
 void mi_launch_dn_bounds(const DenoiseBufs &b, size_t n, float absSigma, hipStream_t st) {

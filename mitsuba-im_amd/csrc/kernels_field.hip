@@ -52,6 +52,35 @@ DEV v3 fieldAlbedo(const DScene &sc, const Tabs<false> &tb, int material, float 
     return fieldDiffuseEval(sc, tb, m, u, v) * MI_PI;
 }
 
+// prevPosition (include/mi355pt.h has the normative wording): Bprev - Bcur, the displacement since the last mi_scene_mark_frame of the point with the hit's barycentrics
+// on the hit triangle.  Bcur repeats fillHit's expression on the record's corners, Bprev is the same expression on the marked vertices, gathered through the record's
+// own i0..i2 (< n_verts: the indices k_tri_records gathers with); a member of a shape group takes both through its instance's to_world, current and marked
+// (inst < n_instances).  Null tables -- a scene that was never marked -- stand for the current ones.  What did not move gives the same bits twice, so the difference is 0.
+DEV v3 fieldDisplacement(const DScene &sc, const FieldArgs &fa, int inst, uint32_t prim, float u, float v) {
+    const TriShade &ts = sc.shade[prim];
+    const float bx = 1 - u - v, by = u, bz = v;
+    v3 bcur = (ld3(ts.p0) * bx + ld3(ts.p1) * by) + ld3(ts.p2) * bz, bprev = bcur;
+    if (fa.prev_pos) bprev = (ld3(fa.prev_pos + (size_t) ts.i0 * 3) * bx + ld3(fa.prev_pos + (size_t) ts.i1 * 3) * by) + ld3(fa.prev_pos + (size_t) ts.i2 * 3) * bz;
+    if (inst >= 0) {
+        const float *cur = sc.instances[inst].to_world;
+        bprev = xfPoint(fa.prev_inst ? fa.prev_inst + (size_t) inst * 12 : cur, bprev); bcur = xfPoint(cur, bcur);
+    }
+    return bprev - bcur;
+}
+// motion, the reference's `d` configuration (src/integrators/misc/motion.cpp:258-269) with the marked frame as the target: the film position and the camera distance
+// of `pprev` under the marked camera minus those of `p` under the current one.  false: a point at or behind one of the two cameras
+DEV bool fieldMotion(const FieldArgs &fa, v3 p, v3 pprev, v3 &motion) {
+    const float *a = fa.m_prev, *b = fa.m_cur;
+    const float wp = ((a[8] * pprev.x + a[9] * pprev.y) + a[10] * pprev.z) + a[11], wc = ((b[8] * p.x + b[9] * p.y) + b[10] * p.z) + b[11];
+    if (!(wp > 0) || !(wc > 0)) return false;
+    const float xp = (((a[0] * pprev.x + a[1] * pprev.y) + a[2] * pprev.z) + a[3]) / wp, yp = (((a[4] * pprev.x + a[5] * pprev.y) + a[6] * pprev.z) + a[7]) / wp;
+    const float xc = (((b[0] * p.x + b[1] * p.y) + b[2] * p.z) + b[3]) / wc, yc = (((b[4] * p.x + b[5] * p.y) + b[6] * p.z) + b[7]) / wc;
+    const v3 ep = pprev - ld3(fa.o_prev), ec = p - ld3(fa.o_cur);
+    const float dp = sqrtf((ep.x * ep.x + ep.y * ep.y) + ep.z * ep.z), dc = sqrtf((ec.x * ec.x + ec.y * ec.y) + ec.z * ec.z);
+    motion = V(xp - xc, yp - yc, dp - dc);
+    return true;
+}
+
 // All fields of path `pid`: out[3 f + c].  The interaction is rebuilt as k_ray_intersect does (kernels_trace.hip), from the hit record the extend stage left.
 DEV void fieldEval(const DScene &sc, const FieldArgs &fa, const Queues &q, uint64_t pid, float *out) {
     const float4 hr = q.hit[pid]; const uint32_t prim = __float_as_uint(hr.w);
@@ -72,6 +101,11 @@ DEV void fieldEval(const DScene &sc, const FieldArgs &fa, const Queues &q, uint6
     if (fa.needs & (1u << MI_FIELD_ALBEDO)) albedo = fieldAlbedo(sc, tb, h.material, h.uvx, h.uvy);
     if (fa.needs & (1u << MI_FIELD_SHAPE_INDEX)) shapeIndex = inst >= 0 ? -1.0f : (analytic ? (float) (fa.n_meshes + (prim - sc.n_tris)) : (float) fa.tri_shape[prim]);
     if ((fa.needs & (1u << MI_FIELD_PRIM_INDEX)) && !analytic) primIndex = (float) sc.shade[prim].local_prim;
+    v3 pprev = h.p, motion = V(0, 0, 0); bool motionDefined = true;
+    if (fa.needs & ((1u << MI_FIELD_PREV_POSITION) | (1u << MI_FIELD_MOTION))) {
+        if (!analytic) pprev = h.p + fieldDisplacement(sc, fa, inst, prim, u, v);      // an analytic shape cannot move in place
+        if (fa.needs & (1u << MI_FIELD_MOTION)) motionDefined = fieldMotion(fa, h.p, pprev, motion);
+    }
 #pragma unroll
     for (int f = 0; f < MI_MAX_FIELDS; ++f) if ((uint32_t) f < fa.n) {
         v3 val;
@@ -84,6 +118,8 @@ DEV void fieldEval(const DScene &sc, const FieldArgs &fa, const Queues &q, uint6
             case MI_FIELD_UV: val = V(h.uvx, h.uvy, 0.0f); break;
             case MI_FIELD_ALBEDO: val = albedo; break;
             case MI_FIELD_SHAPE_INDEX: val = V(shapeIndex, shapeIndex, shapeIndex); break;
+            case MI_FIELD_PREV_POSITION: val = pprev; break;
+            case MI_FIELD_MOTION: val = motionDefined ? motion : V(fa.undefined[f][0], fa.undefined[f][1], fa.undefined[f][2]); break;
             default: val = V(primIndex, primIndex, primIndex); break;
         }
         out[3 * f] = val.x; out[3 * f + 1] = val.y; out[3 * f + 2] = val.z;

@@ -100,9 +100,16 @@ struct SceneHost {
     // device side of the geometry edits, each table allocated by the first edit that needs it (api.cpp): the vertex array, leafSlotOfPrim, the leaf and node boxes,
     // refitOrder, refitOrderAll, the group boxes of the current edit, the 24-float transform pairs, leafSlotOfInstance
     void *dPos = nullptr, *dLeafSlot = nullptr, *dLeafBox = nullptr, *dNodeBox = nullptr, *dRefitOrder = nullptr, *dRefitOrderAll = nullptr, *dGroupBox = nullptr, *dInstXf = nullptr, *dLeafSlotInst = nullptr;
+    // Frame mark (mi_scene_mark_frame, api.cpp): the "previous" state of the prevPosition / motion fields.  The host keeps the snapshot (a replica uploads it from
+    // here); the two device tables are allocated by the first mark.  A commit clears the mark: previous = current again.
+    bool marked = false; std::vector<float> prevPos, prevInstXf;      // the vertex array; rows 0..2 of every instance's to_world (12 floats each)
+    float prevW2P[12] = {0}, prevOrigin[3] = {0, 0, 0};                   // mi_scene_world_to_pixel's rows and the camera origin at the mark
+    void *dPrevPos = nullptr, *dPrevInst = nullptr;
+    int allocMark();                    // api.cpp: the two device tables, each allocated when missing (sizes follow pos / instances, which no edit changes); 0 = ok
+    int uploadMark();                   // api.cpp: allocMark(), then the host snapshot into them (a replica's upload); 0 = ok
     // Every device allocation the scene owns, listed here and nowhere else: release() frees and clears each, mi_scene_clone clears those of the copy it is about to upload.
     template <typename F> void eachDevicePointer(F f) {
-        void **ps[] = {&dRefitOrderAll, &dGroupBox, &dPos, &dLeafSlot, &dLeafBox, &dNodeBox, &dRefitOrder, &dInstXf, &dLeafSlotInst, &dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
+        void **ps[] = {&dPrevPos, &dPrevInst, &dRefitOrderAll, &dGroupBox, &dPos, &dLeafSlot, &dLeafBox, &dNodeBox, &dRefitOrder, &dInstXf, &dLeafSlotInst, &dMaterialFlags, &dMedia, &dPrimMedia, &dPacketGroups, &dPacketExact, &dTexLevels, &dTexTexels, &dMipLut, &dTriUV, &dTextures, &dMaterialTables, &dInstances, &dEmitterX, &dAnalytic, &dNodes, &dTris, &dShade, &dI2, &dNrm, &dMaterials, &dEmitters, &dEmitterCdf, &dAreaCdf, &dFilter, &dSobolM32, &dSobolVdc, &dSobolVdcInv, &dEnvRGB, &dEnvCols, &dEnvRows, &dEnvWeights, &dEnvGuideRows, &dEnvGuideCols};
         for (void **p : ps) f(*p);
     }
     ~SceneHost() { release(); }

@@ -29,14 +29,16 @@ adaptive sampling, whose film has no field channels.
 
 `--denoise-temporal [MAX_HISTORY]` (with `--denoise`, on `--orbit`, `--spin` and `--focus-pull` sequences of at least two frames) puts the temporal stage in front of
 the filter levels: one history (api.History) serves all frames, every frame's accumulated colour is reprojected into the next through the camera of the edited scene
-and blended with it (api.Render.denoise_temporal; a pixel keeps at most MAX_HISTORY frames, default 32).  The render form takes every surface as static: the
-instances a `--spin` moves lose their history where they move further than the tolerance.  Not with adaptive sampling.  It implies `--sample-offset-per-frame`: frame
+and blended with it (api.Render.denoise_temporal; a pixel keeps at most MAX_HISTORY frames, default 32).  Every frame marks the scene before its edit (Scene.mark_frame) and the
+render carries a `prevPosition` field next to `position` (added like the other guides, not written): the instances a `--spin` moves are reprojected from where they
+were in the previous frame and keep their history.  Not with adaptive sampling.  It implies `--sample-offset-per-frame`: frame
 f renders the sample indices [f spp, (f + 1) spp) after its clear, so that frames carry independent noise.  The render is then created for frames x spp samples per
 pixel, of which every frame takes its own slice (a run stays within the render's sample count; the Sobol' sampler's index layout and the scale of the ray
 differentials follow that count).  Without the flag every frame renders the indices [0, spp) and the files are what they were.
 
 `--orbit N [--orbit-axis x|y|z]` renders a turntable: N frames with the camera rotated in steps of 360 / N degrees about the axis through the centre of the scene's
-box.  The scene is committed once; every frame is an in-place camera edit of the committed scene (Scene.update_camera), a clear and a run -- no tree build, no
+box.  The scene is committed once; every frame is a frame mark (Scene.mark_frame: the state the prevPosition / motion fields call "previous"), an in-place camera edit of the committed scene
+(Scene.update_camera), a clear and a run -- no tree build, no
 upload -- and is written to `<output>_000.<ext>`, `<output>_001.<ext>`, ...
 
 `--spin N [--spin-axis x|y|z]` renders N frames in which every instance of a shape group is turned by 360 k / N degrees (frame k) about the axis through its own placed
@@ -164,6 +166,8 @@ def use_denoise(sc, render, iterations=5, sigmas=None, raw=None, temporal=None, 
     from .api import normalize_fields, MiError, DENOISE_DEFAULTS
     own = normalize_fields(sc.get("fields") or []); names = [n for n, _ in own]
     guides = own + [(g, 0.0) for g in ("shNormal", "position") if g not in names]
+    if temporal is not None and "position" not in names and "prevPosition" not in names:      # the temporal stage's previous positions: the frames mark the scene before their edits
+        guides.append(("prevPosition", 0.0))
     widths = dict(DENOISE_DEFAULTS, iterations=int(iterations))
     if sigmas is not None: widths.update(sigma_color=float(sigmas[0]), sigma_normal=float(sigmas[1]), sigma_position=float(sigmas[2]))
     try:
@@ -226,7 +230,7 @@ def main(argv=None):
     ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITERATIONS", help="filter the radiance on the device with the edge-avoiding a-trous filter, guided by the shNormal / position / albedo field channels (levels, default 5)")
     ap.add_argument("--denoise-sigma", type=float, nargs=3, default=None, metavar=("C", "N", "P"), help="with --denoise: colour, normal and position widths (P < 0: that fraction of the scene's extent)")
     ap.add_argument("--denoise-raw", default=None, metavar="PATH", help="with --denoise: also write the unfiltered radiance")
-    ap.add_argument("--denoise-temporal", type=float, nargs="?", const=32.0, default=None, metavar="MAX_HISTORY", help="with --denoise on a frame sequence: reproject and accumulate the previous frames in front of the filter (frames kept per pixel at the most, default 32); implies --sample-offset-per-frame")
+    ap.add_argument("--denoise-temporal", type=float, nargs="?", const=32.0, default=None, metavar="MAX_HISTORY", help="with --denoise on a frame sequence: reproject and accumulate the previous frames in front of the filter, moved instances from where they were (frames kept per pixel at the most, default 32); implies --sample-offset-per-frame")
     ap.add_argument("--sample-offset-per-frame", action="store_true", help="frame f of a sequence renders the sample indices [f spp, (f + 1) spp): independent noise per frame")
     ap.add_argument("--orbit", type=int, default=0, metavar="N", help="turntable of N frames about the scene box's centre: one commit, one in-place camera edit per frame")
     ap.add_argument("--orbit-axis", choices=["x", "y", "z"], default="y")
@@ -328,7 +332,7 @@ def main(argv=None):
             stem, ext = out.rsplit(".", 1); frame_s = []
             cams = orbit_cameras(sc, a.orbit, a.orbit_axis) if a.orbit else [None] * a.focus_pull
             for f, (dist, c2w) in enumerate(zip(pull, cams)):
-                tf = time.perf_counter()
+                tf = time.perf_counter(); scene.mark_frame()
                 if c2w is not None: scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far)
                 scene.update_lens(sc.aperture_radius, dist); render.clear(); go(f)
                 frame_s.append(time.perf_counter() - tf)
@@ -341,7 +345,7 @@ def main(argv=None):
         if a.orbit:
             stem, ext = out.rsplit(".", 1); frame_s = []
             for f, c2w in enumerate(orbit_cameras(sc, a.orbit, a.orbit_axis)):
-                tf = time.perf_counter()
+                tf = time.perf_counter(); scene.mark_frame()
                 scene.update_camera(sc.sample_to_camera, c2w, sc.near, sc.far); render.clear(); go(f)
                 frame_s.append(time.perf_counter() - tf)
                 if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}", dn=dn, frame=f):
@@ -353,7 +357,7 @@ def main(argv=None):
         if a.spin:
             stem, ext = out.rsplit(".", 1); frame_s = []
             for f, insts in enumerate(spin_instances(sc, a.spin, a.spin_axis)):
-                tf = time.perf_counter()
+                tf = time.perf_counter(); scene.mark_frame()
                 scene.update_instances(insts); render.clear(); go(f)
                 frame_s.append(time.perf_counter() - tf)
                 if not write_outputs(sc, render, f"{stem}_{f:03d}.{ext}", dn=dn, frame=f):
