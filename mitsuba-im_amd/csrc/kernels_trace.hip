@@ -9,7 +9,7 @@
 // Scene::rayIntersect -> ShapeKDTree::rayIntersect (src/librender/skdtree.cpp:112-142): closest hit (t, u, v, prim)
 template <int STACK, int AN, bool WIDE>   // STACK = 0: packet mode; else LDS stack entries per lane (>= the tree's stack need); AN: bit 0 analytic shapes, bit 1 instances; WIDE: 4-wide quantised nodes
 __global__ __launch_bounds__(WG) void k_extend(DScene sc, Queues q, int buf, int ownInterval) {      // ownInterval (launch-uniform): every ray has its (mint, maxt) in the side array; else all take (Epsilon, inf)
-    __shared__ int s_stk[(STACK > 0 ? STACK : 1) * WG];
+    __shared__ int s_stk[(STACK > 0 ? STACK : MI_PACKET_RAY_WORDS) * WG];      // packet mode: the lane's ray copy (trace.h)
     __shared__ f4 s_exact[STACK > 0 ? 1 : MI_PACKET_MAX * 3];
     const uint32_t tid = threadIdx.x;
     unsigned long long rays = 0;
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(WG) void k_extend(DScene sc, Queues q, int buf, int
         v3 o = V(ro.x, ro.y, ro.z), d = V(rd.x, rd.y, rd.z);
         float mint, maxt, t = 0, u = 0, v = 0; uint32_t prim = 0xFFFFFFFFu; bool hit = false; int inst = -1;
         if (clipInterval(sc, o, d, iv.x, iv.y, false, mint, maxt)) {
-            if (STACK == 0) hit = packetIntersect<false, AN>(sc, (AS<true>::p4) s_exact, o, d, mint, maxt, t, prim, u, v);
+            if (STACK == 0) hit = packetIntersect<false, AN>(sc, (AS<true>::p4) s_exact, reinterpret_cast<float *>(s_stk) + tid, o, d, mint, maxt, t, prim, u, v);
             else hit = traverse<false, AN, WIDE>(sc, o, d, mint, maxt, s_stk + tid, t, prim, u, v, inst);
         }
         q.hit[segBase + i] = make_float4(t, u, v, __uint_as_float(hit ? prim : 0xFFFFFFFFu));
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(WG) void k_extend(DScene sc, Queues q, int buf, int
 // deferred `Li += throughput * value * bsdfVal * weight` (path.cpp:196)
 template <int STACK, int AN, bool WIDE>
 __global__ __launch_bounds__(WG) void k_shadow(DScene sc, Queues q) {
-    __shared__ int s_stk[(STACK > 0 ? STACK : 1) * WG];
+    __shared__ int s_stk[(STACK > 0 ? STACK : MI_PACKET_RAY_WORDS) * WG];      // packet mode: the lane's ray copy (trace.h)
     __shared__ f4 s_exact[STACK > 0 ? 1 : MI_PACKET_MAX * 3];
     const uint32_t tid = threadIdx.x;
     if (STACK == 0) packetStage(sc, s_exact);
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(WG) void k_shadow(DScene sc, Queues q) {
         v3 o = V(so.x, so.y, so.z), d = V(sd.x, sd.y, sd.z);
         float mint, maxt, t, u, v; uint32_t prim; bool occluded = false; int inst;
         if (clipInterval(sc, o, d, MI_EPSILON, so.w, true, mint, maxt)) {
-            if (STACK == 0) occluded = packetIntersect<true, AN>(sc, (AS<true>::p4) s_exact, o, d, mint, maxt, t, prim, u, v);
+            if (STACK == 0) occluded = packetIntersect<true, AN>(sc, (AS<true>::p4) s_exact, reinterpret_cast<float *>(s_stk) + tid, o, d, mint, maxt, t, prim, u, v);
             else occluded = traverse<true, AN, WIDE>(sc, o, d, mint, maxt, s_stk + tid, t, prim, u, v, inst);
         }
         if (!occluded) {
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(WG) void k_debug_intersect(DScene sc, const float *
     v3 o = V(r[0], r[1], r[2]), d = V(r[4], r[5], r[6]);
     float mint, maxt, t = 0, u = 0, v = 0; uint32_t prim = 0xFFFFFFFFu; bool hit = false; int inst = -1;
     if (clipInterval(sc, o, d, r[3], r[7], anyHit != 0, mint, maxt)) {
-        if (sc.packet_n) { if (anyHit) hit = packetIntersect<true, 1>(sc, (AS<true>::p4) s_exact, o, d, mint, maxt, t, prim, u, v); else hit = packetIntersect<false, 1>(sc, (AS<true>::p4) s_exact, o, d, mint, maxt, t, prim, u, v); }
+        if (sc.packet_n) { if (anyHit) hit = packetIntersect<true, 1>(sc, (AS<true>::p4) s_exact, reinterpret_cast<float *>(s_stk) + threadIdx.x, o, d, mint, maxt, t, prim, u, v); else hit = packetIntersect<false, 1>(sc, (AS<true>::p4) s_exact, reinterpret_cast<float *>(s_stk) + threadIdx.x, o, d, mint, maxt, t, prim, u, v); }
         else if (sc.bvh_wide) { if (anyHit) hit = traverse<true, 3, true>(sc, o, d, mint, maxt, s_stk + threadIdx.x, t, prim, u, v, inst); else hit = traverse<false, 3, true>(sc, o, d, mint, maxt, s_stk + threadIdx.x, t, prim, u, v, inst); }
         else if (anyHit) hit = traverse<true, 3, false>(sc, o, d, mint, maxt, s_stk + threadIdx.x, t, prim, u, v, inst);
         else hit = traverse<false, 3, false>(sc, o, d, mint, maxt, s_stk + threadIdx.x, t, prim, u, v, inst);
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(WG) void k_ray_intersect(DScene sc, const float *ra
     v3 o = V(r[0], r[1], r[2]), d = V(r[4], r[5], r[6]);
     float mint, maxt, t = 0, u = 0, v = 0; uint32_t prim = 0xFFFFFFFFu; bool hit = false; int inst = -1;
     if (clipInterval(sc, o, d, r[3], r[7], false, mint, maxt)) {
-        if (sc.packet_n) hit = packetIntersect<false, 1>(sc, (AS<true>::p4) s_exact, o, d, mint, maxt, t, prim, u, v);
+        if (sc.packet_n) hit = packetIntersect<false, 1>(sc, (AS<true>::p4) s_exact, reinterpret_cast<float *>(s_stk) + threadIdx.x, o, d, mint, maxt, t, prim, u, v);
         else if (sc.bvh_wide) hit = traverse<false, 3, true>(sc, o, d, mint, maxt, s_stk + threadIdx.x, t, prim, u, v, inst);
         else hit = traverse<false, 3, false>(sc, o, d, mint, maxt, s_stk + threadIdx.x, t, prim, u, v, inst);
     }

@@ -197,10 +197,16 @@ DEV void packetPass1(cgrp g, uint32_t count, v3 o, v3 d, float mint, float maxt,
     }
 }
 // s_exact: the workgroup's LDS copy of the exact Wald records in ORIGINAL triangle order (3 x 16 B each)
+// rayL: this lane's column (MI_PACKET_RAY_WORDS words, stride WG) of LDS scratch; the packet kernels lend it the words the tree walk uses as its stack
+#define MI_PACKET_RAY_WORDS 10
 template <bool ANY, int AN, typename MaskT>
-DEV bool packetIntersectM(const DScene &sc, AS<true>::p4 s_exact, v3 o, v3 d, float mint, float maxt, float &bestT, uint32_t &bestPrim, float &bestU, float &bestV) {
+DEV bool packetIntersectM(const DScene &sc, AS<true>::p4 s_exact, float *rayL, v3 o, v3 d, float mint, float maxt, float &bestT, uint32_t &bestPrim, float &bestU, float &bestV) {
     float best = maxt; uint32_t bprim = 0xFFFFFFFFu; bool found = false; float bu = 0, bv = 0;
     MaskT mask = 0;
+    // pass 2 rotates (o, d) into a candidate's (k, u, v) axes by ADDRESS: words k, k + 1, k + 2 of o.x o.y o.z o.x o.y and of the same five words of d.  The
+    // column belongs to this lane alone (no barrier), is written once per ray, and the reads return the very bits the selects used to pick
+    rayL[0] = o.x; rayL[WG] = o.y; rayL[2 * WG] = o.z; rayL[3 * WG] = o.x; rayL[4 * WG] = o.y;
+    rayL[5 * WG] = d.x; rayL[6 * WG] = d.y; rayL[7 * WG] = d.z; rayL[8 * WG] = d.x; rayL[9 * WG] = d.y;
     const float so1e5 = maxf(maxf(sc.packet_scale, fabsf(o.x)), maxf(fabsf(o.y), fabsf(o.z))) * 1e-5f;
     cgrp groups = (cgrp) sc.packet_groups;
     packetPass1<0, MaskT>(groups, sc.packet_gk[0], o, d, mint, maxt, so1e5, mask);
@@ -209,9 +215,8 @@ DEV bool packetIntersectM(const DScene &sc, AS<true>::p4 s_exact, v3 o, v3 d, fl
     while (mask) {      // pass 2, per lane: the reference's test (triaccel.h:96-158) on this lane's next candidate, written without branches (selects only)
         const uint32_t i = sizeof(MaskT) == 8 ? (uint32_t) __builtin_ctzll((unsigned long long) mask) : (uint32_t) __builtin_ctz((uint32_t) mask); mask &= mask - 1;
         const f4 a = s_exact[i * 3u], b = s_exact[i * 3u + 1u], c = s_exact[i * 3u + 2u];      // k n_u n_v n_d | a_u a_v b_nu b_nv | c_nu c_nv prim pad
-        const bool k0 = __float_as_uint(a.x) == 0u, k1 = __float_as_uint(a.x) == 1u;
-        const float o_u = k0 ? o.y : (k1 ? o.z : o.x), o_v = k0 ? o.z : (k1 ? o.x : o.y), o_k = k0 ? o.x : (k1 ? o.y : o.z);
-        const float d_u = k0 ? d.y : (k1 ? d.z : d.x), d_v = k0 ? d.z : (k1 ? d.x : d.y), d_k = k0 ? d.x : (k1 ? d.y : d.z);
+        const float *rk = rayL + min(__float_as_uint(a.x), 2u) * WG;      // k is 0, 1 or 2 for every record pass 1 can name; the clamp keeps the read inside the column regardless
+        const float o_k = rk[0], o_u = rk[WG], o_v = rk[2 * WG], d_k = rk[5 * WG], d_u = rk[6 * WG], d_v = rk[7 * WG];
         const float tt = (a.w - o_u * a.y - o_v * a.z - o_k) / (d_u * a.y + d_v * a.z + d_k);
         const float hu = o_u + tt * d_u - b.x, hv = o_v + tt * d_v - b.y;
         const float uu = hv * b.z + hu * b.w, vv = hu * c.x + hv * c.y;
@@ -240,9 +245,9 @@ DEV bool packetIntersectM(const DScene &sc, AS<true>::p4 s_exact, v3 o, v3 d, fl
     return found;
 }
 template <bool ANY, int AN>
-DEV bool packetIntersect(const DScene &sc, AS<true>::p4 s_exact, v3 o, v3 d, float mint, float maxt, float &bestT, uint32_t &bestPrim, float &bestU, float &bestV) {
-    if (sc.n_tris <= 32u) return packetIntersectM<ANY, AN, uint32_t>(sc, s_exact, o, d, mint, maxt, bestT, bestPrim, bestU, bestV);      // uniform branch: 32-bit candidate masks
-    return packetIntersectM<ANY, AN, unsigned long long>(sc, s_exact, o, d, mint, maxt, bestT, bestPrim, bestU, bestV);
+DEV bool packetIntersect(const DScene &sc, AS<true>::p4 s_exact, float *rayL, v3 o, v3 d, float mint, float maxt, float &bestT, uint32_t &bestPrim, float &bestU, float &bestV) {
+    if (sc.n_tris <= 32u) return packetIntersectM<ANY, AN, uint32_t>(sc, s_exact, rayL, o, d, mint, maxt, bestT, bestPrim, bestU, bestV);      // uniform branch: 32-bit candidate masks
+    return packetIntersectM<ANY, AN, unsigned long long>(sc, s_exact, rayL, o, d, mint, maxt, bestT, bestPrim, bestU, bestV);
 }
 // stage the exact Wald records of a packet-mode scene in LDS (called by every kernel that uses packetIntersect; ends with a barrier)
 DEV void packetStage(const DScene &sc, f4 *s_exact) {
